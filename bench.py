@@ -26,6 +26,9 @@ N > 1    : `python bench.py --gpus N` without RANK in the environment starts N r
 
 Prints ONE compact JSON line (< 4 KB) on rank 0's stdout; everything else -- per-config dicts, cold renders, the fast mode,
 the CPU restatement's figure, notes -- goes to bench_detail.json next to this file (--detail PATH) and to stderr.
+A plain run measures the headline alone; --full adds every side measurement (film in HBM, cold renders, checkpoints in every
+launch, the precompiled kernel, the other configs, the fast mode, the CPU baselines; N > 1: C3 on the same ranks).
+--dump-outputs DIR writes the film of the last timed step to DIR/film.npy (float32, H x W x 4).
 """
 import argparse
 import glob
@@ -589,14 +592,19 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default="c2", choices=["c2", "c2r", "c3", "c4", "c5"], help="the workload (default: BASELINE configs[1])")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-configs", action="store_true", help="skip the other configs' entries")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the cpu_baseline leg")
+    ap.add_argument("--no-configs", action="store_true", help="--full without the other configs' entries")
     ap.add_argument("--spi", type=int, default=0, help="samples per work item (0 = auto)")
     ap.add_argument("--detail", default=os.environ.get("PINE_BENCH_DETAIL", os.path.join(ROOT, "bench_detail.json")), help="where the full result dict goes")
-    ap.add_argument("--headline-only", action="store_true", help="only the timed headline loop: no side figures, no precompiled-kernel leg, "
-                    "no other configs, no CPU leg (counter passes: every path-kernel dispatch of the run is the headline's)")
+    ap.add_argument("--full", action="store_true", help="everything beside the headline too: film in HBM, cold renders, checkpoints in "
+                    "every launch, the precompiled kernel, the other configs (N > 1: C3 on the same ranks), the fast mode, the CPU baselines")
+    ap.add_argument("--headline-only", action="store_true", help="only the timed headline loop, even with --full (counter passes: every "
+                    "path-kernel dispatch of the run is the headline's)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the film of the last timed step (float32, H x W x 4) to DIR/film.npy")
     args = ap.parse_args()
     if args.headline_only:
+        args.full = False
+    if not args.full:
         args.no_cpu = args.no_configs = True
     if args.gpus < 1:
         raise SystemExit("--gpus must be at least 1")
@@ -637,8 +645,12 @@ def main():
     spec = None if want_specialised() else False
 
     res = measure(args.config, args.steps, args.warmup, env, args.spi, specialize=spec)
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "film.npy"), np.ascontiguousarray(res["film_host"], dtype=np.float32))
     # N > 1: BASELINE names C3 (1920x1080) as the 8-GPU workload; the headline stays C2 so that N = 1 equals the single-GPU
-    # record, and C3 is measured right after it on the same ranks (every rank takes part; rank 0 reports)
+    # record, and with --full C3 is measured right after it on the same ranks (every rank takes part; rank 0 reports)
     c3 = None
     if world > 1 and args.config == "c2" and not args.no_configs:
         res["plan"].close()
@@ -662,7 +674,7 @@ def main():
             e["note"] = "BASELINE's multi-GPU workload (configs[2]) on the same ranks, measured after the headline; scaling: strong"
             full["configs"].append(e)
             c3["plan"].close()
-        if world == 1 and not args.headline_only:
+        if world == 1 and args.full:
             # the same K renders without the host copy (film stays in HBM)
             res["plan"].close()
             res["plan"] = None

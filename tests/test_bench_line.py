@@ -134,3 +134,26 @@ def test_the_default_line_on_the_gpu(tmp_path):
     d = json.loads(lines[0])
     assert d["n_gpus"] == 1 and d["film_equals_reference"] is True and d["roofline"]["frac"] > 0.2
     assert d["config"]["kernel_mode"].startswith(("specialised(", "precompiled"))
+
+
+def test_full_and_dump_outputs_are_options():
+    r = _run(["--help"], {})
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+
+
+@pytest.mark.gpu
+def test_a_plain_run_dumps_the_film_of_its_last_step(tmp_path):
+    """A plain run measures the headline alone (no CPU baseline, no side configs) and --dump-outputs writes the film the
+    timed path computed in its last step: the reference's film of C2, bit for bit."""
+    import hashlib
+    import numpy as np
+    import bench
+    r = _run(["--steps", "2", "--warmup", "1", "--detail", str(tmp_path / "detail.json"), "--dump-outputs", str(tmp_path / "out")], {}, timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["ms_per_step"] > 0 and "cpu_baseline" not in d and "configs" not in d
+    film = np.load(tmp_path / "out" / "film.npy")
+    assert film.dtype == np.float32 and film.shape == (640, 640, 4)
+    assert hashlib.md5(film.tobytes()).hexdigest() == bench.golden_md5("C2_cbox_640_s256_d8_committed")

@@ -111,17 +111,27 @@ def test_depth_must_be_positive(oracle):
         oracle.render(ps, (64, 64), spp, 0)
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/src/pine"), reason="reference sources absent")
+def _reference_scene(name):
+    """One scene of tests/golden/oracle_scenes.npz (tools/make_golden.py --live): the reference's film, the scene description it
+    was rendered from, spp, depth."""
+    z = np.load(os.path.join(GOLDEN, "oracle_scenes.npz"))
+    spp, depth = (int(v) for v in z[f"{name}_spp_depth"])
+    return z[f"{name}_film"], str(z[f"{name}_pscene"]), spp, depth
+
+
 def test_oracle_against_live_reference(oracle):
-    """In the build container the real reference binary is available: one fresh config, bit-exact."""
-    if not oracle.have_ref():
-        pytest.skip("oracle/_ref/pine_ref not built")
+    """One fresh config against the real reference's film, bit-exact; where the reference binary is built, its film of the
+    scene is rendered again and must equal the stored one."""
     from pine_amd import scenes
     sc = scenes.cbox((40, 24), "readme")
     ps = sc.describe()
-    ref, _ = oracle.ref_render(ps, (40, 24), 32, 6)
+    ref, ps_ref, spp, depth = _reference_scene("cbox_readme_40x24_s32_d6")
+    assert ps == ps_ref and (spp, depth) == (32, 6)
     got, _ = oracle.render(ps, (40, 24), 32, 6)
     assert_bit_equal(got, ref, "live reference")
+    if oracle.have_ref():
+        live, _ = oracle.ref_render(ps, (40, 24), 32, 6)
+        assert_bit_equal(live, ref, "the reference binary vs its stored film")
 
 
 def test_stats_file_present():
@@ -134,26 +144,30 @@ def test_stats_file_present():
 
 def test_random_scenes_oracle_equals_the_reference_binary(oracle):
     """Fuzzing: seeded random mixes of every shape / material / light kind (pine_amd.scenes.random_scene); the
-    restatement against oracle/_ref/pine_ref, bit for bit.  (tools/fuzz_scenes.py ran 300 seeds both ways.)"""
+    restatement against the films oracle/_ref/pine_ref rendered of them (tests/golden/oracle_scenes.npz), bit for bit, and
+    against the binary itself where it is built.  (tools/fuzz_scenes.py ran 300 seeds both ways.)"""
     import subprocess
+    import tempfile
     from pine_amd import scenes
     exe = os.path.join(os.path.dirname(GOLDEN), "..", "oracle", "_ref", "pine_ref")
-    if not os.access(exe, os.X_OK):
-        pytest.skip("oracle/_ref/pine_ref not built (no /root/reference here)")
-    import tempfile
     for seed, variety in [(k, 1) for k in range(2000, 2012)] + [(k, 2) for k in range(2100, 2106)]:
         # variety 1: + odd film sizes, thin lens, SobolSampler; 2: + fractional Uber lobes, Subsurface meshes (in-path RNG)
         sc, spp, depth, sampler = scenes.random_scene(seed, variety=variety)
         ps = sc.describe()
         w, h = sc.camera.film().size
+        ref, ps_ref, spp_ref, depth_ref = _reference_scene(f"random_{seed}_v{variety}")
+        assert ps == ps_ref and (spp, depth) == (spp_ref, depth_ref), f"random scene {seed}: not the scene the reference rendered"
         mine, _ = oracle.render(ps, (w, h), spp, depth, sampler=sampler)
+        assert_bit_equal(mine, ref, f"random scene {seed}")
+        if not os.access(exe, os.X_OK):
+            continue
         with tempfile.TemporaryDirectory() as tmp:
             sp, fp = os.path.join(tmp, "s.pscene"), os.path.join(tmp, "s.film")
             open(sp, "w").write(ps)
             subprocess.run([exe, "render", sp, str(spp), str(depth), fp] + (["sobol"] if sampler == "sobol" else []),
                            check=True, capture_output=True, timeout=120)
-            ref = np.fromfile(fp, dtype=np.float32).reshape(h, w, 4)
-        assert_bit_equal(mine, ref, f"random scene {seed}")
+            live = np.fromfile(fp, dtype=np.float32).reshape(h, w, 4)
+        assert_bit_equal(live, ref, f"random scene {seed}: the reference binary vs its stored film")
 
 
 @pytest.mark.parametrize("name", EMBREE_FILM_NAMES)

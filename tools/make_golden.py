@@ -6,6 +6,7 @@ and the reference's outputs, no reference source) are committed and travel to th
     python tools/make_golden.py            # everything except the two 640x640 statistics
     python tools/make_golden.py --full     # also C1/C2 whole-image statistics (~1 min of CPU)
     python tools/make_golden.py --bvh --vertices   # the reference's BVH + traversal orders, per-vertex path terms
+    python tools/make_golden.py --live     # the reference's films of the oracle tests' cbox and seeded random scenes
 """
 import hashlib
 import json
@@ -285,8 +286,29 @@ def gltf_fixture(tmp):
     json.dump(out, open(os.path.join(OUT, "gltf_import.json"), "w"), indent=1)
 
 
+# the scenes tests/test_oracle_golden.py renders with the restatement and compares with the reference's films, bit for bit
+LIVE_SCENES = [("cbox_readme_40x24_s32_d6", lambda: (scenes.cbox((40, 24), "readme"), 32, 6, None))] + \
+    [(f"random_{k}_v{v}", lambda k=k, v=v: scenes.random_scene(k, variety=v)) for k, v in [(k, 1) for k in range(2000, 2012)] + [(k, 2) for k in range(2100, 2106)]]
+
+
+def live_fixture(tmp):
+    """tests/golden/oracle_scenes.npz: the reference's films of LIVE_SCENES, with the scene descriptions they were rendered from."""
+    out = {}
+    for name, make in LIVE_SCENES:
+        sc, spp, depth, sampler = make()
+        ps, film, _ = ref_film(sc, spp, depth, tmp, "sobol" if sampler == "sobol" else None)
+        out[f"{name}_pscene"], out[f"{name}_film"] = np.array(ps), film
+        out[f"{name}_spp_depth"] = np.array([spp, depth])
+        print(name, film.shape, hashlib.md5(film.tobytes()).hexdigest())
+    np.savez_compressed(os.path.join(OUT, "oracle_scenes.npz"), **out)
+
+
 def main():
     full = "--full" in sys.argv
+    if "--live" in sys.argv:
+        with tempfile.TemporaryDirectory() as tmp:
+            live_fixture(tmp)
+        return
     if "--gltf" in sys.argv:
         with tempfile.TemporaryDirectory() as tmp:
             gltf_fixture(tmp)

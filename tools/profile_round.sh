@@ -33,6 +33,6 @@ done
 tools/pmc.sh ${tag}_c5pre c5 precompiled $counters > /dev/null 2>&1
 cp gpurun_out/pmc_${tag}_c5pre_summary.txt $out/${tag}_c5_precompiled_pmc_summary.txt
 cp $counters profiles/${tag}_counters.json   # so that the bench line below carries this round's counters
-python3 bench.py --steps 10 --warmup 2 --detail $out/${tag}_bench_detail.json > $out/${tag}_bench.json 2> $out/${tag}_bench.err
+python3 bench.py --full --steps 10 --warmup 2 --detail $out/${tag}_bench_detail.json > $out/${tag}_bench.json 2> $out/${tag}_bench.err
 tail -1 $out/${tag}_bench.json | cut -c1-600
 cut -c1-160 $out/${tag}_kernel_stats.csv
