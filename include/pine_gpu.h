@@ -405,6 +405,45 @@ int pine_gpu_test_powlog(int device, const float* x_host, const float* y_host, i
                          float* log_out);                                           /* powf(x, y), logf(x) */
 int pine_gpu_test_atan(int device, const float* y_host, const float* x_host, int64_t n, float* atan2_out,
                        float* acos_out);                                            /* atan2f(y, x), acosf(x) */
+/* Scalar math of pine_math.h / pine_libm.h over bit patterns, for the sweeps of tests/test_device_math.py.  fn names the
+ * function f(a[, b[, c]]) and the reference it must equal bit for bit:
+ *   SQRT psqrt(a) / RCP prcp(a) / DIV a / b      host IEEE sqrtf, 1.0f / a, a / b (correctly rounded)
+ *   SIN COS LOG ACOS psin pcos plog pacos (a)     glibc sinf cosf logf acosf
+ *   SINCOS psincos(a): two results (sin, cos)     glibc sinf, cosf
+ *   ATAN2 patan2(a, b) / POW ppow(a, b)           glibc atan2f, powf
+ *   MIN pmin(a, b) / MAX pmax(a, b) / CLAMP pclamp(a, b, c)   the same comparison expressions on the host
+ * Comparison: bits equal, +0 != -0; two NaNs are equal (a payload or sign difference is counted in nan_payload_only);
+ * NaN against a number is a mismatch.  stats[4] = checked results, mismatches, nan_payload_only, largest ulp distance of a
+ * mismatch between two non-NaN results (-0 and +0 are 1 apart).  examples[cap][5] = a, b, c, got, want of the first cap
+ * mismatches in input order (SINCOS: b = 0 for the sine result, 1 for the cosine one).  Host threads: at most
+ * min(16, $OMP_NUM_THREADS, hardware threads).  All return 0, < 0 on error. */
+enum {
+  PINE_GPU_MATH_SQRT = 0,
+  PINE_GPU_MATH_RCP = 1,
+  PINE_GPU_MATH_SIN = 2,
+  PINE_GPU_MATH_COS = 3,
+  PINE_GPU_MATH_SINCOS = 4,
+  PINE_GPU_MATH_LOG = 5,
+  PINE_GPU_MATH_ACOS = 6,
+  PINE_GPU_MATH_ATAN2 = 7,
+  PINE_GPU_MATH_POW = 8,
+  PINE_GPU_MATH_DIV = 9,
+  PINE_GPU_MATH_MIN = 10,
+  PINE_GPU_MATH_MAX = 11,
+  PINE_GPU_MATH_CLAMP = 12,
+  PINE_GPU_MATH_COUNT = 13
+};
+/* got[i] = fn(a[i], b[i], c[i]) (SINCOS: got[2i], got[2i+1]) by the device build on HIP device `device`, or by the host
+ * build of the same functions for device = -1.  b and c may be NULL when fn does not read them. */
+int pine_gpu_test_math_eval(int device, int fn, const uint32_t* a, const uint32_t* b, const uint32_t* c, int64_t n,
+                            uint32_t* got);
+/* Host only: compares got (layout of pine_gpu_test_math_eval) with the reference. */
+int pine_gpu_test_math_compare(int fn, const uint32_t* a, const uint32_t* b, const uint32_t* c, const uint32_t* got,
+                               int64_t n, int64_t* stats, uint32_t* examples, int cap);
+/* Evaluates and compares in chunks of 2^26: argument `swept_arg` (0 = a, 1 = b, 2 = c) runs over first + k * stride
+ * (mod 2^32) for k < count, every other argument is fixed_bits; the inputs are generated where fn is evaluated. */
+int pine_gpu_test_math_sweep(int device, int fn, uint32_t fixed_bits, int swept_arg, uint32_t first, uint64_t count,
+                             uint32_t stride, int64_t* stats, uint32_t* examples, int cap);
 /* BVH traversal (bvh.cpp:321-451, 497-548) of the scene's accel for each ray (8 floats: o, d, tmin, tmax), by the nested
  * loops of the scene-in-LDS kernel variants (flat = 0) or the flat state machine of the others (flat = 1).  Per ray
  * 2 * cap + 5 words: [count, count test words ...] (cap words), hit, geometry, triangle, tmax bits of the closest-hit query,

@@ -172,6 +172,11 @@ SIGNATURES = {
     "pine_gpu_test_sincos": (C.c_int, [C.c_int, c_f_p, C.c_int64, c_f_p, c_f_p]),
     "pine_gpu_test_powlog": (C.c_int, [C.c_int, c_f_p, c_f_p, C.c_int64, c_f_p, c_f_p]),
     "pine_gpu_test_atan": (C.c_int, [C.c_int, c_f_p, c_f_p, C.c_int64, c_f_p, c_f_p]),
+    "pine_gpu_test_math_eval": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_int64, C.POINTER(C.c_uint32)]),
+    "pine_gpu_test_math_compare": (C.c_int, [C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_int64,
+                                             C.POINTER(C.c_int64), C.POINTER(C.c_uint32), C.c_int]),
+    "pine_gpu_test_math_sweep": (C.c_int, [C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_uint32, C.c_uint64, C.c_uint32,
+                                           C.POINTER(C.c_int64), C.POINTER(C.c_uint32), C.c_int]),
     "pine_gpu_test_embree_tree": (C.c_int, [c_f_p, C.c_int, C.POINTER(C.c_int), C.c_int]),
     "pine_gpu_test_traverse": (C.c_int, [C.c_void_p, C.c_int, c_f_p, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_uint32)]),
     "pine_gpu_scene_accel_bvhs": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int64]),

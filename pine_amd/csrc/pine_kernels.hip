@@ -34,6 +34,8 @@
 #include <string>
 #include <type_traits>
 #include <algorithm>
+#include <array>
+#include <utility>
 #include <vector>
 
 #include <dlfcn.h>
@@ -46,6 +48,7 @@
 #include "pine_specialize.h"
 #include "pine_variants.h"
 #include "pine_host.h"
+#include "pine_math_check.h"
 
 struct pine_gpu_scene;
 namespace pine_gpu {
@@ -235,6 +238,27 @@ __global__ void test_atan_kernel(const float* y, const float* x, long long n, fl
     at2[i] = patan2(y[i], x[i]);
     ac[i] = pacos(x[i]);
   }
+}
+// pine_gpu_test_math_*: the scalar functions of pine_math.h on bit patterns (pine_math_check.h has math_eval<FN>).
+// inputs from arrays (a != NULL; b, c as the arity needs) or generated: argument `swept` = first + i * stride, the others
+// `fixed`.  out: n * math_width(FN) words.
+template <int FN>
+__global__ void test_math_kernel(const uint32_t* a, const uint32_t* b, const uint32_t* c, uint32_t fixed, int swept,
+                                 uint32_t first, uint32_t stride, long long n, uint32_t* out) {
+  const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t ua, ub = fixed, uc = fixed;
+  if (a) {
+    ua = a[i];
+    if (math_arity(FN) > 1) ub = b[i];
+    if (math_arity(FN) > 2) uc = c[i];
+  } else {
+    const uint32_t v = first + uint32_t(i) * stride;
+    ua = swept == 0 ? v : fixed;
+    ub = swept == 1 ? v : fixed;
+    uc = swept == 2 ? v : fixed;
+  }
+  math_eval<FN>(ua, ub, uc, out + i * math_width(FN));
 }
 __constant__ int kTestPixels[6][2] = {{0, 0}, {1, 0}, {3, 5}, {127, 127}, {128, 5}, {639, 639}};
 __global__ void test_sampler_kernel(DTables T, int spp, float* out) {
@@ -2350,6 +2374,92 @@ int pine_gpu_test_atan(int device, const float* y, const float* x, int64_t n, fl
   hipFree(dc);
   return 0;
 }
+
+// ---- pine_gpu_test_math_*: the scalar functions over bit patterns against their references (pine_math_check.h) -----
+extern "C++" {
+namespace {
+template <int FN>
+void math_launch(const uint32_t* a, const uint32_t* b, const uint32_t* c, uint32_t fixed, int swept, uint32_t first,
+                 uint32_t stride, long long n, uint32_t* out) {
+  hipLaunchKernelGGL(test_math_kernel<FN>, dim3(unsigned((n + 255) / 256)), dim3(256), 0, 0, a, b, c, fixed, swept, first,
+                     stride, n, out);
+}
+using MathLaunch = void (*)(const uint32_t*, const uint32_t*, const uint32_t*, uint32_t, int, uint32_t, uint32_t, long long,
+                            uint32_t*);
+template <int... FN>
+constexpr std::array<MathLaunch, sizeof...(FN)> math_launch_table(std::integer_sequence<int, FN...>) {
+  return {math_launch<FN>...};
+}
+constexpr std::array<MathLaunch, PINE_GPU_MATH_COUNT> kMathLaunch =
+    math_launch_table(std::make_integer_sequence<int, PINE_GPU_MATH_COUNT>());
+}  // namespace
+}  // extern "C++"
+
+int pine_gpu_test_math_eval(int device, int fn, const uint32_t* a, const uint32_t* b, const uint32_t* c, int64_t n, uint32_t* got) {
+  if (device < 0) return math_check::eval_host_arrays(fn, a, b, c, n, got);
+  if (math_check::bad_args(fn, n, a, b, c)) return -1;
+  if (!got) {
+    set_error("bad argument");
+    return -1;
+  }
+  if (need_device(device)) return -1;
+  const int w = math_width(fn), ar = math_arity(fn);
+  const int64_t m = std::max<int64_t>(1, std::min(n, math_check::kChunk));
+  uint32_t* d[4] = {nullptr, nullptr, nullptr, nullptr};
+  int rc = 0;
+  for (int k = 0; k < 4 && !rc; k++)
+    if ((k < ar || k == 3) && hipMalloc((void**)&d[k], m * 4 * (k == 3 ? w : 1)) != hipSuccess) rc = -1;
+  const uint32_t* src[3] = {a, b, c};
+  for (int64_t i0 = 0; i0 < n && !rc; i0 += m) {
+    const int64_t len = std::min(m, n - i0);
+    for (int k = 0; k < ar && !rc; k++)
+      if (hipMemcpy(d[k], src[k] + i0, len * 4, hipMemcpyHostToDevice) != hipSuccess) rc = -1;
+    if (rc) break;
+    kMathLaunch[size_t(fn)](d[0], d[1], d[2], 0u, 0, 0u, 0u, (long long)len, d[3]);
+    if (hipGetLastError() != hipSuccess || hipMemcpy(got + i0 * w, d[3], len * 4 * w, hipMemcpyDeviceToHost) != hipSuccess) rc = -1;
+  }
+  for (int k = 0; k < 4; k++)
+    if (d[k]) hipFree(d[k]);
+  if (rc) {
+    set_error(std::string("pine_gpu_test_math_eval: ") + hipGetErrorString(hipGetLastError()));
+    return -1;
+  }
+  return 0;
+}
+
+int pine_gpu_test_math_compare(int fn, const uint32_t* a, const uint32_t* b, const uint32_t* c, const uint32_t* got, int64_t n,
+                               int64_t* stats, uint32_t* examples, int cap) {
+  return math_check::compare(fn, a, b, c, got, n, stats, examples, cap);
+}
+
+int pine_gpu_test_math_sweep(int device, int fn, uint32_t fixed_bits, int swept_arg, uint32_t first, uint64_t count, uint32_t stride,
+                             int64_t* stats, uint32_t* examples, int cap) {
+  if (device < 0) return math_check::sweep_host(fn, fixed_bits, swept_arg, first, count, stride, stats, examples, cap);
+  if (math_check::bad_sweep_args(fn, swept_arg, count, stats, examples, cap) || need_device(device)) return -1;
+  const int w = math_width(fn);
+  const int64_t m = std::max<int64_t>(1, std::min<int64_t>(int64_t(count), math_check::kChunk));
+  uint32_t* h = nullptr;  // one chunk's results, pinned for the copies
+  uint32_t* d = nullptr;
+  HIP_OK(hipHostMalloc((void**)&h, m * w * 4, hipHostMallocDefault));
+  if (hipMalloc((void**)&d, m * w * 4) != hipSuccess) {
+    hipHostFree(h);
+    set_error("pine_gpu_test_math_sweep: out of device memory");
+    return -1;
+  }
+  const math_check::ChunkEval on_device = [&](uint32_t start, int64_t len, uint32_t* out) {
+    kMathLaunch[size_t(fn)](nullptr, nullptr, nullptr, fixed_bits, swept_arg, start, stride, (long long)len, d);
+    if (hipGetLastError() != hipSuccess || hipMemcpy(out, d, len * w * 4, hipMemcpyDeviceToHost) != hipSuccess) {
+      set_error(std::string("pine_gpu_test_math_sweep: ") + hipGetErrorString(hipGetLastError()));
+      return -1;
+    }
+    return 0;
+  };
+  const int rc = math_check::sweep(fn, fixed_bits, swept_arg, first, count, stride, on_device, h, stats, examples, cap);
+  hipFree(d);
+  hipHostFree(h);
+  return rc;
+}
+
 int pine_gpu_test_sampler(int device, int spp_req, float* out, int64_t capacity) {
   if (need_device(device)) return -1;
   TableBlob tables_blob;

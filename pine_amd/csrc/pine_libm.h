@@ -11,11 +11,14 @@
 //
 // The algorithm and coefficients are glibc's published ones (sysdeps/ieee754/flt-32/s_sincosf.h,
 // s_sincosf_data.c; LGPL/MIT "ARM optimized routines" sinf.c); restated here, not copied from the
-// reference repo (the reference contains no libm).  Verified exhaustively against the container's
-// libm for |x| < 120 by tests/test_libm.py (host build of this same header).
+// reference repo (the reference contains no libm).  Verified against the host libm on every float
+// (finite, +-inf, NaN) by tools/check_libm.cpp (host build of this same header, subsampled in
+// tests/test_libm.py) and, for the device build, by tests/test_device_math.py.
 //
-// Domain: |x| < 120 handled exactly like glibc's fast path; larger |x| (never produced by the
-// samplers: arguments are in [-pi/4, 2*pi]) fall back to a double-precision fmod reduction.
+// Domain: every float.  |x| < 120 takes glibc's fast path (reduce_fast); larger finite |x| (never
+// produced by the samplers: their arguments are in [-pi/4, 2*pi]) take glibc's large-argument path
+// (reduce_large: exact integer product with 192 bits of 4/pi) in a cold branch; +-inf and NaN give
+// NaN as glibc's __math_invalidf does.
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -79,13 +82,45 @@ PINE_HD double reduce_fast(double x, int* np) {
   return __builtin_fma(-(double)n, hpi, x);
 }
 
-PINE_HD double reduce_slow(double x, int* np) {
-  // not on any sampler path (|x| >= 120); plain double reduction, within 1 ulp of libm
-  const double hpi = 0x1.921FB54442D18p0;
-  double q = x / hpi;
-  double nq = q < 0 ? (double)(long long)(q - 0.5) : (double)(long long)(q + 0.5);
-  *np = (int)((long long)nq & 3);
-  return x - nq * hpi;
+// reduce_large (glibc s_sincosf.h): |x| >= 2 given as its bits (the sign is ignored).  A 32 x 96 -> 128 bit integer
+// product with 4/pi, taken from a 192-bit table that adds 8 new bits per entry (so that any 96-bit window starts on an
+// entry), gives the exact 2.62 fixed-point remainder; n = its integer part rounded, the quadrant; returns the remainder
+// (in [-pi/4, pi/4]) in binary64, accurate to 33 bits.  Only n & 3 of the quadrant is meaningful.
+PINE_HD uint32_t inv_pio4_tab(unsigned i) {
+  static constexpr uint32_t T[24] = {
+      0xa2u,       0xa2f9u,     0xa2f983u,   0xa2f9836eu, 0xf9836e4eu, 0x836e4e44u, 0x6e4e4415u, 0x4e441529u,
+      0x441529fcu, 0x1529fc27u, 0x29fc2757u, 0xfc2757d1u, 0x2757d1f5u, 0x57d1f534u, 0xd1f534ddu, 0xf534ddc0u,
+      0x34ddc0dbu, 0xddc0db62u, 0xc0db6295u, 0xdb629599u, 0x6295993cu, 0x95993c43u, 0x993c4390u, 0x3c439041u,
+  };
+  return T[i];  // i <= 15 + 8
+}
+PINE_HD double reduce_large(uint32_t xi, int* np) {
+  const unsigned base = (xi >> 26) & 15;
+  const int shift = (xi >> 23) & 7;
+  xi = (xi & 0xffffffu) | 0x800000u;
+  xi <<= shift;
+  uint64_t res0 = uint32_t(xi * inv_pio4_tab(base));  // (low 32 bits only: they land in the top word)
+  const uint64_t res1 = uint64_t(xi) * inv_pio4_tab(base + 4);
+  const uint64_t res2 = uint64_t(xi) * inv_pio4_tab(base + 8);
+  res0 = (res2 >> 32) | (res0 << 32);
+  res0 += res1;
+  const uint64_t n = (res0 + (1ull << 61)) >> 62;
+  res0 -= n << 62;
+  *np = int(n);
+  return double(int64_t(res0)) * 0x1.921FB54442D18p-62;  // (2.62 fixed point in quadrants) * pi/2 / 2^62
+}
+
+// sinf/cosf for |y| >= 120 (finite): glibc's large-argument branch.  The reduction works on |y|; the original sign enters
+// through the quadrant used for the signs (n + sign), the polynomial parity stays n.  Behind __builtin_expect in the
+// callers: no sampler reaches it.
+PINE_HD float sinf_large(float y, bool cosine) {
+  const uint32_t xi = asuint(y);
+  int n;
+  const double x = reduce_large(xi, &n);
+  const int ns = n + int(xi >> 31);
+  const double sign = (ns & 3) == 1 || (ns & 3) == 2 ? -1.0 : 1.0;
+  const double csign = (ns & 2) ? -1.0 : 1.0;
+  return sin_poly(x * sign, x * x, cosine ? n ^ 1 : n, csign);
 }
 
 PINE_HD float sinf_glibc(float y) {
@@ -96,12 +131,12 @@ PINE_HD float sinf_glibc(float y) {
     if (abstop12(y) < abstop12(0x1p-12f)) return y;
     return sin_poly(x, s, 0, 1.0);
   }
-  if (abstop12(y) < abstop12(120.0f))
+  if (__builtin_expect(abstop12(y) < abstop12(120.0f), 1))
     x = reduce_fast(x, &n);
   else if (abstop12(y) < abstop12(__builtin_inff()))
-    x = reduce_slow(x, &n);
+    return sinf_large(y, false);
   else
-    return y - y;  // inf/nan -> nan
+    return (y - y) / (y - y);  // inf/nan -> nan (__math_invalidf)
   const double sign = (n & 3) == 1 || (n & 3) == 2 ? -1.0 : 1.0;  // {1,-1,-1,1}[n&3]
   const double csign = (n & 2) ? -1.0 : 1.0;
   return sin_poly(x * sign, x * x, n, csign);
@@ -115,12 +150,12 @@ PINE_HD float cosf_glibc(float y) {
     if (abstop12(y) < abstop12(0x1p-12f)) return 1.0f;
     return sin_poly(x, x2, 1, 1.0);
   }
-  if (abstop12(y) < abstop12(120.0f))
+  if (__builtin_expect(abstop12(y) < abstop12(120.0f), 1))
     x = reduce_fast(x, &n);
   else if (abstop12(y) < abstop12(__builtin_inff()))
-    x = reduce_slow(x, &n);
+    return sinf_large(y, true);
   else
-    return y - y;
+    return (y - y) / (y - y);  // inf/nan -> nan (__math_invalidf)
   const double sign = (n & 3) == 1 || (n & 3) == 2 ? -1.0 : 1.0;
   const double csign = (n & 2) ? -1.0 : 1.0;
   return sin_poly(x * sign, x * x, n ^ 1, csign);
@@ -185,8 +220,9 @@ PINE_HD void sincosf_glibc(float y, float& sn, float& cs) {
 // Algorithm restated; the numeric tables are the published ones (sysdeps/ieee754/flt-32/e_powf_log2_data.c,
 // e_logf_data.c, e_exp2f_data.c), checked against the copy inside the container's libm.so.6.  As for
 // sinf/cosf, every a*b+c is a fused multiply-add because x86-64 glibc runs its -mfma build.
-// tools/check_libm.cpp: 0 mismatches against the container's libm over every float x in [0, 1] with
-// y = 5 (Schlick), 2^31 positive floats for logf and 10^9 random (x, y) pairs.
+// tools/check_libm_pow.cpp: 0 mismatches against the container's libm over every float x in [0, 1] with
+// y = 5 (Schlick), 2^31 positive floats for logf and 10^9 random (x, y) pairs; tests/test_device_math.py: the device
+// build over every x at y = 5, every argument of logf, and strided sweeps of either argument at special values.
 // The tables are constant arrays read with one (lane-indexed) load per lookup.  They were switch statements of immediates
 // until round 3: the compiler hoisted every 64-bit immediate of the select chains out of the kernel's persistent loop --
 // a hundred VGPRs of loop-invariant constants, ALL of the stage-queued kernel's register spills (98 of 108 spilled VGPRs
@@ -306,6 +342,7 @@ PINE_HD int powf_checkint(uint32_t iy) {  // 0: not an integer, 1: odd, 2: even
   if (iy & (1u << (0x7f + 23 - e))) return 1;
   return 2;
 }
+PINE_HD bool powf_signaling(uint32_t ix) { return 2 * (ix ^ 0x00400000u) > 2u * 0x7fc00000u; }  // issignalingf_inline
 PINE_HD bool powf_zeroinfnan(uint32_t ix) { return 2 * ix - 1 >= 2u * 0x7f800000u - 1; }
 PINE_HD float powf_glibc(float x, float y) {
   uint32_t sign_bias = 0;
@@ -314,8 +351,8 @@ PINE_HD float powf_glibc(float x, float y) {
   if (ix - 0x00800000u >= 0x7f800000u - 0x00800000u || powf_zeroinfnan(iy)) {
     // x < 0x1p-126 or inf or nan, or y is 0 or inf or nan
     if (powf_zeroinfnan(iy)) {
-      if (2 * iy == 0) return 1.0f;
-      if (ix == 0x3f800000u) return 1.0f;
+      if (2 * iy == 0) return powf_signaling(ix) ? x + y : 1.0f;  // pow(x, +-0) = 1 except for a signalling NaN x
+      if (ix == 0x3f800000u) return powf_signaling(iy) ? x + y : 1.0f;
       if (2 * ix > 2u * 0x7f800000u || 2 * iy > 2u * 0x7f800000u) return x + y;
       if (2 * ix == 2 * 0x3f800000u) return 1.0f;
       if ((2 * ix < 2 * 0x3f800000u) == !(iy & 0x80000000u)) return 0.0f;  // |x|<1 && y==inf or |x|>1 && y==-inf

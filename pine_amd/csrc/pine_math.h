@@ -25,11 +25,13 @@ PINE_HD float pabs(float v) { return fabsf(v); }
 // Correctly rounded sqrt / reciprocal, short forms.  hipcc's IEEE expansions cost 16 (sqrtf) and 11
 // (1.0f/x) VALU instructions because they also cover operands near the exponent limits.  For
 // ordinary operands a shorter sequence returns the SAME correctly rounded result; that is not an
-// argument but a measurement: tools/rcp_test.hip compares them with the expansions over all 2^32 bit
-// patterns on gfx950 and finds zero mismatches for biased exponents in [26, 230] (sqrt: v_rsq_f32,
-// s = x*y, h = y/2, one residual step) and [2, 252] (reciprocal: v_rcp_f32 + one Newton step).  The
-// guards below are strictly inside those ranges; anything else (zero, denormal, huge, inf, NaN)
-// redoes the operation with the full expansion in a rarely taken branch.
+// argument but a measurement: tools/rcp_test.hip compared candidate sequences with the expansions over
+// all 2^32 bit patterns on gfx950 and found zero mismatches for biased exponents in [26, 230] (sqrt:
+// v_rsq_f32, s = x*y, h = y/2, one residual step) and [2, 252] (reciprocal: v_rcp_f32 + one Newton
+// step).  The guards below are strictly inside those ranges; anything else (zero, denormal, huge, inf,
+// NaN) redoes the operation with the full expansion in a rarely taken branch.  What ships -- these
+// functions with their guards, compiled with the path kernels' flags -- is compared with the host's
+// correctly rounded sqrtf and 1.0f / x on all 2^32 arguments by tests/test_device_math.py.
 // (-DPINE_NO_SHORT_FORMS: plain expansions everywhere, for A/B runs.)
 // PINE_FAST_MATH (pine_kernels_fast.hip only -- the declared-tolerance variants behind PINE_GPU_FLAG_FAST): the hardware's
 // 1-ulp v_sqrt_f32 / v_rcp_f32 without refinement or range guards, the device's native sin / cos / pow / log instead of

@@ -1,7 +1,8 @@
 """CPU: the AddressSanitizer + UndefinedBehaviorSanitizer leg.  tools/sanitize builds the host code
 that handles caller-supplied data -- pine_amd/csrc/pine_host.cpp (scene building, BVH build, node folding, film
 finalize), pine_amd/host/prl.cpp (the parser / interpreter of untrusted script text) with pine_amd/host/gltf_import.hpp
-(the reader of untrusted binary glTF files) -- and the oracle with -fsanitize=address,undefined, and runs CPU tests, a
+(the reader of untrusted binary glTF files), the host halves of the scalar-math test hooks (pine_math_check.h) -- and the
+oracle with -fsanitize=address,undefined, and runs CPU tests, a
 mutation fuzzer of the PRL front-end and one of the glTF importer against those libraries.  A sanitizer report aborts the child process, so a zero exit status means there was none.
 (GPU AddressSanitizer is not available on this pool: the device entry points of the sanitizer build fail as on a
 host without a GPU, tools/sanitize/nogpu_entry_points.cpp.)"""
@@ -19,7 +20,8 @@ def test_host_code_is_clean_under_asan_and_ubsan():
     if not shutil.which("g++") or not os.path.exists(subprocess.run(["gcc", "-print-file-name=libasan.so"], capture_output=True, text=True).stdout.strip()):
         pytest.skip("no g++ / libasan here")
     env = dict(os.environ, PINE_FUZZ_MUTANTS="120")
-    r = subprocess.run([os.path.join(ROOT, "tools", "sanitize", "run.sh"), "tests/test_prl.py", "tests/test_abi.py", "-m", "not gpu",
+    r = subprocess.run([os.path.join(ROOT, "tools", "sanitize", "run.sh"), "tests/test_prl.py", "tests/test_abi.py",
+                        "tests/test_device_math.py", "-m", "not gpu",
                         "-k", "not bench and not product_does_not"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     tail = (r.stdout + r.stderr)[-3000:]

@@ -1,17 +1,29 @@
-// tools/check_libm.cpp -- exhaustive host check of pine_amd/csrc/pine_libm.h against the
-// container's libm (the one the reference links).  Usage: check_libm [stride]   (stride 1 = all floats with |x|<120)
+// tools/check_libm.cpp -- exhaustive host check of pine_amd/csrc/pine_libm.h's sinf / cosf / sincosf against the
+// host libm (the one the reference links): every float -- finite, +-inf and NaN, both signs; NaN results compared bit
+// for bit too.  Usage: check_libm [stride]   (stride 1 = all 2^32 bit patterns)
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <thread>
 #include <vector>
 #include <atomic>
 #include "../pine_amd/csrc/pine_libm.h"
 
+// host threads: at most min(16, $OMP_NUM_THREADS, hardware threads) -- a command's share of a shared machine, not its size
+static unsigned threads() {
+  unsigned n = std::thread::hardware_concurrency();
+  if (n == 0) n = 1;
+  if (n > 16) n = 16;
+  if (const char* e = getenv("OMP_NUM_THREADS"))
+    if (atoi(e) > 0 && unsigned(atoi(e)) < n) n = unsigned(atoi(e));
+  return n;
+}
+
 int main(int argc, char** argv) {
   uint32_t stride = argc > 1 ? (uint32_t)atoi(argv[1]) : 1;
-  const uint32_t hi = 0x42F00000u;  // 120.0f
-  unsigned nt = std::thread::hardware_concurrency();
+  const uint64_t hi = 0x80000000ull;  // magnitudes 0 .. NaN 0x7fffffff, with both signs below
+  unsigned nt = threads();
   std::atomic<uint64_t> bad_sin{0}, bad_cos{0}, total{0};
   std::vector<std::thread> th;
   for (unsigned t = 0; t < nt; t++)

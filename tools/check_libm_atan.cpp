@@ -11,13 +11,23 @@
 #include <vector>
 #include "../pine_amd/csrc/pine_libm.h"
 
+// host threads: at most min(16, $OMP_NUM_THREADS, hardware threads) -- a command's share of a shared machine, not its size
+static unsigned threads() {
+  unsigned n = std::thread::hardware_concurrency();
+  if (n == 0) n = 1;
+  if (n > 16) n = 16;
+  if (const char* e = getenv("OMP_NUM_THREADS"))
+    if (atoi(e) > 0 && unsigned(atoi(e)) < n) n = unsigned(atoi(e));
+  return n;
+}
+
 static bool same(float a, float b) {
   if (a != a && b != b) return true;  // (any NaN: payloads are not compared)
   return memcmp(&a, &b, 4) == 0;
 }
 int main(int argc, char** argv) {
   const unsigned long long per_thread = argc > 1 ? strtoull(argv[1], nullptr, 10) : 500000000ull;
-  const unsigned nt = std::thread::hardware_concurrency();
+  const unsigned nt = threads();
   std::atomic<unsigned long long> bad_atan{0}, bad_acos{0}, bad_atan2{0}, n1{0}, n2{0};
   std::vector<std::thread> th;
   for (unsigned t = 0; t < nt; t++)

@@ -9,13 +9,23 @@
 #include <vector>
 #include "../pine_amd/csrc/pine_libm.h"
 
+// host threads: at most min(16, $OMP_NUM_THREADS, hardware threads) -- a command's share of a shared machine, not its size
+static unsigned threads() {
+  unsigned n = std::thread::hardware_concurrency();
+  if (n == 0) n = 1;
+  if (n > 16) n = 16;
+  if (const char* e = getenv("OMP_NUM_THREADS"))
+    if (atoi(e) > 0 && unsigned(atoi(e)) < n) n = unsigned(atoi(e));
+  return n;
+}
+
 static uint64_t mix(uint64_t x) { x ^= x >> 33; x *= 0xff51afd7ed558ccdULL; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ULL; x ^= x >> 33; return x; }
 static float f32(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
 static bool same(float a, float b) { return !memcmp(&a, &b, 4) || (a != a && b != b); }
 
 int main(int argc, char** argv) {
   const uint64_t pairs = argc > 1 ? strtoull(argv[1], nullptr, 10) : 1000000000ull;
-  unsigned nt = std::thread::hardware_concurrency();
+  unsigned nt = threads();
   std::atomic<uint64_t> bad_schlick{0}, bad_log{0}, bad_pairs{0}, bad_special{0};
   std::vector<std::thread> th;
   for (unsigned t = 0; t < nt; t++)

@@ -11,6 +11,7 @@
 
 #include "../../include/pine_gpu.h"
 #include "../../pine_amd/csrc/pine_host.h"
+#include "../../pine_amd/csrc/pine_math_check.h"
 
 #include "../../pine_amd/csrc/pine_specialize.h"
 #include "../../pine_amd/csrc/pine_embree_order.h"
@@ -69,6 +70,19 @@ int pine_gpu_test_sincos(int, const float*, int64_t, float*, float*) { return fa
 int pine_gpu_test_powlog(int, const float*, const float*, int64_t, float*, float*) { return fail(); }
 int pine_gpu_test_atan(int, const float*, const float*, int64_t, float*, float*) { return fail(); }
 int pine_gpu_test_traverse(pine_gpu_scene*, int, const float*, int64_t, int, int, uint32_t*) { return fail(); }
+// (the host halves are the real thing, pine_math_check.h: the comparison, the references, the host build of the functions)
+int pine_gpu_test_math_eval(int device, int fn, const uint32_t* a, const uint32_t* b, const uint32_t* c, int64_t n, uint32_t* got) {
+  return device < 0 ? pine_gpu::math_check::eval_host_arrays(fn, a, b, c, n, got) : fail();
+}
+int pine_gpu_test_math_compare(int fn, const uint32_t* a, const uint32_t* b, const uint32_t* c, const uint32_t* got, int64_t n,
+                               int64_t* stats, uint32_t* examples, int cap) {
+  return pine_gpu::math_check::compare(fn, a, b, c, got, n, stats, examples, cap);
+}
+int pine_gpu_test_math_sweep(int device, int fn, uint32_t fixed_bits, int swept_arg, uint32_t first, uint64_t count, uint32_t stride,
+                             int64_t* stats, uint32_t* examples, int cap) {
+  return device < 0 ? pine_gpu::math_check::sweep_host(fn, fixed_bits, swept_arg, first, count, stride, stats, examples, cap)
+                    : fail();
+}
 // (host code: the real thing, so that the sanitizers see the hierarchy builder -- same body as in pine_kernels.hip)
 int pine_gpu_test_embree_tree(const float* boxes, int n, int* words, int cap) {
   if (!boxes || !words || n < 0) return fail();
