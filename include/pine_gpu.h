@@ -237,7 +237,7 @@ typedef struct {
                                     message.  Never the default, never the parity gate. */
 #define PINE_GPU_FLAG_DEVICE_BVH 8 /* build the BVH on the GPU (the same level-synchronous binned-SAH build as on the host, same tree, same
                                     primitive order: pine_amd/csrc/pine_bvh_build_device.h) when the plan is the first to need the scene's
-                                    accel; also $PINE_GPU_DEVICE_BVH=1.  pine_gpu_plan_stats.accel_built_on_device says what happened. */
+                                    accel.  pine_gpu_plan_stats.accel_built_on_device says what happened. */
 #define PINE_GPU_FLAG_DEBUG_FORCE_BAIL 0x100 /* test hook: the stage-queued path kernel raises its protocol-failure
                                     bail-out at once; every synchronising entry point must then FAIL (never return the film) */
 /* Scene-specialised kernels.  The path kernel can be compiled FOR THE SCENE: (1) with exactly the scene's

@@ -126,6 +126,28 @@ PINE_HD int build_lomuto(const unsigned char* pred, int* perm, int n) {
     }
   return tail;
 }
+// The formulation of the device build (pine_bvh_build_device.h: a prefix sum and pointer jumping) on the host, for the CPU
+// test of its equivalence with build_lomuto (serial loops standing for the
+// data-parallel ones).
+inline int build_lomuto_by_chains(const unsigned char* pred, int* perm, int n) {
+  std::vector<int> T(size_t(n) + 1, 0);
+  for (int i = 0; i < n; i++) T[size_t(i) + 1] = T[size_t(i)] + (pred[i] ? 1 : 0);
+  const int left = T[size_t(n)];
+  int f0 = n;
+  for (int i = n - 1; i >= 0; i--)
+    if (!pred[i]) f0 = i;
+  for (int i = 0; i < n; i++)
+    if (pred[i]) perm[T[size_t(i)]] = i;
+  const int K = n - f0, R = left - f0;
+  std::vector<int> src(size_t(K > 0 ? K : 0));
+  for (int k = 0; k < K; k++) src[size_t(k)] = pred[f0 + k] ? T[size_t(f0 + k)] - f0 : k;
+  int rounds = 1;
+  while ((1 << rounds) < K) rounds++;
+  for (int r = 0; r <= rounds; r++)
+    for (int k = 0; k < K; k++) src[size_t(k)] = src[size_t(src[size_t(k)])];
+  for (int q = 0; q < n - left; q++) perm[left + q] = f0 + src[size_t(R + q)];
+  return left;
+}
 
 // Host build of every BVH of a scene: `prims` holds the primitives of all BVHs back to back (meshes in geometry order,
 // the top level last), `roots` one task per BVH covering its range, in the order the BVHs' roots are to be numbered.

@@ -3,6 +3,8 @@
 #include "pine_host.h"
 #include "pine_specialize.h"
 #include "pine_bvh_build.h"
+#include "pine_embree_order.h"
+#include "pine_math_check.h"
 
 #include <algorithm>
 #include <cmath>
@@ -1446,6 +1448,71 @@ int pine_gpu_shard_of_pixel(int film_w, int x, int y, int world) {
   }
   const int tiles_x = (film_w + 7) / 8;
   return ((y / 8) * tiles_x + x / 8) % world;
+}
+
+int64_t pine_gpu_packed_slab_floats(int film_w, int film_h, int world) {
+  if (film_w <= 0 || film_h <= 0 || world < 1) return -1;
+  const int64_t tiles = int64_t((film_w + 7) / 8) * ((film_h + 7) / 8);
+  return (tiles + world - 1) / world * 64 * 4;
+}
+
+int pine_gpu_packed_offset(int film_w, int film_h, int world, int x, int y, int* rank_out, int64_t* float4_index_out) {
+  if (film_w <= 0 || film_h <= 0 || world < 1 || x < 0 || y < 0 || x >= film_w || y >= film_h) {
+    set_error("bad argument");
+    return -1;
+  }
+  const int tiles_x = (film_w + 7) / 8;
+  const int tile = (y / 8) * tiles_x + x / 8;
+  if (rank_out) *rank_out = tile % world;
+  if (float4_index_out) *float4_index_out = int64_t(tile / world) * 64 + (y % 8) * 8 + x % 8;
+  return 0;
+}
+
+/* Test hook (host only): the reference's Lomuto partition as a sequential swap loop (perm_seq) and as the prefix-sum +
+ * pointer-jumping formulation the device build uses (perm_par); returns the number of trues, < 0 if the two disagree. */
+int pine_gpu_test_lomuto(const unsigned char* pred, int n, int* perm_seq, int* perm_par) {
+  if (!pred || !perm_seq || !perm_par || n < 0) {
+    set_error("bad argument");
+    return -1;
+  }
+  for (int i = 0; i < n; i++) perm_seq[i] = i;
+  const int a = build_lomuto(pred, perm_seq, n);
+  const int b = build_lomuto_by_chains(pred, perm_par, n);
+  if (a != b || memcmp(perm_seq, perm_par, size_t(n) * sizeof(int)) != 0) {
+    set_error("the two partition formulations disagree");
+    return -2;
+  }
+  return a;
+}
+
+int pine_gpu_test_embree_tree(const float* boxes, int n, int* words, int cap) {
+  if (!boxes || !words || n < 0) {
+    set_error("bad argument");
+    return -1;
+  }
+  std::vector<float> bx(boxes, boxes + 6 * size_t(n));
+  std::vector<int> places(size_t(n), 0);
+  for (int i = 0; i < n; i++) places[size_t(i)] = i;
+  EmbreeOrderTree tree;
+  std::string why;
+  if (!tree.build(bx, places, why)) {
+    set_error(why);
+    return -1;
+  }
+  if (1 + 8 * int(tree.nodes.size()) > cap) {
+    set_error("capacity");
+    return -1;
+  }
+  int k = 0;
+  words[k++] = tree.root;
+  for (const EmbreeNode& nd : tree.nodes)
+    for (int i = 0; i < 8; i++) words[k++] = nd.child[i];
+  return k;
+}
+
+int pine_gpu_test_math_compare(int fn, const uint32_t* a, const uint32_t* b, const uint32_t* c, const uint32_t* got, int64_t n,
+                               int64_t* stats, uint32_t* examples, int cap) {
+  return math_check::compare(fn, a, b, c, got, n, stats, examples, cap);
 }
 
 int64_t pine_gpu_scene_describe(pine_gpu_scene* s, char* buf, int64_t capacity) {

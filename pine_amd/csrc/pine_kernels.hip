@@ -20,41 +20,12 @@
 // No MFMA (no dense contraction here); the kernel is VALU/latency bound on cbox-class scenes.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-#include <chrono>
+#include <climits>
 #include <cmath>
-#include <cstdio>
 #include <cstring>
-#include <map>
-#include <memory>
 #include <deque>
-#include <map>
-#include <memory>
-#include <mutex>
-#include <string>
-#include <type_traits>
-#include <algorithm>
-#include <array>
-#include <utility>
-#include <vector>
 
-#include <dlfcn.h>
-#include <signal.h>
-#include <sys/stat.h>
-#include <thread>
-
-#include "../../include/pine_gpu.h"
-#include "pine_device.h"
-#include "pine_specialize.h"
-#include "pine_variants.h"
-#include "pine_host.h"
-#include "pine_math_check.h"
-
-struct pine_gpu_scene;
-namespace pine_gpu {
-SceneHost& scene_host(pine_gpu_scene* s);
-}  // namespace pine_gpu
-#include "pine_kernels_device.h"
+#include "pine_plan.h"
 #include "pine_bvh_build_device.h"
 #include "pine_embree_order.h"
 #include "../data/rcpps_table.h"
@@ -210,364 +181,12 @@ __global__ void __launch_bounds__(kBlock) unpack_film_kernel(int film_w, int fil
   film[size_t(py) * film_w + px] = slabs[(size_t(rank) * tiles_per_rank + ltile) * 64u + p];
 }
 
-// ------------------------------------------------------------------------------------------------
-// Device-side unit-test kernels (parity of the building blocks against the oracle)
-// ------------------------------------------------------------------------------------------------
-__global__ void test_sincos_kernel(const float* x, long long n, float* s, float* c) {
-  const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-  if (i < n) {
-    // the branch-free shared-reduction form the kernels call, cross-checked against the two single functions
-    float sn, cs;
-    psincos(x[i], sn, cs);
-    const float s1 = psin(x[i]), c1 = pcos(x[i]);
-    const bool same = __float_as_uint(s1) == __float_as_uint(sn) && __float_as_uint(c1) == __float_as_uint(cs);
-    s[i] = same ? sn : __uint_as_float(0x7fc00001u);
-    c[i] = same ? cs : __uint_as_float(0x7fc00001u);
-  }
-}
-__global__ void test_powlog_kernel(const float* x, const float* y, long long n, float* p, float* l) {
-  const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-  if (i < n) {
-    p[i] = ppow(x[i], y[i]);
-    l[i] = plog(x[i]);
-  }
-}
-__global__ void test_atan_kernel(const float* y, const float* x, long long n, float* at2, float* ac) {
-  const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-  if (i < n) {
-    at2[i] = patan2(y[i], x[i]);
-    ac[i] = pacos(x[i]);
-  }
-}
-// pine_gpu_test_math_*: the scalar functions of pine_math.h on bit patterns (pine_math_check.h has math_eval<FN>).
-// inputs from arrays (a != NULL; b, c as the arity needs) or generated: argument `swept` = first + i * stride, the others
-// `fixed`.  out: n * math_width(FN) words.
-template <int FN>
-__global__ void test_math_kernel(const uint32_t* a, const uint32_t* b, const uint32_t* c, uint32_t fixed, int swept,
-                                 uint32_t first, uint32_t stride, long long n, uint32_t* out) {
-  const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  uint32_t ua, ub = fixed, uc = fixed;
-  if (a) {
-    ua = a[i];
-    if (math_arity(FN) > 1) ub = b[i];
-    if (math_arity(FN) > 2) uc = c[i];
-  } else {
-    const uint32_t v = first + uint32_t(i) * stride;
-    ua = swept == 0 ? v : fixed;
-    ub = swept == 1 ? v : fixed;
-    uc = swept == 2 ? v : fixed;
-  }
-  math_eval<FN>(ua, ub, uc, out + i * math_width(FN));
-}
-__constant__ int kTestPixels[6][2] = {{0, 0}, {1, 0}, {3, 5}, {127, 127}, {128, 5}, {639, 639}};
-__global__ void test_sampler_kernel(DTables T, int spp, float* out) {
-  // one thread per (pixel, pass); layout identical to oracle_sampler_stream
-  const int pix = blockIdx.x;
-  if (threadIdx.x != 0) return;
-  float* o = out + size_t(pix) * spp * (260 + 270);
-  DSampler s;
-  s.px = kTestPixels[pix][0];
-  s.py = kTestPixels[pix][1];
-  s.dimension = 0;
-  s.index = 0;
-  size_t k = 0;
-  for (int i = 0; i < spp; i++) {
-    for (int d = 0; d < 130; d++) {
-      const f2 v = sampler_get2d(T, s);
-      o[k++] = v.x;
-      o[k++] = v.y;
-    }
-    s.dimension = 0;
-    s.index++;
-  }
-  s.index = 0;
-  for (int i = 0; i < spp; i++) {
-    for (int d = 0; d < 90; d++) {
-      o[k++] = sampler_get1d(T, s);
-      const f2 v = sampler_get2d(T, s);
-      o[k++] = v.x;
-      o[k++] = v.y;
-    }
-    s.dimension = 0;
-    s.index++;
-  }
-}
-__global__ void test_rng_kernel(unsigned long long* out) {
-  const int pix = threadIdx.x;
-  if (pix >= 6) return;
-  unsigned long long* o = out + pix * 19;
-  const uint64_t h = hash_pixel(kTestPixels[pix][0], kTestPixels[pix][1], 0);
-  o[0] = h;
-  DRng g = rng_seed(h);
-  o[1] = g.s0;
-  o[2] = g.s1;
-  for (int i = 0; i < 16; i++) o[3 + i] = (unsigned long long)(uint32_t)as_int(rng_nextf(g));
-}
-// The primitives a ray's traversal tests, in order, and its result: the nested loops of the scene-in-LDS variants
-// (FLAT = false: scene_traverse / mesh_traverse) or the flat state machine of the F_LDS_TOP variants (pine_trav.h).
-// One thread per ray, 64 per block; out: per ray `cap` words closest (count, words...), 4 result words (hit, geometry,
-// triangle, tmax bits), `cap` words any-hit, 1 result word.
-// (MODE 2: the closest-hit query in EmbreeAccel's order, PINE_GPU_FLAG_ORDER_EMBREE; the any-hit query is the nested loops')
-template <int MODE>
-__global__ void __launch_bounds__(64) test_traverse_kernel(DeviceScene S, const float* rays, long long nrays, int cap, unsigned* out) {
-  constexpr bool FLAT = MODE == 1;
-  constexpr unsigned F = FLAT ? (F_ALL | F_LDS_TOP) : MODE == 2 ? (F_ALL | F_EMBREE) : F_ALL;
-  using StackT = typename std::conditional<FLAT, unsigned short, int>::type;
-  extern __shared__ __attribute__((aligned(16))) int lds_raw[];
-  StackT* const stack = reinterpret_cast<StackT*>(lds_raw) + threadIdx.x;
-  SceneView V;
-  V.tri_verts = S.tri_verts, V.tri_leaf = S.tri_leaf, V.tri_attrs = S.tri_attrs;
-  V.lds_nodes = nullptr, V.lds_node_count = 0, V.lds_tri_entries = nullptr, V.lds_tri_verts = nullptr;
-  V.stack_top = S.stack_top, V.num_shapes = S.num_shapes;
-  V.leaf = S.leaf, V.nodes = S.nodes, V.shapes = S.shapes, V.materials = S.materials, V.bvhs = S.bvhs, V.prims = nullptr;
-  V.lights = S.lights, V.node_ops = S.node_ops;
-  V.etree = reinterpret_cast<const EmbreeNode*>(reinterpret_cast<const char*>(S.blob) + S.off_etree), V.etree_root = S.etree_root;
-  V.emesh = reinterpret_cast<const int*>(reinterpret_cast<const char*>(S.blob) + S.off_emesh), V.num_emesh = S.num_emesh;
-  V.rcpps = reinterpret_cast<const unsigned*>(reinterpret_cast<const char*>(S.blob) + S.off_rcpps);
-  const long long i = blockIdx.x * 64ll + threadIdx.x;
-  const bool live = i < nrays;
-  const float* q = rays + (live ? i : 0) * 8;
-  unsigned* o = out + (live ? i : 0) * (2ll * cap + 5);
-  for (int pass = 0; pass < 2; pass++) {
-    DRay ray{f3{q[0], q[1], q[2]}, f3{q[3], q[4], q[5]}, q[6], q[7]};
-    TravLog log{o + (pass ? cap + 4 : 0) + 1, 0, cap - 1};
-    bool hit = false;
-    int geom = 0, prim = 0;
-    if constexpr (FLAT) {
-      TravState ts;
-      trav_begin(V, ts);
-      if (!live) ts.done = 1;
-      const DRayOct oct = make_oct(ray);
-      if (pass == 0) trav_trips<false, F, 64>(V, ray, oct, ts, stack, 0, 1 << 30, nullptr, &log);
-      else trav_trips<true, F, 64>(V, ray, oct, ts, stack, 0, 1 << 30, nullptr, &log);
-      hit = ts.hit_geom >= 0;
-      geom = ts.hit_geom, prim = ts.hit_prim;
-    } else if (live) {
-      hit = pass == 0 ? scene_traverse<false, F, 64>(V, ray, stack, geom, prim, &log) : scene_traverse<true, F, 64>(V, ray, stack, geom, prim, &log);
-    }
-    if (live) {
-      o[pass ? cap + 4 : 0] = unsigned(log.n);
-      if (pass == 0) {
-        o[cap] = hit ? 1u : 0u;
-        o[cap + 1] = hit ? unsigned(geom & kPrimIndexMask) : 0u;
-        // (a mesh hit reports the triangle's index within its mesh, as the reference does; elsewhere the word is unused: 0)
-        const bool on_mesh = hit && (geom >> kPrimKindShift) == SHAPE_MESH;
-        o[cap + 2] = on_mesh ? unsigned(prim - S.bvhs[as_int(S.shapes[geom & kPrimIndexMask].f[2])].prim_base) : 0u;
-        o[cap + 3] = __float_as_uint(ray.tmax);
-      } else {
-        o[2 * cap + 4] = hit ? 1u : 0u;
-      }
-    }
-  }
-}
-__global__ void test_shapes_kernel(const DShape* shapes, int num_shapes, const float* rays, long long nrays,
-                                   float* out) {
-  const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-  if (i >= nrays * num_shapes) return;
-  const int g = int(i / nrays);
-  const long long r = i % nrays;
-  const float* q = rays + r * 8;
-  DRay ray{f3{q[0], q[1], q[2]}, f3{q[3], q[4], q[5]}, q[6], q[7]};
-  float* o = out + i * 11;
-  const DShape* S = &shapes[g];
-  o[0] = shape_hit(S, ray) ? 1.0f : 0.0f;
-  DRay r2 = ray;
-  const bool h = shape_intersect(S, r2);
-  o[1] = h ? 1.0f : 0.0f;
-  o[2] = r2.tmax;
-  DSurface it;
-  it.p = it.n = mk3(0.0f);
-  it.uv = f2{0, 0};
-  if (h) shape_surface_info(S, ray_at(r2, r2.tmax), it);
-  o[3] = it.p.x, o[4] = it.p.y, o[5] = it.p.z;
-  o[6] = it.n.x, o[7] = it.n.y, o[8] = it.n.z;
-  o[9] = it.uv.x, o[10] = it.uv.y;
-}
-
 // ================================================================================================
 // Host side: plans, launches
 // ================================================================================================
-#define HIP_OK(expr)                                                                          \
-  do {                                                                                        \
-    hipError_t e_ = (expr);                                                                   \
-    if (e_ != hipSuccess) {                                                                   \
-      set_error(std::string(#expr) + ": " + hipGetErrorString(e_));                           \
-      (void)hipGetLastError(); /* reported here: do not leave it sticky for the caller's next HIP user */ \
-      return -1;                                                                              \
-    }                                                                                         \
-  } while (0)
-
-static std::string g_table_path;
-// The packed tables are immutable once read; users take a shared snapshot, so a concurrent
-// pine_gpu_set_table_path (which only drops the library's own reference) cannot free them under a reader.
-using TableBlob = std::shared_ptr<const std::vector<uint8_t>>;
-static TableBlob g_tables;
-static std::mutex g_table_mutex;
 static std::atomic<float> g_progress{0.0f};
 static std::atomic<const volatile unsigned long long*> g_progress_src{nullptr};
 static std::atomic<unsigned long long> g_progress_total{0};
-
-static int load_tables(TableBlob& out) {
-  std::lock_guard<std::mutex> lock(g_table_mutex);
-  if (g_tables) {
-    out = g_tables;
-    return 0;
-  }
-  if (g_table_path.empty()) {
-    // not set by the host: $PINE_GPU_TABLES, else data/bluesobol_u8.bin next to the directory this library sits in
-    // (pine_amd/lib/libpine_gpu.so -> pine_amd/data/), wherever the process was started from
-    if (const char* env = getenv("PINE_GPU_TABLES")) g_table_path = env;
-    else {
-      Dl_info info;
-      if (dladdr(reinterpret_cast<const void*>(&load_tables), &info) && info.dli_fname) {
-        std::string lib = info.dli_fname;
-        const size_t slash = lib.rfind('/');
-        g_table_path = (slash == std::string::npos ? std::string(".") : lib.substr(0, slash)) + "/../data/bluesobol_u8.bin";
-      }
-    }
-  }
-  if (g_table_path.empty()) {
-    set_error("BlueSobol table path not set (pine_gpu_set_table_path)");
-    return -1;
-  }
-  FILE* f = fopen(g_table_path.c_str(), "rb");
-  if (!f) {
-    set_error("cannot open " + g_table_path);
-    return -1;
-  }
-  std::vector<uint8_t> buf(65536 + 9 * 262144);
-  size_t n = fread(buf.data(), 1, buf.size(), f);
-  fclose(f);
-  if (n != buf.size()) {
-    set_error("short read of " + g_table_path);
-    return -1;
-  }
-  g_tables = std::make_shared<const std::vector<uint8_t>>(std::move(buf));
-  out = g_tables;
-  return 0;
-}
-// The device keeps sobol_256spp_256d transposed ([dimension][sample] instead of [sample][dimension]):
-// lanes of a wave usually ask for the same dimension at 64 different (ranked) sample rows, which is
-// one 256-byte row here instead of 64 cache lines 256 bytes apart.
-static std::vector<uint8_t> transposed_sobol(const std::vector<uint8_t>& tables) {
-  std::vector<uint8_t> t(65536);
-  for (int s = 0; s < 256; s++)
-    for (int d = 0; d < 256; d++) t[d * 256 + s] = tables[s * 256 + d];
-  return t;
-}
-static int effective_spp(int spp) {  // BlueSobolSampler ctor sampler.cpp:115-121
-  if (spp > 256) spp = 256;
-  if (spp <= 0) return 0;
-  int x = spp - 1;
-  for (unsigned i = 1; i < 32; i <<= 1) x |= x >> i;
-  return x + 1;
-}
-
-// Device memory of plans comes from a process-wide pool: hipMalloc / hipFree of the big per-plan buffers (the per-sample
-// radiance buffer is 1.7 GB for a 640 x 640 x 256 render, 6.8 GB for 1920 x 1080) cost 30 - 90 ms per plan, which is most of
-// what a ONE-SHOT render (pine_gpu_path_render: create, launch, destroy -- what PathIntegrator::render does) spends outside
-// its kernels.  A destroyed plan's blocks of 256 KB and more go to a per-device free list instead and the next plan takes
-// the smallest one that fits within 25 %; at most $PINE_GPU_POOL_MB (default 16 384; 0: no pool) are kept,
-// pine_gpu_release_cached_memory() frees them.  No kernel reads a buffer before writing it (hipMalloc does not clear either).
-struct DevicePool {
-  struct Block {
-    void* p;
-    size_t bytes;
-    int device;
-  };
-  std::mutex mu;
-  std::vector<Block> free_blocks;
-  std::map<void*, Block> live;  // pooled-size allocations handed out
-  size_t pooled = 0, cap = size_t(16384) << 20;
-  DevicePool() {
-    if (const char* e = getenv("PINE_GPU_POOL_MB")) cap = size_t(atoll(e) > 0 ? atoll(e) : 0) << 20;
-  }
-  static DevicePool& get() {
-    static DevicePool* q = new DevicePool();  // (never destroyed: plans may be destroyed during static destruction)
-    return *q;
-  }
-  static constexpr size_t kMinPooled = size_t(256) << 10;
-  hipError_t alloc(void** out, size_t bytes) {
-    *out = nullptr;
-    if (bytes < kMinPooled || cap == 0) return hipMalloc(out, bytes);
-    int device = 0;
-    (void)hipGetDevice(&device);
-    const size_t want = (bytes + (size_t(2) << 20) - 1) & ~((size_t(2) << 20) - 1);
-    {
-      std::lock_guard<std::mutex> lock(mu);
-      int best = -1;
-      for (size_t i = 0; i < free_blocks.size(); i++) {
-        const Block& b = free_blocks[i];
-        if (b.device != device || b.bytes < want || b.bytes > want + want / 4) continue;
-        if (best < 0 || b.bytes < free_blocks[size_t(best)].bytes) best = int(i);
-      }
-      if (best >= 0) {
-        const Block b = free_blocks[size_t(best)];
-        free_blocks.erase(free_blocks.begin() + best);
-        pooled -= b.bytes;
-        live[b.p] = b;
-        *out = b.p;
-        return hipSuccess;
-      }
-    }
-    hipError_t e = hipMalloc(out, want);
-    if (e != hipSuccess) {  // memory is short: give the pool back and try once more
-      release_all();
-      (void)hipGetLastError();
-      e = hipMalloc(out, want);
-    }
-    if (e == hipSuccess) {
-      std::lock_guard<std::mutex> lock(mu);
-      live[*out] = Block{*out, want, device};
-    }
-    return e;
-  }
-  void free(void* p) {
-    if (!p) return;
-    Block b{nullptr, 0, 0};
-    {
-      std::lock_guard<std::mutex> lock(mu);
-      auto it = live.find(p);
-      if (it != live.end()) {
-        b = it->second;
-        live.erase(it);
-        if (pooled + b.bytes <= cap) {
-          free_blocks.push_back(b);
-          pooled += b.bytes;
-          return;
-        }
-      }
-    }
-    (void)hipFree(p);  // (a small allocation, or the pool is full)
-  }
-  void release_all() {
-    std::vector<Block> blocks;
-    {
-      std::lock_guard<std::mutex> lock(mu);
-      blocks.swap(free_blocks);
-      pooled = 0;
-    }
-    int keep = 0;
-    (void)hipGetDevice(&keep);
-    for (const Block& b : blocks) {
-      (void)hipSetDevice(b.device);
-      (void)hipFree(b.p);
-    }
-    (void)hipSetDevice(keep);
-  }
-};
-#define POOL_ALLOC(ptr, bytes) DevicePool::get().alloc((void**)&(ptr), (bytes))
-
-template <class T>
-static int upload(T*& dptr, const std::vector<T>& v) {
-  dptr = nullptr;
-  size_t bytes = std::max<size_t>(v.size(), 1) * sizeof(T);
-  HIP_OK(POOL_ALLOC(dptr, bytes));
-  if (!v.empty()) HIP_OK(hipMemcpy(dptr, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-  return 0;
-}
-
 // depth of the inner-node tree below `node` (= traversal stack entries that can be live)
 static int bvh_depth(const std::vector<DNode>& nodes, int node) {
   const DNode& n = nodes[node];
@@ -638,69 +257,6 @@ static int validate_device_scene(const FlatAccel& A, const std::vector<DShape>& 
 
 using namespace pine_gpu;
 
-struct pine_gpu_plan {
-  int device = 0;
-  pine_gpu_render_params params{};
-  DeviceScene S{};
-  WorkParams W{};
-  int film_w = 0, film_h = 0;
-  // device buffers
-  char* d_blob = nullptr;  // nodes | shapes | materials | bvhs | prims | lights
-  float* d_tri = nullptr;
-  float* d_tri_leaf = nullptr;
-  uint4* d_tri_packets = nullptr;
-  uint8_t* d_halton = nullptr;
-  float* d_tri_attrs = nullptr;
-  uint8_t* d_tables = nullptr;
-  int variant = -1;
-  int queue_variant = -1;   // >= 0: the stage-queued kernel is used instead of path_trace_kernel
-  const PineFastVariant* fast = nullptr;  // PINE_GPU_FLAG_FAST: the declared-tolerance variant that runs instead (pine_kernels_fast.hip)
-  uint32_t* d_ctxg = nullptr;
-  ulonglong2* d_ckpt = nullptr;
-  // The RNG checkpoints are a function of the film partition and the sample counts alone: the plan's FIRST launch computes them,
-  // later launches reuse the table (they wait for `ckpt_done` when they run on another stream).  $PINE_GPU_CKPT_EVERY_LAUNCH=1: as
-  // before round 4, every launch recomputes it (measurement aid).
-  bool ckpt_valid = false, ckpt_every_launch = false;
-  hipEvent_t ckpt_done = nullptr;
-  hipStream_t ckpt_stream = nullptr;
-  float* d_vertex_log = nullptr;        // test hook (pine_gpu_plan_vertex_log)
-  int* d_tile_order = nullptr;          // tile classes (WorkParams::tile_order), or null
-  std::vector<int> tile_order;          // ... its host copy (empty: local tile t is film tile t * shard_world + shard_rank)
-  float4* d_samples = nullptr;
-  float* d_fold = nullptr;
-  Counters* d_counters = nullptr;
-  int grid = 0;
-  size_t lds_bytes = 0;
-  bool serial_rng = false;
-  // per-launch HIP events (prepass start / path kernel start / resolve start / end) for the last
-  // kEvRing launches: reading them (stats_get) averages over the launches since the previous read,
-  // so a timed loop never has to synchronise inside
-  static constexpr int kEvRing = 64;
-  hipEvent_t ev[kEvRing][4] = {};
-  unsigned long long launch_count = 0, stats_read_upto = 0;
-  bool timed = false;
-  bool launched = false;
-  hipStream_t last_stream = nullptr;
-  unsigned long long* h_progress = nullptr;  // host-mapped progress word (PINE_GPU_FLAG_PROGRESS)
-  float accel_build_ms = 0.0f, upload_ms = 0.0f;  // host-side cost of plan creation (reported by stats_get)
-  bool accel_on_device = false;
-  // PINE_GPU_FLAG_SPECIALIZE: the queue kernel compiled for this scene (pine_specialize.h); null: the precompiled variant
-  std::shared_ptr<struct LoadedKernel> spec_loaded;  // (shared with every plan of this geometry on this device: LoadedKernels)
-  hipModule_t spec_module = nullptr;
-  hipFunction_t spec_fn = nullptr;
-  unsigned spec_features = 0;  // ... its feature set (the scene's own), and whether the scene's BVH is baked in
-  bool spec_baked = false;
-  KernelRequest spec_request;  // what to compile (filled at plan creation)
-  std::chrono::steady_clock::time_point spec_t0;
-  bool spec_explicit = false;  // the caller asked for the scene's kernel (PINE_GPU_FLAG_SPECIALIZE): failures are errors
-  int spec_source = 0;         // kSpecSource*: where the scene's kernel came / comes from
-  // background build (the default mode, PINE_GPU_FLAG_SPECIALIZE_ASYNC): a job of the process-wide queue; a launch adopts its result
-  std::atomic<int> spec_state{0};  // kSpecNone / kSpecBuilding / kSpecAdopted / kSpecFailed
-  std::shared_ptr<struct SpecJob> spec_job;
-  std::string spec_async_error;
-  float specialize_ms = 0.0f;
-};
-
 // Scene-specialised kernels (pine_specialize.h): the stage-queued kernel compiled FOR THIS SCENE.
 //  (1) its exact feature set: the precompiled variants are a handful of supersets (pine_variants.h) -- a scene of spheres
 //      under a point light runs the everything-but-Subsurface kernel and pays for every shape kind, node programs and the
@@ -720,7 +276,6 @@ struct pine_gpu_plan {
 // PINE_GPU_FLAG_SPECIALIZE (or $PINE_GPU_SPECIALIZE=1): the caller WANTS the scene's kernel -- plan creation waits for the
 // compiler and a kernel that cannot be built fails the plan; with _ASYNC the build runs in the background as above but a
 // failure is still reported (specialized == -1).  PINE_GPU_FLAG_NO_SPECIALIZE / $PINE_GPU_SPECIALIZE=0: precompiled only.
-enum : int { kSpecNone = 0, kSpecBuilding, kSpecBuilt, kSpecAdopted, kSpecFailed };
 enum : int { kSpecSourceNone = 0, kSpecSourceCache = 1, kSpecSourceCompiledHere = 2, kSpecSourceBackground = 3 };
 
 namespace pine_gpu {
@@ -730,106 +285,6 @@ AbiFingerprint abi_fingerprint() {
                         kTravRecordDwords, kQCtxGlobalDwordsPlain, kQCtxGlobalDwordsSss};
 }
 }  // namespace pine_gpu
-
-// The background compile queue.  A job is one code object (content key); plans hold a shared_ptr and poll `state`.  Workers
-// are started on demand, run jobs in order, skip jobs nobody waits for any more, and exit when the queue is empty.  The
-// singleton is never destroyed (worker threads may outlive static destruction); at process exit an atexit handler raises
-// `closing`, ends running compilers (their own process groups) and joins the workers, so nothing of ours runs while the
-// runtime goes down and no half-written build directory is left behind.
-struct SpecJob {
-  KernelRequest req;
-  std::atomic<int> state{kSpecBuilding};
-  std::atomic<int> waiters{0};
-  std::string error;  // (written before `state` becomes kSpecFailed)
-  float compile_ms = 0.0f;
-};
-struct SpecQueue {
-  static constexpr int kSpecWorkers = 2, kMaxPending = 6;
-  std::mutex mu;
-  std::map<std::string, std::shared_ptr<SpecJob>> jobs;  // by key: every job ever started in this process
-  std::deque<std::shared_ptr<SpecJob>> pending;
-  std::vector<std::thread> workers;
-  int running = 0;
-  std::atomic<int> children[kSpecWorkers];
-  std::atomic<bool> closing{false};
-  static SpecQueue& get() {
-    static SpecQueue* q = [] {
-      SpecQueue* x = new SpecQueue();
-      for (auto& c : x->children) c.store(0);
-      atexit([] { SpecQueue::get().shutdown(); });
-      return x;
-    }();
-    return *q;
-  }
-  // the job for `req` (already keyed): an existing one, or a new one queued for a worker; null when the queue is full
-  // (`retry_failed`: a kernel whose build failed earlier in this process is tried again -- the caller asked for it by flag;
-  //  the automatic mode does not spend a compiler run per plan on a kernel that does not build)
-  std::shared_ptr<SpecJob> submit(const KernelRequest& req, bool retry_failed) {
-    std::lock_guard<std::mutex> lock(mu);
-    if (closing.load()) return nullptr;
-    auto it = jobs.find(req.key);
-    if (it != jobs.end() && (it->second->state.load() != kSpecFailed || !retry_failed)) return it->second;
-    if (int(pending.size()) >= kMaxPending) return nullptr;
-    auto job = std::make_shared<SpecJob>();
-    job->req = req;
-    jobs[req.key] = job;
-    pending.push_back(job);
-    if (running < kSpecWorkers) {
-      const int slot = running++;
-      workers.emplace_back([this, slot] { work(slot); });
-    }
-    return job;
-  }
-  void work(int slot) {
-    for (;;) {
-      std::shared_ptr<SpecJob> job;
-      {
-        std::lock_guard<std::mutex> lock(mu);
-        while (!pending.empty() && !job) {
-          job = pending.front();
-          pending.pop_front();
-          if (job->waiters.load() == 0 || closing.load()) {  // nobody wants it any more
-            job->error = "cancelled";
-            job->state.store(kSpecFailed);
-            jobs.erase(job->req.key);
-            job.reset();
-          }
-        }
-        if (!job) {
-          running--;
-          return;
-        }
-      }
-      const auto t0 = std::chrono::steady_clock::now();
-      std::string err;
-      struct stat st;
-      const bool ok = (stat(job->req.path.c_str(), &st) == 0 && st.st_size > 0) || kernel_compile(job->req, err, &children[slot]);
-      job->compile_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-      job->error = err;
-      job->req.baked.clear();  // (the text is no longer needed: waiting plans keep their own copy)
-      job->req.baked.shrink_to_fit();
-      job->state.store(ok ? kSpecBuilt : kSpecFailed);
-      if (ok) {  // later plans find the code object on disk; only failures are remembered
-        std::lock_guard<std::mutex> lock(mu);
-        jobs.erase(job->req.key);
-      }
-    }
-  }
-  void shutdown() {
-    closing.store(true);
-    for (auto& c : children) {
-      const int pid = c.load();
-      if (pid > 0) kill(-pid, SIGKILL);  // the compiler's process group
-    }
-    std::vector<std::thread> w;
-    {
-      std::lock_guard<std::mutex> lock(mu);
-      w.swap(workers);
-    }
-    for (auto& t : w)
-      if (t.joinable()) t.join();
-  }
-};
 
 // A code object loaded into a device's context, shared by the plans that run it: hipModuleLoadData of a scene's kernel is a
 // millisecond or two, which a one-shot render (create, launch, destroy) of the same geometry would pay on every call.  The
@@ -876,14 +331,38 @@ struct LoadedKernels {
   }
 };
 
+// The plan-time measurement aids, read from the environment once per plan: the phases of plan_build read only
+// this.  The numbers are kUnset when their variable is not set.
+constexpr int kUnset = INT_MIN;
+struct PlanKnobs {
+  // PINE_GPU_SPECIALIZE (0: precompiled kernels only, else as PINE_GPU_FLAG_SPECIALIZE), _LDS_TRIS, _XSTAGE, _TRAV_MIN_LANES,
+  // _TRAV_MIN_TRIPS, _MAX_PIXELS, _FAIR_PERIOD, _POOL_ITEMS
+  int specialize, lds_tris, xstage, trav_min_lanes, trav_min_trips, max_pixels, fair_period, pool_items;
+  // PINE_GPU_SPECIALIZE_FORCE, _NO_LDS_SCENE, _KERNEL=mega, _NO_TILE_CLASSES, _NO_FORK, _CKPT_EVERY_LAUNCH (not 0)
+  bool specialize_force, no_lds_scene, mega, no_tile_classes, no_fork, ckpt_every_launch;
+  double idle_budget_s;  // PINE_GPU_IDLE_BUDGET_S: the path kernel's watchdog, 30 s
+};
+static PlanKnobs read_knobs() {
+  auto num = [](const char* name) { return getenv(name) ? atoi(getenv(name)) : kUnset; };
+  auto set = [](const char* name) { return getenv(name) != nullptr; };
+  const char* kernel = getenv("PINE_GPU_KERNEL");
+  const char* budget = getenv("PINE_GPU_IDLE_BUDGET_S");
+  const int ckpt = num("PINE_GPU_CKPT_EVERY_LAUNCH");
+  return PlanKnobs{num("PINE_GPU_SPECIALIZE"), num("PINE_GPU_LDS_TRIS"), num("PINE_GPU_XSTAGE"), num("PINE_GPU_TRAV_MIN_LANES"),
+                   num("PINE_GPU_TRAV_MIN_TRIPS"), num("PINE_GPU_MAX_PIXELS"), num("PINE_GPU_FAIR_PERIOD"), num("PINE_GPU_POOL_ITEMS"),
+                   set("PINE_GPU_SPECIALIZE_FORCE"), set("PINE_GPU_NO_LDS_SCENE"), kernel && std::string(kernel) == "mega",
+                   set("PINE_GPU_NO_TILE_CLASSES"), set("PINE_GPU_NO_FORK"), ckpt != kUnset && ckpt != 0,
+                   budget && atof(budget) > 0 ? atof(budget) : 30.0};
+}
+
 static int plan_adopt_kernel(pine_gpu_plan* p, bool compile_here);
 static int plan_specialize(pine_gpu_plan* p, const FlatAccel& A, const std::vector<DShape>& shapes, const std::vector<int>& packed_prims,
-                           const pine_gpu_render_params* prm, unsigned need) {
+                           const pine_gpu_render_params* prm, unsigned need, const PlanKnobs& K) {
   // explicit: the caller asked for the scene's kernel (failures are errors); automatic: the default (failures are silent)
   bool explicit_want = (prm->flags & PINE_GPU_FLAG_SPECIALIZE) != 0;
   bool automatic = !explicit_want && !(prm->flags & PINE_GPU_FLAG_NO_SPECIALIZE);
-  if (const char* e = getenv("PINE_GPU_SPECIALIZE")) {
-    if (atoi(e) != 0) explicit_want = true, automatic = false;
+  if (K.specialize != kUnset) {
+    if (K.specialize != 0) explicit_want = true, automatic = false;
     else explicit_want = automatic = false;
   }
   if ((!explicit_want && !automatic) || p->queue_variant < 0 || (prm->flags & (PINE_GPU_FLAG_FAST | PINE_GPU_FLAG_VERTEX_LOG))) return 0;
@@ -893,13 +372,12 @@ static int plan_specialize(pine_gpu_plan* p, const FlatAccel& A, const std::vect
   unsigned exact = (V.features & kLayout) | need;
   std::string baked;
   // (a baked scene IS pine's visiting order as code: the EmbreeAccel order mode keeps to the feature-set level)
-  if (!(prm->flags & (PINE_GPU_FLAG_SPECIALIZE_NO_BAKE | PINE_GPU_FLAG_ORDER_EMBREE)) && getenv("PINE_GPU_SPECIALIZE_NO_BAKE") == nullptr) {
+  if (!(prm->flags & (PINE_GPU_FLAG_SPECIALIZE_NO_BAKE | PINE_GPU_FLAG_ORDER_EMBREE))) {
     if (!(V.features & F_XSTAGE) && A.top_prim_begin == 0) baked = generate_baked_scene(A, shapes, packed_prims);
     // one mesh under a small top level, traversal stages (C5's class): the top level as code, the mesh left to the flat traversal
-    else if ((V.features & F_XSTAGE) && A.bvhs.size() == 2 && getenv("PINE_GPU_SPECIALIZE_NO_TOP") == nullptr)
-      baked = generate_baked_scene(A, shapes, packed_prims, true);
+    else if ((V.features & F_XSTAGE) && A.bvhs.size() == 2) baked = generate_baked_scene(A, shapes, packed_prims, true);
   }
-  if (baked.empty() && exact == V.features && getenv("PINE_GPU_SPECIALIZE_FORCE") == nullptr) return 0;  // (FORCE: experiments through $PINE_GPU_SPECIALIZE_EXTRA)
+  if (baked.empty() && exact == V.features && !K.specialize_force) return 0;  // (FORCE: experiments through $PINE_GPU_SPECIALIZE_EXTRA)
   if (!baked.empty()) exact |= F_BAKED;
   hipDeviceProp_t prop;
   HIP_OK(hipGetDeviceProperties(&prop, prm->device));
@@ -949,7 +427,6 @@ static int plan_specialize(pine_gpu_plan* p, const FlatAccel& A, const std::vect
     p->spec_async_error = "the background compile queue is full";
     return 0;
   }
-  p->spec_job->waiters.fetch_add(1);
   p->spec_state.store(kSpecBuilding);
   return 0;
 }
@@ -1184,8 +661,19 @@ static bool build_tri_packets(const FlatAccel& A, std::vector<uint32_t>& out, in
   return true;
 }
 
-static int plan_build(pine_gpu_plan* p, pine_gpu_scene* scene, const pine_gpu_render_params* prm) {
-  SceneHost& H = scene_host(scene);
+// ---- plan_build and its phases, in the order it runs them ----
+// What assemble_scene leaves for the later phases: host copies of the records it uploaded.
+struct SceneParts {
+  std::vector<DShape> shapes;
+  std::vector<DMaterial> materials;  // literals folded, node programs attached
+  std::vector<DNodeOp> node_ops;
+  std::vector<int> packed_prims;     // top-level entries: geometry | emissive | kind (pine_types.h)
+  std::vector<DLight> lights;        // + the environment light last (lightsampler.cpp:6-10)
+  size_t tri_packet_bytes = 0;        // (0: no triangle packets, build_tri_packets)
+};
+
+// The samples per pixel the plan renders, or -1.
+static int check_params(const SceneHost& H, const pine_gpu_render_params* prm) {
   if (!H.has_camera) {
     set_error("scene has no camera");
     return -1;
@@ -1217,34 +705,18 @@ static int plan_build(pine_gpu_plan* p, pine_gpu_scene* scene, const pine_gpu_re
     set_error(halton ? "HaltonSampler on the device: at most 4096 samples per pixel" : "SobolSampler on the device: at most 4096 samples per pixel");
     return -1;
   }
-  const bool spp_pow2 = (spp & (spp - 1)) == 0;  // (BlueSampler's effective spp always is; SobolSampler / HaltonSampler take any count)
   if (prm->shard_world < 1 || prm->shard_rank < 0 || prm->shard_rank >= prm->shard_world) {
     set_error("bad shard rank/world");
     return -1;
   }
-  TableBlob tables_blob;
-  if (load_tables(tables_blob)) return -1;
-  const std::vector<uint8_t>& g_tables = *tables_blob;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    set_error("no HIP device available: the PathIntegrator hot path requires an AMD GPU (no CPU fallback)");
-    return -1;
-  }
-  HIP_OK(hipSetDevice(prm->device));
-  p->device = prm->device;
-  p->params = *prm;
-  const auto t_build0 = std::chrono::steady_clock::now();
-  if (!H.accel.built) {
-    const char* e = getenv("PINE_GPU_DEVICE_BVH");
-    H.build_on_device = ((prm->flags & PINE_GPU_FLAG_DEVICE_BVH) || (e && atoi(e) != 0)) ? prm->device : -1;
-    H.build_accel();
-  }
-  const auto t_build1 = std::chrono::steady_clock::now();
-  p->accel_build_ms = std::chrono::duration<float, std::milli>(t_build1 - t_build0).count();
-  p->accel_on_device = H.built_on_device;
-  const FlatAccel& A = H.accel;
+  return spp;
+}
 
-  std::vector<DShape> shapes;
+// The scene's records on the device: the blob of small records, the triangles and their LDS packets; the traversal stack
+// depth, checked with every index before anything is launched.
+static int assemble_scene(pine_gpu_plan* p, SceneHost& H, const pine_gpu_render_params* prm, SceneParts& sp) {
+  const FlatAccel& A = H.accel;
+  std::vector<DShape>& shapes = sp.shapes;
   for (auto& g : H.geometries) shapes.push_back(g.shape);
   // one blob for the small records (16-byte aligned sections), so a workgroup can stage it in LDS
   std::vector<char> blob;
@@ -1257,13 +729,12 @@ static int plan_build(pine_gpu_plan* p, pine_gpu_scene* scene, const pine_gpu_re
   DeviceScene& S = p->S;
   S.off_nodes = put(A.nodes.data(), A.nodes.size() * sizeof(DNode));
   S.off_shapes = put(shapes.data(), shapes.size() * sizeof(DShape));
-  std::vector<DMaterial> dev_materials;  // literals folded, node programs attached
-  std::vector<DNodeOp> node_ops;
-  if (!H.compile_node_programs(dev_materials, node_ops)) return -1;
-  S.off_materials = put(dev_materials.data(), dev_materials.size() * sizeof(DMaterial));
-  S.off_node_ops = put(node_ops.data(), node_ops.size() * sizeof(DNodeOp));
+  if (!H.compile_node_programs(sp.materials, sp.node_ops)) return -1;
+  S.off_materials = put(sp.materials.data(), sp.materials.size() * sizeof(DMaterial));
+  S.off_node_ops = put(sp.node_ops.data(), sp.node_ops.size() * sizeof(DNodeOp));
   S.off_bvhs = put(A.bvhs.data(), A.bvhs.size() * sizeof(DBvh));
-  std::vector<int> packed_prims = A.prims;  // top-level entries: geometry | emissive | kind (pine_types.h)
+  std::vector<int>& packed_prims = sp.packed_prims;
+  packed_prims = A.prims;
   for (size_t i = size_t(A.top_prim_begin); i < packed_prims.size(); i++) {
     const int g = packed_prims[i];
     if (g > kPrimIndexMask) {
@@ -1282,9 +753,9 @@ static int plan_build(pine_gpu_plan* p, pine_gpu_scene* scene, const pine_gpu_re
   }
   S.off_leaf = put(leaf_shapes.data(), leaf_shapes.size() * sizeof(DShape));
   S.top_prim_begin = A.top_prim_begin;
-  std::vector<DLight> light_list = H.lights;  // + the environment light last (lightsampler.cpp:6-10)
-  if (H.has_env) light_list.push_back(H.env);
-  S.off_lights = put(light_list.data(), light_list.size() * sizeof(DLight));
+  sp.lights = H.lights;
+  if (H.has_env) sp.lights.push_back(H.env);
+  S.off_lights = put(sp.lights.data(), sp.lights.size() * sizeof(DLight));
   // PINE_GPU_FLAG_ORDER_EMBREE: the hierarchy EmbreeAccel walks over the non-mesh shapes (pine_embree_order.h), the meshes' places
   // in `leaf` (tested first), and -- behind the part of the blob that scene-in-LDS variants copy -- the RCPPS estimates
   const bool order_embree = (prm->flags & PINE_GPU_FLAG_ORDER_EMBREE) != 0;
@@ -1340,27 +811,12 @@ static int plan_build(pine_gpu_plan* p, pine_gpu_scene* scene, const pine_gpu_re
   if (upload(p->d_tri_leaf, A.tri_leaf)) return -1;
   std::vector<uint32_t> tri_packets;
   int tri_packet_entries = 0, tri_packet_verts = 0;
-  const bool have_tri_packets = build_tri_packets(A, tri_packets, tri_packet_entries, tri_packet_verts);
-  if (have_tri_packets) {
+  if (build_tri_packets(A, tri_packets, tri_packet_entries, tri_packet_verts)) {
     HIP_OK(POOL_ALLOC(p->d_tri_packets, tri_packets.size() * 4));
     HIP_OK(hipMemcpy(p->d_tri_packets, tri_packets.data(), tri_packets.size() * 4, hipMemcpyHostToDevice));
   }
-  const size_t tri_packet_bytes = tri_packets.size() * 4;
+  sp.tri_packet_bytes = tri_packets.size() * 4;
   if (upload(p->d_tri_attrs, A.tri_attrs)) return -1;
-  // tables: sobol + the selected spp variant
-  int k = 0;
-  while ((1 << k) < spp) k++;
-  if (sobol) k = 0;  // (SobolSampler reads no table; any variant keeps the BlueSampler window loads in bounds)
-  // device layout: sobolT 64 KiB | scramble 128 KiB | rank 128 KiB | 64 bytes = rank[0..63] again, so
-  // a pixel's 40 consecutive ranking bytes never need the reference's modulo wrap
-  HIP_OK(POOL_ALLOC(p->d_tables, 65536 + 262144 + 64));
-  {
-    const std::vector<uint8_t> st = transposed_sobol(g_tables);
-    HIP_OK(hipMemcpy(p->d_tables, st.data(), 65536, hipMemcpyHostToDevice));
-  }
-  HIP_OK(hipMemcpy(p->d_tables + 65536, g_tables.data() + 65536 + size_t(k) * 262144, 262144, hipMemcpyHostToDevice));
-  HIP_OK(hipMemcpy(p->d_tables + 65536 + 262144, g_tables.data() + 65536 + size_t(k) * 262144 + 131072, 64,
-                   hipMemcpyHostToDevice));
 
   S.blob = reinterpret_cast<const uint4*>(p->d_blob);
   S.nodes = reinterpret_cast<const DNode*>(p->d_blob + S.off_nodes);
@@ -1371,52 +827,11 @@ static int plan_build(pine_gpu_plan* p, pine_gpu_scene* scene, const pine_gpu_re
   S.leaf = reinterpret_cast<const DShape*>(p->d_blob + S.off_leaf) - S.top_prim_begin;
   S.lights = reinterpret_cast<const DLight*>(p->d_blob + S.off_lights);
   S.node_ops = reinterpret_cast<const DNodeOp*>(p->d_blob + S.off_node_ops);
-  S.tri_verts = p->d_tri;
-  S.tri_leaf = reinterpret_cast<const float4*>(p->d_tri_leaf);
-  S.tri_attrs = p->d_tri_attrs;
-  S.lds_nodes = 0;
-  S.tri_packets = p->d_tri_packets;
-  S.tri_packet_entries = tri_packet_entries;
-  S.tri_packet_verts = tri_packet_verts;
-  S.lds_tris = 0;
-  S.num_lights = int(light_list.size());
-  S.env_light = H.has_env ? int(light_list.size()) - 1 : -1;
-  S.num_shapes = int(shapes.size());
+  S.tri_verts = p->d_tri, S.tri_leaf = reinterpret_cast<const float4*>(p->d_tri_leaf), S.tri_attrs = p->d_tri_attrs;
+  S.tri_packets = p->d_tri_packets, S.tri_packet_entries = tri_packet_entries, S.tri_packet_verts = tri_packet_verts;
+  S.lds_nodes = 0, S.lds_tris = 0;
+  S.num_lights = int(sp.lights.size()), S.env_light = H.has_env ? int(sp.lights.size()) - 1 : -1, S.num_shapes = int(shapes.size());
   S.cam = H.camera;
-  S.tables.sobol = p->d_tables;
-  S.tables.scramble = p->d_tables + 65536;
-  S.tables.rank = p->d_tables + 65536 + 131072;
-  S.tables.lds_sobol = nullptr;
-  S.tables.lds_tile = nullptr;
-  S.tables.lds_scr = nullptr;
-  S.tables.tile_stride = 0;
-  S.tables.win_lo = 0;
-  S.tables.win_len = 0;
-  S.tables.kind = halton ? 2 : sobol ? 1 : 0;
-  S.tables.halton_primes = nullptr;
-  S.tables.halton_perms = nullptr;
-  if (halton) {
-    const HaltonHostTables& ht = halton_host_tables();
-    const size_t head = size_t(2 * kHaltonDims) * sizeof(int), bytes = head + ht.perms.size() * sizeof(uint16_t);
-    HIP_OK(POOL_ALLOC(p->d_halton, bytes));
-    HIP_OK(hipMemcpy(p->d_halton, ht.primes_and_sums.data(), head, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(p->d_halton + head, ht.perms.data(), ht.perms.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-    S.tables.halton_primes = reinterpret_cast<const int*>(p->d_halton);
-    S.tables.halton_perms = reinterpret_cast<const uint16_t*>(p->d_halton + head);
-  }
-  {
-    // SobolSampler(spp): log2_spp = psl::log2i(spp); init(image_size): nbase4_digits =
-    // log2i(roundup2(max(w, h))) + (log2_spp + 1) / 2   (sampler.h:127-129, sampler.cpp:81-84)
-    int l2 = 0;
-    while ((2 << l2) <= spp) l2++;
-    int res = 1;
-    while (res < std::max(H.camera.W, H.camera.H)) res *= 2;
-    int lr = 0;
-    while ((2 << lr) <= res) lr++;
-    S.tables.sobol_log2_spp = l2;
-    S.tables.sobol_digits = lr + (l2 + 1) / 2;
-  }
-  S.spp = spp;
   S.max_path_length = prm->max_path_length;
   int d_top = 0, d_mesh = 0;
   for (size_t b = 0; b < A.bvhs.size(); b++) {
@@ -1427,15 +842,57 @@ static int plan_build(pine_gpu_plan* p, pine_gpu_scene* scene, const pine_gpu_re
   }
   S.stack_top = d_top;
   S.stack_total = std::max(1, d_top + d_mesh);
-  if (validate_device_scene(A, shapes, dev_materials.size(), light_list, S.stack_top, S.stack_total)) return -1;
-  p->lds_bytes = kLdsFixedBytes + size_t(S.stack_total) * kBlock * sizeof(int);
-  if (p->lds_bytes > 64 * 1024) {
-    set_error("BVH too deep for the LDS traversal stack");
-    return -1;
+  return validate_device_scene(A, shapes, sp.materials.size(), sp.lights, S.stack_top, S.stack_total);
+}
+
+// BlueSampler's tables (sobol + the selected spp variant), HaltonSampler's, SobolSampler's digit counts.
+static int upload_sampler_tables(pine_gpu_plan* p, const std::vector<uint8_t>& tables, const pine_gpu_render_params* prm, int spp) {
+  const bool halton = prm->sampler == PINE_GPU_SAMPLER_HALTON;
+  const bool sobol = prm->sampler == PINE_GPU_SAMPLER_SOBOL || halton;
+  int k = 0;
+  while ((1 << k) < spp) k++;
+  if (sobol) k = 0;  // (SobolSampler reads no table; any variant keeps the BlueSampler window loads in bounds)
+  // device layout: sobolT 64 KiB | scramble 128 KiB | rank 128 KiB | 64 bytes = rank[0..63] again, so
+  // a pixel's 40 consecutive ranking bytes never need the reference's modulo wrap
+  HIP_OK(POOL_ALLOC(p->d_tables, 65536 + 262144 + 64));
+  {
+    const std::vector<uint8_t> st = transposed_sobol(tables);
+    HIP_OK(hipMemcpy(p->d_tables, st.data(), 65536, hipMemcpyHostToDevice));
   }
-  // kernel specialisation: the smallest compiled feature set that covers the scene
+  HIP_OK(hipMemcpy(p->d_tables + 65536, tables.data() + 65536 + size_t(k) * 262144, 262144, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(p->d_tables + 65536 + 262144, tables.data() + 65536 + size_t(k) * 262144 + 131072, 64,
+                   hipMemcpyHostToDevice));
+  DTables& T = p->S.tables;
+  T.sobol = p->d_tables, T.scramble = p->d_tables + 65536, T.rank = p->d_tables + 65536 + 131072;
+  T.lds_sobol = nullptr, T.lds_tile = nullptr, T.lds_scr = nullptr;
+  T.tile_stride = 0, T.win_lo = 0, T.win_len = 0;
+  T.kind = halton ? 2 : sobol ? 1 : 0;
+  T.halton_primes = nullptr, T.halton_perms = nullptr;
+  if (halton) {
+    const HaltonHostTables& ht = halton_host_tables();
+    const size_t head = size_t(2 * kHaltonDims) * sizeof(int), bytes = head + ht.perms.size() * sizeof(uint16_t);
+    HIP_OK(POOL_ALLOC(p->d_halton, bytes));
+    HIP_OK(hipMemcpy(p->d_halton, ht.primes_and_sums.data(), head, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(p->d_halton + head, ht.perms.data(), ht.perms.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+    T.halton_primes = reinterpret_cast<const int*>(p->d_halton), T.halton_perms = reinterpret_cast<const uint16_t*>(p->d_halton + head);
+  }
+  // SobolSampler(spp): log2_spp = psl::log2i(spp); init(image_size): nbase4_digits =
+  // log2i(roundup2(max(w, h))) + (log2_spp + 1) / 2   (sampler.h:127-129, sampler.cpp:81-84)
+  int l2 = 0;
+  while ((2 << l2) <= spp) l2++;
+  int res = 1;
+  while (res < std::max(p->S.cam.W, p->S.cam.H)) res *= 2;
+  int lr = 0;
+  while ((2 << lr) <= res) lr++;
+  T.sobol_log2_spp = l2;
+  T.sobol_digits = lr + (l2 + 1) / 2;
+  return 0;
+}
+
+// The F_* features the scene needs: kernel specialisation takes the smallest compiled feature set that covers them.
+static unsigned scene_features(const SceneParts& sp, const pine_gpu_render_params* prm) {
   unsigned need = 0;
-  for (auto& sh : shapes) {
+  for (auto& sh : sp.shapes) {
     switch (sh.kind) {
       case SHAPE_AABB: need |= F_AABB; break;
       case SHAPE_OBB: need |= F_OBB; break;
@@ -1447,133 +904,188 @@ static int plan_build(pine_gpu_plan* p, pine_gpu_scene* scene, const pine_gpu_re
       default: break;
     }
   }
-  for (auto& m : dev_materials) {
+  for (auto& m : sp.materials) {
     if (m.kind == MAT_UBER || m.kind >= MAT_METAL) need |= F_UBER;  // the microfacet lobes
     if (m.kind == MAT_SUBSURFACE) need |= F_SSS;
   }
-  if (!node_ops.empty()) need |= F_NODES;
-  if (sobol) need |= F_SOBOL;
-  if (order_embree) need |= F_EMBREE;
+  if (!sp.node_ops.empty()) need |= F_NODES;
+  if (prm->sampler == PINE_GPU_SAMPLER_SOBOL || prm->sampler == PINE_GPU_SAMPLER_HALTON) need |= F_SOBOL;
+  if (prm->flags & PINE_GPU_FLAG_ORDER_EMBREE) need |= F_EMBREE;
   // (SobolSampler / HaltonSampler with Subsurface: a BSSRDF walk draws from the sampler at every step and the sampler's dimension
   //  counter outgrows the packed path state -- the F_SSS | F_SOBOL variants keep it in a word of its own: kBigDim)
-  for (auto& L : light_list)
+  for (auto& L : sp.lights)
     if (L.kind != LIGHT_AREA) need |= F_LIGHTS;
-  const bool lds_ok = size_t(S.blob_bytes) <= 32 * 1024 && getenv("PINE_GPU_NO_LDS_SCENE") == nullptr;
+  return need;
+}
+
+// A stage-queued variant's (exact or declared-tolerance) LDS bytes for this scene before the node and triangle caches; 0 when
+// its layout does not fit.
+static size_t queue_variant_lds(const PineKernelVariant& V, const DeviceScene& S, size_t num_nodes, bool lds_ok) {
+  const unsigned F = V.features;
+  if ((F & F_LDS_SCENE) && !lds_ok) return 0;  // (a scene-in-global variant later in the table is the fallback when LDS is short)
+  if ((F & F_LDS_TOP) && num_nodes > 65535) return 0;  // 16-bit stack entries
+  const size_t rest_bytes = size_t(S.blob_bytes - S.off_shapes);
+  if ((F & F_LDS_REST) && rest_bytes > 12 * 1024) return 0;
+  const size_t stack_bytes = std::max(V.min_stack, size_t(S.stack_total) * kQBlock * ((F & F_LDS_TOP) ? sizeof(unsigned short) : sizeof(int)));
+  const size_t lds = V.fixed_lds + stack_bytes + ((F & F_LDS_SCENE) ? size_t(S.blob_bytes) : 0) + ((F & F_LDS_REST) ? rest_bytes : 0);
+  return lds > 160 * 1024 ? 0 : lds;
+}
+
+// LDS left after a stage-queued variant's fixed parts goes to the BVH node cache first, then -- when ALL nodes are in and there
+// is still room -- to the triangle packets.  Measured on the icosphere scene (profiles/HISTORY.md 6.3): packets in place of the
+// 288 deepest nodes change nothing (191.7 vs 190.1 ms), so nodes are never evicted for them.
+// PINE_GPU_LDS_TRIS=0 / 1: never / whenever the packets fit, before the nodes (measurement aid).
+static void place_lds_caches(pine_gpu_plan* p, unsigned F, size_t lds, const FlatAccel& A, const SceneParts& sp, const PlanKnobs& K) {
+  DeviceScene& S = p->S;
+  bool tris = false;
+  if ((F & F_LDS_TOP) && (F & F_MESH) && sp.tri_packet_bytes > 0 && lds < 160 * 1024 && K.lds_tris != 0) {
+    const size_t room = 160 * 1024 - lds;
+    tris = K.lds_tris == 1 ? sp.tri_packet_bytes <= room : sp.tri_packet_bytes + A.nodes.size() * sizeof(DNode) <= room;
+  }
+  p->lds_bytes = lds;
+  S.lds_nodes = 0;
+  S.lds_tris = tris ? 1 : 0;
+  if (S.lds_tris) p->lds_bytes += sp.tri_packet_bytes;
+  if (F & F_LDS_TOP) {
+    S.lds_nodes = int(std::min<size_t>(A.nodes.size(), (160 * 1024 - p->lds_bytes) / sizeof(DNode)));
+    p->lds_bytes += size_t(S.lds_nodes) * sizeof(DNode);
+  }
+}
+
+// The kernel that renders: the first compiled variant that covers `need` -- of the stage-queued kernel when one fits, else of
+// the megakernel; with PINE_GPU_FLAG_FAST one of the few declared-tolerance variants (pine_kernels_fast.hip).
+static int choose_variants(pine_gpu_plan* p, const FlatAccel& A, const SceneParts& sp, const pine_gpu_render_params* prm, unsigned need,
+                           const PlanKnobs& K) {
+  DeviceScene& S = p->S;
+  const bool order_embree = (prm->flags & PINE_GPU_FLAG_ORDER_EMBREE) != 0;
+  p->lds_bytes = kLdsFixedBytes + size_t(S.stack_total) * kBlock * sizeof(int);
+  if (p->lds_bytes > 64 * 1024) {
+    set_error("BVH too deep for the LDS traversal stack");
+    return -1;
+  }
+  const bool lds_ok = size_t(S.blob_bytes) <= 32 * 1024 && !K.no_lds_scene;
   p->variant = -1;
   for (int v = 0; v < kNumVariants; v++) {
     const unsigned F = kVariants[v].features;
     if ((F & need) != need) continue;
     if (((F & F_LDS_SCENE) != 0) != lds_ok) continue;
     if (((F & F_EMBREE) != 0) != order_embree) continue;  // (the order mode's twin variants: never without the flag)
-    if (getenv("PINE_GPU_WPS") && atoi(getenv("PINE_GPU_WPS")) != kVariants[v].waves_per_simd) continue;
     p->variant = v;
     break;
   }
   if (p->variant >= 0 && (kVariants[p->variant].features & F_LDS_SCENE)) p->lds_bytes += size_t(S.blob_bytes);
   // The stage-queued kernel is the default whenever a variant covers the scene and its LDS fits;
   // PINE_GPU_KERNEL=mega forces the lane-owns-a-path kernel, which covers every scene.
-  // LDS left after a variant's fixed parts goes to the BVH node cache first, then -- when ALL nodes are in and there is
-  // still room -- to the triangle packets.  Measured on the icosphere scene (profiles/HISTORY.md 6.3): packets in place of the 288
-  // deepest nodes change nothing (191.7 vs 190.1 ms), so nodes are never evicted for them.
-  // PINE_GPU_LDS_TRIS=0 / 1: never / whenever the packets fit, before the nodes (measurement aid).
-  auto lds_tris_fit = [&](unsigned F, size_t lds) -> bool {
-    if (!(F & F_LDS_TOP) || !(F & F_MESH) || !have_tri_packets || lds >= 160 * 1024) return false;
-    const size_t room = 160 * 1024 - lds;
-    const char* e = getenv("PINE_GPU_LDS_TRIS");
-    if (e && atoi(e) == 0) return false;
-    if (e && atoi(e) == 1) return tri_packet_bytes <= room;
-    return tri_packet_bytes + A.nodes.size() * sizeof(DNode) <= room;
-  };
   p->queue_variant = -1;
-  {
-    const char* ksel = getenv("PINE_GPU_KERNEL");
-    const bool want_queue = !(ksel && std::string(ksel) == "mega");
-    if (want_queue) {
-      const char* no_top = getenv("PINE_GPU_NO_LDS_TOP");  // (measurement aid: keep every node in global memory)
-      for (int v = 0; v < kNumQueueVariants; v++) {
-        const unsigned F = kQueueVariants[v].features;
-        if ((F & need) != need) continue;
-        if (((F & F_VLOG) != 0) != ((prm->flags & PINE_GPU_FLAG_VERTEX_LOG) != 0)) continue;  // (the test hook's twin variants)
-        if (((F & F_EMBREE) != 0) != order_embree) continue;                                   // (the order mode's twin variants)
-        if ((F & F_LDS_SCENE) && !lds_ok) continue;  // (a scene-in-global variant later in the table is the fallback when LDS is short)
-        if ((F & F_LDS_TOP) && A.nodes.size() > 65535) continue;  // 16-bit stack entries
-        const size_t rest_bytes = size_t(S.blob_bytes - S.off_shapes);
-        if ((F & F_LDS_REST) && rest_bytes > 12 * 1024) continue;
-        const size_t stack_bytes = std::max(kQueueVariants[v].min_stack,
-                                            size_t(S.stack_total) * kQBlock * ((F & F_LDS_TOP) ? sizeof(unsigned short) : sizeof(int)));
-        const size_t lds = kQueueVariants[v].fixed_lds + stack_bytes + ((F & F_LDS_SCENE) ? size_t(S.blob_bytes) : 0) +
-                           ((F & F_LDS_REST) ? rest_bytes : 0);
-        if (lds > 160 * 1024) continue;
-        // (measurement aid: PINE_GPU_XSTAGE=1 also passes over the stage-less F_LDS_TOP variants, so that the scene lands on a
-        //  traversal-stage variant whose layout its own kernel -- exact feature set, pine_specialize.h -- then inherits)
-        if ((F & F_LDS_TOP) && !(F & F_XSTAGE) && getenv("PINE_GPU_XSTAGE") && atoi(getenv("PINE_GPU_XSTAGE")) == 1) continue;
-        if (F & F_XSTAGE) {
-          // traversal stages only where refilling pays: a scene with meshes, (nearly) all nodes in this variant's LDS.
-          // PINE_GPU_XSTAGE=0 / 1: never / always (measurement aid, tools/xstage_ab.py).
-          const size_t cached = no_top ? 0 : std::min<size_t>(A.nodes.size(), (160 * 1024 - lds) / sizeof(DNode));
-          bool want = (need & F_MESH) != 0 && cached * 10 >= A.nodes.size() * 9;
-          if (const char* e = getenv("PINE_GPU_XSTAGE")) want = atoi(e) != 0;
-          if (!want) continue;  // (the same feature set without F_XSTAGE follows in the table)
-        }
-        p->queue_variant = v;
-        p->lds_bytes = lds;
-        S.lds_nodes = 0;
-        S.lds_tris = lds_tris_fit(F, lds) ? 1 : 0;
-        if (S.lds_tris) p->lds_bytes += tri_packet_bytes;
-        if (F & F_LDS_TOP) {
-          S.lds_nodes = int(std::min<size_t>(A.nodes.size(), (160 * 1024 - p->lds_bytes) / sizeof(DNode)));
-          if (no_top) S.lds_nodes = 0;
-          p->lds_bytes += size_t(S.lds_nodes) * sizeof(DNode);
-        }
-        break;
-      }
+  for (int v = 0; v < kNumQueueVariants && !K.mega; v++) {
+    const unsigned F = kQueueVariants[v].features;
+    if ((F & need) != need) continue;
+    if (((F & F_VLOG) != 0) != ((prm->flags & PINE_GPU_FLAG_VERTEX_LOG) != 0)) continue;  // (the test hook's twin variants)
+    if (((F & F_EMBREE) != 0) != order_embree) continue;                                   // (the order mode's twin variants)
+    const size_t lds = queue_variant_lds(kQueueVariants[v], S, A.nodes.size(), lds_ok);
+    if (lds == 0) continue;
+    // (measurement aid: PINE_GPU_XSTAGE=1 also passes over the stage-less F_LDS_TOP variants, so that the scene lands on a
+    //  traversal-stage variant whose layout its own kernel -- exact feature set, pine_specialize.h -- then inherits)
+    if ((F & F_LDS_TOP) && !(F & F_XSTAGE) && K.xstage == 1) continue;
+    if (F & F_XSTAGE) {
+      // traversal stages only where refilling pays: a scene with meshes, (nearly) all nodes in this variant's LDS.
+      // PINE_GPU_XSTAGE=0 / 1: never / always (measurement aid, tools/xstage_ab.py).
+      const size_t cached = std::min<size_t>(A.nodes.size(), (160 * 1024 - lds) / sizeof(DNode));
+      bool want = (need & F_MESH) != 0 && cached * 10 >= A.nodes.size() * 9;
+      if (K.xstage != kUnset) want = K.xstage != 0;
+      if (!want) continue;  // (the same feature set without F_XSTAGE follows in the table)
     }
+    p->queue_variant = v;
+    place_lds_caches(p, F, lds, A, sp, K);
+    break;
   }
-
-  if (plan_specialize(p, A, shapes, packed_prims, prm, need)) return -1;
-
   if (p->variant < 0 && p->queue_variant < 0) {  // (only experiment builds lack the all-features megakernel)
     set_error("no kernel variant covers this scene");
     return -1;
   }
-  if (prm->flags & PINE_GPU_FLAG_FAST) {
-    // declared-tolerance arithmetic: one of the few variants pine_kernels_fast.hip compiles, chosen by the same rules
-    int nf = 0;
-    const PineFastVariant* fv = pine_gpu_fast_variants(&nf);
-    p->fast = nullptr;
-    for (int v = 0; v < nf && !p->fast; v++) {
-      const unsigned F = fv[v].features;
-      if ((F & need) != need) continue;
-      if ((F & F_LDS_SCENE) && !lds_ok) continue;
-      if ((F & F_LDS_TOP) && A.nodes.size() > 65535) continue;
-      const size_t rest_bytes = size_t(S.blob_bytes - S.off_shapes);
-      if ((F & F_LDS_REST) && rest_bytes > 12 * 1024) continue;
-      const size_t stack_bytes = std::max(fv[v].min_stack, size_t(S.stack_total) * kQBlock * ((F & F_LDS_TOP) ? sizeof(unsigned short) : sizeof(int)));
-      const size_t lds = fv[v].fixed_lds + stack_bytes + ((F & F_LDS_SCENE) ? size_t(S.blob_bytes) : 0) + ((F & F_LDS_REST) ? rest_bytes : 0);
-      if (lds > 160 * 1024) continue;
-      p->fast = &fv[v];
-      p->lds_bytes = lds;
-      S.lds_nodes = 0;
-      S.lds_tris = lds_tris_fit(F, lds) ? 1 : 0;
-      if (S.lds_tris) p->lds_bytes += tri_packet_bytes;
-      if (F & F_LDS_TOP) {
-        S.lds_nodes = int(std::min<size_t>(A.nodes.size(), (160 * 1024 - p->lds_bytes) / sizeof(DNode)));
-        p->lds_bytes += size_t(S.lds_nodes) * sizeof(DNode);
-      }
-    }
-    if (!p->fast) {
-      set_error("PINE_GPU_FLAG_FAST: no declared-tolerance kernel variant covers this scene (exact mode renders it)");
-      return -1;
-    }
-    p->queue_variant = -1;
+  if (!(prm->flags & PINE_GPU_FLAG_FAST)) return 0;
+  // declared-tolerance arithmetic: one of the few variants pine_kernels_fast.hip compiles, chosen by the same rules
+  int nf = 0;
+  const PineFastVariant* fv = pine_gpu_fast_variants(&nf);
+  p->fast = nullptr;
+  for (int v = 0; v < nf && !p->fast; v++) {
+    const unsigned F = fv[v].features;
+    if ((F & need) != need) continue;
+    const size_t lds = queue_variant_lds(fv[v], S, A.nodes.size(), lds_ok);
+    if (lds == 0) continue;
+    p->fast = &fv[v];
+    place_lds_caches(p, F, lds, A, sp, K);
   }
+  if (!p->fast) {
+    set_error("PINE_GPU_FLAG_FAST: no declared-tolerance kernel variant covers this scene (exact mode renders it)");
+    return -1;
+  }
+  p->queue_variant = -1;
+  return 0;
+}
 
-  // scenes whose materials draw from the per-pixel RNG inside radiance() (Uber with fractional
-  // metallic/transmission: sampler.h:317-324; BSSRDF channel pick: bxdf.cpp:335) make a pixel's
-  // samples sequentially dependent: one item = the whole pixel.
+// Tile classes (WorkParams::serial_tiles): in a scene whose only in-path RNG consumer is the BSSRDF channel pick and whose other
+// materials are Diffuse / Emissive, a path draws from the pixel's RNG only while it has met nothing but Subsurface surfaces --
+// so a pixel none of whose camera rays can reach a Subsurface shape makes NO in-path draw, its samples are independent (RNG
+// state of sample s = the seed advanced 4 s steps, as in a scene without in-path draws) and need not form a chain.
+// Conservative test per 8x8 tile: the world boxes of the Subsurface shapes projected through the pinhole camera, two pixels of
+// margin.  Splits this shard's tiles into those a Subsurface shape may reach (`serial`) and the others (`free_tiles`); false
+// (lists empty) when the camera or the materials rule the test out: a thin lens, a box behind the camera, other materials.
+static bool tile_classes(const SceneHost& H, const SceneParts& sp, const WorkParams& W, std::vector<int>& serial, std::vector<int>& free_tiles) {
+  if (H.camera.len_radius != 0.0f) return false;
+  for (auto& m : sp.materials)
+    if (m.kind != MAT_EMISSIVE && m.kind != MAT_DIFFUSE && m.kind != MAT_SUBSURFACE) return false;
+  // inverse of the camera's linear part (columns x, y, z of c2w), in double
+  const float* c = H.camera.c2w;
+  const double a[3][3] = {{c[0], c[3], c[6]}, {c[1], c[4], c[7]}, {c[2], c[5], c[8]}};  // a[row][col]
+  const double det = a[0][0] * (a[1][1] * a[2][2] - a[1][2] * a[2][1]) - a[0][1] * (a[1][0] * a[2][2] - a[1][2] * a[2][0]) +
+                     a[0][2] * (a[1][0] * a[2][1] - a[1][1] * a[2][0]);
+  if (!(std::fabs(det) > 1e-12) || !(H.camera.fov2d[0] > 0) || !(H.camera.fov2d[1] > 0)) return false;
+  double inv[3][3];
+  inv[0][0] = (a[1][1] * a[2][2] - a[1][2] * a[2][1]) / det, inv[0][1] = (a[0][2] * a[2][1] - a[0][1] * a[2][2]) / det, inv[0][2] = (a[0][1] * a[1][2] - a[0][2] * a[1][1]) / det;
+  inv[1][0] = (a[1][2] * a[2][0] - a[1][0] * a[2][2]) / det, inv[1][1] = (a[0][0] * a[2][2] - a[0][2] * a[2][0]) / det, inv[1][2] = (a[0][2] * a[1][0] - a[0][0] * a[1][2]) / det;
+  inv[2][0] = (a[1][0] * a[2][1] - a[1][1] * a[2][0]) / det, inv[2][1] = (a[0][1] * a[2][0] - a[0][0] * a[2][1]) / det, inv[2][2] = (a[0][0] * a[1][1] - a[0][1] * a[1][0]) / det;
+  // pixel rectangles [x0, x1] x [y0, y1] that the Subsurface shapes can project into
+  struct Rect2 { double x0, y0, x1, y1; };
+  std::vector<Rect2> rects;
+  for (size_t g = 0; g < sp.shapes.size(); g++) {
+    if (sp.materials[size_t(sp.shapes[g].material)].kind != MAT_SUBSURFACE) continue;
+    const HostAABB b = H.geometry_aabb(int(g));
+    Rect2 r{1e300, 1e300, -1e300, -1e300};
+    for (int corner = 0; corner < 8; corner++) {
+      const double P[3] = {double((corner & 1) ? b.upper.x : b.lower.x) - H.camera.position[0], double((corner & 2) ? b.upper.y : b.lower.y) - H.camera.position[1],
+                           double((corner & 4) ? b.upper.z : b.lower.z) - H.camera.position[2]};
+      if (!(std::isfinite(P[0]) && std::isfinite(P[1]) && std::isfinite(P[2]))) return false;
+      const double qx = inv[0][0] * P[0] + inv[0][1] * P[1] + inv[0][2] * P[2], qy = inv[1][0] * P[0] + inv[1][1] * P[1] + inv[1][2] * P[2],
+                   qz = inv[2][0] * P[0] + inv[2][1] * P[1] + inv[2][2] * P[2];
+      if (!(qz > 1e-4)) return false;  // a corner at or behind the camera plane: no bounded projection
+      const double fx = ((qx / qz) / H.camera.fov2d[0] * 0.5 + 0.5) * H.camera.W, fy = ((qy / qz) / H.camera.fov2d[1] * 0.5 + 0.5) * H.camera.H;
+      r.x0 = std::min(r.x0, fx), r.y0 = std::min(r.y0, fy), r.x1 = std::max(r.x1, fx), r.y1 = std::max(r.y1, fy);
+    }
+    // margin: the pixel's own extent (jitter in [0, 1)) + two pixels for every rounding on the way
+    r.x0 -= 3.0, r.y0 -= 3.0, r.x1 += 2.0, r.y1 += 2.0;
+    rects.push_back(r);
+  }
+  for (int lt = 0; lt < W.num_local_tiles; lt++) {
+    const int tile = lt * W.shard_world + W.shard_rank;
+    const int tx = tile % W.tiles_x, ty = tile / W.tiles_x;
+    const double x0 = tx * kTile, y0 = ty * kTile, x1 = x0 + kTile, y1 = y0 + kTile;
+    bool touched = false;
+    for (const Rect2& r : rects)
+      if (x0 <= r.x1 && x1 >= r.x0 && y0 <= r.y1 && y1 >= r.y0) touched = true;
+    (touched ? serial : free_tiles).push_back(tile);
+  }
+  return true;
+}
+
+// The work decomposition: tiles of this shard, samples per work item, tile classes.  Scenes whose materials draw from the
+// per-pixel RNG inside radiance() (Uber with fractional metallic/transmission: sampler.h:317-324; BSSRDF channel pick:
+// bxdf.cpp:335) make a pixel's samples sequentially dependent: one item = the whole pixel (p->serial_rng).
+static int choose_items(pine_gpu_plan* p, const SceneHost& H, const SceneParts& sp, const pine_gpu_render_params* prm, int spp, const PlanKnobs& K,
+                        bool& uber_rng) {
   bool in_path_rng = false;
-  bool uber_rng = false;  // ... at any Uber vertex of a path, whatever came before it
-  for (auto& m : dev_materials) {
+  uber_rng = false;  // ... at any Uber vertex of a path, whatever came before it
+  for (auto& m : sp.materials) {
     if (m.kind == MAT_SUBSURFACE) in_path_rng = true;
     if (m.kind == MAT_UBER && (m.prog[2] >= 0 || m.prog[3] >= 0)) uber_rng = true;  // value known only at the surface
     if (m.kind == MAT_UBER) {
@@ -1583,13 +1095,14 @@ static int plan_build(pine_gpu_plan* p, pine_gpu_scene* scene, const pine_gpu_re
   }
   in_path_rng |= uber_rng;
   p->serial_rng = in_path_rng;
+  const bool spp_pow2 = (spp & (spp - 1)) == 0;  // (BlueSampler's effective spp always is; SobolSampler / HaltonSampler take any count)
+  const unsigned qf = p->fast ? p->fast->features : p->queue_variant >= 0 ? kQueueVariants[p->queue_variant].features : 0u;
   int kspi = prm->samples_per_item;
   if (in_path_rng) kspi = spp;
   else if (kspi <= 0) {
     // stage-queued kernel: two samples per item for the scene-in-LDS variants (cbox-class scenes, all pixels alike: half the
     // checkpoint prepass and hand-outs, C2 13.93 -> 13.75 ms per step, C3 69.9 -> 68.4), one where pixels differ a lot
     // (10 000 cones: 8.06 ms at one, 8.52 at two); the megakernel four
-    const unsigned qf = p->fast ? p->fast->features : p->queue_variant >= 0 ? kQueueVariants[p->queue_variant].features : 0u;
     kspi = (p->queue_variant >= 0 || p->fast) ? ((qf & F_LDS_SCENE) ? std::min(spp, 2) : 1) : std::min(spp, 4);
   }
   if (kspi > spp) kspi = spp;
@@ -1620,80 +1133,22 @@ static int plan_build(pine_gpu_plan* p, pine_gpu_scene* scene, const pine_gpu_re
   W.total_items = (unsigned long long)W.num_local_tiles * W.items_per_pixel * 64ull;
   W.tile_order = nullptr;
   W.serial_tiles = 0;
-  {
-    // Tile classes (WorkParams::serial_tiles): in a scene whose only in-path RNG consumer is the BSSRDF channel pick and
-    // whose other materials are Diffuse / Emissive, a path draws from the pixel's RNG only while it has met nothing but
-    // Subsurface surfaces -- so a pixel none of whose camera rays can reach a Subsurface shape makes NO in-path draw, its
-    // samples are independent (RNG state of sample s = the seed advanced 4 s steps, as in a scene without in-path draws)
-    // and need not form a chain.  Conservative test per 8x8 tile: the world boxes of the Subsurface shapes projected
-    // through the pinhole camera, two pixels of margin.  Everything else (thin lens, a box behind the camera, other
-    // materials, the megakernel) keeps one whole-pixel item per pixel.  PINE_GPU_NO_TILE_CLASSES: off (measurement aid).
-    const unsigned qf = p->queue_variant >= 0 ? kQueueVariants[p->queue_variant].features : p->fast ? p->fast->features : 0u;
-    bool ok = in_path_rng && !uber_rng && (qf & F_SSS) != 0 && H.camera.len_radius == 0.0f && getenv("PINE_GPU_NO_TILE_CLASSES") == nullptr &&
-              getenv("PINE_GPU_NO_FORK") == nullptr && spp > 1 && spp_pow2;  // (the independent class splits a pixel's samples by shifts and masks)
-    for (auto& m : dev_materials)
-      if (m.kind != MAT_EMISSIVE && m.kind != MAT_DIFFUSE && m.kind != MAT_SUBSURFACE) ok = false;
-    if (ok) {
-      // inverse of the camera's linear part (columns x, y, z of c2w), in double
-      const float* c = H.camera.c2w;
-      const double a[3][3] = {{c[0], c[3], c[6]}, {c[1], c[4], c[7]}, {c[2], c[5], c[8]}};  // a[row][col]
-      const double det = a[0][0] * (a[1][1] * a[2][2] - a[1][2] * a[2][1]) - a[0][1] * (a[1][0] * a[2][2] - a[1][2] * a[2][0]) +
-                         a[0][2] * (a[1][0] * a[2][1] - a[1][1] * a[2][0]);
-      if (!(std::fabs(det) > 1e-12) || !(H.camera.fov2d[0] > 0) || !(H.camera.fov2d[1] > 0)) ok = false;
-      double inv[3][3];
-      if (ok) {
-        inv[0][0] = (a[1][1] * a[2][2] - a[1][2] * a[2][1]) / det, inv[0][1] = (a[0][2] * a[2][1] - a[0][1] * a[2][2]) / det, inv[0][2] = (a[0][1] * a[1][2] - a[0][2] * a[1][1]) / det;
-        inv[1][0] = (a[1][2] * a[2][0] - a[1][0] * a[2][2]) / det, inv[1][1] = (a[0][0] * a[2][2] - a[0][2] * a[2][0]) / det, inv[1][2] = (a[0][2] * a[1][0] - a[0][0] * a[1][2]) / det;
-        inv[2][0] = (a[1][0] * a[2][1] - a[1][1] * a[2][0]) / det, inv[2][1] = (a[0][1] * a[2][0] - a[0][0] * a[2][1]) / det, inv[2][2] = (a[0][0] * a[1][1] - a[0][1] * a[1][0]) / det;
-      }
-      // pixel rectangles [x0, x1] x [y0, y1] that the Subsurface shapes can project into
-      struct Rect2 { double x0, y0, x1, y1; };
-      std::vector<Rect2> rects;
-      for (size_t g = 0; ok && g < shapes.size(); g++) {
-        if (dev_materials[size_t(shapes[g].material)].kind != MAT_SUBSURFACE) continue;
-        const HostAABB b = H.geometry_aabb(int(g));
-        Rect2 r{1e300, 1e300, -1e300, -1e300};
-        for (int corner = 0; corner < 8 && ok; corner++) {
-          const double P[3] = {double((corner & 1) ? b.upper.x : b.lower.x) - H.camera.position[0], double((corner & 2) ? b.upper.y : b.lower.y) - H.camera.position[1],
-                               double((corner & 4) ? b.upper.z : b.lower.z) - H.camera.position[2]};
-          if (!(std::isfinite(P[0]) && std::isfinite(P[1]) && std::isfinite(P[2]))) { ok = false; break; }
-          const double qx = inv[0][0] * P[0] + inv[0][1] * P[1] + inv[0][2] * P[2], qy = inv[1][0] * P[0] + inv[1][1] * P[1] + inv[1][2] * P[2],
-                       qz = inv[2][0] * P[0] + inv[2][1] * P[1] + inv[2][2] * P[2];
-          if (!(qz > 1e-4)) { ok = false; break; }  // a corner at or behind the camera plane: no bounded projection
-          const double fx = ((qx / qz) / H.camera.fov2d[0] * 0.5 + 0.5) * H.camera.W, fy = ((qy / qz) / H.camera.fov2d[1] * 0.5 + 0.5) * H.camera.H;
-          r.x0 = std::min(r.x0, fx), r.y0 = std::min(r.y0, fy), r.x1 = std::max(r.x1, fx), r.y1 = std::max(r.y1, fy);
-        }
-        // margin: the pixel's own extent (jitter in [0, 1)) + two pixels for every rounding on the way
-        r.x0 -= 3.0, r.y0 -= 3.0, r.x1 += 2.0, r.y1 += 2.0;
-        rects.push_back(r);
-      }
-      if (ok) {
-        std::vector<int> serial, free_tiles;
-        for (int lt = 0; lt < W.num_local_tiles; lt++) {
-          const int tile = lt * W.shard_world + W.shard_rank;
-          const int tx = tile % W.tiles_x, ty = tile / W.tiles_x;
-          const double x0 = tx * kTile, y0 = ty * kTile, x1 = x0 + kTile, y1 = y0 + kTile;
-          bool touched = false;
-          for (const Rect2& r : rects)
-            if (x0 <= r.x1 && x1 >= r.x0 && y0 <= r.y1 && y1 >= r.y0) touched = true;
-          (touched ? serial : free_tiles).push_back(tile);
-        }
-        if (!free_tiles.empty() && !serial.empty()) {
-          p->tile_order = serial;
-          p->tile_order.insert(p->tile_order.end(), free_tiles.begin(), free_tiles.end());
-          W.serial_tiles = int(serial.size());
-          // the independent class: one sample per item, RNG checkpoints (the Subsurface variants are F_LDS_TOP ones)
-          W.samples_per_item = 1;
-          W.items_per_pixel = spp;
-          W.log2_items_per_pixel = 0;
-          while ((1 << W.log2_items_per_pixel) < W.items_per_pixel) W.log2_items_per_pixel++;
-          W.total_items = (unsigned long long)W.serial_tiles * 64ull + (unsigned long long)(W.num_local_tiles - W.serial_tiles) * W.items_per_pixel * 64ull;
-        } else if (serial.empty()) {
-          // no camera ray can reach a Subsurface shape from this shard's tiles: nothing to do here, the scene stays
-          // "one item per pixel" (rare, and a launch without chains would need the checkpoint prepass for every tile)
-        }
-      }
-    }
+  // Everything but the Subsurface variants, Diffuse / Emissive scenes (the megakernel among them) keeps one whole-pixel item
+  // per pixel; so does a shard none of whose tiles a Subsurface shape can reach (rare, and a launch without chains would need
+  // the checkpoint prepass for every tile).  PINE_GPU_NO_TILE_CLASSES: off (measurement aid).
+  std::vector<int> serial, free_tiles;
+  if (in_path_rng && !uber_rng && (qf & F_SSS) != 0 && !K.no_tile_classes && !K.no_fork && spp > 1 &&
+      spp_pow2 &&  // (the independent class splits a pixel's samples by shifts and masks)
+      tile_classes(H, sp, W, serial, free_tiles) && !free_tiles.empty() && !serial.empty()) {
+    p->tile_order = serial;
+    p->tile_order.insert(p->tile_order.end(), free_tiles.begin(), free_tiles.end());
+    W.serial_tiles = int(serial.size());
+    // the independent class: one sample per item, RNG checkpoints (the Subsurface variants are F_LDS_TOP ones)
+    W.samples_per_item = 1;
+    W.items_per_pixel = spp;
+    W.log2_items_per_pixel = 0;
+    while ((1 << W.log2_items_per_pixel) < W.items_per_pixel) W.log2_items_per_pixel++;
+    W.total_items = (unsigned long long)W.serial_tiles * 64ull + (unsigned long long)(W.num_local_tiles - W.serial_tiles) * W.items_per_pixel * 64ull;
   }
   // packing limits of the kernels: pixel coordinates travel as 16 + 16 bits, the sample-buffer index of a
   // context as 32 bits
@@ -1705,49 +1160,55 @@ static int plan_build(pine_gpu_plan* p, pine_gpu_scene* scene, const pine_gpu_re
     set_error("film pixels x samples per pixel of one shard must stay below 2^32 (render in several shards)");
     return -1;
   }
-  {
-    double budget_s = 30.0;
-    if (const char* e = getenv("PINE_GPU_IDLE_BUDGET_S")) budget_s = atof(e) > 0 ? atof(e) : budget_s;
-    W.idle_budget_ticks = (unsigned long long)(budget_s * 100e6);  // wall_clock64(): 100 MHz
-  }
+  return 0;
+}
+
+// The scheduling defaults of the kernels (WorkParams), measurement aids applied.
+static void schedule_params(pine_gpu_plan* p, const FlatAccel& A, const pine_gpu_render_params* prm, bool uber_rng, const PlanKnobs& K) {
+  WorkParams& W = p->W;
+  const bool in_path_rng = p->serial_rng;
+  W.idle_budget_ticks = (unsigned long long)(K.idle_budget_s * 100e6);  // wall_clock64(): 100 MHz
   W.debug_force_bail = (prm->flags & PINE_GPU_FLAG_DEBUG_FORCE_BAIL) ? 1 : 0;
   // Traversal stages of the X variants (pine_queue_kernel.h): a wave goes to retire / refill its lanes when fewer than
   // trav_min_lanes of them are still travelling, at the earliest trav_min_trips trips after the last time.  Measured
   // (profiles/HISTORY.md 6.3): refilling pays when (nearly) the whole BVH sits in LDS (icosphere scene: 212 -> 185 ms); when most node
   // fetches go to L2 it costs -- the rays a wave picks up later are not the neighbours of the ones it has, and the
   // traversal waits on memory (10 000 cones: 9.8 ms without, 10.9 ms with) -- so there a wave runs its rays to the end.
-  W.trav_min_lanes = (S.lds_nodes > 0 && size_t(S.lds_nodes) * 10 >= A.nodes.size() * 9) ? 48 : 0;  // (nearly) all nodes in LDS
+  W.trav_min_lanes = (p->S.lds_nodes > 0 && size_t(p->S.lds_nodes) * 10 >= A.nodes.size() * 9) ? 48 : 0;  // (nearly) all nodes in LDS
   W.trav_min_trips = 8;
   // (a kernel with the top level baked in, pine_specialize.h: most rays end in the code part and free their lanes at once;
   //  refilling after three trips instead of eight: C5 107.3 -> 100.2 ms)
   if (!p->spec_request.baked.empty() && (p->spec_request.features & F_XSTAGE)) W.trav_min_trips = 3;
-  if (const char* e = getenv("PINE_GPU_TRAV_MIN_LANES")) W.trav_min_lanes = atoi(e);
-  if (const char* e = getenv("PINE_GPU_TRAV_MIN_TRIPS")) W.trav_min_trips = atoi(e) > 0 ? atoi(e) : 1;
+  if (K.trav_min_lanes != kUnset) W.trav_min_lanes = K.trav_min_lanes;
+  if (K.trav_min_trips != kUnset) W.trav_min_trips = K.trav_min_trips > 0 ? K.trav_min_trips : 1;
   // Subsurface is the only in-path user of the RNG and only before a path's first non-delta bounce: such a path hands its
   // pixel's next sample on when it has made that bounce (pine_queue_kernel.h, "sample tokens")
-  W.fork_sealed = (in_path_rng && !uber_rng && getenv("PINE_GPU_NO_FORK") == nullptr) ? 1 : 0;
+  W.fork_sealed = (in_path_rng && !uber_rng && !K.no_fork) ? 1 : 0;
   // ... and then a workgroup keeps at most 320 pixels in flight (each with one unsealed path; the other contexts trace the
   // sealed rest of earlier samples): when the work-item pool runs dry little is left half-done, so the workgroups end closer
   // together (C5: 178 -> 171 ms; 192 ... 384 within 1 %, 512 and more as without a limit)
   W.max_pixels = W.fork_sealed ? 320 : (1 << 20);
-  if (const char* e = getenv("PINE_GPU_MAX_PIXELS")) W.max_pixels = atoi(e) > 0 ? atoi(e) : W.max_pixels;
+  if (K.max_pixels > 0) W.max_pixels = K.max_pixels;
   // A workgroup claims 512 items at a time; when an item is a pixel's whole sample sequence (serial-RNG scenes) that is
   // tens of milliseconds of its time, and the last claims decide when the launch ends: one 8x8 tile at a time there.
   W.pick_spins = 8;
   W.fair_period = 8;
-  if (const char* e = getenv("PINE_GPU_FAIR_PERIOD")) W.fair_period = atoi(e);
-  if (const char* e = getenv("PINE_GPU_PICK_SPINS")) W.pick_spins = atoi(e) > 0 ? atoi(e) : 1;
+  if (K.fair_period != kUnset) W.fair_period = K.fair_period;
   W.pool_items = in_path_rng ? 64 : 512;
-  if (const char* e = getenv("PINE_GPU_POOL_ITEMS")) W.pool_items = atoi(e) > 0 ? atoi(e) : W.pool_items;
+  if (K.pool_items > 0) W.pool_items = K.pool_items;
   if (W.serial_tiles > 0) W.pool_items = 64;  // tile classes: a claim never straddles the boundary between the classes (a multiple of 64)
   W.progress = nullptr;
   W.vertex_log = nullptr;
+}
+
+// The launch shape (grid, work-item claims) and every buffer the launches use.
+static int size_and_allocate(pine_gpu_plan* p, const pine_gpu_render_params* prm, int spp, const PlanKnobs& K) {
+  WorkParams& W = p->W;
   if (prm->flags & PINE_GPU_FLAG_PROGRESS) {
     HIP_OK(hipHostMalloc((void**)&p->h_progress, sizeof(unsigned long long), hipHostMallocMapped));
     *p->h_progress = 0;
     HIP_OK(hipHostGetDevicePointer((void**)&W.progress, p->h_progress, 0));
   }
-
   hipDeviceProp_t prop;
   HIP_OK(hipGetDeviceProperties(&prop, prm->device));
   int blocks_per_cu = 0;
@@ -1762,14 +1223,12 @@ static int plan_build(pine_gpu_plan* p, pine_gpu_scene* scene, const pine_gpu_re
   }
   if (blocks_per_cu < 1) blocks_per_cu = 1;
   if (blocks_per_cu > 8) blocks_per_cu = 8;
-  const char* env_bpc = getenv("PINE_GPU_BLOCKS_PER_CU");
-  if (env_bpc && atoi(env_bpc) > 0) blocks_per_cu = atoi(env_bpc);
   unsigned long long want = (W.total_items + kBlock - 1) / kBlock;
   const int qctx = p->fast ? p->fast->ctx : p->queue_variant >= 0 ? kQueueVariants[p->queue_variant].ctx : 0;
   if (queued) want = (W.total_items + qctx - 1) / qctx;
   p->grid = int(std::min<unsigned long long>(want, (unsigned long long)prop.multiProcessorCount * blocks_per_cu));
   if (p->grid < 1) p->grid = 1;
-  if (!in_path_rng && getenv("PINE_GPU_POOL_ITEMS") == nullptr) {
+  if (!p->serial_rng && K.pool_items == kUnset) {
     // work-item claims of the stage-queued kernel: 1/32 of a workgroup's share, between 512 and 2048 (a claim is a run of
     // neighbouring tiles: larger ones keep a workgroup's camera rays together and are fewer -- 10 000 cones 8.00 -> 7.88 ms
     // at 2048, 7.81 at 4096, 8.4 at 8192 where the last claims unbalance the end; cbox indifferent up to 2048)
@@ -1781,7 +1240,7 @@ static int plan_build(pine_gpu_plan* p, pine_gpu_scene* scene, const pine_gpu_re
 
   if (W.items_per_pixel > 1)
     HIP_OK(POOL_ALLOC(p->d_ckpt, (size_t)(W.num_local_tiles - W.serial_tiles) * W.items_per_pixel * 64 * sizeof(ulonglong2)));
-    p->ckpt_every_launch = getenv("PINE_GPU_CKPT_EVERY_LAUNCH") && atoi(getenv("PINE_GPU_CKPT_EVERY_LAUNCH")) != 0;
+  p->ckpt_every_launch = K.ckpt_every_launch;
   if (!p->tile_order.empty()) {
     HIP_OK(POOL_ALLOC(p->d_tile_order, p->tile_order.size() * sizeof(int)));
     HIP_OK(hipMemcpy(p->d_tile_order, p->tile_order.data(), p->tile_order.size() * sizeof(int), hipMemcpyHostToDevice));
@@ -1800,6 +1259,43 @@ static int plan_build(pine_gpu_plan* p, pine_gpu_scene* scene, const pine_gpu_re
   if (p->timed)
     for (auto& slot : p->ev)
       for (auto& e : slot) HIP_OK(hipEventCreate(&e));
+  return 0;
+}
+
+static int plan_build(pine_gpu_plan* p, pine_gpu_scene* scene, const pine_gpu_render_params* prm) {
+  const PlanKnobs K = read_knobs();
+  SceneHost& H = scene_host(scene);
+  const int spp = check_params(H, prm);
+  if (spp < 0) return -1;
+  TableBlob tables_blob;
+  if (load_tables(tables_blob)) return -1;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+    set_error("no HIP device available: the PathIntegrator hot path requires an AMD GPU (no CPU fallback)");
+    return -1;
+  }
+  HIP_OK(hipSetDevice(prm->device));
+  p->device = prm->device;
+  p->params = *prm;
+  const auto t_build0 = std::chrono::steady_clock::now();
+  if (!H.accel.built) {
+    H.build_on_device = (prm->flags & PINE_GPU_FLAG_DEVICE_BVH) ? prm->device : -1;
+    H.build_accel();
+  }
+  const auto t_build1 = std::chrono::steady_clock::now();
+  p->accel_build_ms = std::chrono::duration<float, std::milli>(t_build1 - t_build0).count();
+  p->accel_on_device = H.built_on_device;
+  const FlatAccel& A = H.accel;
+
+  SceneParts sp;
+  if (assemble_scene(p, H, prm, sp) || upload_sampler_tables(p, *tables_blob, prm, spp)) return -1;
+  p->S.spp = spp;
+  const unsigned need = scene_features(sp, prm);
+  if (choose_variants(p, A, sp, prm, need, K) || plan_specialize(p, A, sp.shapes, sp.packed_prims, prm, need, K)) return -1;
+  bool uber_rng = false;
+  if (choose_items(p, H, sp, prm, spp, K, uber_rng)) return -1;
+  schedule_params(p, A, prm, uber_rng, K);
+  if (size_and_allocate(p, prm, spp, K)) return -1;
   HIP_OK(hipDeviceSynchronize());
   p->upload_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_build1).count();
   return 0;
@@ -1894,24 +1390,6 @@ void pine_gpu_release_cached_memory(void) {
 
 int pine_gpu_plan_launch(pine_gpu_plan* p, void* film_dev, void* stream) { return plan_launch(p, film_dev, stream, false); }
 int pine_gpu_plan_launch_packed(pine_gpu_plan* p, void* slab_dev, void* stream) { return plan_launch(p, slab_dev, stream, true); }
-
-int64_t pine_gpu_packed_slab_floats(int film_w, int film_h, int world) {
-  if (film_w <= 0 || film_h <= 0 || world < 1) return -1;
-  const int64_t tiles = int64_t((film_w + kTile - 1) / kTile) * ((film_h + kTile - 1) / kTile);
-  return (tiles + world - 1) / world * 64 * 4;
-}
-
-int pine_gpu_packed_offset(int film_w, int film_h, int world, int x, int y, int* rank_out, int64_t* float4_index_out) {
-  if (film_w <= 0 || film_h <= 0 || world < 1 || x < 0 || y < 0 || x >= film_w || y >= film_h) {
-    set_error("bad argument");
-    return -1;
-  }
-  const int tiles_x = (film_w + kTile - 1) / kTile;
-  const int tile = (y / kTile) * tiles_x + x / kTile;
-  if (rank_out) *rank_out = tile % world;
-  if (float4_index_out) *float4_index_out = int64_t(tile / world) * 64 + (y % kTile) * kTile + x % kTile;
-  return 0;
-}
 
 int pine_gpu_film_unpack(int film_w, int film_h, int world, int device, const void* slabs_dev, void* film_dev, void* stream_) {
   if (!slabs_dev || !film_dev || film_w <= 0 || film_h <= 0 || world < 1) {
@@ -2044,36 +1522,6 @@ int pine_gpu_plan_debug_sections(pine_gpu_plan* p, uint64_t out[16]) {
     if (rh[i]) fprintf(stderr, "region %2d: entries %llu avg active lanes %.2f\n", i, rh[i], double(rl[i]) / double(rh[i]));
 #endif
   return 0;
-}
-
-int pine_gpu_plan_test_traverse_baked(pine_gpu_plan* p, const float* rays, int64_t nrays, uint32_t* out) {
-  if (!p || !rays || !out || nrays <= 0) {
-    set_error("null argument");
-    return -1;
-  }
-  if (!p->spec_module || !p->spec_baked) {
-    set_error("the plan has no baked scene (PINE_GPU_FLAG_SPECIALIZE, a scene that qualifies)");
-    return -1;
-  }
-  HIP_OK(hipSetDevice(p->device));
-  hipFunction_t fn;
-  HIP_OK(hipModuleGetFunction(&fn, p->spec_module, "pine_baked_traverse_test"));
-  float* dr = nullptr;
-  unsigned* dout = nullptr;
-  int rc = -1;
-  do {
-    if (hipMalloc((void**)&dr, size_t(nrays) * 32) != hipSuccess || hipMalloc((void**)&dout, size_t(nrays) * 16) != hipSuccess) break;
-    if (hipMemcpy(dr, rays, size_t(nrays) * 32, hipMemcpyHostToDevice) != hipSuccess) break;
-    long long n = nrays;
-    void* args[] = {&dr, &n, &dout};
-    if (hipModuleLaunchKernel(fn, unsigned((nrays + 63) / 64), 1, 1, 64, 1, 1, 0, nullptr, args, nullptr) != hipSuccess) break;
-    if (hipMemcpy(out, dout, size_t(nrays) * 16, hipMemcpyDeviceToHost) != hipSuccess) break;
-    rc = 0;
-  } while (0);
-  if (rc) set_error(std::string("pine_gpu_plan_test_traverse_baked: ") + hipGetErrorString(hipGetLastError()));
-  (void)hipFree(dr);
-  (void)hipFree(dout);
-  return rc;
 }
 
 int64_t pine_gpu_plan_vertex_log(pine_gpu_plan* p, float* out, int64_t capacity) {
@@ -2295,307 +1743,4 @@ int pine_gpu_path_render_multi(pine_gpu_scene* scene, const pine_gpu_render_para
   }
   return pine_gpu_path_render_devices(scene, prm, list, n, film_out);
 }
-
-/* Test hook (host only): the reference's Lomuto partition as a sequential swap loop (perm_seq) and as the prefix-sum +
- * pointer-jumping formulation the device build uses (perm_par); returns the number of trues, < 0 if the two disagree. */
-int pine_gpu_test_lomuto(const unsigned char* pred, int n, int* perm_seq, int* perm_par) {
-  if (!pred || !perm_seq || !perm_par || n < 0) {
-    set_error("bad argument");
-    return -1;
-  }
-  for (int i = 0; i < n; i++) perm_seq[i] = i;
-  const int a = build_lomuto(pred, perm_seq, n);
-  const int b = build_lomuto_by_chains(pred, perm_par, n);
-  if (a != b || memcmp(perm_seq, perm_par, size_t(n) * sizeof(int)) != 0) {
-    set_error("the two partition formulations disagree");
-    return -2;
-  }
-  return a;
-}
-
-// ---- device unit-test hooks -------------------------------------------------------------------
-static int need_device(int device) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    set_error("no HIP device available");
-    return -1;
-  }
-  HIP_OK(hipSetDevice(device));
-  return 0;
-}
-int pine_gpu_test_sincos(int device, const float* x, int64_t n, float* s, float* c) {
-  if (need_device(device)) return -1;
-  float *dx, *ds, *dc;
-  HIP_OK(hipMalloc((void**)&dx, n * 4));
-  HIP_OK(hipMalloc((void**)&ds, n * 4));
-  HIP_OK(hipMalloc((void**)&dc, n * 4));
-  HIP_OK(hipMemcpy(dx, x, n * 4, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(test_sincos_kernel, dim3(unsigned((n + 255) / 256)), dim3(256), 0, 0, dx, (long long)n, ds, dc);
-  HIP_OK(hipMemcpy(s, ds, n * 4, hipMemcpyDeviceToHost));
-  HIP_OK(hipMemcpy(c, dc, n * 4, hipMemcpyDeviceToHost));
-  hipFree(dx);
-  hipFree(ds);
-  hipFree(dc);
-  return 0;
-}
-int pine_gpu_test_powlog(int device, const float* x, const float* y, int64_t n, float* pw, float* lg) {
-  if (need_device(device)) return -1;
-  float *dx, *dy, *dp, *dl;
-  HIP_OK(hipMalloc((void**)&dx, n * 4));
-  HIP_OK(hipMalloc((void**)&dy, n * 4));
-  HIP_OK(hipMalloc((void**)&dp, n * 4));
-  HIP_OK(hipMalloc((void**)&dl, n * 4));
-  HIP_OK(hipMemcpy(dx, x, n * 4, hipMemcpyHostToDevice));
-  HIP_OK(hipMemcpy(dy, y, n * 4, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(test_powlog_kernel, dim3(unsigned((n + 255) / 256)), dim3(256), 0, 0, dx, dy, (long long)n, dp, dl);
-  HIP_OK(hipMemcpy(pw, dp, n * 4, hipMemcpyDeviceToHost));
-  HIP_OK(hipMemcpy(lg, dl, n * 4, hipMemcpyDeviceToHost));
-  hipFree(dx);
-  hipFree(dy);
-  hipFree(dp);
-  hipFree(dl);
-  return 0;
-}
-int pine_gpu_test_atan(int device, const float* y, const float* x, int64_t n, float* at2, float* ac) {
-  if (need_device(device)) return -1;
-  float *dy, *dx, *da, *dc;
-  HIP_OK(hipMalloc((void**)&dy, n * 4));
-  HIP_OK(hipMalloc((void**)&dx, n * 4));
-  HIP_OK(hipMalloc((void**)&da, n * 4));
-  HIP_OK(hipMalloc((void**)&dc, n * 4));
-  HIP_OK(hipMemcpy(dy, y, n * 4, hipMemcpyHostToDevice));
-  HIP_OK(hipMemcpy(dx, x, n * 4, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(test_atan_kernel, dim3(unsigned((n + 255) / 256)), dim3(256), 0, 0, dy, dx, (long long)n, da, dc);
-  HIP_OK(hipMemcpy(at2, da, n * 4, hipMemcpyDeviceToHost));
-  HIP_OK(hipMemcpy(ac, dc, n * 4, hipMemcpyDeviceToHost));
-  hipFree(dy);
-  hipFree(dx);
-  hipFree(da);
-  hipFree(dc);
-  return 0;
-}
-
-// ---- pine_gpu_test_math_*: the scalar functions over bit patterns against their references (pine_math_check.h) -----
-extern "C++" {
-namespace {
-template <int FN>
-void math_launch(const uint32_t* a, const uint32_t* b, const uint32_t* c, uint32_t fixed, int swept, uint32_t first,
-                 uint32_t stride, long long n, uint32_t* out) {
-  hipLaunchKernelGGL(test_math_kernel<FN>, dim3(unsigned((n + 255) / 256)), dim3(256), 0, 0, a, b, c, fixed, swept, first,
-                     stride, n, out);
-}
-using MathLaunch = void (*)(const uint32_t*, const uint32_t*, const uint32_t*, uint32_t, int, uint32_t, uint32_t, long long,
-                            uint32_t*);
-template <int... FN>
-constexpr std::array<MathLaunch, sizeof...(FN)> math_launch_table(std::integer_sequence<int, FN...>) {
-  return {math_launch<FN>...};
-}
-constexpr std::array<MathLaunch, PINE_GPU_MATH_COUNT> kMathLaunch =
-    math_launch_table(std::make_integer_sequence<int, PINE_GPU_MATH_COUNT>());
-}  // namespace
-}  // extern "C++"
-
-int pine_gpu_test_math_eval(int device, int fn, const uint32_t* a, const uint32_t* b, const uint32_t* c, int64_t n, uint32_t* got) {
-  if (device < 0) return math_check::eval_host_arrays(fn, a, b, c, n, got);
-  if (math_check::bad_args(fn, n, a, b, c)) return -1;
-  if (!got) {
-    set_error("bad argument");
-    return -1;
-  }
-  if (need_device(device)) return -1;
-  const int w = math_width(fn), ar = math_arity(fn);
-  const int64_t m = std::max<int64_t>(1, std::min(n, math_check::kChunk));
-  uint32_t* d[4] = {nullptr, nullptr, nullptr, nullptr};
-  int rc = 0;
-  for (int k = 0; k < 4 && !rc; k++)
-    if ((k < ar || k == 3) && hipMalloc((void**)&d[k], m * 4 * (k == 3 ? w : 1)) != hipSuccess) rc = -1;
-  const uint32_t* src[3] = {a, b, c};
-  for (int64_t i0 = 0; i0 < n && !rc; i0 += m) {
-    const int64_t len = std::min(m, n - i0);
-    for (int k = 0; k < ar && !rc; k++)
-      if (hipMemcpy(d[k], src[k] + i0, len * 4, hipMemcpyHostToDevice) != hipSuccess) rc = -1;
-    if (rc) break;
-    kMathLaunch[size_t(fn)](d[0], d[1], d[2], 0u, 0, 0u, 0u, (long long)len, d[3]);
-    if (hipGetLastError() != hipSuccess || hipMemcpy(got + i0 * w, d[3], len * 4 * w, hipMemcpyDeviceToHost) != hipSuccess) rc = -1;
-  }
-  for (int k = 0; k < 4; k++)
-    if (d[k]) hipFree(d[k]);
-  if (rc) {
-    set_error(std::string("pine_gpu_test_math_eval: ") + hipGetErrorString(hipGetLastError()));
-    return -1;
-  }
-  return 0;
-}
-
-int pine_gpu_test_math_compare(int fn, const uint32_t* a, const uint32_t* b, const uint32_t* c, const uint32_t* got, int64_t n,
-                               int64_t* stats, uint32_t* examples, int cap) {
-  return math_check::compare(fn, a, b, c, got, n, stats, examples, cap);
-}
-
-int pine_gpu_test_math_sweep(int device, int fn, uint32_t fixed_bits, int swept_arg, uint32_t first, uint64_t count, uint32_t stride,
-                             int64_t* stats, uint32_t* examples, int cap) {
-  if (device < 0) return math_check::sweep_host(fn, fixed_bits, swept_arg, first, count, stride, stats, examples, cap);
-  if (math_check::bad_sweep_args(fn, swept_arg, count, stats, examples, cap) || need_device(device)) return -1;
-  const int w = math_width(fn);
-  const int64_t m = std::max<int64_t>(1, std::min<int64_t>(int64_t(count), math_check::kChunk));
-  uint32_t* h = nullptr;  // one chunk's results, pinned for the copies
-  uint32_t* d = nullptr;
-  HIP_OK(hipHostMalloc((void**)&h, m * w * 4, hipHostMallocDefault));
-  if (hipMalloc((void**)&d, m * w * 4) != hipSuccess) {
-    hipHostFree(h);
-    set_error("pine_gpu_test_math_sweep: out of device memory");
-    return -1;
-  }
-  const math_check::ChunkEval on_device = [&](uint32_t start, int64_t len, uint32_t* out) {
-    kMathLaunch[size_t(fn)](nullptr, nullptr, nullptr, fixed_bits, swept_arg, start, stride, (long long)len, d);
-    if (hipGetLastError() != hipSuccess || hipMemcpy(out, d, len * w * 4, hipMemcpyDeviceToHost) != hipSuccess) {
-      set_error(std::string("pine_gpu_test_math_sweep: ") + hipGetErrorString(hipGetLastError()));
-      return -1;
-    }
-    return 0;
-  };
-  const int rc = math_check::sweep(fn, fixed_bits, swept_arg, first, count, stride, on_device, h, stats, examples, cap);
-  hipFree(d);
-  hipHostFree(h);
-  return rc;
-}
-
-int pine_gpu_test_sampler(int device, int spp_req, float* out, int64_t capacity) {
-  if (need_device(device)) return -1;
-  TableBlob tables_blob;
-  if (load_tables(tables_blob)) return -1;
-  const std::vector<uint8_t>& g_tables = *tables_blob;
-  const int spp = effective_spp(spp_req);
-  const int64_t need = int64_t(6) * spp * (260 + 270);
-  if (capacity < need) {
-    set_error("capacity too small");
-    return -1;
-  }
-  int k = 0;
-  while ((1 << k) < spp) k++;
-  uint8_t* dt;
-  float* dout;
-  HIP_OK(hipMalloc((void**)&dt, 65536 + 262144));
-  {
-    const std::vector<uint8_t> st = transposed_sobol(g_tables);
-    HIP_OK(hipMemcpy(dt, st.data(), 65536, hipMemcpyHostToDevice));
-  }
-  HIP_OK(hipMemcpy(dt + 65536, g_tables.data() + 65536 + size_t(k) * 262144, 262144, hipMemcpyHostToDevice));
-  HIP_OK(hipMalloc((void**)&dout, need * 4));
-  DTables T{dt, dt + 65536, dt + 65536 + 131072, nullptr, nullptr, 0};
-  hipLaunchKernelGGL(test_sampler_kernel, dim3(6), dim3(64), 0, 0, T, spp, dout);
-  HIP_OK(hipMemcpy(out, dout, need * 4, hipMemcpyDeviceToHost));
-  hipFree(dt);
-  hipFree(dout);
-  return 0;
-}
-int pine_gpu_test_rng(int device, uint64_t* out, int64_t capacity) {
-  if (need_device(device)) return -1;
-  if (capacity < 6 * 19) {
-    set_error("capacity too small");
-    return -1;
-  }
-  unsigned long long* d;
-  HIP_OK(hipMalloc((void**)&d, 6 * 19 * 8));
-  hipLaunchKernelGGL(test_rng_kernel, dim3(1), dim3(64), 0, 0, d);
-  HIP_OK(hipMemcpy(out, d, 6 * 19 * 8, hipMemcpyDeviceToHost));
-  hipFree(d);
-  return 0;
-}
-int pine_gpu_test_embree_tree(const float* boxes, int n, int* words, int cap) {
-  if (!boxes || !words || n < 0) {
-    set_error("bad argument");
-    return -1;
-  }
-  std::vector<float> bx(boxes, boxes + 6 * size_t(n));
-  std::vector<int> places(size_t(n), 0);
-  for (int i = 0; i < n; i++) places[size_t(i)] = i;
-  EmbreeOrderTree tree;
-  std::string why;
-  if (!tree.build(bx, places, why)) {
-    set_error(why);
-    return -1;
-  }
-  if (1 + 8 * int(tree.nodes.size()) > cap) {
-    set_error("capacity");
-    return -1;
-  }
-  int k = 0;
-  words[k++] = tree.root;
-  for (const EmbreeNode& nd : tree.nodes)
-    for (int i = 0; i < 8; i++) words[k++] = nd.child[i];
-  return k;
-}
-int pine_gpu_test_traverse(pine_gpu_scene* scene, int device, const float* rays, int64_t nrays, int flat, int cap, uint32_t* out) {
-  if (!scene || !rays || !out || cap < 2 || nrays < 0) {
-    set_error("bad argument");
-    return -1;
-  }
-  if (need_device(device)) return -1;
-  // the scene as the kernels see it: a plan's device records (nothing is rendered)
-  pine_gpu_render_params prm{};
-  prm.spp = 1, prm.max_path_length = 2, prm.device = device, prm.shard_rank = 0, prm.shard_world = 1;
-  prm.flags = PINE_GPU_FLAG_NO_SPECIALIZE | (flat == 2 ? PINE_GPU_FLAG_ORDER_EMBREE : 0);
-  pine_gpu_plan* p = pine_gpu_plan_create(scene, &prm);
-  if (!p) return -1;
-  int rc = -1;
-  float* dr = nullptr;
-  unsigned* dout = nullptr;
-  const size_t words = size_t(nrays) * (2 * size_t(cap) + 5);
-  do {
-    if (flat == 1 && p->S.stack_total > 0 && scene_host(scene).accel.nodes.size() > 65535) {
-      set_error("the flat traversal keeps 16-bit node ids");
-      break;
-    }
-    if (hipMalloc((void**)&dr, std::max<int64_t>(nrays, 1) * 32) != hipSuccess || hipMalloc((void**)&dout, std::max<size_t>(words, 1) * 4) != hipSuccess) break;
-    if (hipMemcpy(dr, rays, nrays * 32, hipMemcpyHostToDevice) != hipSuccess || hipMemset(dout, 0, std::max<size_t>(words, 1) * 4) != hipSuccess) break;
-    const size_t lds = size_t(std::max(1, p->S.stack_total)) * 64 * (flat == 1 ? sizeof(unsigned short) : sizeof(int));
-    if (nrays > 0) {
-      if (flat == 1) hipLaunchKernelGGL(test_traverse_kernel<1>, dim3(unsigned((nrays + 63) / 64)), dim3(64), lds, 0, p->S, dr, (long long)nrays, cap, dout);
-      else if (flat == 2) hipLaunchKernelGGL(test_traverse_kernel<2>, dim3(unsigned((nrays + 63) / 64)), dim3(64), lds, 0, p->S, dr, (long long)nrays, cap, dout);
-      else hipLaunchKernelGGL(test_traverse_kernel<0>, dim3(unsigned((nrays + 63) / 64)), dim3(64), lds, 0, p->S, dr, (long long)nrays, cap, dout);
-    }
-    if (hipMemcpy(out, dout, words * 4, hipMemcpyDeviceToHost) != hipSuccess) break;
-    rc = 0;
-  } while (0);
-  if (rc) set_error(std::string("pine_gpu_test_traverse: ") + hipGetErrorString(hipGetLastError()));
-  (void)hipFree(dr);
-  (void)hipFree(dout);
-  pine_gpu_plan_destroy(p);
-  return rc;
-}
-
-int pine_gpu_test_shapes(pine_gpu_scene* scene, int device, const float* rays, int64_t nrays, float* out,
-                         int64_t capacity) {
-  if (!scene || !rays || !out) {
-    set_error("null argument");
-    return -1;
-  }
-  if (need_device(device)) return -1;
-  SceneHost& H = scene_host(scene);
-  std::vector<DShape> shapes;
-  for (auto& g : H.geometries)
-    if (g.shape.kind != SHAPE_MESH) shapes.push_back(g.shape);
-  const int64_t need = int64_t(shapes.size()) * nrays * 11;
-  if (capacity < need) {
-    set_error("capacity too small");
-    return -1;
-  }
-  DShape* ds;
-  float *dr, *dout;
-  if (upload(ds, shapes)) return -1;
-  HIP_OK(hipMalloc((void**)&dr, nrays * 32));
-  HIP_OK(hipMemcpy(dr, rays, nrays * 32, hipMemcpyHostToDevice));
-  HIP_OK(hipMalloc((void**)&dout, std::max<int64_t>(need, 1) * 4));
-  const long long total = (long long)shapes.size() * nrays;
-  if (total > 0)
-    hipLaunchKernelGGL(test_shapes_kernel, dim3(unsigned((total + 255) / 256)), dim3(256), 0, 0, ds,
-                       int(shapes.size()), dr, (long long)nrays, dout);
-  HIP_OK(hipMemcpy(out, dout, need * 4, hipMemcpyDeviceToHost));
-  hipFree(ds);
-  hipFree(dr);
-  hipFree(dout);
-  return 0;
-}
-
 }  // extern "C"

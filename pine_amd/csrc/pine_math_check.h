@@ -1,9 +1,10 @@
 // pine_amd/csrc/pine_math_check.h -- the test hooks pine_gpu_test_math_eval / _compare / _sweep (include/pine_gpu.h):
 // the scalar functions of pine_math.h by PINE_GPU_MATH_* code, evaluated on bit patterns and compared with their
-// references.  math_eval<FN> is compiled for both sides: pine_kernels.hip's test_math_kernel instantiates it for the
+// references.  math_eval<FN> is compiled for both sides: pine_test_hooks.hip's test_math_kernel instantiates it for the
 // device with the path kernels' flags, and its host build is the device = -1 path.  Everything else here is host code
-// (the references, the comparison, the chunked sweep), shared by the product library and the sanitizer build of the host
-// code (tools/sanitize), which has no device half.
+// (the references, the comparison, the chunked sweep), shared by the product library (pine_test_hooks.hip; the comparison's
+// hook, pine_gpu_test_math_compare, is in pine_host.cpp) and the sanitizer build of the host code (tools/sanitize), which
+// has no device half.
 #pragma once
 #include <stdint.h>
 #include <stdlib.h>

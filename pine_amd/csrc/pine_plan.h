@@ -1,0 +1,282 @@
+// pine_amd/csrc/pine_plan.h -- what the host side of the two kernel translation units shares: the plan record
+// (struct pine_gpu_plan), HIP_OK, the sampler-table loader, the device memory pool and need_device.  Included by
+// pine_kernels.hip (plans, launches) and pine_test_hooks.hip (the device unit-test hooks).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <cstdio>
+#include <map>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include <dlfcn.h>
+
+#include "../../include/pine_gpu.h"
+#include "pine_host.h"
+#include "pine_specialize.h"
+#include "pine_variants.h"
+
+struct pine_gpu_scene;
+namespace pine_gpu {
+SceneHost& scene_host(pine_gpu_scene* s);
+}  // namespace pine_gpu
+#include "pine_kernels_device.h"
+namespace pine_gpu {
+
+#define HIP_OK(expr)                                                                          \
+  do {                                                                                        \
+    hipError_t e_ = (expr);                                                                   \
+    if (e_ != hipSuccess) {                                                                   \
+      set_error(std::string(#expr) + ": " + hipGetErrorString(e_));                           \
+      (void)hipGetLastError(); /* reported here: do not leave it sticky for the caller's next HIP user */ \
+      return -1;                                                                              \
+    }                                                                                         \
+  } while (0)
+
+inline std::string g_table_path;  // (inline: one loader state for every translation unit)
+// The packed tables are immutable once read; users take a shared snapshot, so a concurrent
+// pine_gpu_set_table_path (which only drops the library's own reference) cannot free them under a reader.
+using TableBlob = std::shared_ptr<const std::vector<uint8_t>>;
+inline TableBlob g_tables;
+inline std::mutex g_table_mutex;
+
+inline int load_tables(TableBlob& out) {
+  std::lock_guard<std::mutex> lock(g_table_mutex);
+  if (g_tables) {
+    out = g_tables;
+    return 0;
+  }
+  if (g_table_path.empty()) {
+    // not set by the host: $PINE_GPU_TABLES, else data/bluesobol_u8.bin next to the directory this library sits in
+    // (pine_amd/lib/libpine_gpu.so -> pine_amd/data/), wherever the process was started from
+    if (const char* env = getenv("PINE_GPU_TABLES")) g_table_path = env;
+    else {
+      Dl_info info;
+      if (dladdr(reinterpret_cast<const void*>(&load_tables), &info) && info.dli_fname) {
+        std::string lib = info.dli_fname;
+        const size_t slash = lib.rfind('/');
+        g_table_path = (slash == std::string::npos ? std::string(".") : lib.substr(0, slash)) + "/../data/bluesobol_u8.bin";
+      }
+    }
+  }
+  if (g_table_path.empty()) {
+    set_error("BlueSobol table path not set (pine_gpu_set_table_path)");
+    return -1;
+  }
+  FILE* f = fopen(g_table_path.c_str(), "rb");
+  if (!f) {
+    set_error("cannot open " + g_table_path);
+    return -1;
+  }
+  std::vector<uint8_t> buf(65536 + 9 * 262144);
+  size_t n = fread(buf.data(), 1, buf.size(), f);
+  fclose(f);
+  if (n != buf.size()) {
+    set_error("short read of " + g_table_path);
+    return -1;
+  }
+  g_tables = std::make_shared<const std::vector<uint8_t>>(std::move(buf));
+  out = g_tables;
+  return 0;
+}
+// The device keeps sobol_256spp_256d transposed ([dimension][sample] instead of [sample][dimension]):
+// lanes of a wave usually ask for the same dimension at 64 different (ranked) sample rows, which is
+// one 256-byte row here instead of 64 cache lines 256 bytes apart.
+static std::vector<uint8_t> transposed_sobol(const std::vector<uint8_t>& tables) {
+  std::vector<uint8_t> t(65536);
+  for (int s = 0; s < 256; s++)
+    for (int d = 0; d < 256; d++) t[d * 256 + s] = tables[s * 256 + d];
+  return t;
+}
+static int effective_spp(int spp) {  // BlueSobolSampler ctor sampler.cpp:115-121
+  if (spp > 256) spp = 256;
+  if (spp <= 0) return 0;
+  int x = spp - 1;
+  for (unsigned i = 1; i < 32; i <<= 1) x |= x >> i;
+  return x + 1;
+}
+
+// Device memory of plans comes from a process-wide pool: hipMalloc / hipFree of the big per-plan buffers (the per-sample
+// radiance buffer is 1.7 GB for a 640 x 640 x 256 render, 6.8 GB for 1920 x 1080) cost 30 - 90 ms per plan, which is most of
+// what a ONE-SHOT render (pine_gpu_path_render: create, launch, destroy -- what PathIntegrator::render does) spends outside
+// its kernels.  A destroyed plan's blocks of 256 KB and more go to a per-device free list instead and the next plan takes
+// the smallest one that fits within 25 %; at most $PINE_GPU_POOL_MB (default 16 384; 0: no pool) are kept,
+// pine_gpu_release_cached_memory() frees them.  No kernel reads a buffer before writing it (hipMalloc does not clear either).
+struct DevicePool {
+  struct Block {
+    void* p;
+    size_t bytes;
+    int device;
+  };
+  std::mutex mu;
+  std::vector<Block> free_blocks;
+  std::map<void*, Block> live;  // pooled-size allocations handed out
+  size_t pooled = 0, cap = size_t(16384) << 20;
+  DevicePool() {
+    if (const char* e = getenv("PINE_GPU_POOL_MB")) cap = size_t(atoll(e) > 0 ? atoll(e) : 0) << 20;
+  }
+  static DevicePool& get() {
+    static DevicePool* q = new DevicePool();  // (never destroyed: plans may be destroyed during static destruction)
+    return *q;
+  }
+  static constexpr size_t kMinPooled = size_t(256) << 10;
+  hipError_t alloc(void** out, size_t bytes) {
+    *out = nullptr;
+    if (bytes < kMinPooled || cap == 0) return hipMalloc(out, bytes);
+    int device = 0;
+    (void)hipGetDevice(&device);
+    const size_t want = (bytes + (size_t(2) << 20) - 1) & ~((size_t(2) << 20) - 1);
+    {
+      std::lock_guard<std::mutex> lock(mu);
+      int best = -1;
+      for (size_t i = 0; i < free_blocks.size(); i++) {
+        const Block& b = free_blocks[i];
+        if (b.device != device || b.bytes < want || b.bytes > want + want / 4) continue;
+        if (best < 0 || b.bytes < free_blocks[size_t(best)].bytes) best = int(i);
+      }
+      if (best >= 0) {
+        const Block b = free_blocks[size_t(best)];
+        free_blocks.erase(free_blocks.begin() + best);
+        pooled -= b.bytes;
+        live[b.p] = b;
+        *out = b.p;
+        return hipSuccess;
+      }
+    }
+    hipError_t e = hipMalloc(out, want);
+    if (e != hipSuccess) {  // memory is short: give the pool back and try once more
+      release_all();
+      (void)hipGetLastError();
+      e = hipMalloc(out, want);
+    }
+    if (e == hipSuccess) {
+      std::lock_guard<std::mutex> lock(mu);
+      live[*out] = Block{*out, want, device};
+    }
+    return e;
+  }
+  void free(void* p) {
+    if (!p) return;
+    Block b{nullptr, 0, 0};
+    {
+      std::lock_guard<std::mutex> lock(mu);
+      auto it = live.find(p);
+      if (it != live.end()) {
+        b = it->second;
+        live.erase(it);
+        if (pooled + b.bytes <= cap) {
+          free_blocks.push_back(b);
+          pooled += b.bytes;
+          return;
+        }
+      }
+    }
+    (void)hipFree(p);  // (a small allocation, or the pool is full)
+  }
+  void release_all() {
+    std::vector<Block> blocks;
+    {
+      std::lock_guard<std::mutex> lock(mu);
+      blocks.swap(free_blocks);
+      pooled = 0;
+    }
+    int keep = 0;
+    (void)hipGetDevice(&keep);
+    for (const Block& b : blocks) {
+      (void)hipSetDevice(b.device);
+      (void)hipFree(b.p);
+    }
+    (void)hipSetDevice(keep);
+  }
+};
+#define POOL_ALLOC(ptr, bytes) DevicePool::get().alloc((void**)&(ptr), (bytes))
+
+template <class T>
+static int upload(T*& dptr, const std::vector<T>& v) {
+  dptr = nullptr;
+  size_t bytes = std::max<size_t>(v.size(), 1) * sizeof(T);
+  HIP_OK(POOL_ALLOC(dptr, bytes));
+  if (!v.empty()) HIP_OK(hipMemcpy(dptr, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+  return 0;
+}
+static int need_device(int device) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+    set_error("no HIP device available");
+    return -1;
+  }
+  HIP_OK(hipSetDevice(device));
+  return 0;
+}
+
+}  // namespace pine_gpu
+
+using namespace pine_gpu;
+
+struct pine_gpu_plan {
+  int device = 0;
+  pine_gpu_render_params params{};
+  DeviceScene S{};
+  WorkParams W{};
+  int film_w = 0, film_h = 0;
+  // device buffers
+  char* d_blob = nullptr;  // nodes | shapes | materials | bvhs | prims | lights
+  float* d_tri = nullptr;
+  float* d_tri_leaf = nullptr;
+  uint4* d_tri_packets = nullptr;
+  uint8_t* d_halton = nullptr;
+  float* d_tri_attrs = nullptr;
+  uint8_t* d_tables = nullptr;
+  int variant = -1;
+  int queue_variant = -1;   // >= 0: the stage-queued kernel is used instead of path_trace_kernel
+  const PineFastVariant* fast = nullptr;  // PINE_GPU_FLAG_FAST: the declared-tolerance variant that runs instead (pine_kernels_fast.hip)
+  uint32_t* d_ctxg = nullptr;
+  ulonglong2* d_ckpt = nullptr;
+  // The RNG checkpoints are a function of the film partition and the sample counts alone: the plan's FIRST launch computes them,
+  // later launches reuse the table (they wait for `ckpt_done` when they run on another stream).  $PINE_GPU_CKPT_EVERY_LAUNCH=1: as
+  // before round 4, every launch recomputes it (measurement aid).
+  bool ckpt_valid = false, ckpt_every_launch = false;
+  hipEvent_t ckpt_done = nullptr;
+  hipStream_t ckpt_stream = nullptr;
+  float* d_vertex_log = nullptr;        // test hook (pine_gpu_plan_vertex_log)
+  int* d_tile_order = nullptr;          // tile classes (WorkParams::tile_order), or null
+  std::vector<int> tile_order;          // ... its host copy (empty: local tile t is film tile t * shard_world + shard_rank)
+  float4* d_samples = nullptr;
+  float* d_fold = nullptr;
+  Counters* d_counters = nullptr;
+  int grid = 0;
+  size_t lds_bytes = 0;
+  bool serial_rng = false;
+  // per-launch HIP events (prepass start / path kernel start / resolve start / end) for the last
+  // kEvRing launches: reading them (stats_get) averages over the launches since the previous read,
+  // so a timed loop never has to synchronise inside
+  static constexpr int kEvRing = 64;
+  hipEvent_t ev[kEvRing][4] = {};
+  unsigned long long launch_count = 0, stats_read_upto = 0;
+  bool timed = false;
+  bool launched = false;
+  hipStream_t last_stream = nullptr;
+  unsigned long long* h_progress = nullptr;  // host-mapped progress word (PINE_GPU_FLAG_PROGRESS)
+  float accel_build_ms = 0.0f, upload_ms = 0.0f;  // host-side cost of plan creation (reported by stats_get)
+  bool accel_on_device = false;
+  // PINE_GPU_FLAG_SPECIALIZE: the queue kernel compiled for this scene (pine_specialize.h); null: the precompiled variant
+  std::shared_ptr<struct LoadedKernel> spec_loaded;  // (shared with every plan of this geometry on this device: LoadedKernels)
+  hipModule_t spec_module = nullptr;
+  hipFunction_t spec_fn = nullptr;
+  unsigned spec_features = 0;  // ... its feature set (the scene's own), and whether the scene's BVH is baked in
+  bool spec_baked = false;
+  KernelRequest spec_request;  // what to compile (filled at plan creation)
+  std::chrono::steady_clock::time_point spec_t0;
+  bool spec_explicit = false;  // the caller asked for the scene's kernel (PINE_GPU_FLAG_SPECIALIZE): failures are errors
+  int spec_source = 0;         // kSpecSource*: where the scene's kernel came / comes from
+  // background build (the default mode, PINE_GPU_FLAG_SPECIALIZE_ASYNC): a job of the process-wide queue; a launch adopts its result
+  std::atomic<int> spec_state{0};  // kSpecNone / kSpecBuilding / kSpecAdopted / kSpecFailed
+  std::shared_ptr<SpecJob> spec_job;
+  std::string spec_async_error;
+  float specialize_ms = 0.0f;
+};

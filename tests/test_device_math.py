@@ -5,7 +5,7 @@ reference links), or the same comparison expressions on the host (include/pine_g
 
 CPU: the comparator reports each kind of error with its input; the host build of the same functions (device = -1) passes
 strided sweeps of every function and the edge-value sets.
-GPU: the device build, compiled with the path kernels' flags in pine_kernels.hip: all 2^32 arguments of the one-argument
+GPU: the device build, compiled with the path kernels' flags in pine_test_hooks.hip: all 2^32 arguments of the one-argument
 functions and of powf(x, 5) (Schlick), strided sweeps of the two-argument ones at fixed special values, the edge-value
 cross products, and random division pairs."""
 import ctypes as C

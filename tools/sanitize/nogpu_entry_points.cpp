@@ -1,11 +1,11 @@
 // tools/sanitize/nogpu_entry_points.cpp -- SANITIZER BUILD ONLY (tools/sanitize/Makefile), never part of the product.
 //
 // The host side of libpine_gpu.so (pine_amd/csrc/pine_host.cpp: scene building, shape constructors, BVH build,
-// node folding, .pscene dump, film finalize) is plain C++ and is what parses caller-supplied data; the CPU leg of
-// the test-suite exercises exactly that code.  GPU AddressSanitizer is not available on this pool, so the
-// sanitizer build compiles pine_host.cpp with g++ -fsanitize=address,undefined and takes the device-side entry
-// points (pine_amd/csrc/pine_kernels.hip) from here: every one of them fails the way the real library fails on
-// a host without a HIP device.  Nothing is rendered by this build.
+// node folding, .pscene dump, film finalize, the host-only test hooks) is plain C++ and is what parses caller-supplied
+// data; the CPU leg of the test-suite exercises exactly that code.  GPU AddressSanitizer is not available on this pool,
+// so the sanitizer build compiles pine_host.cpp with g++ -fsanitize=address,undefined and takes the device-side entry
+// points (pine_amd/csrc/pine_kernels.hip, pine_test_hooks.hip) from here: every one of them fails the way the real
+// library fails on a host without a HIP device.  Nothing is rendered by this build.
 #include <cstdint>
 #include <string>
 
@@ -14,7 +14,6 @@
 #include "../../pine_amd/csrc/pine_math_check.h"
 
 #include "../../pine_amd/csrc/pine_specialize.h"
-#include "../../pine_amd/csrc/pine_embree_order.h"
 
 // (the structure sizes a run-time compiled kernel is checked against come from the device half of the library: none here --
 //  a kernel compiled through this build's pine_gpu_test_specialize_compile fails its static_assert, as it should)
@@ -47,23 +46,7 @@ int pine_gpu_plan_check(pine_gpu_plan*) { return fail(); }
 int pine_gpu_plan_debug_sections(pine_gpu_plan*, uint64_t*) { return fail(); }
 int pine_gpu_plan_read_samples(pine_gpu_plan*, float*, int64_t) { return fail(); }
 int64_t pine_gpu_plan_vertex_log(pine_gpu_plan*, float*, int64_t) { return fail(); }
-int64_t pine_gpu_packed_slab_floats(int film_w, int film_h, int world) {
-  if (film_w <= 0 || film_h <= 0 || world < 1) return -1;
-  const int64_t tiles = int64_t((film_w + 7) / 8) * ((film_h + 7) / 8);
-  return (tiles + world - 1) / world * 64 * 4;
-}
-int pine_gpu_packed_offset(int film_w, int film_h, int world, int x, int y, int* rank_out, int64_t* float4_index_out) {
-  if (film_w <= 0 || film_h <= 0 || world < 1 || x < 0 || y < 0 || x >= film_w || y >= film_h) {
-    set_error("bad argument");
-    return -1;
-  }
-  const int tile = (y / 8) * ((film_w + 7) / 8) + x / 8;
-  if (rank_out) *rank_out = tile % world;
-  if (float4_index_out) *float4_index_out = int64_t(tile / world) * 64 + (y % 8) * 8 + x % 8;
-  return 0;
-}
 int pine_gpu_film_unpack(int, int, int, int, const void*, void*, void*) { return fail(); }
-int pine_gpu_test_lomuto(const unsigned char*, int, int*, int*) { return fail(); }
 int pine_gpu_test_sampler(int, int, float*, int64_t) { return fail(); }
 int pine_gpu_test_rng(int, uint64_t*, int64_t) { return fail(); }
 int pine_gpu_test_sincos(int, const float*, int64_t, float*, float*) { return fail(); }
@@ -74,30 +57,10 @@ int pine_gpu_test_traverse(pine_gpu_scene*, int, const float*, int64_t, int, int
 int pine_gpu_test_math_eval(int device, int fn, const uint32_t* a, const uint32_t* b, const uint32_t* c, int64_t n, uint32_t* got) {
   return device < 0 ? pine_gpu::math_check::eval_host_arrays(fn, a, b, c, n, got) : fail();
 }
-int pine_gpu_test_math_compare(int fn, const uint32_t* a, const uint32_t* b, const uint32_t* c, const uint32_t* got, int64_t n,
-                               int64_t* stats, uint32_t* examples, int cap) {
-  return pine_gpu::math_check::compare(fn, a, b, c, got, n, stats, examples, cap);
-}
 int pine_gpu_test_math_sweep(int device, int fn, uint32_t fixed_bits, int swept_arg, uint32_t first, uint64_t count, uint32_t stride,
                              int64_t* stats, uint32_t* examples, int cap) {
   return device < 0 ? pine_gpu::math_check::sweep_host(fn, fixed_bits, swept_arg, first, count, stride, stats, examples, cap)
                     : fail();
-}
-// (host code: the real thing, so that the sanitizers see the hierarchy builder -- same body as in pine_kernels.hip)
-int pine_gpu_test_embree_tree(const float* boxes, int n, int* words, int cap) {
-  if (!boxes || !words || n < 0) return fail();
-  std::vector<float> bx(boxes, boxes + 6 * size_t(n));
-  std::vector<int> places(size_t(n), 0);
-  for (int i = 0; i < n; i++) places[size_t(i)] = i;
-  pine_gpu::EmbreeOrderTree tree;
-  std::string why;
-  if (!tree.build(bx, places, why)) return fail();
-  if (1 + 8 * int(tree.nodes.size()) > cap) return fail();
-  int k = 0;
-  words[k++] = tree.root;
-  for (const pine_gpu::EmbreeNode& nd : tree.nodes)
-    for (int i = 0; i < 8; i++) words[k++] = nd.child[i];
-  return k;
 }
 int pine_gpu_test_shapes(pine_gpu_scene*, int, const float*, int64_t, float*, int64_t) { return fail(); }
 int pine_gpu_plan_test_traverse_baked(pine_gpu_plan*, const float*, int64_t, uint32_t*) { return fail(); }
