@@ -465,6 +465,11 @@ int pine_gpu_plan_test_traverse_baked(pine_gpu_plan*, const float* rays_host, in
 int pine_gpu_scene_accel_bvhs(pine_gpu_scene*, int32_t* out, int64_t capacity_words);
 int pine_gpu_test_shapes(pine_gpu_scene*, int device, const float* rays_host, int64_t nrays,
                          float* out_host, int64_t capacity);                        /* layout of oracle_shapes */
+/* The precompiled path-kernel variants (pine_variants.h) in the order of the host's first-fit search: kind 0 the stage-queued
+ * kernel, 1 the megakernel.  Up to `cap` entries of features (F_* bits), ctx (path contexts per workgroup; 0 for the
+ * megakernel) and order; any of the arrays may be NULL.  Returns the number of variants, < 0 on error.  Needs no GPU.
+ * With $PINE_GPU_TEST_VARIANT=queue:<order> / mega:<order> plan creation considers that variant only (tests/test_kernel_matrix.py). */
+int pine_gpu_test_kernel_variants(int kind, uint32_t* features, int32_t* ctx, int32_t* order, int cap);
 
 /* ---- Film (host side, after the hot path) ----------------------------------------------------
  * Film::finalize + tone mapping + to_uint8_array: src/pine/core/film.cpp:12-27,66-68,

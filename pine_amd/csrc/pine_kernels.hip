@@ -341,6 +341,10 @@ struct PlanKnobs {
   // PINE_GPU_SPECIALIZE_FORCE, _NO_LDS_SCENE, _KERNEL=mega, _NO_TILE_CLASSES, _NO_FORK, _CKPT_EVERY_LAUNCH (not 0)
   bool specialize_force, no_lds_scene, mega, no_tile_classes, no_fork, ckpt_every_launch;
   double idle_budget_s;  // PINE_GPU_IDLE_BUDGET_S: the path kernel's watchdog, 30 s
+  // Test hooks (tests/test_kernel_matrix.py).  PINE_GPU_TEST_VARIANT=queue:<order> / mega:<order>: choose_variants considers
+  // that precompiled variant only (pin_kind 0 / 1; -1 unset, 2 malformed) and the plan never specialises.
+  // PINE_GPU_TEST_LDS_NODES=<n>: F_LDS_TOP variants cache at most n BVH nodes in LDS.
+  int pin_kind, pin_order, lds_nodes_cap;
 };
 static PlanKnobs read_knobs() {
   auto num = [](const char* name) { return getenv(name) ? atoi(getenv(name)) : kUnset; };
@@ -348,16 +352,26 @@ static PlanKnobs read_knobs() {
   const char* kernel = getenv("PINE_GPU_KERNEL");
   const char* budget = getenv("PINE_GPU_IDLE_BUDGET_S");
   const int ckpt = num("PINE_GPU_CKPT_EVERY_LAUNCH");
+  int pin_kind = -1, pin_order = -1;
+  if (const char* pin = getenv("PINE_GPU_TEST_VARIANT")) {
+    const std::string s = pin;
+    const size_t colon = s.find(':');
+    const std::string kind = s.substr(0, colon), digits = colon == std::string::npos ? "" : s.substr(colon + 1);
+    pin_kind = kind == "queue" ? 0 : kind == "mega" ? 1 : 2;
+    if (digits.empty() || digits.size() > 6 || digits.find_first_not_of("0123456789") != std::string::npos) pin_kind = 2;
+    else pin_order = atoi(digits.c_str());
+  }
   return PlanKnobs{num("PINE_GPU_SPECIALIZE"), num("PINE_GPU_LDS_TRIS"), num("PINE_GPU_XSTAGE"), num("PINE_GPU_TRAV_MIN_LANES"),
                    num("PINE_GPU_TRAV_MIN_TRIPS"), num("PINE_GPU_MAX_PIXELS"), num("PINE_GPU_FAIR_PERIOD"), num("PINE_GPU_POOL_ITEMS"),
                    set("PINE_GPU_SPECIALIZE_FORCE"), set("PINE_GPU_NO_LDS_SCENE"), kernel && std::string(kernel) == "mega",
                    set("PINE_GPU_NO_TILE_CLASSES"), set("PINE_GPU_NO_FORK"), ckpt != kUnset && ckpt != 0,
-                   budget && atof(budget) > 0 ? atof(budget) : 30.0};
+                   budget && atof(budget) > 0 ? atof(budget) : 30.0, pin_kind, pin_order, num("PINE_GPU_TEST_LDS_NODES")};
 }
 
 static int plan_adopt_kernel(pine_gpu_plan* p, bool compile_here);
 static int plan_specialize(pine_gpu_plan* p, const FlatAccel& A, const std::vector<DShape>& shapes, const std::vector<int>& packed_prims,
                            const pine_gpu_render_params* prm, unsigned need, const PlanKnobs& K) {
+  if (K.pin_kind >= 0) return 0;  // (PINE_GPU_TEST_VARIANT: the pinned variant renders; no cache lookup)
   // explicit: the caller asked for the scene's kernel (failures are errors); automatic: the default (failures are silent)
   bool explicit_want = (prm->flags & PINE_GPU_FLAG_SPECIALIZE) != 0;
   bool automatic = !explicit_want && !(prm->flags & PINE_GPU_FLAG_NO_SPECIALIZE);
@@ -531,6 +545,20 @@ int pine_gpu_plan_check(pine_gpu_plan* p) {
   Counters c;
   HIP_OK(hipMemcpy(&c, p->d_counters, sizeof c, hipMemcpyDeviceToHost));
   return plan_check_counters(c);
+}
+
+int pine_gpu_test_kernel_variants(int kind, uint32_t* features, int32_t* ctx, int32_t* order, int cap) {
+  if (kind != 0 && kind != 1) {
+    set_error("pine_gpu_test_kernel_variants: kind is 0 (stage-queued kernel) or 1 (megakernel)");
+    return -1;
+  }
+  const std::vector<PineKernelVariant>& t = kind == 0 ? kQueueVariants : kVariants;
+  for (int i = 0; i < int(t.size()) && i < cap; i++) {
+    if (features) features[i] = t[size_t(i)].features;
+    if (ctx) ctx[i] = t[size_t(i)].ctx;
+    if (order) order[i] = t[size_t(i)].order;
+  }
+  return int(t.size());
 }
 
 int pine_gpu_set_table_path(const char* path) {
@@ -948,8 +976,58 @@ static void place_lds_caches(pine_gpu_plan* p, unsigned F, size_t lds, const Fla
   if (S.lds_tris) p->lds_bytes += sp.tri_packet_bytes;
   if (F & F_LDS_TOP) {
     S.lds_nodes = int(std::min<size_t>(A.nodes.size(), (160 * 1024 - p->lds_bytes) / sizeof(DNode)));
+    if (K.lds_nodes_cap != kUnset) S.lds_nodes = std::min(S.lds_nodes, std::max(K.lds_nodes_cap, 0));  // (test hook: the cache's edge)
     p->lds_bytes += size_t(S.lds_nodes) * sizeof(DNode);
   }
+}
+
+// PINE_GPU_TEST_VARIANT (test hook, tests/test_kernel_matrix.py): the one precompiled variant the knob names, under the rules of
+// the first-fit search below -- except that a pinned scene-in-global megakernel variant may take a scene that would fit LDS, and
+// a pinned traversal-stage variant a scene without meshes (as PINE_GPU_XSTAGE=1 allows).  One that does not cover the scene
+// fails the plan.
+static int choose_pinned_variant(pine_gpu_plan* p, const FlatAccel& A, const SceneParts& sp, const pine_gpu_render_params* prm,
+                                 unsigned need, bool lds_ok, const PlanKnobs& K) {
+  DeviceScene& S = p->S;
+  if (K.pin_kind == 2) {
+    set_error("PINE_GPU_TEST_VARIANT: expected queue:<order> or mega:<order>");
+    return -1;
+  }
+  if (prm->flags & PINE_GPU_FLAG_FAST) {
+    set_error("PINE_GPU_TEST_VARIANT: not with PINE_GPU_FLAG_FAST (the declared-tolerance variants are not pinned)");
+    return -1;
+  }
+  const bool mega = K.pin_kind == 1, order_embree = (prm->flags & PINE_GPU_FLAG_ORDER_EMBREE) != 0;
+  const std::vector<PineKernelVariant>& table = mega ? kVariants : kQueueVariants;
+  const std::string pin = std::string("PINE_GPU_TEST_VARIANT=") + (mega ? "mega:" : "queue:") + std::to_string(K.pin_order);
+  int v = -1;
+  for (int i = 0; i < int(table.size()); i++)
+    if (table[size_t(i)].order == K.pin_order) v = i;
+  if (v < 0) {
+    set_error(pin + ": no such kernel variant");
+    return -1;
+  }
+  const PineKernelVariant& V = table[size_t(v)];
+  const unsigned F = V.features;
+  const char* why = nullptr;
+  size_t lds = 0;
+  if ((F & need) != need) why = "the scene needs features it lacks";
+  else if (((F & F_EMBREE) != 0) != order_embree) why = order_embree ? "not a variant of EmbreeAccel's order" : "a variant of EmbreeAccel's order";
+  else if (!mega && ((F & F_VLOG) != 0) != ((prm->flags & PINE_GPU_FLAG_VERTEX_LOG) != 0))
+    why = (F & F_VLOG) ? "a per-vertex-log twin: PINE_GPU_FLAG_VERTEX_LOG only" : "no per-vertex log compiled in";
+  else if (mega && (F & F_LDS_SCENE) && !lds_ok) why = "the scene does not fit LDS";
+  else if (!mega && (lds = queue_variant_lds(V, S, A.nodes.size(), lds_ok)) == 0) why = "its LDS layout does not fit the scene";
+  if (why) {
+    set_error(pin + ": pinned kernel variant does not cover this scene (" + why + ")");
+    return -1;
+  }
+  if (mega) {
+    p->variant = v, p->queue_variant = -1;
+    if (F & F_LDS_SCENE) p->lds_bytes += size_t(S.blob_bytes);
+  } else {
+    p->variant = -1, p->queue_variant = v;
+    place_lds_caches(p, F, lds, A, sp, K);
+  }
+  return 0;
 }
 
 // The kernel that renders: the first compiled variant that covers `need` -- of the stage-queued kernel when one fits, else of
@@ -964,6 +1042,7 @@ static int choose_variants(pine_gpu_plan* p, const FlatAccel& A, const ScenePart
     return -1;
   }
   const bool lds_ok = size_t(S.blob_bytes) <= 32 * 1024 && !K.no_lds_scene;
+  if (K.pin_kind >= 0) return choose_pinned_variant(p, A, sp, prm, need, lds_ok, K);
   p->variant = -1;
   for (int v = 0; v < kNumVariants; v++) {
     const unsigned F = kVariants[v].features;

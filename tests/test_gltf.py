@@ -68,11 +68,12 @@ def test_imported_scene_on_the_gpu_equals_the_reference(kernel, monkeypatch):
         want = json.load(open(os.path.join(GOLDEN, "gltf_import.json")))[key]
         sc = _scene()
         w, h = want["size"]
-        plan = pa.Plan(sc, want["spp"], want["depth"])
+        plan = pa.Plan(sc, want["spp"], want["depth"], specialize=False)
         film = torch.zeros((h, w, 4), dtype=torch.float32, device="cuda")
         plan.launch(film.data_ptr(), torch.cuda.current_stream().cuda_stream)
         torch.cuda.synchronize()
         plan.check()
+        assert plan.stats().specialized == 0
         assert hashlib.md5(film.cpu().numpy().tobytes()).hexdigest() == want["md5"], key
         plan.close()
 

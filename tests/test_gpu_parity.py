@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from conftest import SOBOL_FILM_NAMES, HALTON_FILM_NAMES, GOLDEN, FILM_NAMES, assert_bit_equal, load_film
+from film_scenes import film_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -147,11 +148,14 @@ def _render(scene, spp, depth, **kw):
     import torch
     import pine_amd as pa
     w, h = scene.camera.film().size
+    kw.setdefault("specialize", False)  # (the precompiled kernel, whatever the machine's kernel cache holds; True where a test says so)
     plan = pa.Plan(scene, spp, depth, **kw)
     film = torch.full((h, w, 4), -1.0, dtype=torch.float32, device="cuda")
     plan.launch(film.data_ptr(), torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
     st = plan.stats()
+    if not kw["specialize"]:
+        assert st.specialized == 0
     out = film.cpu().numpy()
     plan.close()
     return out, st
@@ -161,26 +165,7 @@ LIBM_TOLERANCE_FILMS = set()  # (was {"mats_zoo_64_s32_d6"} until powf/logf beca
 
 
 def _scene_for(name):
-    import pine_amd as pa
-    from pine_amd import scenes
-    return {
-        "cbox_committed_64_s16_d4": lambda: scenes.cbox((64, 64), "committed"),
-        "cbox_readme_64_s16_d4": lambda: scenes.cbox((64, 64), "readme"),
-        "cbox_readme_64_s256_d8": lambda: scenes.cbox((64, 64), "readme"),
-        "cbox_rect_readme_64_s64_d5": lambda: scenes.cbox((64, 64), "readme", False),
-        "cbox_committed_ragged_45x37_s8_d3": lambda: scenes.cbox((45, 37), "committed"),
-        "cbox_readme_64_s1_d1": lambda: scenes.cbox((64, 64), "readme"),
-        "zoo_48_s16_d5": lambda: scenes.shapes_zoo((48, 48)),
-        "classic_cones12_90x45_s32_d6": lambda: scenes.classic_cones((90, 45), 12),
-        "sss_48_s32_d8": lambda: scenes.sss((48, 48), 1),
-        "mats_zoo_64_s32_d6": lambda: scenes.materials_zoo((64, 64)),
-        "classic_checker_cones8_90x45_s32_d6": lambda: scenes.classic_cones((90, 45), 8, checker_floor=True),
-        "lights_zoo_64_s32_d6": lambda: scenes.lights_zoo((64, 64)),
-        "lights_nosky_48_s16_d4": lambda: scenes.lights_zoo((48, 48), with_sky=False),
-        "xshapes_48_s16_d5": lambda: scenes.xshapes_zoo((48, 48)),
-        "xshapes_nolights_40_s8_d3": lambda: scenes.xshapes_zoo((40, 40), extra_lights=False),
-        "mesh_glossy_48_s32_d6": lambda: scenes.sss((48, 48), 2, skin=pa.Glossy([0.9, 0.5, 0.3], 0.15), emissive_mesh=True),
-    }[name]()
+    return film_scene(name)
 
 
 @pytest.mark.parametrize("name", FILM_NAMES)
@@ -201,14 +186,7 @@ def test_film_matches_reference_golden(name):
 
 
 def _sobol_scene_for(name):
-    from pine_amd import scenes
-    return {
-        "sobol_cbox_readme_48_s8_d4": lambda: scenes.cbox((48, 48), "readme"),
-        "sobol_cbox_ragged_45x37_s12_d3": lambda: scenes.cbox((45, 37), "committed"),
-        "sobol_mats_zoo_32_s16_d6": lambda: scenes.materials_zoo((32, 32)),
-        "sobol_cbox_readme_24_s512_d5": lambda: scenes.cbox((24, 24), "readme"),
-        "sobol_sss_32_s8_d6": lambda: scenes.sss((32, 32), 2),
-    }[name]()
+    return film_scene(name)
 
 
 @pytest.mark.parametrize("name", SOBOL_FILM_NAMES)
@@ -232,11 +210,8 @@ def test_halton_sampler_film_matches_reference_golden(name):
     permutations derived on the host from a default-seeded RNG, pixel offsets through the 128 x 243 grid) against the film
     the REAL reference rendered with HaltonSampler, 8 and 12 samples per pixel (any count: sampler.h:44-46)."""
     import pine_amd as pa
-    from pine_amd import scenes
     ref, ps, spp, depth = load_film(name)
-    sc = {"halton_cbox_readme_40_s8_d4": lambda: scenes.cbox((40, 40), "readme"),
-          "halton_mats_zoo_32_s12_d6": lambda: scenes.materials_zoo((32, 32)),
-          "halton_sss_24x20_s12_d5": lambda: scenes.sss((24, 20), 1, camera="committed")}[name]()
+    sc = film_scene(name)
     assert sc.describe() == ps
     film, st = _render(sc, pa.HaltonSampler(spp), depth)
     assert st.spp_effective == spp
@@ -314,7 +289,7 @@ def test_per_sample_radiance_matches_oracle(oracle):
     import pine_amd as pa
     from pine_amd import scenes
     sc = scenes.cbox((24, 16), "readme")
-    plan = pa.Plan(sc, 16, 6)
+    plan = pa.Plan(sc, 16, 6, specialize=False)
     film = torch.zeros((16, 24, 4), device="cuda")
     plan.launch(film.data_ptr(), torch.cuda.current_stream().cuda_stream)
     got = plan.read_samples()
@@ -352,7 +327,7 @@ def test_packed_slabs_unpack_to_the_same_film():
     for world in (1, 2, 5):
         slabs = []
         for r in range(world):
-            plan = pa.Plan(sc, 16, 5, shard_rank=r, shard_world=world)
+            plan = pa.Plan(sc, 16, 5, shard_rank=r, shard_world=world, specialize=False)
             slab = torch.full((plan.slab_floats(),), -7.0, dtype=torch.float32, device="cuda")
             plan.launch_packed(slab.data_ptr(), torch.cuda.current_stream().cuda_stream)
             torch.cuda.synchronize()
@@ -382,7 +357,7 @@ def test_tile_classes_under_sharding_and_packed_slabs(path_kernel):
         for r in range(world):
             f, st_r = _render(sc, 32, 6, shard_rank=r, shard_world=world)
             tot += f
-            plan = pa.Plan(sc, 32, 6, shard_rank=r, shard_world=world)
+            plan = pa.Plan(sc, 32, 6, shard_rank=r, shard_world=world, specialize=False)
             slab = torch.full((plan.slab_floats(),), -7.0, dtype=torch.float32, device="cuda")
             plan.launch_packed(slab.data_ptr(), torch.cuda.current_stream().cuda_stream)
             torch.cuda.synchronize()
@@ -504,7 +479,7 @@ def test_random_scenes_shard_sums_and_packed_slabs():
         for r in range(world):
             f, _ = _render(sc, spp, depth, sampler=sampler, shard_rank=r, shard_world=world)
             tot += f
-            plan = pa.Plan(sc, spp, depth, sampler=sampler, shard_rank=r, shard_world=world)
+            plan = pa.Plan(sc, spp, depth, sampler=sampler, shard_rank=r, shard_world=world, specialize=False)
             plan.launch_packed(slabs[r].data_ptr(), torch.cuda.current_stream().cuda_stream)
             torch.cuda.synchronize()
             plan.close()
@@ -592,7 +567,7 @@ def test_kernel_bail_out_is_reported_by_every_entry_point(path_kernel):
     with pytest.raises(pa.PineError, match="bailed out"):
         plan.stats()
     plan.close()
-    good = pa.Plan(sc, 8, 4)
+    good = pa.Plan(sc, 8, 4, specialize=False)
     good.launch(film.data_ptr(), torch.cuda.current_stream().cuda_stream)
     good.check()
     ref = pa.PathIntegrator(pa.BlueSampler(8), 4).render(sc).pixels
