@@ -393,6 +393,49 @@ int64_t pine_gpu_plan_vertex_log(pine_gpu_plan*, float* out, int64_t capacity_fl
  * layout [(y*W+x)*spp + s].  Test/debug aid. */
 int pine_gpu_plan_read_samples(pine_gpu_plan*, float* out_host, int64_t capacity_floats);
 
+/* ---- Rendering in sample passes: a running film, bounded device memory, the same bits ----
+ * A plan created WITH PASSES renders its film in n launches.  Pass j traces its share of the work, folds it into a running
+ * per-pixel sum the plan owns (the reference's `L += ...` continued with the same roundings) and writes a viewable film;
+ * after the last pass the film is bit for bit what pine_gpu_plan_launch of an ordinary plan writes.  The per-sample buffer
+ * and the RNG checkpoints are sized for one pass, not for spp.
+ *   - pixels whose samples are independent work items render the samples [j * P, min(spp, (j + 1) * P)) in pass j, P =
+ *     pass_samples rounded down to a multiple of the plan's samples per item; their film value after pass j is
+ *     (L_0 + ... + L_{m-1}) / m, m the samples so far, w = 1;
+ *   - pixels that are one whole-pixel item (Subsurface tiles a camera ray can reach, fractional Uber, a SobolSampler /
+ *     HaltonSampler count that is not a power of two) cannot be split by sample: their 8x8 tiles are dealt out in n slices,
+ *     one slice per pass, all samples at once -- final once their slice has run, (0, 0, 0, 0) before.
+ * n = ceil(spp / P); pass_samples <= 0 or >= spp: one pass, an ordinary plan.  An intermediate film is a PREVIEW, nothing
+ * more: it is not the film of a render with fewer samples (BlueSampler's tables depend on the total spp).
+ * Passes run in the order 0 .. n-1 (pass 0 starts the film afresh); any other order fails and launches nothing.
+ * pine_gpu_plan_launch / _launch_packed of such a plan run all passes in order on the stream.  Plan stats after any pass:
+ * vertices / shadow_rays / walk_steps are summed over the passes since pass 0, the three timings are per whole sequence
+ * (from the last passes launched, at most 64); a bail-out of any pass fails them.  pine_gpu_plan_read_samples and the vertex log are
+ * refused when n > 1 (the rows are gone by design). */
+pine_gpu_plan* pine_gpu_plan_create_passes(pine_gpu_scene*, const pine_gpu_render_params*, int32_t pass_samples);
+int pine_gpu_plan_pass_count(pine_gpu_plan*); /* 1 for an ordinary plan */
+/* out = first sample, samples (the independent class's window of the pass), first whole-pixel tile, tiles (the pass's slice:
+ * positions in the plan's order of whole-pixel tiles -- the tile classes' order, else the shard's natural tile order) */
+int pine_gpu_plan_pass_info(pine_gpu_plan*, int pass, int32_t out[4]);
+int pine_gpu_plan_launch_pass(pine_gpu_plan*, int pass, void* film_dev, void* stream);
+/* The plan's tile order: the film tile (row-major index of the 8x8 tile) of every local tile, whole-pixel tiles of a plan
+ * with tile classes first -- the order pass_info's tile numbers refer to.  Returns the number of local tiles. */
+int pine_gpu_plan_tile_order(pine_gpu_plan*, int32_t* out, int cap);
+/* bytes asked of the device for: per-sample rows | RNG checkpoints | running sum + carried RNG states | all buffers of the plan */
+int pine_gpu_plan_device_bytes(pine_gpu_plan*, int64_t out[4]);
+/* The planner itself, on the host (no GPU): the passes of one shard of a film_w x film_h film whose independent items are
+ * samples_per_item samples (== spp: every pixel is one whole-pixel item) and `serial_tiles` of whose tiles are whole-pixel
+ * tiles of a plan with tile classes.  Writes four numbers per pass as pine_gpu_plan_pass_info does, as many passes as fit
+ * `cap` int32; returns the number of passes, < 0 on a bad argument. */
+int pine_gpu_pass_schedule(int film_w, int film_h, int shard_rank, int shard_world, int spp, int samples_per_item, int serial_tiles,
+                           int pass_samples, int32_t* out, int cap);
+/* One-shot form with a running film: after every pass the host film is downloaded into film_out_host and `cb` (may be
+ * NULL) is called with it; a non-zero return stops the render: the function returns PINE_GPU_RENDER_STOPPED and
+ * film_out_host holds the last film delivered.  pine_gpu_progress() counts over the whole sequence. */
+#define PINE_GPU_RENDER_STOPPED 1
+typedef int (*pine_gpu_pass_callback)(void* user, int pass, int pass_count, const float* film_host);
+int pine_gpu_path_render_passes(pine_gpu_scene*, const pine_gpu_render_params*, int32_t pass_samples, float* film_out_host,
+                                pine_gpu_pass_callback cb, void* user);
+
 /* Host test hook: the reference's partition (src/psl/algorithm.h:394-402) as its sequential swap loop and as the data-parallel
  * formulation of the device BVH build; both permutations out, < 0 if they disagree. */
 int pine_gpu_test_lomuto(const unsigned char* pred, int n, int* perm_sequential, int* perm_parallel);

@@ -77,6 +77,10 @@ FLAG_ORDER_EMBREE = 0x4000
 FLAG_ORDER_NEAREST = FLAG_ORDER_EMBREE  # (former name)
 
 # every symbol include/pine_gpu.h declares, with its signature
+# pine_gpu_pass_callback: int (*)(void* user, int pass, int pass_count, const float* film_host)
+PASS_CALLBACK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float))
+RENDER_STOPPED = 1  # PINE_GPU_RENDER_STOPPED
+
 SIGNATURES = {
     "pine_gpu_last_error": (C.c_char_p, []),
     "pine_gpu_progress": (C.c_float, []),
@@ -164,6 +168,14 @@ SIGNATURES = {
     "pine_gpu_plan_stats_get": (C.c_int, [C.c_void_p, C.POINTER(PlanStats)]),
     "pine_gpu_plan_check": (C.c_int, [C.c_void_p]),
     "pine_gpu_plan_read_samples": (C.c_int, [C.c_void_p, c_f_p, C.c_int64]),
+    "pine_gpu_plan_create_passes": (C.c_void_p, [C.c_void_p, C.POINTER(RenderParams), C.c_int32]),
+    "pine_gpu_plan_pass_count": (C.c_int, [C.c_void_p]),
+    "pine_gpu_plan_pass_info": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32)]),
+    "pine_gpu_plan_launch_pass": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "pine_gpu_plan_tile_order": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int]),
+    "pine_gpu_plan_device_bytes": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "pine_gpu_pass_schedule": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int]),
+    "pine_gpu_path_render_passes": (C.c_int, [C.c_void_p, C.POINTER(RenderParams), C.c_int32, c_f_p, PASS_CALLBACK, C.c_void_p]),
     "pine_gpu_plan_debug_sections": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "pine_gpu_plan_vertex_log": (C.c_int64, [C.c_void_p, c_f_p, C.c_int64]),
     "pine_gpu_test_lomuto": (C.c_int, [C.POINTER(C.c_uint8), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),

@@ -569,13 +569,16 @@ class Plan:
     """A PathIntegrator bound to a scene with all device state resident (bench / multi-GPU)."""
 
     def __init__(self, scene, spp, max_path_length, device=0, shard_rank=0, shard_world=1,
-                 samples_per_item=0, timing=False, sampler="blue", flags=0, specialize=None, order="pine"):
+                 samples_per_item=0, timing=False, sampler="blue", flags=0, specialize=None, order="pine", pass_samples=None):
         """spp: an int (BlueSampler(spp), or SobolSampler(spp) with sampler="sobol") or a sampler object.
         specialize: None -- the library's default: the scene's own kernel from the cache, else compiled in the background
         while the precompiled kernel renders; True -- PINE_GPU_FLAG_SPECIALIZE: wait for the compiler at plan creation, fail if
         the kernel cannot be built; False -- PINE_GPU_FLAG_NO_SPECIALIZE: precompiled kernels only (stats().specialized tells).
         order: "pine" -- closest hits in pine-BVH order, Accel(BVH()) (the default and the parity gate); "embree" --
-        PINE_GPU_FLAG_ORDER_EMBREE: the order of the reference's default accel, EmbreeAccel (order-dependent shapes appear as under it)."""
+        PINE_GPU_FLAG_ORDER_EMBREE: the order of the reference's default accel, EmbreeAccel (order-dependent shapes appear as under it).
+        pass_samples: render in passes of about this many samples per pixel (pine_gpu_plan_create_passes): launch_pass(j, ...)
+        for j = 0 .. pass_count - 1 folds each pass into a running film; the last one leaves the film launch() of an ordinary
+        plan writes, bit for bit, with sample and checkpoint buffers sized for one pass.  None: an ordinary plan."""
         flags = int(flags) | _specialize_flags(specialize) | _order_flags(order)
         if scene.camera is None:
             raise PineError("scene has no camera")
@@ -586,13 +589,44 @@ class Plan:
         self.params = _lib.RenderParams(int(spp), int(max_path_length), int(device), int(shard_rank),
                                         int(shard_world), int(samples_per_item),
                                         (_lib.FLAG_TIMING if timing else 0) | int(flags), kind)
-        h = lib.pine_gpu_plan_create(scene._h, C.byref(self.params))
+        if pass_samples is None:
+            h = lib.pine_gpu_plan_create(scene._h, C.byref(self.params))
+        else:
+            h = lib.pine_gpu_plan_create_passes(scene._h, C.byref(self.params), int(pass_samples))
         if not h:
             raise PineError("PathIntegrator: " + _lib.last_error())
         self._h = C.c_void_p(h)
 
     def launch(self, film_dev_ptr, stream_ptr=0):
+        """One whole render (a plan with passes: all of them, in order)."""
         check(lib.pine_gpu_plan_launch(self._h, C.c_void_p(film_dev_ptr), C.c_void_p(stream_ptr)), "render")
+
+    @property
+    def pass_count(self):
+        return check(lib.pine_gpu_plan_pass_count(self._h), "pass_count")
+
+    def pass_info(self, j):
+        """(first sample, samples, first whole-pixel tile, tiles) of pass j."""
+        out = (C.c_int32 * 4)()
+        check(lib.pine_gpu_plan_pass_info(self._h, int(j), out), "pass_info")
+        return tuple(out)
+
+    def launch_pass(self, j, film_dev_ptr, stream_ptr=0):
+        """Pass j (in order 0 .. pass_count - 1): the film holds the running result afterwards."""
+        check(lib.pine_gpu_plan_launch_pass(self._h, int(j), C.c_void_p(film_dev_ptr), C.c_void_p(stream_ptr)), "render")
+
+    def tile_order(self):
+        """Film tile of every local tile, in the plan's order (pass_info's tile numbers index it)."""
+        n = check(lib.pine_gpu_plan_tile_order(self._h, None, 0), "tile_order")
+        out = (C.c_int32 * max(n, 1))()
+        check(lib.pine_gpu_plan_tile_order(self._h, out, n), "tile_order")
+        return list(out[:n])
+
+    def device_bytes(self):
+        """Bytes asked of the device: (sample rows, RNG checkpoints, running sum + carried RNG states, all plan buffers)."""
+        out = (C.c_int64 * 4)()
+        check(lib.pine_gpu_plan_device_bytes(self._h, out), "device_bytes")
+        return tuple(out)
 
     def launch_packed(self, slab_dev_ptr, stream_ptr=0):
         """Multi-GPU form: write only this rank's tiles, tile-major, into a slab of slab_floats() floats."""
@@ -658,13 +692,29 @@ class PathIntegrator:
         self.sampler, self.max_path_length, self.device, self.flags = sampler, int(max_path_length), device, int(flags)
         self.devices = list(devices) if devices else None
 
-    def render(self, scene):
+    def render(self, scene, pass_samples=None, on_pass=None):
+        """pass_samples: render in passes of about that many samples per pixel (one device); on_pass(j, n, film) is called
+        with the running film (an (H, W, 4) array, valid during the call) after every pass and stops the render by
+        returning something true -- the film returned is then the last one delivered.  The finished film is the same, bit
+        for bit, with or without passes."""
         if scene.camera is None:
             raise PineError("scene has no camera")
         film = scene.camera.film()
         prm = _lib.RenderParams(self.sampler.requested, self.max_path_length, self.device, 0, 1, 0, self.flags,
                                 getattr(self.sampler, "kind", 0))
         out = np.zeros((film.size[1], film.size[0], 4), dtype=np.float32)
+        if pass_samples is not None or on_pass is not None:
+            if self.devices:
+                raise PineError("PathIntegrator.render: passes render on one device")
+            self.stopped = False
+
+            def _cb(_user, j, n, _film):
+                return 1 if (on_pass is not None and on_pass(j, n, out)) else 0
+            rc = check(lib.pine_gpu_path_render_passes(scene._h, C.byref(prm), int(pass_samples or 0), out.ctypes.data_as(_lib.c_f_p),
+                                                       _lib.PASS_CALLBACK(_cb), None), "PathIntegrator.render")
+            self.stopped = rc == _lib.RENDER_STOPPED
+            film.pixels = out
+            return film
         if self.devices:
             arr = (C.c_int * len(self.devices))(*self.devices)
             check(lib.pine_gpu_path_render_devices(scene._h, C.byref(prm), arr, len(self.devices), out.ctypes.data_as(_lib.c_f_p)),

@@ -697,6 +697,25 @@ std::string SceneHost::describe() const {
 // ================================================================================================
 // C ABI (host part)
 // ================================================================================================
+namespace pine_gpu {
+bool plan_passes(int num_local_tiles, int spp, int samples_per_item, int serial_tiles, int pass_samples, PassPlan& out) {
+  if (num_local_tiles < 0 || spp < 1 || samples_per_item < 1 || samples_per_item > spp || spp % samples_per_item != 0 || serial_tiles < 0 ||
+      serial_tiles > num_local_tiles) {
+    set_error("pass planner: bad argument");
+    return false;
+  }
+  out = PassPlan();
+  out.whole_tiles = samples_per_item == spp ? num_local_tiles : serial_tiles;
+  out.free_tiles = num_local_tiles - out.whole_tiles;
+  int P = pass_samples <= 0 || pass_samples >= spp ? spp : pass_samples;
+  if (out.free_tiles > 0) P = std::max(samples_per_item, P / samples_per_item * samples_per_item);
+  out.P = P;
+  out.n = (spp + P - 1) / P;
+  out.slice = (out.whole_tiles + out.n - 1) / out.n;
+  return true;
+}
+}  // namespace pine_gpu
+
 using namespace pine_gpu;
 
 struct pine_gpu_scene {
@@ -1439,6 +1458,27 @@ int pine_gpu_scene_camera_record(pine_gpu_scene* s, float out[20]) {
   memset(out, 0, 80);
   memcpy(out, &s->host.camera, sizeof(DCamera));
   return 0;
+}
+
+int pine_gpu_pass_schedule(int film_w, int film_h, int shard_rank, int shard_world, int spp, int samples_per_item, int serial_tiles,
+                           int pass_samples, int32_t* out, int cap) {
+  if (film_w <= 0 || film_h <= 0 || shard_world < 1 || shard_rank < 0 || shard_rank >= shard_world || (cap > 0 && !out)) {
+    set_error("bad argument");
+    return -1;
+  }
+  const long long tiles = (long long)((film_w + 7) / 8) * ((film_h + 7) / 8);
+  const long long local = (tiles - shard_rank + shard_world - 1) / shard_world;
+  if (local > INT32_MAX) {
+    set_error("bad argument");
+    return -1;
+  }
+  PassPlan pp;
+  if (!plan_passes(int(local), spp, samples_per_item, serial_tiles, pass_samples, pp)) return -1;
+  for (int j = 0; j < pp.n && (j + 1) * 4 <= cap; j++) {
+    const PassPlan::Pass a = pp.pass(j, spp);
+    out[j * 4] = a.first_sample, out[j * 4 + 1] = a.samples, out[j * 4 + 2] = a.first_tile, out[j * 4 + 3] = a.tiles;
+  }
+  return pp.n;
 }
 
 int pine_gpu_shard_of_pixel(int film_w, int x, int y, int world) {

@@ -3,6 +3,7 @@
 // (derived quantities), camera setup, area-light list, and pine's BVH build, flattened into the
 // GPU records of pine_types.h.
 #pragma once
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -147,5 +148,26 @@ struct SceneHost {
 };
 
 void set_error(const std::string& msg);
+
+// The pass planner (plans created with passes): how a render of `spp` samples per pixel is split into launches
+// that keep at most about `pass_samples` sample rows per tile.  Tiles whose work items are whole pixels (`whole_tiles` of
+// the shard's `num_local_tiles`: all of them when an item is the whole pixel, else the tile classes' serial tiles) are dealt
+// out in slices of `slice` tiles, one slice per pass, with all their samples; the independent class renders the samples
+// [j * P, min(spp, (j + 1) * P)) of every pixel in pass j.  P is a multiple of the samples per item when the class has tiles.
+struct PassPlan {
+  int n = 1, P = 0, whole_tiles = 0, free_tiles = 0, slice = 0;
+  struct Pass { int first_sample, samples, first_tile, tiles; };
+  Pass pass(int j, int spp) const {
+    const int s0 = int(std::min<long long>(spp, (long long)j * P)), s1 = int(std::min<long long>(spp, (long long)(j + 1) * P));
+    const int t0 = int(std::min<long long>(whole_tiles, (long long)j * slice)), t1 = int(std::min<long long>(whole_tiles, (long long)(j + 1) * slice));
+    return Pass{s0, s1 - s0, t0, t1 - t0};
+  }
+  // sample rows (of 64 pixels) pass j keeps
+  unsigned long long rows(int j, int spp) const {
+    const Pass a = pass(j, spp);
+    return (unsigned long long)a.tiles * unsigned(spp) + (unsigned long long)free_tiles * unsigned(a.samples);
+  }
+};
+bool plan_passes(int num_local_tiles, int spp, int samples_per_item, int serial_tiles, int pass_samples, PassPlan& out);
 
 }  // namespace pine_gpu

@@ -167,6 +167,83 @@ __global__ void __launch_bounds__(kBlock) resolve_kernel(WorkParams W, int film_
   if ((threadIdx.x & 63) == 0) atomicAdd(&counters->vertices, verts);
 }
 
+// The same sum CONTINUED from pass to pass (plans created with passes): `sum` holds one float4 per local pixel,
+// (((L_0 + L_1) + ...) + L_{m-1}) of the samples resolved so far -- the partial result of the loop above, so going on from it
+// rounds exactly as the one launch does.  Tiles of the whole-pixel class ([0, whole_tiles) in the plan's tile order) get all
+// spp rows in the pass that renders their slice and none in the others: their film pixel is final from then on and
+// (0, 0, 0, 0) before.  Tiles of the independent class get `free_rows` rows in every pass; their film pixel is the running
+// mean sum / samples_so_far -- after the last pass sum / spp, the division above.  W is the PLAN's work decomposition.
+struct ResolvePass {
+  int film_w, film_h, spp;
+  int whole_tiles, slice_first, slice_tiles;  // the whole-pixel class; the slice of it this pass rendered
+  int free_rows;                               // sample rows of this pass per tile of the independent class
+  int first_pass;                              // ... and whether they are the pixel's first (the sum starts from zero)
+  int samples_so_far;                          // ... and the samples of a pixel of that class up to and including this pass
+  int packed;
+};
+__global__ void __launch_bounds__(kBlock) resolve_accumulate_kernel(WorkParams W, ResolvePass R, const float4* __restrict__ samples,
+                                                                   float4* __restrict__ sum, float4* __restrict__ film,
+                                                                   Counters* __restrict__ counters) {
+  const unsigned long long t = blockIdx.x * (unsigned long long)kBlock + threadIdx.x;
+  const int ltile = int(t >> 6);
+  if (ltile >= W.num_local_tiles) return;  // (whole waves: one wave per tile)
+  const int p = int(t & 63);
+  const int tile = film_tile_of(W, ltile);
+  const int px = (tile % W.tiles_x) * kTile + (p & 7), py = (tile / W.tiles_x) * kTile + (p >> 3);
+  const bool inside = px < R.film_w && py < R.film_h;
+  float4* const acc = sum + (unsigned long long)ltile * 64ull + p;
+  const float4* row = nullptr;
+  int rows = 0;
+  bool carried = false, shown = true;
+  float divisor = float(R.spp);
+  if (ltile < R.whole_tiles) {
+    if (ltile >= R.slice_first && ltile < R.slice_first + R.slice_tiles) {
+      row = samples + (unsigned long long)(ltile - R.slice_first) * (unsigned)R.spp * 64ull + p;
+      rows = R.spp;
+    } else if (ltile < R.slice_first) {
+      carried = true;  // an earlier pass finished it
+    } else {
+      shown = false;
+    }
+  } else {
+    row = samples + ((unsigned long long)R.slice_tiles * (unsigned)R.spp + (unsigned long long)(ltile - R.whole_tiles) * (unsigned)R.free_rows) * 64ull + p;
+    rows = R.free_rows;
+    carried = !R.first_pass;
+    divisor = float(R.samples_so_far);
+  }
+  if (!inside) rows = 0, carried = false;
+  f3 L = mk3(0.0f);
+  if (carried) {
+    const float4 a = *acc;
+    L = f3{a.x, a.y, a.z};
+  }
+  unsigned long long verts = 0;
+  int s = 0;
+  for (; s + 8 <= rows; s += 8) {
+    float4 v[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) v[j] = row[(unsigned long long)(s + j) * 64ull];
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      L = L + f3{v[j].x, v[j].y, v[j].z};
+      verts += (unsigned long long)v[j].w;
+    }
+  }
+  for (; s < rows; s++) {
+    const float4 v = row[(unsigned long long)s * 64ull];
+    L = L + f3{v.x, v.y, v.z};
+    verts += (unsigned long long)v.w;
+  }
+  if (inside) {
+    if (rows > 0) *acc = make_float4(L.x, L.y, L.z, 0.0f);
+    const f3 m = L / divisor;
+    const size_t out_index = R.packed ? size_t(tile / W.shard_world) * 64u + size_t(p) : size_t(py) * R.film_w + px;
+    film[out_index] = shown ? make_float4(m.x, m.y, m.z, 1.0f) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  }
+  for (int off = 32; off > 0; off >>= 1) verts += __shfl_down(verts, off);
+  if ((threadIdx.x & 63) == 0 && verts) atomicAdd(&counters->vertices, verts);
+}
+
 // Multi-GPU: scatter the gathered per-rank slabs [rank][local tile][pixel in tile] into the row-major film.
 __global__ void __launch_bounds__(kBlock) unpack_film_kernel(int film_w, int film_h, int tiles_x, int total_tiles, int world,
                                                             int tiles_per_rank, const float4* __restrict__ slabs,
@@ -187,6 +264,7 @@ __global__ void __launch_bounds__(kBlock) unpack_film_kernel(int film_w, int fil
 static std::atomic<float> g_progress{0.0f};
 static std::atomic<const volatile unsigned long long*> g_progress_src{nullptr};
 static std::atomic<unsigned long long> g_progress_total{0};
+static std::atomic<unsigned long long> g_progress_base{0};  // (a render in passes: the items of the passes already done)
 // depth of the inner-node tree below `node` (= traversal stack entries that can be live)
 static int bvh_depth(const std::vector<DNode>& nodes, int node) {
   const DNode& n = nodes[node];
@@ -526,7 +604,7 @@ float pine_gpu_progress(void) {
   const volatile unsigned long long* src = g_progress_src.load();
   if (src) {
     const unsigned long long total = g_progress_total.load();
-    const float f = total ? float(double(*src) / double(total)) : 0.0f;
+    const float f = total ? float(double(g_progress_base.load() + *src) / double(total)) : 0.0f;
     return f < 1.0f ? f : 1.0f;
   }
   return g_progress.load();
@@ -595,6 +673,8 @@ void pine_gpu_plan_destroy(pine_gpu_plan* p) {
   DevicePool::get().free(p->d_tile_order);
   DevicePool::get().free(p->d_vertex_log);
   DevicePool::get().free(p->d_samples);
+  DevicePool::get().free(p->d_sum);
+  DevicePool::get().free(p->d_rng_carry);
   DevicePool::get().free(p->d_fold);
   DevicePool::get().free(p->d_counters);
   p->spec_loaded.reset();  // (the module stays loaded while the process-wide table or another plan holds it)
@@ -1235,11 +1315,57 @@ static int choose_items(pine_gpu_plan* p, const SceneHost& H, const SceneParts& 
     set_error("film sides above 65535 are not supported");
     return -1;
   }
+  // the pass window of an ordinary launch: the whole render
+  W.pass_first_chunk = 0;
+  W.pass_chunks = W.items_per_pixel;
+  W.pass_chunks_magic = W.pass_chunks > 1 ? unsigned(((1ull << 32) + unsigned(W.pass_chunks) - 1) / unsigned(W.pass_chunks)) : 0u;
+  W.pass_row_stride = spp;
+  W.free_tile_base = W.serial_tiles;
+  W.pass_first_serial_tile = 0;
+  if (!plan_passes(W.num_local_tiles, spp, W.samples_per_item, W.serial_tiles, p->pass_samples_req, p->pass_plan)) return -1;
+  if (p->pass_plan.n > 1) {
+    // a plan with passes: the 32-bit sample-buffer index covers one pass (its rows, and the rows before its first sample that
+    // decode_item adds to a whole-pixel item's base)
+    for (int j = 0; j < p->pass_plan.n; j++)
+      if ((p->pass_plan.rows(j, spp) + unsigned(p->pass_plan.pass(j, spp).first_sample)) * 64ull >= (1ull << 32)) {
+        set_error("film pixels x samples of one pass must stay below 2^32 (fewer samples per pass, or several shards)");
+        return -1;
+      }
+    return 0;
+  }
   if ((unsigned long long)W.num_local_tiles * 64ull * (unsigned long long)spp >= (1ull << 32)) {
     set_error("film pixels x samples per pixel of one shard must stay below 2^32 (render in several shards)");
     return -1;
   }
   return 0;
+}
+
+// The work decomposition of pass j of a plan with passes: the plan's, with the pass window in place of the whole render.
+static WorkParams pass_work(const pine_gpu_plan* p, int j) {
+  WorkParams W = p->W;
+  const int spp = p->S.spp;
+  const PassPlan::Pass a = p->pass_plan.pass(j, spp);
+  if (p->W.items_per_pixel == 1) {
+    // every pixel is one whole-pixel item (one class, serial_tiles == 0): a slice of the shard's tiles
+    W.free_tile_base = a.first_tile;
+    W.total_items = (unsigned long long)a.tiles * 64ull;
+    return W;
+  }
+  W.serial_tiles = a.tiles;
+  W.pass_first_serial_tile = a.first_tile;
+  W.free_tile_base = p->W.serial_tiles;
+  W.pass_first_chunk = a.first_sample / W.samples_per_item;
+  W.pass_chunks = a.samples / W.samples_per_item;
+  W.pass_chunks_magic = W.pass_chunks > 1 ? unsigned(((1ull << 32) + unsigned(W.pass_chunks) - 1) / unsigned(W.pass_chunks)) : 0u;
+  W.pass_row_stride = a.samples;
+  W.total_items = (unsigned long long)a.tiles * 64ull + (unsigned long long)p->pass_plan.free_tiles * unsigned(W.pass_chunks) * 64ull;
+  if (p->W.serial_tiles > 0 && a.tiles == 0) {
+    // tile classes, a pass whose slice of whole-pixel tiles is empty: only independent one-sample items, no pixel's chain to
+    // hand on and none in flight to bound
+    W.fork_sealed = 0;
+    W.max_pixels = 1 << 20;
+  }
+  return W;
 }
 
 // The scheduling defaults of the kernels (WorkParams), measurement aids applied.
@@ -1302,30 +1428,55 @@ static int size_and_allocate(pine_gpu_plan* p, const pine_gpu_render_params* prm
   }
   if (blocks_per_cu < 1) blocks_per_cu = 1;
   if (blocks_per_cu > 8) blocks_per_cu = 8;
-  unsigned long long want = (W.total_items + kBlock - 1) / kBlock;
+  // (a plan with passes: the launch shape, the claims and the buffers are sized for its largest pass)
+  const PassPlan& PP = p->pass_plan;
+  unsigned long long launch_items = W.total_items, sample_rows = (unsigned long long)W.num_local_tiles * unsigned(spp);
+  int ckpt_chunks = W.items_per_pixel;
+  if (PP.n > 1) {
+    launch_items = sample_rows = 0;
+    ckpt_chunks = 0;
+    for (int j = 0; j < PP.n; j++) {
+      const WorkParams Wj = pass_work(p, j);
+      launch_items = std::max(launch_items, Wj.total_items);
+      sample_rows = std::max(sample_rows, PP.rows(j, spp));
+      ckpt_chunks = std::max(ckpt_chunks, Wj.pass_chunks);
+    }
+  }
+  unsigned long long want = (launch_items + kBlock - 1) / kBlock;
   const int qctx = p->fast ? p->fast->ctx : p->queue_variant >= 0 ? kQueueVariants[p->queue_variant].ctx : 0;
-  if (queued) want = (W.total_items + qctx - 1) / qctx;
+  if (queued) want = (launch_items + qctx - 1) / qctx;
   p->grid = int(std::min<unsigned long long>(want, (unsigned long long)prop.multiProcessorCount * blocks_per_cu));
   if (p->grid < 1) p->grid = 1;
   if (!p->serial_rng && K.pool_items == kUnset) {
     // work-item claims of the stage-queued kernel: 1/32 of a workgroup's share, between 512 and 2048 (a claim is a run of
     // neighbouring tiles: larger ones keep a workgroup's camera rays together and are fewer -- 10 000 cones 8.00 -> 7.88 ms
     // at 2048, 7.81 at 4096, 8.4 at 8192 where the last claims unbalance the end; cbox indifferent up to 2048)
-    unsigned long long share = W.total_items / ((unsigned long long)p->grid * 32ull);
+    unsigned long long share = launch_items / ((unsigned long long)p->grid * 32ull);
     int claim = 512;
     while (claim < 2048 && (unsigned long long)claim * 2ull <= share) claim *= 2;
     W.pool_items = claim;
   }
 
-  if (W.items_per_pixel > 1)
-    HIP_OK(POOL_ALLOC(p->d_ckpt, (size_t)(W.num_local_tiles - W.serial_tiles) * W.items_per_pixel * 64 * sizeof(ulonglong2)));
+  if (W.items_per_pixel > 1) {
+    p->bytes_ckpt = (size_t)(W.num_local_tiles - W.serial_tiles) * ckpt_chunks * 64 * sizeof(ulonglong2);
+    HIP_OK(POOL_ALLOC(p->d_ckpt, p->bytes_ckpt));
+    if (PP.n > 1) {
+      p->bytes_carry = (size_t)PP.free_tiles * 64 * sizeof(ulonglong2);
+      HIP_OK(POOL_ALLOC(p->d_rng_carry, p->bytes_carry));
+    }
+  }
+  if (PP.n > 1) {
+    HIP_OK(POOL_ALLOC(p->d_sum, (size_t)W.num_local_tiles * 64 * sizeof(float4)));
+    p->bytes_carry += (size_t)W.num_local_tiles * 64 * sizeof(float4);
+  }
   p->ckpt_every_launch = K.ckpt_every_launch;
   if (!p->tile_order.empty()) {
     HIP_OK(POOL_ALLOC(p->d_tile_order, p->tile_order.size() * sizeof(int)));
     HIP_OK(hipMemcpy(p->d_tile_order, p->tile_order.data(), p->tile_order.size() * sizeof(int), hipMemcpyHostToDevice));
     W.tile_order = p->d_tile_order;
   }
-  HIP_OK(POOL_ALLOC(p->d_samples, (size_t)W.num_local_tiles * spp * 64 * sizeof(float4)));
+  p->bytes_samples = size_t(sample_rows) * 64 * sizeof(float4);
+  HIP_OK(POOL_ALLOC(p->d_samples, p->bytes_samples));
   const size_t fold_slots = queued ? size_t(p->grid) * qctx : size_t(p->grid) * kBlock;
   HIP_OK(POOL_ALLOC(p->d_fold, size_t(prm->max_path_length) * 8 * fold_slots * sizeof(float)));
   if (queued) {
@@ -1356,6 +1507,7 @@ static int plan_build(pine_gpu_plan* p, pine_gpu_scene* scene, const pine_gpu_re
   HIP_OK(hipSetDevice(prm->device));
   p->device = prm->device;
   p->params = *prm;
+  const size_t tally0 = g_alloc_tally;
   const auto t_build0 = std::chrono::steady_clock::now();
   if (!H.accel.built) {
     H.build_on_device = (prm->flags & PINE_GPU_FLAG_DEVICE_BVH) ? prm->device : -1;
@@ -1375,17 +1527,19 @@ static int plan_build(pine_gpu_plan* p, pine_gpu_scene* scene, const pine_gpu_re
   if (choose_items(p, H, sp, prm, spp, K, uber_rng)) return -1;
   schedule_params(p, A, prm, uber_rng, K);
   if (size_and_allocate(p, prm, spp, K)) return -1;
+  p->bytes_total = g_alloc_tally - tally0;
   HIP_OK(hipDeviceSynchronize());
   p->upload_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_build1).count();
   return 0;
 }
 
-pine_gpu_plan* pine_gpu_plan_create(pine_gpu_scene* scene, const pine_gpu_render_params* prm) {
+static pine_gpu_plan* plan_create(pine_gpu_scene* scene, const pine_gpu_render_params* prm, int pass_samples) {
   if (!scene || !prm) {
     set_error("null argument");
     return nullptr;
   }
   pine_gpu_plan* p = new pine_gpu_plan();
+  p->pass_samples_req = pass_samples;
   if (plan_build(p, scene, prm)) {
     std::string keep = pine_gpu_last_error();
     pine_gpu_plan_destroy(p);
@@ -1394,6 +1548,89 @@ pine_gpu_plan* pine_gpu_plan_create(pine_gpu_scene* scene, const pine_gpu_render
   }
   return p;
 }
+pine_gpu_plan* pine_gpu_plan_create(pine_gpu_scene* scene, const pine_gpu_render_params* prm) { return plan_create(scene, prm, 0); }
+pine_gpu_plan* pine_gpu_plan_create_passes(pine_gpu_scene* scene, const pine_gpu_render_params* prm, int32_t pass_samples) {
+  return plan_create(scene, prm, pass_samples);
+}
+
+// The path kernel of the plan -- the scene's own, a declared-tolerance, a stage-queued or a megakernel variant -- over the
+// work decomposition W, its samples going to `samples` (+ sample index * 64, decode_item).
+static int launch_path_kernel(pine_gpu_plan* p, WorkParams& W, float4* samples, int grid, hipStream_t stream) {
+  const ulonglong2* ckpt = p->d_ckpt;
+  if (p->fast) {
+    // (a kernel of the other translation unit: same argument layout, launched untyped)
+    void* args[] = {&p->S, &W, &ckpt, &samples, &p->d_fold, &p->d_ctxg, &p->d_counters};
+    HIP_OK(hipLaunchKernel(p->fast->fn, dim3(grid), dim3(kQBlock), args, p->lds_bytes, stream));
+  } else if (p->spec_fn) {
+    void* args[] = {&p->S, &W, &ckpt, &samples, &p->d_fold, &p->d_ctxg, &p->d_counters};
+    HIP_OK(hipModuleLaunchKernel(p->spec_fn, unsigned(grid), 1, 1, kQBlock, 1, 1, unsigned(p->lds_bytes), stream, args, nullptr));
+  } else if (p->queue_variant >= 0) {
+    void* args[] = {&p->S, &W, &ckpt, &samples, &p->d_fold, &p->d_ctxg, &p->d_counters};
+    HIP_OK(hipLaunchKernel(kQueueVariants[p->queue_variant].fn, dim3(grid), dim3(kQBlock), args, p->lds_bytes, stream));
+  } else {
+    void* args[] = {&p->S, &W, &ckpt, &samples, &p->d_fold, &p->d_counters};
+    HIP_OK(hipLaunchKernel(kVariants[p->variant].fn, dim3(grid), dim3(kBlock), args, p->lds_bytes, stream));
+  }
+  return 0;
+}
+
+// Pass j of a plan with passes (pass_plan.n > 1): checkpoint prepass from the carried RNG states, the path kernel over the
+// pass window, the resolve that continues the running sum and writes the film.
+static int plan_launch_pass(pine_gpu_plan* p, int j, void* film_dev, hipStream_t stream, bool packed) {
+  const PassPlan& PP = p->pass_plan;
+  if (j < 0 || j >= PP.n || (j != 0 && j != p->next_pass)) {
+    set_error("passes run in order: pass " + std::to_string(j) + " asked for, pass " + std::to_string(p->next_pass >= PP.n ? 0 : p->next_pass) +
+              (p->next_pass > 0 && p->next_pass < PP.n ? " (or 0, which starts the film afresh)" : "") + " is next; nothing was launched");
+    return -1;
+  }
+  HIP_OK(hipSetDevice(p->device));
+  (void)hipGetLastError();
+  plan_poll_background(p);  // (a scene kernel that arrives between two passes renders the rest: the same bits)
+  if (j == 0) g_progress.store(0.0f);
+  const int spp = p->S.spp;
+  const PassPlan::Pass a = PP.pass(j, spp);
+  WorkParams W = pass_work(p, j);
+  const size_t film_bytes = size_t(p->film_w) * p->film_h * sizeof(float4);
+  if (p->W.shard_world > 1 && !packed) HIP_OK(hipMemsetAsync(film_dev, 0, film_bytes, stream));
+  // the counters of the sequence start with pass 0; every pass hands out its own items from zero
+  HIP_OK(hipMemsetAsync(p->d_counters, 0, j == 0 ? sizeof(Counters) : sizeof(unsigned long long), stream));
+  static_assert(offsetof(Counters, next_item) == 0, "the per-pass reset clears next_item");
+  hipEvent_t* ev = p->ev[p->launch_count % pine_gpu_plan::kEvRing];
+  if (p->timed) HIP_OK(hipEventRecord(ev[0], stream));
+  const bool has_work = W.total_items > 0;
+  if (has_work && p->W.items_per_pixel > 1 && PP.free_tiles > 0) {
+    const unsigned long long n = (unsigned long long)PP.free_tiles * 64ull;
+    hipLaunchKernelGGL(rng_checkpoint_kernel, dim3(unsigned((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, W, p->film_w, p->film_h,
+                       spp, p->d_ckpt, PP.free_tiles, p->d_rng_carry);
+    p->ckpt_valid = false;
+  }
+  if (p->timed) HIP_OK(hipEventRecord(ev[1], stream));
+  if (has_work) {
+    const int qctx = p->fast ? p->fast->ctx : p->queue_variant >= 0 ? kQueueVariants[p->queue_variant].ctx : kBlock;  // items a workgroup holds
+    const int grid = int(std::min<unsigned long long>((unsigned long long)p->grid, (W.total_items + qctx - 1) / qctx));
+    // (the rows before the pass's first sample are not in the buffer: see decode_item)
+    float4* const samples = p->d_samples - size_t(W.pass_first_chunk) * size_t(W.samples_per_item) * 64u;
+    if (launch_path_kernel(p, W, samples, grid, stream)) return -1;
+  }
+  if (p->timed) HIP_OK(hipEventRecord(ev[2], stream));
+  if (p->W.num_local_tiles > 0) {
+    ResolvePass R;
+    R.film_w = p->film_w, R.film_h = p->film_h, R.spp = spp;
+    R.whole_tiles = PP.whole_tiles, R.slice_first = a.first_tile, R.slice_tiles = a.tiles;
+    R.free_rows = a.samples, R.first_pass = j == 0 ? 1 : 0, R.samples_so_far = a.first_sample + a.samples;
+    R.packed = packed ? 1 : 0;
+    const unsigned long long n = (unsigned long long)p->W.num_local_tiles * 64ull;
+    hipLaunchKernelGGL(resolve_accumulate_kernel, dim3(unsigned((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, p->W, R, p->d_samples,
+                       p->d_sum, (float4*)film_dev, p->d_counters);
+  }
+  if (p->timed) HIP_OK(hipEventRecord(ev[3], stream));
+  HIP_OK(hipGetLastError());
+  p->launched = true;
+  p->launch_count++;
+  p->last_stream = stream;
+  p->next_pass = j + 1;
+  return 0;
+}
 
 static int plan_launch(pine_gpu_plan* p, void* film_dev, void* stream_, bool packed) {
   if (!p || !film_dev) {
@@ -1401,6 +1638,11 @@ static int plan_launch(pine_gpu_plan* p, void* film_dev, void* stream_, bool pac
     return -1;
   }
   hipStream_t stream = (hipStream_t)stream_;
+  if (p->pass_plan.n > 1) {  // a plan with passes: all of them, in order
+    for (int j = 0; j < p->pass_plan.n; j++)
+      if (plan_launch_pass(p, j, film_dev, stream, packed)) return -1;
+    return 0;
+  }
   HIP_OK(hipSetDevice(p->device));
   (void)hipGetLastError();  // (HIP's last error is sticky: what the check at the end reports must come from THIS launch's calls)
   // a background build that has finished: this launch and every later one run the scene's own kernel.  (A code object the
@@ -1416,9 +1658,10 @@ static int plan_launch(pine_gpu_plan* p, void* film_dev, void* stream_, bool pac
   const bool has_work = p->W.num_local_tiles > 0;
   if (has_work && p->W.items_per_pixel > 1) {
     if (!p->ckpt_valid || p->ckpt_every_launch) {
-      const unsigned long long n = (unsigned long long)(p->W.num_local_tiles - p->W.serial_tiles) * 64ull;
+      const int free_tiles = p->W.num_local_tiles - p->W.serial_tiles;
+      const unsigned long long n = (unsigned long long)free_tiles * 64ull;
       hipLaunchKernelGGL(rng_checkpoint_kernel, dim3(unsigned((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream,
-                         p->W, p->film_w, p->film_h, p->S.spp, p->d_ckpt);
+                         p->W, p->film_w, p->film_h, p->S.spp, p->d_ckpt, free_tiles, (ulonglong2*)nullptr);
       if (!p->ckpt_done) HIP_OK(hipEventCreateWithFlags(&p->ckpt_done, hipEventDisableTiming));
       HIP_OK(hipEventRecord(p->ckpt_done, stream));
       p->ckpt_stream = stream;
@@ -1428,25 +1671,7 @@ static int plan_launch(pine_gpu_plan* p, void* film_dev, void* stream_, bool pac
     }
   }
   if (p->timed) HIP_OK(hipEventRecord(ev[1], stream));
-  if (!has_work) {
-  } else if (p->fast) {
-    // (a kernel of the other translation unit: same argument layout, launched untyped)
-    const ulonglong2* ckpt = p->d_ckpt;
-    void* args[] = {&p->S, &p->W, &ckpt, &p->d_samples, &p->d_fold, &p->d_ctxg, &p->d_counters};
-    HIP_OK(hipLaunchKernel(p->fast->fn, dim3(p->grid), dim3(kQBlock), args, p->lds_bytes, stream));
-  } else if (p->spec_fn) {
-    const ulonglong2* ckpt = p->d_ckpt;
-    void* args[] = {&p->S, &p->W, &ckpt, &p->d_samples, &p->d_fold, &p->d_ctxg, &p->d_counters};
-    HIP_OK(hipModuleLaunchKernel(p->spec_fn, unsigned(p->grid), 1, 1, kQBlock, 1, 1, unsigned(p->lds_bytes), stream, args, nullptr));
-  } else if (p->queue_variant >= 0) {
-    const ulonglong2* ckpt = p->d_ckpt;
-    void* args[] = {&p->S, &p->W, &ckpt, &p->d_samples, &p->d_fold, &p->d_ctxg, &p->d_counters};
-    HIP_OK(hipLaunchKernel(kQueueVariants[p->queue_variant].fn, dim3(p->grid), dim3(kQBlock), args, p->lds_bytes, stream));
-  } else {
-    const ulonglong2* ckpt = p->d_ckpt;
-    void* args[] = {&p->S, &p->W, &ckpt, &p->d_samples, &p->d_fold, &p->d_counters};
-    HIP_OK(hipLaunchKernel(kVariants[p->variant].fn, dim3(p->grid), dim3(kBlock), args, p->lds_bytes, stream));
-  }
+  if (has_work && launch_path_kernel(p, p->W, p->d_samples, p->grid, stream)) return -1;
   if (p->timed) HIP_OK(hipEventRecord(ev[2], stream));
   if (has_work) {
     const unsigned long long n = (unsigned long long)p->W.num_local_tiles * 64ull;
@@ -1468,6 +1693,55 @@ void pine_gpu_release_cached_memory(void) {
 }
 
 int pine_gpu_plan_launch(pine_gpu_plan* p, void* film_dev, void* stream) { return plan_launch(p, film_dev, stream, false); }
+int pine_gpu_plan_launch_pass(pine_gpu_plan* p, int pass, void* film_dev, void* stream) {
+  if (!p || !film_dev) {
+    set_error("null argument");
+    return -1;
+  }
+  if (p->pass_plan.n > 1) return plan_launch_pass(p, pass, film_dev, (hipStream_t)stream, false);
+  if (pass != 0) {
+    set_error("this plan has one pass: pass 0");
+    return -1;
+  }
+  return plan_launch(p, film_dev, stream, false);
+}
+int pine_gpu_plan_pass_count(pine_gpu_plan* p) {
+  if (!p) {
+    set_error("null argument");
+    return -1;
+  }
+  return p->pass_plan.n;
+}
+int pine_gpu_plan_pass_info(pine_gpu_plan* p, int pass, int32_t out[4]) {
+  if (!p || !out) {
+    set_error("null argument");
+    return -1;
+  }
+  if (pass < 0 || pass >= p->pass_plan.n) {
+    set_error("no such pass");
+    return -1;
+  }
+  const PassPlan::Pass a = p->pass_plan.pass(pass, p->S.spp);
+  out[0] = a.first_sample, out[1] = a.samples, out[2] = a.first_tile, out[3] = a.tiles;
+  return 0;
+}
+int pine_gpu_plan_tile_order(pine_gpu_plan* p, int32_t* out, int cap) {
+  if (!p || (cap > 0 && !out)) {
+    set_error("null argument");
+    return -1;
+  }
+  for (int lt = 0; lt < p->W.num_local_tiles && lt < cap; lt++)
+    out[lt] = p->tile_order.empty() ? lt * p->W.shard_world + p->W.shard_rank : p->tile_order[size_t(lt)];
+  return p->W.num_local_tiles;
+}
+int pine_gpu_plan_device_bytes(pine_gpu_plan* p, int64_t out[4]) {
+  if (!p || !out) {
+    set_error("null argument");
+    return -1;
+  }
+  out[0] = int64_t(p->bytes_samples), out[1] = int64_t(p->bytes_ckpt), out[2] = int64_t(p->bytes_carry), out[3] = int64_t(p->bytes_total);
+  return 0;
+}
 int pine_gpu_plan_launch_packed(pine_gpu_plan* p, void* slab_dev, void* stream) { return plan_launch(p, slab_dev, stream, true); }
 
 int pine_gpu_film_unpack(int film_w, int film_h, int world, int device, const void* slabs_dev, void* film_dev, void* stream_) {
@@ -1534,6 +1808,10 @@ int pine_gpu_plan_stats_get(pine_gpu_plan* p, pine_gpu_plan_stats* out) {
       unsigned long long first = p->stats_read_upto;
       if (p->launch_count - first > (unsigned long long)pine_gpu_plan::kEvRing) first = p->launch_count - pine_gpu_plan::kEvRing;
       if (first == p->launch_count) first = p->launch_count - 1;  // nothing new: report the last launch again
+      // a plan with passes: every pass is a slot of the ring; the timings are those of ONE sequence -- the sum over its last
+      // passes (at most kEvRing of them, scaled to the sequence's length when it has more)
+      const unsigned long long np = (unsigned long long)p->pass_plan.n;
+      if (np > 1) first = p->launch_count - std::min<unsigned long long>({np, p->launch_count, (unsigned long long)pine_gpu_plan::kEvRing});
       double a = 0, b = 0, c3 = 0;
       for (unsigned long long i = first; i < p->launch_count; i++) {
         hipEvent_t* ev = p->ev[i % pine_gpu_plan::kEvRing];
@@ -1543,11 +1821,11 @@ int pine_gpu_plan_stats_get(pine_gpu_plan* p, pine_gpu_plan_stats* out) {
         HIP_OK(hipEventElapsedTime(&z, ev[2], ev[3]));
         a += x, b += y, c3 += z;
       }
-      const double n = double(p->launch_count - first);
+      const double n = np > 1 ? double(p->launch_count - first) / double(np) : double(p->launch_count - first);
       out->prepass_ms = float(a / n);
       out->trace_ms = float(b / n);
       out->resolve_ms = float(c3 / n);
-      out->timed_launches = int32_t(p->launch_count - first);
+      out->timed_launches = np > 1 ? 1 : int32_t(p->launch_count - first);
       p->stats_read_upto = p->launch_count;
     }
   }
@@ -1612,6 +1890,10 @@ int64_t pine_gpu_plan_vertex_log(pine_gpu_plan* p, float* out, int64_t capacity)
     set_error("the per-vertex log needs a plan created with PINE_GPU_FLAG_VERTEX_LOG (stage-queued kernel, the two variants compiled with the hook)");
     return -1;
   }
+  if (p->pass_plan.n > 1) {
+    set_error("the per-vertex log is not kept by a plan with passes");
+    return -1;
+  }
   const int64_t n = int64_t(p->film_w) * p->film_h * p->S.spp * p->S.max_path_length * kVertexLogFloats;
   if (n > (int64_t(1) << 27)) {
     set_error("the per-vertex log is meant for small films (at most 2^27 floats)");
@@ -1636,6 +1918,10 @@ int64_t pine_gpu_plan_vertex_log(pine_gpu_plan* p, float* out, int64_t capacity)
 int pine_gpu_plan_read_samples(pine_gpu_plan* p, float* out, int64_t capacity) {
   if (!p || !out) {
     set_error("null argument");
+    return -1;
+  }
+  if (p->pass_plan.n > 1) {
+    set_error("a plan with passes keeps the sample rows of one pass only: read_samples needs an ordinary plan");
     return -1;
   }
   const int spp = p->S.spp;
@@ -1697,6 +1983,57 @@ int pine_gpu_path_render(pine_gpu_scene* scene, const pine_gpu_render_params* pr
   DevicePool::get().free(d_film);
   pine_gpu_plan_destroy(p);
   if (rc) set_error(keep);
+  return rc;
+}
+
+int pine_gpu_path_render_passes(pine_gpu_scene* scene, const pine_gpu_render_params* prm, int32_t pass_samples, float* film_out,
+                                pine_gpu_pass_callback cb, void* user) {
+  if (!scene || !prm || !film_out) {
+    set_error("null argument");
+    return -1;
+  }
+  pine_gpu_render_params prm2 = *prm;
+  prm2.flags |= PINE_GPU_FLAG_PROGRESS;
+  pine_gpu_plan* p = pine_gpu_plan_create_passes(scene, &prm2, pass_samples);
+  if (!p) return -1;
+  int rc = -1;
+  void* d_film = nullptr;
+  const size_t bytes = size_t(p->film_w) * p->film_h * 16;
+  const int n = p->pass_plan.n;
+  do {
+    if (DevicePool::get().alloc(&d_film, bytes) != hipSuccess) {
+      set_error("hipMalloc(film) failed");
+      break;
+    }
+    // get_progress() over the whole sequence: the items of the passes done + those the running pass has claimed
+    unsigned long long total = 0;
+    for (int j = 0; j < n; j++) total += n > 1 ? pass_work(p, j).total_items : p->W.total_items;
+    g_progress_total.store(total);
+    g_progress_base.store(0);
+    g_progress_src.store(p->h_progress);
+    bool ok = true;
+    for (int j = 0; j < n && ok && rc < 0; j++) {
+      ok = pine_gpu_plan_launch_pass(p, j, d_film, nullptr) == 0;
+      if (ok && hipMemcpy(film_out, d_film, bytes, hipMemcpyDeviceToHost) != hipSuccess) {
+        set_error("film download failed");
+        ok = false;
+      }
+      if (ok) ok = pine_gpu_plan_check(p) == 0;  // a bailed-out pass leaves an incomplete film: fail
+      if (!ok) break;
+      *p->h_progress = 0;  // (the pass has finished: nothing writes the word until the next launch)
+      g_progress_base.fetch_add(n > 1 ? pass_work(p, j).total_items : p->W.total_items);
+      if (cb && cb(user, j, n, film_out) != 0) rc = PINE_GPU_RENDER_STOPPED;
+    }
+    if (ok && rc < 0) rc = 0;
+  } while (0);
+  g_progress_src.store(nullptr);
+  g_progress_base.store(0);
+  g_progress.store(rc == 0 ? 1.0f : 0.0f);
+  std::string keep = rc < 0 ? pine_gpu_last_error() : "";
+  if (rc < 0) (void)hipDeviceSynchronize();
+  DevicePool::get().free(d_film);
+  pine_gpu_plan_destroy(p);
+  if (rc < 0) set_error(keep);
   return rc;
 }
 

@@ -214,6 +214,16 @@ struct WorkParams {
   // [((py * film_w + px) * spp + sample) * max_path_length + level] -- the layout of `pine_ref vertices` (oracle/ref_driver.cpp):
   // kind | length | direct term (3) | bs.f (3) | cosine | bs.pdf | is_delta | mis | returned light pdf (-1: none) | returned Lo (3)
   float* vertex_log;
+  // The pass window (plans created with passes; an ordinary launch: the whole render).  A launch hands out the
+  // whole-pixel items of `serial_tiles` tiles (local tiles pass_first_serial_tile ...) and, for every tile of the independent
+  // class (local tiles free_tile_base ...), the chunks [pass_first_chunk, pass_first_chunk + pass_chunks) of each pixel.
+  // Read by decode_item only: cold, like the rest of the work decomposition.
+  int pass_first_chunk;
+  int pass_chunks;             // ordinary launch: items_per_pixel
+  unsigned pass_chunks_magic;  // ceil(2^32 / pass_chunks)
+  int pass_row_stride;         // sample rows a tile of the independent class has in the sample buffer (ordinary launch: spp)
+  int free_tile_base;          // ordinary launch: serial_tiles
+  int pass_first_serial_tile;  // ordinary launch: 0
 };
 constexpr int kVertexLogFloats = 16;
 // get_progress() (integrator.cpp:17-19): every 16th / 64th pool claim posts the claimed-item count to host memory
@@ -709,9 +719,17 @@ __device__ __forceinline__ ItemInfo decode_item(const WorkParams& W, int film_w,
   const unsigned long long rel = it.serial ? item : item - serial_items;
   const int p = int(rel & 63);
   const unsigned long long tc = rel >> 6;
-  // spp and k are powers of two: shifts instead of 64-bit divisions (this runs once per camera sample)
-  const int chunk = it.serial ? 0 : int(tc & (unsigned long long)(W.items_per_pixel - 1));
-  const int ltile = it.serial ? int(tc) : W.serial_tiles + int(tc >> W.log2_items_per_pixel);
+  // (tile of the class, chunk of the pass) = tc / pass_chunks and the remainder: the chunks of a pass need not be a power of
+  // two, so -- as for tiles_x below -- a multiplication with the rounded-up reciprocal and one fix-up step instead of a
+  // 64-bit division (this runs once per work item; tc < 2^26: a launch has fewer than 2^32 sample rows)
+  unsigned q = unsigned(tc), chunk = 0;
+  if (!it.serial && W.pass_chunks != 1) {
+    q = unsigned((uint64_t(unsigned(tc)) * W.pass_chunks_magic) >> 32);
+    if (q * unsigned(W.pass_chunks) > unsigned(tc)) q--;
+    chunk = unsigned(tc) - q * unsigned(W.pass_chunks);
+  }
+  if (!it.serial) chunk += unsigned(W.pass_first_chunk);
+  const int ltile = (it.serial ? W.pass_first_serial_tile : W.free_tile_base) + int(q);
   const int tile = film_tile_of(W, ltile);
   it.ckpt_index = rel;
   // tile / tiles_x by multiplication with the rounded-up reciprocal + one fix-up step (exact for any
@@ -722,8 +740,14 @@ __device__ __forceinline__ ItemInfo decode_item(const WorkParams& W, int film_w,
   const int tx = tile - int(ty) * W.tiles_x;
   it.px = tx * kTile + (p & 7);
   it.py = ty * kTile + (p >> 3);
-  it.chunk = chunk;
-  it.sample_base = (unsigned long long)ltile * (unsigned)spp * 64ull + (unsigned)p;
+  it.chunk = int(chunk);
+  // The sample buffer of a launch: [whole-pixel tile of the launch][spp rows], then [independent tile][pass_row_stride rows].
+  // The kernels store sample s at sample_base + s * 64 with the ABSOLUTE s, and the host hands them the buffer's address
+  // less the rows before the pass's first sample: a sample lands in its pass-relative row, a whole-pixel item (all of whose
+  // samples are in the launch) gets those rows added here.  An ordinary launch: local tile * spp * 64 + p, no offset.
+  const unsigned long long first_row = (unsigned long long)(unsigned(W.pass_first_chunk) * unsigned(W.samples_per_item));
+  it.sample_base = it.serial ? ((unsigned long long)q * (unsigned)spp + first_row) * 64ull + (unsigned)p
+                             : ((unsigned long long)W.serial_tiles * (unsigned)spp + (unsigned long long)q * (unsigned)W.pass_row_stride) * 64ull + (unsigned)p;
   it.valid = it.px < film_w && it.py < film_h;
   return it;
 }
@@ -731,22 +755,29 @@ __device__ __forceinline__ ItemInfo decode_item(const WorkParams& W, int film_w,
 // RNG state at the start of every item: the reference reseeds per pixel (sampler.h:286-290) and
 // then draws 4 floats per camera sample (path.cpp:35); when nothing inside radiance() touches the
 // RNG the state at sample s is the seed advanced 4*s steps.
+// A plan with passes (`carry` not null): the walk is CARRIED from pass to pass -- 16 bytes per pixel of the class, the state
+// at the pass's first sample, read here (seeded in the pass that starts at sample 0) and left for the next pass.
 static __global__ void __launch_bounds__(kBlock) rng_checkpoint_kernel(WorkParams W, int film_w, int film_h, int spp,
-                                                               ulonglong2* ckpt) {
-  // one thread per (local tile of the independent class, pixel in tile); walks the whole pixel, storing at chunk starts
+                                                               ulonglong2* ckpt, int free_tiles, ulonglong2* carry) {
+  // one thread per (local tile of the independent class, pixel in tile); walks the pixel's samples of the launch, storing at chunk starts
   const unsigned long long t = blockIdx.x * (unsigned long long)kBlock + threadIdx.x;
-  const unsigned long long n = (unsigned long long)(W.num_local_tiles - W.serial_tiles) * 64ull;
+  const unsigned long long n = (unsigned long long)free_tiles * 64ull;
   if (t >= n) return;
   const int p = int(t & 63);
   const int ptile = int(t >> 6);  // (position among the independent tiles: ItemInfo::ckpt_index counts from there)
-  const int tile = film_tile_of(W, W.serial_tiles + ptile);
+  const int tile = film_tile_of(W, W.free_tile_base + ptile);
   const int px = (tile % W.tiles_x) * kTile + (p & 7), py = (tile / W.tiles_x) * kTile + (p >> 3);
   DRng g = rng_seed(hash_pixel(px, py, 0));
-  for (int c = 0; c < W.items_per_pixel; c++) {
-    const unsigned long long item = ((unsigned long long)ptile * W.items_per_pixel + c) * 64ull + p;
+  if (carry && W.pass_first_chunk != 0) {
+    const ulonglong2 c = carry[t];
+    g = DRng{c.x, c.y};
+  }
+  for (int c = 0; c < W.pass_chunks; c++) {
+    const unsigned long long item = ((unsigned long long)ptile * W.pass_chunks + c) * 64ull + p;
     ckpt[item] = make_ulonglong2(g.s0, g.s1);
     for (int i = 0; i < 4 * W.samples_per_item; i++) rng_next64(g);
   }
+  if (carry) carry[t] = make_ulonglong2(g.s0, g.s1);
   (void)film_w, (void)film_h, (void)spp;
 }
 

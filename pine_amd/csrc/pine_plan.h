@@ -107,6 +107,7 @@ static int effective_spp(int spp) {  // BlueSobolSampler ctor sampler.cpp:115-12
 // its kernels.  A destroyed plan's blocks of 256 KB and more go to a per-device free list instead and the next plan takes
 // the smallest one that fits within 25 %; at most $PINE_GPU_POOL_MB (default 16 384; 0: no pool) are kept,
 // pine_gpu_release_cached_memory() frees them.  No kernel reads a buffer before writing it (hipMalloc does not clear either).
+inline thread_local size_t g_alloc_tally = 0;  // bytes asked of DevicePool::alloc by this thread (plan_build: pine_gpu_plan_device_bytes)
 struct DevicePool {
   struct Block {
     void* p;
@@ -127,6 +128,7 @@ struct DevicePool {
   static constexpr size_t kMinPooled = size_t(256) << 10;
   hipError_t alloc(void** out, size_t bytes) {
     *out = nullptr;
+    g_alloc_tally += bytes;
     if (bytes < kMinPooled || cap == 0) return hipMalloc(out, bytes);
     int device = 0;
     (void)hipGetDevice(&device);
@@ -247,6 +249,14 @@ struct pine_gpu_plan {
   int* d_tile_order = nullptr;          // tile classes (WorkParams::tile_order), or null
   std::vector<int> tile_order;          // ... its host copy (empty: local tile t is film tile t * shard_world + shard_rank)
   float4* d_samples = nullptr;
+  // Passes (pine_gpu_plan_create_passes; pass_plan.n == 1: an ordinary plan, none of the buffers below).  The running sum is
+  // one float4 per local pixel ([local tile][pixel in tile], .w unused); the carried RNG states one per pixel of the independent class.
+  int pass_samples_req = 0;
+  PassPlan pass_plan;
+  int next_pass = 0;                        // the pass that may be launched next (0 may always be)
+  float4* d_sum = nullptr;
+  ulonglong2* d_rng_carry = nullptr;
+  size_t bytes_samples = 0, bytes_ckpt = 0, bytes_carry = 0, bytes_total = 0;
   float* d_fold = nullptr;
   Counters* d_counters = nullptr;
   int grid = 0;

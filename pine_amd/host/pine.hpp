@@ -8,6 +8,7 @@
 #pragma once
 #include <array>
 #include <cstdint>
+#include <functional>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -248,7 +249,11 @@ class PathIntegrator {
     flags_ |= on ? PINE_GPU_FLAG_SPECIALIZE : PINE_GPU_FLAG_NO_SPECIALIZE;
     return *this;
   }
-  void render(Scene& scene) {
+  // pass_samples > 0 or on_pass: render in passes of about that many samples per pixel on one device
+  // (pine_gpu_path_render_passes): the same film, bit for bit, from sample and checkpoint buffers sized for one pass;
+  // on_pass(pass, pass_count, film) sees the running film after every pass and stops the render by returning non-zero --
+  // render() then returns false and the film holds the last one delivered.
+  bool render(Scene& scene, int pass_samples = 0, std::function<int(int, int, const float*)> on_pass = nullptr) {
     pine_gpu_render_params p{};
     p.flags = flags_;
     p.spp = sampler_.requested;
@@ -257,11 +262,22 @@ class PathIntegrator {
     p.shard_rank = 0;
     p.shard_world = 1;
     p.sampler = sampler_.kind;
+    if (pass_samples > 0 || on_pass) {
+      if (devices_.size() > 1) throw Error("PathIntegrator::render: passes render on one device");
+      const pine_gpu_pass_callback cb = [](void* user, int pass, int count, const float* film) -> int {
+        auto& fn = *static_cast<std::function<int(int, int, const float*)>*>(user);
+        return fn ? fn(pass, count, film) : 0;
+      };
+      const int rc = pine_gpu_path_render_passes(scene.handle(), &p, pass_samples, scene.camera.film_.pixels.data(), cb, &on_pass);
+      check(rc, "PathIntegrator::render");
+      return rc != PINE_GPU_RENDER_STOPPED;
+    }
     if (devices_.size() > 1)
       check(pine_gpu_path_render_devices(scene.handle(), &p, devices_.data(), int(devices_.size()), scene.camera.film_.pixels.data()),
             "PathIntegrator::render");
     else
       check(pine_gpu_path_render(scene.handle(), &p, scene.camera.film_.pixels.data()), "PathIntegrator::render");
+    return true;
   }
 
  private:

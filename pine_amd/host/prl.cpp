@@ -1962,10 +1962,30 @@ Interp::Interp() {
         q = *end == ',' ? end + 1 : end;
       }
     }
-    if (devices.size() > 1)
+    // $PINE_PRL_PASSES = P (pine-mi355x --passes): render in passes of about P samples per pixel -- the same film, device memory
+    // for one pass; $PINE_PRL_PREVIEW = FILE.png (--preview): the running film, finalised and written after every pass
+    const char* passes = getenv("PINE_PRL_PASSES");
+    const char* preview = getenv("PINE_PRL_PREVIEW");
+    if (devices.size() > 1) {
+      if (passes || preview) fail("PathIntegrator.render: --passes / --preview render on one device");
       gpu_check(pine_gpu_path_render_devices(s->h, &prm, devices.data(), int(devices.size()), f->pixels.data()), "PathIntegrator.render");
-    else
+    } else if (passes || preview) {
+      struct Preview {
+        FilmObj* film;
+        const char* path;
+      } pv{f.get(), preview};
+      const pine_gpu_pass_callback on_pass = [](void* user, int, int, const float* film) -> int {
+        const Preview* v = static_cast<const Preview*>(user);
+        if (!v->path) return 0;
+        std::vector<uint8_t> rgba(size_t(v->film->w) * v->film->h * 4);
+        if (pine_gpu_film_finalize_u8(film, v->film->w, v->film->h, v->film->tone, rgba.data()) == 0)
+          (void)png_writer::write_rgba8(v->path, v->film->w, v->film->h, rgba.data());  // (a preview that cannot be written does not stop the render)
+        return 0;
+      };
+      gpu_check(pine_gpu_path_render_passes(s->h, &prm, passes ? atoi(passes) : 0, f->pixels.data(), on_pass, &pv), "PathIntegrator.render");
+    } else {
       gpu_check(pine_gpu_path_render(s->h, &prm, f->pixels.data()), "PathIntegrator.render");
+    }
     in.last_film = f;
     return Value();
   });

@@ -38,6 +38,16 @@ pine_gpu_plan* pine_gpu_plan_create(pine_gpu_scene*, const pine_gpu_render_param
   fail();
   return nullptr;
 }
+pine_gpu_plan* pine_gpu_plan_create_passes(pine_gpu_scene*, const pine_gpu_render_params*, int32_t) {
+  fail();
+  return nullptr;
+}
+int pine_gpu_plan_pass_count(pine_gpu_plan*) { return fail(); }
+int pine_gpu_plan_pass_info(pine_gpu_plan*, int, int32_t*) { return fail(); }
+int pine_gpu_plan_launch_pass(pine_gpu_plan*, int, void*, void*) { return fail(); }
+int pine_gpu_plan_tile_order(pine_gpu_plan*, int32_t*, int) { return fail(); }
+int pine_gpu_plan_device_bytes(pine_gpu_plan*, int64_t*) { return fail(); }
+int pine_gpu_path_render_passes(pine_gpu_scene*, const pine_gpu_render_params*, int32_t, float*, pine_gpu_pass_callback, void*) { return fail(); }
 int pine_gpu_plan_launch(pine_gpu_plan*, void*, void*) { return fail(); }
 int pine_gpu_plan_launch_packed(pine_gpu_plan*, void*, void*) { return fail(); }
 void pine_gpu_plan_destroy(pine_gpu_plan*) {}
