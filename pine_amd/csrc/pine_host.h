@@ -149,8 +149,9 @@ struct SceneHost {
 
 void set_error(const std::string& msg);
 
-// The pass planner (plans created with passes): how a render of `spp` samples per pixel is split into launches
-// that keep at most about `pass_samples` sample rows per tile.  Tiles whose work items are whole pixels (`whole_tiles` of
+// The pass planner: how a render of `spp` samples per pixel is split into launches that keep at most about
+// `pass_samples` sample rows per tile -- one launch with every row (n = 1, P = spp, slice = whole_tiles) when pass_samples
+// is not positive: an ordinary plan is a plan of one pass.  Tiles whose work items are whole pixels (`whole_tiles` of
 // the shard's `num_local_tiles`: all of them when an item is the whole pixel, else the tile classes' serial tiles) are dealt
 // out in slices of `slice` tiles, one slice per pass, with all their samples; the independent class renders the samples
 // [j * P, min(spp, (j + 1) * P)) of every pixel in pass j.  P is a multiple of the samples per item when the class has tiles.

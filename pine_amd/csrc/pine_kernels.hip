@@ -128,51 +128,14 @@ static const VariantTables& variant_tables() {
 // One wave per tile, lane = pixel in tile: every sample row is one coalesced 1 KiB read.
 // `packed` != 0: the output is this rank's tile-major slab [local tile][pixel in tile] (multi-GPU gather)
 // instead of the row-major film.
-__global__ void __launch_bounds__(kBlock) resolve_kernel(WorkParams W, int film_w, int film_h, int spp,
-                                                        const float4* __restrict__ samples, float4* __restrict__ film,
-                                                        Counters* __restrict__ counters, int packed) {
-  const unsigned long long t = blockIdx.x * (unsigned long long)kBlock + threadIdx.x;
-  const int ltile = int(t >> 6);
-  if (ltile >= W.num_local_tiles) return;
-  const int p = int(t & 63);
-  const int tile = film_tile_of(W, ltile);
-  const int px = (tile % W.tiles_x) * kTile + (p & 7), py = (tile / W.tiles_x) * kTile + (p >> 3);
-  if (px >= film_w || py >= film_h) return;
-  const float4* row = samples + (unsigned long long)ltile * (unsigned)spp * 64ull + p;
-  f3 L = mk3(0.0f);
-  unsigned long long verts = 0;
-  // the sum is sequential in s (path.cpp:34-37), the loads need not be: 8 rows in flight per lane
-  int s = 0;
-  for (; s + 8 <= spp; s += 8) {
-    float4 v[8];
-#pragma unroll
-    for (int j = 0; j < 8; j++) v[j] = row[(unsigned long long)(s + j) * 64ull];
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-      L = L + f3{v[j].x, v[j].y, v[j].z};
-      verts += (unsigned long long)v[j].w;
-    }
-  }
-  for (; s < spp; s++) {
-    const float4 v = row[(unsigned long long)s * 64ull];
-    L = L + f3{v.x, v.y, v.z};
-    verts += (unsigned long long)v.w;
-  }
-  const f3 m = L / float(spp);
-  // (the slab is tile-major in the shard's NATURAL tile order, whatever order the launch works in: tile_order)
-  const size_t out_index = packed ? size_t(tile / W.shard_world) * 64u + size_t(p) : size_t(py) * film_w + px;
-  film[out_index] = make_float4(m.x, m.y, m.z, 1.0f);
-  // radiance() invocation count of the launch (the unit of the roofline's algorithmic bytes)
-  for (int off = 32; off > 0; off >>= 1) verts += __shfl_down(verts, off);
-  if ((threadIdx.x & 63) == 0) atomicAdd(&counters->vertices, verts);
-}
-
-// The same sum CONTINUED from pass to pass (plans created with passes): `sum` holds one float4 per local pixel,
-// (((L_0 + L_1) + ...) + L_{m-1}) of the samples resolved so far -- the partial result of the loop above, so going on from it
-// rounds exactly as the one launch does.  Tiles of the whole-pixel class ([0, whole_tiles) in the plan's tile order) get all
-// spp rows in the pass that renders their slice and none in the others: their film pixel is final from then on and
+//
+// The sum is CONTINUED from pass to pass: `sum` holds one float4 per local pixel,
+// (((L_0 + L_1) + ...) + L_{m-1}) of the samples resolved so far -- the partial result of the loop below, so going on from it
+// rounds exactly as one launch over all rows does.  Tiles of the whole-pixel class ([0, whole_tiles) in the plan's tile order)
+// get all spp rows in the pass that renders their slice and none in the others: their film pixel is final from then on and
 // (0, 0, 0, 0) before.  Tiles of the independent class get `free_rows` rows in every pass; their film pixel is the running
-// mean sum / samples_so_far -- after the last pass sum / spp, the division above.  W is the PLAN's work decomposition.
+// mean sum / samples_so_far -- after the last pass sum / spp.  A plan of one pass: the slice is the whole class, free_rows =
+// samples_so_far = spp, and `sum` is null -- nothing carried, nothing kept.  W is the PLAN's work decomposition.
 struct ResolvePass {
   int film_w, film_h, spp;
   int whole_tiles, slice_first, slice_tiles;  // the whole-pixel class; the slice of it this pass rendered
@@ -181,9 +144,9 @@ struct ResolvePass {
   int samples_so_far;                          // ... and the samples of a pixel of that class up to and including this pass
   int packed;
 };
-__global__ void __launch_bounds__(kBlock) resolve_accumulate_kernel(WorkParams W, ResolvePass R, const float4* __restrict__ samples,
-                                                                   float4* __restrict__ sum, float4* __restrict__ film,
-                                                                   Counters* __restrict__ counters) {
+__global__ void __launch_bounds__(kBlock) resolve_kernel(WorkParams W, ResolvePass R, const float4* __restrict__ samples,
+                                                        float4* __restrict__ sum, float4* __restrict__ film,
+                                                        Counters* __restrict__ counters) {
   const unsigned long long t = blockIdx.x * (unsigned long long)kBlock + threadIdx.x;
   const int ltile = int(t >> 6);
   if (ltile >= W.num_local_tiles) return;  // (whole waves: one wave per tile)
@@ -191,7 +154,6 @@ __global__ void __launch_bounds__(kBlock) resolve_accumulate_kernel(WorkParams W
   const int tile = film_tile_of(W, ltile);
   const int px = (tile % W.tiles_x) * kTile + (p & 7), py = (tile / W.tiles_x) * kTile + (p >> 3);
   const bool inside = px < R.film_w && py < R.film_h;
-  float4* const acc = sum + (unsigned long long)ltile * 64ull + p;
   const float4* row = nullptr;
   int rows = 0;
   bool carried = false, shown = true;
@@ -211,13 +173,15 @@ __global__ void __launch_bounds__(kBlock) resolve_accumulate_kernel(WorkParams W
     carried = !R.first_pass;
     divisor = float(R.samples_so_far);
   }
-  if (!inside) rows = 0, carried = false;
+  if (!inside) rows = 0;
+  float4* const acc = sum && inside ? sum + (unsigned long long)ltile * 64ull + p : nullptr;
   f3 L = mk3(0.0f);
-  if (carried) {
+  if (carried && acc) {
     const float4 a = *acc;
     L = f3{a.x, a.y, a.z};
   }
   unsigned long long verts = 0;
+  // the sum is sequential in s (path.cpp:34-37), the loads need not be: 8 rows in flight per lane
   int s = 0;
   for (; s + 8 <= rows; s += 8) {
     float4 v[8];
@@ -235,11 +199,13 @@ __global__ void __launch_bounds__(kBlock) resolve_accumulate_kernel(WorkParams W
     verts += (unsigned long long)v.w;
   }
   if (inside) {
-    if (rows > 0) *acc = make_float4(L.x, L.y, L.z, 0.0f);
+    if (acc && rows > 0) *acc = make_float4(L.x, L.y, L.z, 0.0f);
     const f3 m = L / divisor;
+    // (the slab is tile-major in the shard's NATURAL tile order, whatever order the launch works in: tile_order)
     const size_t out_index = R.packed ? size_t(tile / W.shard_world) * 64u + size_t(p) : size_t(py) * R.film_w + px;
     film[out_index] = shown ? make_float4(m.x, m.y, m.z, 1.0f) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   }
+  // radiance() invocation count of the launch (the unit of the roofline's algorithmic bytes)
   for (int off = 32; off > 0; off >>= 1) verts += __shfl_down(verts, off);
   if ((threadIdx.x & 63) == 0 && verts) atomicAdd(&counters->vertices, verts);
 }
@@ -769,6 +735,31 @@ static bool build_tri_packets(const FlatAccel& A, std::vector<uint32_t>& out, in
   return true;
 }
 
+// The plan's precompiled path kernel: the declared-tolerance variant, else the stage-queued one, else the megakernel's.  (The
+// scene's own kernel, spec_fn, replaces a stage-queued variant and keeps its contexts and LDS layout.)
+struct PathKernel {
+  const void* fn;
+  unsigned features;
+  int ctx;    // work items a workgroup holds: the stage-queued kernel's path contexts, the megakernel's threads
+  int block;  // threads per workgroup
+  bool queued() const { return block == kQBlock; }  // the stage-queued kernel (exact or declared-tolerance build)
+};
+static_assert(kQBlock != kBlock, "PathKernel::queued tells the two kernels apart by their workgroup size");
+static PathKernel plan_kernel(const pine_gpu_plan* p) {
+  if (p->fast) return {p->fast->fn, p->fast->features, p->fast->ctx, kQBlock};
+  if (p->queue_variant >= 0) {
+    const PineKernelVariant& V = kQueueVariants[p->queue_variant];
+    return {V.fn, V.features, V.ctx, kQBlock};
+  }
+  const PineKernelVariant& V = kVariants[p->variant];
+  return {V.fn, V.features, kBlock, kBlock};
+}
+
+// Local tile -> tile of the film: the host twin of film_tile_of.
+static int plan_film_tile(const pine_gpu_plan* p, int ltile) {
+  return p->tile_order.empty() ? ltile * p->W.shard_world + p->W.shard_rank : p->tile_order[size_t(ltile)];
+}
+
 // ---- plan_build and its phases, in the order it runs them ----
 // What assemble_scene leaves for the later phases: host copies of the records it uploaded.
 struct SceneParts {
@@ -1255,14 +1246,14 @@ static int choose_items(pine_gpu_plan* p, const SceneHost& H, const SceneParts& 
   in_path_rng |= uber_rng;
   p->serial_rng = in_path_rng;
   const bool spp_pow2 = (spp & (spp - 1)) == 0;  // (BlueSampler's effective spp always is; SobolSampler / HaltonSampler take any count)
-  const unsigned qf = p->fast ? p->fast->features : p->queue_variant >= 0 ? kQueueVariants[p->queue_variant].features : 0u;
+  const PathKernel kernel = plan_kernel(p);
   int kspi = prm->samples_per_item;
   if (in_path_rng) kspi = spp;
   else if (kspi <= 0) {
     // stage-queued kernel: two samples per item for the scene-in-LDS variants (cbox-class scenes, all pixels alike: half the
     // checkpoint prepass and hand-outs, C2 13.93 -> 13.75 ms per step, C3 69.9 -> 68.4), one where pixels differ a lot
     // (10 000 cones: 8.06 ms at one, 8.52 at two); the megakernel four
-    kspi = (p->queue_variant >= 0 || p->fast) ? ((qf & F_LDS_SCENE) ? std::min(spp, 2) : 1) : std::min(spp, 4);
+    kspi = kernel.queued() ? ((kernel.features & F_LDS_SCENE) ? std::min(spp, 2) : 1) : std::min(spp, 4);
   }
   if (kspi > spp) kspi = spp;
   if (!spp_pow2) {
@@ -1296,7 +1287,7 @@ static int choose_items(pine_gpu_plan* p, const SceneHost& H, const SceneParts& 
   // per pixel; so does a shard none of whose tiles a Subsurface shape can reach (rare, and a launch without chains would need
   // the checkpoint prepass for every tile).  PINE_GPU_NO_TILE_CLASSES: off (measurement aid).
   std::vector<int> serial, free_tiles;
-  if (in_path_rng && !uber_rng && (qf & F_SSS) != 0 && !K.no_tile_classes && !K.no_fork && spp > 1 &&
+  if (in_path_rng && !uber_rng && kernel.queued() && (kernel.features & F_SSS) != 0 && !K.no_tile_classes && !K.no_fork && spp > 1 &&
       spp_pow2 &&  // (the independent class splits a pixel's samples by shifts and masks)
       tile_classes(H, sp, W, serial, free_tiles) && !free_tiles.empty() && !serial.empty()) {
     p->tile_order = serial;
@@ -1315,7 +1306,7 @@ static int choose_items(pine_gpu_plan* p, const SceneHost& H, const SceneParts& 
     set_error("film sides above 65535 are not supported");
     return -1;
   }
-  // the pass window of an ordinary launch: the whole render
+  // the pass window of the plan's W: the whole render (pass_work narrows it to a pass)
   W.pass_first_chunk = 0;
   W.pass_chunks = W.items_per_pixel;
   W.pass_chunks_magic = W.pass_chunks > 1 ? unsigned(((1ull << 32) + unsigned(W.pass_chunks) - 1) / unsigned(W.pass_chunks)) : 0u;
@@ -1323,24 +1314,20 @@ static int choose_items(pine_gpu_plan* p, const SceneHost& H, const SceneParts& 
   W.free_tile_base = W.serial_tiles;
   W.pass_first_serial_tile = 0;
   if (!plan_passes(W.num_local_tiles, spp, W.samples_per_item, W.serial_tiles, p->pass_samples_req, p->pass_plan)) return -1;
-  if (p->pass_plan.n > 1) {
-    // a plan with passes: the 32-bit sample-buffer index covers one pass (its rows, and the rows before its first sample that
-    // decode_item adds to a whole-pixel item's base)
-    for (int j = 0; j < p->pass_plan.n; j++)
-      if ((p->pass_plan.rows(j, spp) + unsigned(p->pass_plan.pass(j, spp).first_sample)) * 64ull >= (1ull << 32)) {
-        set_error("film pixels x samples of one pass must stay below 2^32 (fewer samples per pass, or several shards)");
-        return -1;
-      }
-    return 0;
-  }
-  if ((unsigned long long)W.num_local_tiles * 64ull * (unsigned long long)spp >= (1ull << 32)) {
-    set_error("film pixels x samples per pixel of one shard must stay below 2^32 (render in several shards)");
-    return -1;
-  }
+  // the 32-bit sample-buffer index covers one pass: its rows, and the rows before its first sample that decode_item adds to a
+  // whole-pixel item's base (one pass: all tiles x 64 x spp)
+  const PassPlan& PP = p->pass_plan;
+  for (int j = 0; j < PP.n; j++)
+    if ((PP.rows(j, spp) + unsigned(PP.pass(j, spp).first_sample)) * 64ull >= (1ull << 32)) {
+      set_error(PP.n > 1 ? "film pixels x samples of one pass must stay below 2^32 (fewer samples per pass, or several shards)"
+                         : "film pixels x samples per pixel of one shard must stay below 2^32 (render in several shards)");
+      return -1;
+    }
   return 0;
 }
 
-// The work decomposition of pass j of a plan with passes: the plan's, with the pass window in place of the whole render.
+// The work decomposition of pass j: the plan's, with the pass window in place of the whole render.  The only pass of a plan of
+// one (slice = the whole-pixel class, samples [0, spp)) gets the plan's W back, field for field.
 static WorkParams pass_work(const pine_gpu_plan* p, int j) {
   WorkParams W = p->W;
   const int spp = p->S.spp;
@@ -1417,34 +1404,26 @@ static int size_and_allocate(pine_gpu_plan* p, const pine_gpu_render_params* prm
   hipDeviceProp_t prop;
   HIP_OK(hipGetDeviceProperties(&prop, prm->device));
   int blocks_per_cu = 0;
-  const bool queued = p->queue_variant >= 0 || p->fast;  // the stage-queued kernel (exact or declared-tolerance build)
-  const void* const queue_fn = p->fast ? p->fast->fn : p->queue_variant >= 0 ? (const void*)kQueueVariants[p->queue_variant].fn : nullptr;
-  const unsigned queue_features = p->fast ? p->fast->features : p->queue_variant >= 0 ? kQueueVariants[p->queue_variant].features : 0u;
-  if (queued) {
+  const PathKernel kernel = plan_kernel(p);
+  if (kernel.queued()) {
     blocks_per_cu = 1;  // one 1024-thread workgroup per CU owns the CU's LDS
-    HIP_OK(hipFuncSetAttribute(queue_fn, hipFuncAttributeMaxDynamicSharedMemorySize, int(p->lds_bytes)));
+    HIP_OK(hipFuncSetAttribute(kernel.fn, hipFuncAttributeMaxDynamicSharedMemorySize, int(p->lds_bytes)));
   } else {
-    HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, (const void*)kVariants[p->variant].fn, kBlock, p->lds_bytes));
+    HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, kernel.fn, kBlock, p->lds_bytes));
   }
   if (blocks_per_cu < 1) blocks_per_cu = 1;
   if (blocks_per_cu > 8) blocks_per_cu = 8;
-  // (a plan with passes: the launch shape, the claims and the buffers are sized for its largest pass)
+  // (the launch shape, the claims and the buffers are sized for the plan's largest pass)
   const PassPlan& PP = p->pass_plan;
-  unsigned long long launch_items = W.total_items, sample_rows = (unsigned long long)W.num_local_tiles * unsigned(spp);
-  int ckpt_chunks = W.items_per_pixel;
-  if (PP.n > 1) {
-    launch_items = sample_rows = 0;
-    ckpt_chunks = 0;
-    for (int j = 0; j < PP.n; j++) {
-      const WorkParams Wj = pass_work(p, j);
-      launch_items = std::max(launch_items, Wj.total_items);
-      sample_rows = std::max(sample_rows, PP.rows(j, spp));
-      ckpt_chunks = std::max(ckpt_chunks, Wj.pass_chunks);
-    }
+  unsigned long long launch_items = 0, sample_rows = 0;
+  int ckpt_chunks = 0;
+  for (int j = 0; j < PP.n; j++) {
+    const WorkParams Wj = pass_work(p, j);
+    launch_items = std::max(launch_items, Wj.total_items);
+    sample_rows = std::max(sample_rows, PP.rows(j, spp));
+    ckpt_chunks = std::max(ckpt_chunks, Wj.pass_chunks);
   }
-  unsigned long long want = (launch_items + kBlock - 1) / kBlock;
-  const int qctx = p->fast ? p->fast->ctx : p->queue_variant >= 0 ? kQueueVariants[p->queue_variant].ctx : 0;
-  if (queued) want = (launch_items + qctx - 1) / qctx;
+  const unsigned long long want = (launch_items + kernel.ctx - 1) / kernel.ctx;
   p->grid = int(std::min<unsigned long long>(want, (unsigned long long)prop.multiProcessorCount * blocks_per_cu));
   if (p->grid < 1) p->grid = 1;
   if (!p->serial_rng && K.pool_items == kUnset) {
@@ -1477,12 +1456,12 @@ static int size_and_allocate(pine_gpu_plan* p, const pine_gpu_render_params* prm
   }
   p->bytes_samples = size_t(sample_rows) * 64 * sizeof(float4);
   HIP_OK(POOL_ALLOC(p->d_samples, p->bytes_samples));
-  const size_t fold_slots = queued ? size_t(p->grid) * qctx : size_t(p->grid) * kBlock;
+  const size_t fold_slots = size_t(p->grid) * kernel.ctx;
   HIP_OK(POOL_ALLOC(p->d_fold, size_t(prm->max_path_length) * 8 * fold_slots * sizeof(float)));
-  if (queued) {
+  if (kernel.queued()) {
     // per-context records, then (Subsurface variants) every workgroup's ring of sample-token slots
-    const size_t token_dwords = (queue_features & F_SSS) ? size_t(p->grid) * (qctx <= 1024 ? 1024 : 2048) * kQTokenDwords : 0;
-    HIP_OK(POOL_ALLOC(p->d_ctxg, (size_t(p->grid) * qctx * q_ctx_global_dwords(queue_features) + token_dwords) * sizeof(uint32_t)));
+    const size_t token_dwords = (kernel.features & F_SSS) ? size_t(p->grid) * (kernel.ctx <= 1024 ? 1024 : 2048) * kQTokenDwords : 0;
+    HIP_OK(POOL_ALLOC(p->d_ctxg, (size_t(p->grid) * kernel.ctx * q_ctx_global_dwords(kernel.features) + token_dwords) * sizeof(uint32_t)));
   }
   HIP_OK(POOL_ALLOC(p->d_counters, sizeof(Counters)));
   p->timed = (prm->flags & PINE_GPU_FLAG_TIMING) != 0;
@@ -1553,29 +1532,23 @@ pine_gpu_plan* pine_gpu_plan_create_passes(pine_gpu_scene* scene, const pine_gpu
   return plan_create(scene, prm, pass_samples);
 }
 
-// The path kernel of the plan -- the scene's own, a declared-tolerance, a stage-queued or a megakernel variant -- over the
-// work decomposition W, its samples going to `samples` (+ sample index * 64, decode_item).
+// The path kernel of the plan -- the scene's own, or the precompiled one -- over the work decomposition W, its samples going
+// to `samples` (+ sample index * 64, decode_item).
 static int launch_path_kernel(pine_gpu_plan* p, WorkParams& W, float4* samples, int grid, hipStream_t stream) {
   const ulonglong2* ckpt = p->d_ckpt;
-  if (p->fast) {
-    // (a kernel of the other translation unit: same argument layout, launched untyped)
-    void* args[] = {&p->S, &W, &ckpt, &samples, &p->d_fold, &p->d_ctxg, &p->d_counters};
-    HIP_OK(hipLaunchKernel(p->fast->fn, dim3(grid), dim3(kQBlock), args, p->lds_bytes, stream));
-  } else if (p->spec_fn) {
-    void* args[] = {&p->S, &W, &ckpt, &samples, &p->d_fold, &p->d_ctxg, &p->d_counters};
-    HIP_OK(hipModuleLaunchKernel(p->spec_fn, unsigned(grid), 1, 1, kQBlock, 1, 1, unsigned(p->lds_bytes), stream, args, nullptr));
-  } else if (p->queue_variant >= 0) {
-    void* args[] = {&p->S, &W, &ckpt, &samples, &p->d_fold, &p->d_ctxg, &p->d_counters};
-    HIP_OK(hipLaunchKernel(kQueueVariants[p->queue_variant].fn, dim3(grid), dim3(kQBlock), args, p->lds_bytes, stream));
-  } else {
-    void* args[] = {&p->S, &W, &ckpt, &samples, &p->d_fold, &p->d_counters};
-    HIP_OK(hipLaunchKernel(kVariants[p->variant].fn, dim3(grid), dim3(kBlock), args, p->lds_bytes, stream));
-  }
+  const PathKernel kernel = plan_kernel(p);
+  // (the kernels of the other translation units: same argument layout, launched untyped; the megakernel has no context records)
+  void* queue_args[] = {&p->S, &W, &ckpt, &samples, &p->d_fold, &p->d_ctxg, &p->d_counters};
+  void* mega_args[] = {&p->S, &W, &ckpt, &samples, &p->d_fold, &p->d_counters};
+  if (p->spec_fn)
+    HIP_OK(hipModuleLaunchKernel(p->spec_fn, unsigned(grid), 1, 1, kQBlock, 1, 1, unsigned(p->lds_bytes), stream, queue_args, nullptr));
+  else
+    HIP_OK(hipLaunchKernel(kernel.fn, dim3(grid), dim3(kernel.block), kernel.queued() ? queue_args : mega_args, p->lds_bytes, stream));
   return 0;
 }
 
-// Pass j of a plan with passes (pass_plan.n > 1): checkpoint prepass from the carried RNG states, the path kernel over the
-// pass window, the resolve that continues the running sum and writes the film.
+// Pass j of the plan -- the only place that enqueues a render: checkpoint prepass, the path kernel over the pass window, the
+// resolve that continues the running sum and writes the film.  A plan of one pass renders the whole film here.
 static int plan_launch_pass(pine_gpu_plan* p, int j, void* film_dev, hipStream_t stream, bool packed) {
   const PassPlan& PP = p->pass_plan;
   if (j < 0 || j >= PP.n || (j != 0 && j != p->next_pass)) {
@@ -1584,8 +1557,11 @@ static int plan_launch_pass(pine_gpu_plan* p, int j, void* film_dev, hipStream_t
     return -1;
   }
   HIP_OK(hipSetDevice(p->device));
-  (void)hipGetLastError();
-  plan_poll_background(p);  // (a scene kernel that arrives between two passes renders the rest: the same bits)
+  (void)hipGetLastError();  // (HIP's last error is sticky: what the check at the end reports must come from THIS launch's calls)
+  // a background build that has finished: this launch and every later one run the scene's own kernel -- between two passes
+  // too: the same bits.  (A code object the runtime refuses leaves the precompiled kernel in place -- same film; plan stats say
+  // which one runs.)
+  plan_poll_background(p);
   if (j == 0) g_progress.store(0.0f);
   const int spp = p->S.spp;
   const PassPlan::Pass a = PP.pass(j, spp);
@@ -1597,17 +1573,29 @@ static int plan_launch_pass(pine_gpu_plan* p, int j, void* film_dev, hipStream_t
   static_assert(offsetof(Counters, next_item) == 0, "the per-pass reset clears next_item");
   hipEvent_t* ev = p->ev[p->launch_count % pine_gpu_plan::kEvRing];
   if (p->timed) HIP_OK(hipEventRecord(ev[0], stream));
+  // (a shard can own no tile at all -- more ranks than 8x8 tiles: nothing to launch, the film / slab stays zero)
   const bool has_work = W.total_items > 0;
   if (has_work && p->W.items_per_pixel > 1 && PP.free_tiles > 0) {
-    const unsigned long long n = (unsigned long long)PP.free_tiles * 64ull;
-    hipLaunchKernelGGL(rng_checkpoint_kernel, dim3(unsigned((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, W, p->film_w, p->film_h,
-                       spp, p->d_ckpt, PP.free_tiles, p->d_rng_carry);
-    p->ckpt_valid = false;
+    // a plan of one pass computes its checkpoints once and keeps them; a pass of a longer sequence walks on from the carried states
+    if (PP.n > 1 || !p->ckpt_valid || p->ckpt_every_launch) {
+      const unsigned long long n = (unsigned long long)PP.free_tiles * 64ull;
+      hipLaunchKernelGGL(rng_checkpoint_kernel, dim3(unsigned((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, W, p->film_w, p->film_h,
+                         spp, p->d_ckpt, PP.free_tiles, p->d_rng_carry);
+      if (PP.n == 1) {
+        if (!p->ckpt_done) HIP_OK(hipEventCreateWithFlags(&p->ckpt_done, hipEventDisableTiming));
+        HIP_OK(hipEventRecord(p->ckpt_done, stream));
+        p->ckpt_stream = stream;
+        p->ckpt_valid = true;
+      }
+    } else if (stream != p->ckpt_stream) {
+      HIP_OK(hipStreamWaitEvent(stream, p->ckpt_done, 0));
+    }
   }
   if (p->timed) HIP_OK(hipEventRecord(ev[1], stream));
   if (has_work) {
-    const int qctx = p->fast ? p->fast->ctx : p->queue_variant >= 0 ? kQueueVariants[p->queue_variant].ctx : kBlock;  // items a workgroup holds
-    const int grid = int(std::min<unsigned long long>((unsigned long long)p->grid, (W.total_items + qctx - 1) / qctx));
+    // (the largest pass fills p->grid: the only pass of a plan of one)
+    const int ctx = plan_kernel(p).ctx;
+    const int grid = int(std::min<unsigned long long>((unsigned long long)p->grid, (W.total_items + ctx - 1) / ctx));
     // (the rows before the pass's first sample are not in the buffer: see decode_item)
     float4* const samples = p->d_samples - size_t(W.pass_first_chunk) * size_t(W.samples_per_item) * 64u;
     if (launch_path_kernel(p, W, samples, grid, stream)) return -1;
@@ -1620,8 +1608,8 @@ static int plan_launch_pass(pine_gpu_plan* p, int j, void* film_dev, hipStream_t
     R.free_rows = a.samples, R.first_pass = j == 0 ? 1 : 0, R.samples_so_far = a.first_sample + a.samples;
     R.packed = packed ? 1 : 0;
     const unsigned long long n = (unsigned long long)p->W.num_local_tiles * 64ull;
-    hipLaunchKernelGGL(resolve_accumulate_kernel, dim3(unsigned((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, p->W, R, p->d_samples,
-                       p->d_sum, (float4*)film_dev, p->d_counters);
+    hipLaunchKernelGGL(resolve_kernel, dim3(unsigned((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, p->W, R, p->d_samples, p->d_sum,
+                       (float4*)film_dev, p->d_counters);
   }
   if (p->timed) HIP_OK(hipEventRecord(ev[3], stream));
   HIP_OK(hipGetLastError());
@@ -1632,57 +1620,14 @@ static int plan_launch_pass(pine_gpu_plan* p, int j, void* film_dev, hipStream_t
   return 0;
 }
 
-static int plan_launch(pine_gpu_plan* p, void* film_dev, void* stream_, bool packed) {
+// All passes of the plan, in order.
+static int plan_launch(pine_gpu_plan* p, void* film_dev, void* stream, bool packed) {
   if (!p || !film_dev) {
     set_error("null argument");
     return -1;
   }
-  hipStream_t stream = (hipStream_t)stream_;
-  if (p->pass_plan.n > 1) {  // a plan with passes: all of them, in order
-    for (int j = 0; j < p->pass_plan.n; j++)
-      if (plan_launch_pass(p, j, film_dev, stream, packed)) return -1;
-    return 0;
-  }
-  HIP_OK(hipSetDevice(p->device));
-  (void)hipGetLastError();  // (HIP's last error is sticky: what the check at the end reports must come from THIS launch's calls)
-  // a background build that has finished: this launch and every later one run the scene's own kernel.  (A code object the
-  // runtime refuses leaves the precompiled kernel in place -- same film; plan stats say which one runs.)
-  plan_poll_background(p);
-  g_progress.store(0.0f);
-  const size_t film_bytes = size_t(p->film_w) * p->film_h * sizeof(float4);
-  if (p->W.shard_world > 1 && !packed) HIP_OK(hipMemsetAsync(film_dev, 0, film_bytes, stream));
-  HIP_OK(hipMemsetAsync(p->d_counters, 0, sizeof(Counters), stream));
-  hipEvent_t* ev = p->ev[p->launch_count % pine_gpu_plan::kEvRing];
-  if (p->timed) HIP_OK(hipEventRecord(ev[0], stream));
-  // (a shard can own no tile at all -- more ranks than 8x8 tiles: nothing to launch, the film / slab stays zero)
-  const bool has_work = p->W.num_local_tiles > 0;
-  if (has_work && p->W.items_per_pixel > 1) {
-    if (!p->ckpt_valid || p->ckpt_every_launch) {
-      const int free_tiles = p->W.num_local_tiles - p->W.serial_tiles;
-      const unsigned long long n = (unsigned long long)free_tiles * 64ull;
-      hipLaunchKernelGGL(rng_checkpoint_kernel, dim3(unsigned((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream,
-                         p->W, p->film_w, p->film_h, p->S.spp, p->d_ckpt, free_tiles, (ulonglong2*)nullptr);
-      if (!p->ckpt_done) HIP_OK(hipEventCreateWithFlags(&p->ckpt_done, hipEventDisableTiming));
-      HIP_OK(hipEventRecord(p->ckpt_done, stream));
-      p->ckpt_stream = stream;
-      p->ckpt_valid = true;
-    } else if (stream != p->ckpt_stream) {
-      HIP_OK(hipStreamWaitEvent(stream, p->ckpt_done, 0));
-    }
-  }
-  if (p->timed) HIP_OK(hipEventRecord(ev[1], stream));
-  if (has_work && launch_path_kernel(p, p->W, p->d_samples, p->grid, stream)) return -1;
-  if (p->timed) HIP_OK(hipEventRecord(ev[2], stream));
-  if (has_work) {
-    const unsigned long long n = (unsigned long long)p->W.num_local_tiles * 64ull;
-    hipLaunchKernelGGL(resolve_kernel, dim3(unsigned((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, p->W,
-                       p->film_w, p->film_h, p->S.spp, p->d_samples, (float4*)film_dev, p->d_counters, packed ? 1 : 0);
-  }
-  if (p->timed) HIP_OK(hipEventRecord(ev[3], stream));
-  HIP_OK(hipGetLastError());
-  p->launched = true;
-  p->launch_count++;
-  p->last_stream = stream;
+  for (int j = 0; j < p->pass_plan.n; j++)
+    if (plan_launch_pass(p, j, film_dev, (hipStream_t)stream, packed)) return -1;
   return 0;
 }
 
@@ -1698,12 +1643,11 @@ int pine_gpu_plan_launch_pass(pine_gpu_plan* p, int pass, void* film_dev, void* 
     set_error("null argument");
     return -1;
   }
-  if (p->pass_plan.n > 1) return plan_launch_pass(p, pass, film_dev, (hipStream_t)stream, false);
-  if (pass != 0) {
+  if (p->pass_plan.n == 1 && pass != 0) {
     set_error("this plan has one pass: pass 0");
     return -1;
   }
-  return plan_launch(p, film_dev, stream, false);
+  return plan_launch_pass(p, pass, film_dev, (hipStream_t)stream, false);
 }
 int pine_gpu_plan_pass_count(pine_gpu_plan* p) {
   if (!p) {
@@ -1731,7 +1675,7 @@ int pine_gpu_plan_tile_order(pine_gpu_plan* p, int32_t* out, int cap) {
     return -1;
   }
   for (int lt = 0; lt < p->W.num_local_tiles && lt < cap; lt++)
-    out[lt] = p->tile_order.empty() ? lt * p->W.shard_world + p->W.shard_rank : p->tile_order[size_t(lt)];
+    out[lt] = plan_film_tile(p, lt);
   return p->W.num_local_tiles;
 }
 int pine_gpu_plan_device_bytes(pine_gpu_plan* p, int64_t out[4]) {
@@ -1767,12 +1711,11 @@ int pine_gpu_plan_stats_get(pine_gpu_plan* p, pine_gpu_plan_stats* out) {
   }
   memset(out, 0, sizeof *out);
   HIP_OK(hipSetDevice(p->device));
-  out->camera_samples = (unsigned long long)p->W.num_local_tiles * 64ull * p->S.spp;
   // tiles on the film border may be partially outside: count real pixels
   {
     unsigned long long px = 0;
     for (int lt = 0; lt < p->W.num_local_tiles; lt++) {
-      int tile = p->tile_order.empty() ? lt * p->W.shard_world + p->W.shard_rank : p->tile_order[size_t(lt)];
+      int tile = plan_film_tile(p, lt);
       int tx = tile % p->W.tiles_x, ty = tile / p->W.tiles_x;
       int w = std::min(kTile, p->film_w - tx * kTile), h = std::min(kTile, p->film_h - ty * kTile);
       px += (unsigned long long)w * h;
@@ -1786,11 +1729,11 @@ int pine_gpu_plan_stats_get(pine_gpu_plan* p, pine_gpu_plan_stats* out) {
   out->specialized = p->spec_fn ? (p->spec_baked ? 2 : 1) : p->spec_state.load() == kSpecFailed ? -1 : 0;
   out->specialize_source = p->spec_fn || p->spec_state.load() == kSpecBuilding ? p->spec_source : 0;
   out->specialize_pending = p->spec_state.load() == kSpecBuilding ? 1 : 0;
-  out->kernel_features = p->spec_fn ? p->spec_features : p->fast ? p->fast->features : p->queue_variant >= 0 ? kQueueVariants[p->queue_variant].features
-                                                                                         : p->variant >= 0 ? kVariants[p->variant].features : 0u;
+  const PathKernel kernel = plan_kernel(p);
+  out->kernel_features = p->spec_fn ? p->spec_features : kernel.features;
   out->specialize_ms = p->specialize_ms;
   out->grid_blocks = p->grid;
-  out->block_threads = (p->queue_variant >= 0 || p->fast) ? kQBlock : kBlock;
+  out->block_threads = kernel.block;
   out->lds_bytes = int(p->lds_bytes);
   out->accel_build_ms = p->accel_build_ms;
   out->accel_built_on_device = p->accel_on_device ? 1 : 0;
@@ -1936,7 +1879,7 @@ int pine_gpu_plan_read_samples(pine_gpu_plan* p, float* out, int64_t capacity) {
   HIP_OK(hipMemcpy(tmp.data(), p->d_samples, tmp.size() * 4, hipMemcpyDeviceToHost));
   memset(out, 0, size_t(need) * 4);
   for (int lt = 0; lt < p->W.num_local_tiles; lt++) {
-    int tile = p->tile_order.empty() ? lt * p->W.shard_world + p->W.shard_rank : p->tile_order[size_t(lt)];
+    int tile = plan_film_tile(p, lt);
     int tx = tile % p->W.tiles_x, ty = tile / p->W.tiles_x;
     for (int q = 0; q < 64; q++) {
       int px = tx * kTile + (q & 7), py = ty * kTile + (q >> 3);
@@ -1949,43 +1892,6 @@ int pine_gpu_plan_read_samples(pine_gpu_plan* p, float* out, int64_t capacity) {
   return 0;
 }
 
-int pine_gpu_path_render(pine_gpu_scene* scene, const pine_gpu_render_params* prm, float* film_out) {
-  if (!scene || !prm || !film_out) {
-    set_error("null argument");
-    return -1;
-  }
-  pine_gpu_render_params prm2 = *prm;
-  prm2.flags |= PINE_GPU_FLAG_PROGRESS;  // the reference's CLI polls get_progress() while render() runs (src/cli/pine.cpp:36-40)
-  pine_gpu_plan* p = pine_gpu_plan_create(scene, &prm2);
-  if (!p) return -1;
-  int rc = -1;
-  void* d_film = nullptr;
-  const size_t bytes = size_t(p->film_w) * p->film_h * 16;
-  do {
-    if (DevicePool::get().alloc(&d_film, bytes) != hipSuccess) {
-      set_error("hipMalloc(film) failed");
-      break;
-    }
-    g_progress_total.store(p->W.total_items);
-    g_progress_src.store(p->h_progress);
-    if (pine_gpu_plan_launch(p, d_film, nullptr)) break;
-    if (hipMemcpy(film_out, d_film, bytes, hipMemcpyDeviceToHost) != hipSuccess) {
-      set_error("film download failed");
-      break;
-    }
-    if (pine_gpu_plan_check(p)) break;  // a bailed-out path kernel leaves an incomplete film: fail, do not return it as a result
-    rc = 0;
-  } while (0);
-  g_progress_src.store(nullptr);
-  g_progress.store(rc ? 0.0f : 1.0f);
-  std::string keep = rc ? pine_gpu_last_error() : "";
-  if (rc) (void)hipDeviceSynchronize();  // (a failed launch may still be running: nothing of it may touch a block the pool hands out again)
-  DevicePool::get().free(d_film);
-  pine_gpu_plan_destroy(p);
-  if (rc) set_error(keep);
-  return rc;
-}
-
 int pine_gpu_path_render_passes(pine_gpu_scene* scene, const pine_gpu_render_params* prm, int32_t pass_samples, float* film_out,
                                 pine_gpu_pass_callback cb, void* user) {
   if (!scene || !prm || !film_out) {
@@ -1993,7 +1899,7 @@ int pine_gpu_path_render_passes(pine_gpu_scene* scene, const pine_gpu_render_par
     return -1;
   }
   pine_gpu_render_params prm2 = *prm;
-  prm2.flags |= PINE_GPU_FLAG_PROGRESS;
+  prm2.flags |= PINE_GPU_FLAG_PROGRESS;  // the reference's CLI polls get_progress() while render() runs (src/cli/pine.cpp:36-40)
   pine_gpu_plan* p = pine_gpu_plan_create_passes(scene, &prm2, pass_samples);
   if (!p) return -1;
   int rc = -1;
@@ -2007,7 +1913,7 @@ int pine_gpu_path_render_passes(pine_gpu_scene* scene, const pine_gpu_render_par
     }
     // get_progress() over the whole sequence: the items of the passes done + those the running pass has claimed
     unsigned long long total = 0;
-    for (int j = 0; j < n; j++) total += n > 1 ? pass_work(p, j).total_items : p->W.total_items;
+    for (int j = 0; j < n; j++) total += pass_work(p, j).total_items;
     g_progress_total.store(total);
     g_progress_base.store(0);
     g_progress_src.store(p->h_progress);
@@ -2018,10 +1924,10 @@ int pine_gpu_path_render_passes(pine_gpu_scene* scene, const pine_gpu_render_par
         set_error("film download failed");
         ok = false;
       }
-      if (ok) ok = pine_gpu_plan_check(p) == 0;  // a bailed-out pass leaves an incomplete film: fail
+      if (ok) ok = pine_gpu_plan_check(p) == 0;  // a bailed-out path kernel leaves an incomplete film: fail, do not return it as a result
       if (!ok) break;
       *p->h_progress = 0;  // (the pass has finished: nothing writes the word until the next launch)
-      g_progress_base.fetch_add(n > 1 ? pass_work(p, j).total_items : p->W.total_items);
+      g_progress_base.fetch_add(pass_work(p, j).total_items);
       if (cb && cb(user, j, n, film_out) != 0) rc = PINE_GPU_RENDER_STOPPED;
     }
     if (ok && rc < 0) rc = 0;
@@ -2030,11 +1936,15 @@ int pine_gpu_path_render_passes(pine_gpu_scene* scene, const pine_gpu_render_par
   g_progress_base.store(0);
   g_progress.store(rc == 0 ? 1.0f : 0.0f);
   std::string keep = rc < 0 ? pine_gpu_last_error() : "";
-  if (rc < 0) (void)hipDeviceSynchronize();
+  if (rc < 0) (void)hipDeviceSynchronize();  // (a failed launch may still be running: nothing of it may touch a block the pool hands out again)
   DevicePool::get().free(d_film);
   pine_gpu_plan_destroy(p);
   if (rc < 0) set_error(keep);
   return rc;
+}
+
+int pine_gpu_path_render(pine_gpu_scene* scene, const pine_gpu_render_params* prm, float* film_out) {
+  return pine_gpu_path_render_passes(scene, prm, 0, film_out, nullptr, nullptr);
 }
 
 /* One process, several devices: shard r of n (8x8-pixel tiles dealt round-robin) renders on devices[r];

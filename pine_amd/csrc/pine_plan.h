@@ -239,9 +239,10 @@ struct pine_gpu_plan {
   const PineFastVariant* fast = nullptr;  // PINE_GPU_FLAG_FAST: the declared-tolerance variant that runs instead (pine_kernels_fast.hip)
   uint32_t* d_ctxg = nullptr;
   ulonglong2* d_ckpt = nullptr;
-  // The RNG checkpoints are a function of the film partition and the sample counts alone: the plan's FIRST launch computes them,
-  // later launches reuse the table (they wait for `ckpt_done` when they run on another stream).  $PINE_GPU_CKPT_EVERY_LAUNCH=1: as
-  // before round 4, every launch recomputes it (measurement aid).
+  // The RNG checkpoints are a function of the film partition and the sample counts alone: the FIRST launch of a plan of one pass
+  // computes them, later launches reuse the table (they wait for `ckpt_done` when they run on another stream).
+  // $PINE_GPU_CKPT_EVERY_LAUNCH=1: as before round 4, every launch recomputes it (measurement aid).  A plan of several passes
+  // keeps the checkpoints of one pass only: each pass computes its own from the carried states.
   bool ckpt_valid = false, ckpt_every_launch = false;
   hipEvent_t ckpt_done = nullptr;
   hipStream_t ckpt_stream = nullptr;
@@ -249,7 +250,7 @@ struct pine_gpu_plan {
   int* d_tile_order = nullptr;          // tile classes (WorkParams::tile_order), or null
   std::vector<int> tile_order;          // ... its host copy (empty: local tile t is film tile t * shard_world + shard_rank)
   float4* d_samples = nullptr;
-  // Passes (pine_gpu_plan_create_passes; pass_plan.n == 1: an ordinary plan, none of the buffers below).  The running sum is
+  // Passes: every launch is a pass of pass_plan (pass_plan.n == 1: an ordinary plan, none of the buffers below).  The running sum is
   // one float4 per local pixel ([local tile][pixel in tile], .w unused); the carried RNG states one per pixel of the independent class.
   int pass_samples_req = 0;
   PassPlan pass_plan;
