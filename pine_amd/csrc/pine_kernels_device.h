@@ -1,7 +1,9 @@
 // pine_amd/csrc/pine_kernels_device.h -- the device side of the PathIntegrator hot path: types shared by host and
 // kernels (DeviceScene, WorkParams, Counters, PackedState), BVH traversal, the lane-owns-a-path kernel and -- through
-// pine_trav.h / pine_queue_kernel.h -- the stage-queued kernel.  Included by pine_kernels.hip (exact arithmetic: the
-// parity build) and by pine_kernels_fast.hip (declared-tolerance arithmetic, under another namespace).
+// pine_trav.h / pine_queue_kernel.h -- the stage-queued kernel.  What a path vertex computes (surface, emission, lobe
+// choice, next-event estimation, fold) is written once, in pine_radiance.h; both kernels call it, and that is why their
+// films are the same bits.  Included by pine_kernels.hip (exact arithmetic: the parity build) and by
+// pine_kernels_fast.hip (declared-tolerance arithmetic, under another namespace).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -852,6 +854,10 @@ struct PackedState {
   __device__ __forceinline__ void set_sealed() { v |= 0x80000000u; }
 };
 
+}  // namespace pine_gpu
+#include "pine_radiance.h"  // the per-vertex steps of radiance(): both path kernels run these
+namespace pine_gpu {
+
 template <unsigned F, int WAVES_PER_SIMD>
 __global__ void __launch_bounds__(kBlock, WAVES_PER_SIMD)
 path_trace_kernel(DeviceScene S, WorkParams W, const ulonglong2* __restrict__ ckpt, float4* __restrict__ samples,
@@ -894,15 +900,7 @@ path_trace_kernel(DeviceScene S, WorkParams W, const ulonglong2* __restrict__ ck
     __syncthreads();
     const char* base = reinterpret_cast<const char*>(dst);
     V.nodes = reinterpret_cast<const DNode*>(base + S.off_nodes);
-    V.shapes = reinterpret_cast<const DShape*>(base + S.off_shapes);
-    V.materials = reinterpret_cast<const DMaterial*>(base + S.off_materials);
-    V.bvhs = reinterpret_cast<const DBvh*>(base + S.off_bvhs);
-    V.prims = nullptr;
-    V.lights = reinterpret_cast<const DLight*>(base + S.off_lights);
-    V.node_ops = reinterpret_cast<const DNodeOp*>(base + S.off_node_ops);
-    V.leaf = reinterpret_cast<const DShape*>(base + S.off_leaf) - S.top_prim_begin;
-    V.etree = reinterpret_cast<const EmbreeNode*>(base + S.off_etree);
-    V.emesh = reinterpret_cast<const int*>(base + S.off_emesh);
+    view_of_blob(base, S, V);
     if (S.off_rcpps < S.blob_bytes) V.rcpps = reinterpret_cast<const unsigned*>(base + S.off_rcpps);
   } else {
     __syncthreads();  // Sobol rows staged above
@@ -969,10 +967,7 @@ path_trace_kernel(DeviceScene S, WorkParams W, const ulonglong2* __restrict__ ck
   PackedState st{0};
   unsigned shadow_count = 0;
   unsigned long long beta_flags = 0;  // 2 bits per level (BSSRDF beta channel); dead code without F_SSS
-  // SobolSampler / HaltonSampler in a scene with Subsurface: a BSSRDF walk draws three dimensions per step and has no bound on
-  // its steps, SobolSampler's dimension counter does not wrap (sampler.h:143-155) and HaltonSampler's wraps at 1000 -- more
-  // than the nine bits of the packed state hold.  These variants keep the counter in a register of its own.
-  constexpr bool kBigDim = (F & F_SSS) != 0 && (F & F_SOBOL) != 0;
+  constexpr bool kBigDim = big_sampler_dimension<F>();  // the sampler's dimension counter in a register of its own
   int big_dim = 0;
   (void)big_dim;
   // wave-uniform private item pool [pool_next, pool_end)
@@ -1057,15 +1052,9 @@ path_trace_kernel(DeviceScene S, WorkParams W, const ulonglong2* __restrict__ ck
           if (S.tables.kind == 2) st.set_dim(2);  // HaltonSampler::start_pixel / start_next_sample: dimension = 2
         if constexpr (kBigDim) big_dim = S.tables.kind == 2 ? 2 : 0;
         const int px = int(pxy & 0xffffu), py = int(pxy >> 16);
-        // g++ evaluates gen_ray's arguments right to left (path.cpp:35): lens first, then jitter
         DRng g = rng_load();
-        const float lx = rng_nextf(g);
-        const float ly = rng_nextf(g);
-        const float jx = rng_nextf(g);
-        const float jy = rng_nextf(g);
+        const DRay r = camera_sample(S.cam, px, py, g);
         rng_store(g);
-        const f2 pf{(float(px) + jx) / float(S.cam.W), (float(py) + jy) / float(S.cam.H)};
-        const DRay r = camera_gen_ray(S.cam, pf, f2{lx, ly});
         ray_o = r.o;
         ray_d = r.d;
         ray_tmax = r.tmax;
@@ -1078,13 +1067,7 @@ path_trace_kernel(DeviceScene S, WorkParams W, const ulonglong2* __restrict__ ck
     if (!alive) continue;
 
     // ---------------- one radiance() invocation (path.cpp:42-124) ----------------
-    DSampler sampler;
-    sampler.px = int(pxy & 0xffffu);
-    sampler.py = int(pxy >> 16);
-    sampler.index = st.s_cur();
-    sampler.dimension = st.dim();
-    if constexpr (kBigDim)
-      if (S.tables.kind != 0) sampler.dimension = big_dim;
+    DSampler sampler = sampler_of<F>(st, pxy, S.tables.kind, [&] { return big_dim; });
     const int pv_length = st.length();
     int geom = -1, prim = 0;
     bool hit;
@@ -1102,40 +1085,19 @@ path_trace_kernel(DeviceScene S, WorkParams W, const ulonglong2* __restrict__ ck
     bool has_light_pdf = false;
     float light_pdf = 0.0f;
 
-    DSurface it;
-    it.p = it.n = mk3(0.0f);
-    it.uv = f2{0, 0};
+    DSurface it{};
     const DShape* shape = nullptr;
     const DMaterial* mat = nullptr;
     if (!hit) {
-      terminal = true;  // path.cpp:75-81
-      if constexpr (F & F_LIGHTS)
-        if (S.env_light >= 0) {
-          Lo = mk3(1.0f) * sky_color_of(ld3(V.lights[S.env_light].color), ray_d);
-          if (!st.is_delta()) {
-            has_light_pdf = true;
-            light_pdf = 1 / (4 * kPi);  // Sky::pdf -- not divided by the light count
-          }
-        }
+      terminal = true;
+      Lo = terminal_radiance<F>(V, S.env_light, S.num_lights, false, shape, it, ray_o, ray_d, ray_tmax, st.is_delta(), has_light_pdf, light_pdf);
     } else {
       REGION(3);  // surface info
       shape = &V.shapes[geom];
       mat = &V.materials[shape->material];
-      const f3 ph = ray_o + ray_tmax * ray_d;
-      bool on_mesh = false;
-      if constexpr (F & F_MESH) on_mesh = shape->kind == SHAPE_MESH;
-      if (on_mesh) {
-        if constexpr (F & F_EMBREE) mesh_surface_info_embree(V.rcpps, V.tri_verts, V.tri_attrs, as_int(shape->f[4]), prim, ray_o, ray_d, it);
-        else mesh_surface_info(V.tri_verts, V.tri_attrs, as_int(shape->f[4]), prim, ph, it);
-      } else shape_surface_info<F>(shape, ph, it);
-      if (mat->kind == MAT_EMISSIVE) {  // path.cpp:83-87
-        Lo = mk3(1.0f) * material_le(mat, it.n, -ray_d);
-        if (!st.is_delta()) {
-          has_light_pdf = true;
-          const DRay ray{ray_o, ray_d, 0.0f, ray_tmax};
-          light_pdf = shape_pdf<F>(shape, ray, it.n);  // lightsampler.cpp:27-29: / lights.size()
-          if (S.num_lights != 1) light_pdf = light_pdf / float(size_t(S.num_lights));  // x / 1.0f == x exactly
-        }
+      hit_surface<F>(V, shape, prim, ray_o, ray_d, ray_tmax, it);
+      if (mat->kind == MAT_EMISSIVE) {
+        Lo = terminal_radiance<F>(V, S.env_light, S.num_lights, true, shape, it, ray_o, ray_d, ray_tmax, st.is_delta(), has_light_pdf, light_pdf);
         terminal = true;
       } else if (pv_length + 1 >= S.max_path_length) {  // path.cpp:89
         terminal = true;
@@ -1148,50 +1110,9 @@ path_trace_kernel(DeviceScene S, WorkParams W, const ulonglong2* __restrict__ ck
       const f3 wi = -ray_d;
       m3 l2w = coordinate_system(it.n);  // interaction.h:14-17
       m3 w2l = transpose(l2w);
-      // ---- material.sample_bxdf (material.h:30-131, material.cpp:9-28) ----
-      const bool diffused = st.diffuse_length() > 0;
-      const float min_roughness = diffused ? 0.6f : 0.0f;  // bxdf.h:15
-      DBxdf bx;
-      bx.kind = BX_DIFFUSE;
-      bx.roughness = 0.0f;
-      bx.ior = 1.0f;
-      bool is_uber = false, is_sss = false, is_lobe = false;
-      if constexpr (F & F_UBER) is_uber = mat->kind == MAT_UBER;
-      if constexpr (F & F_UBER) is_lobe = mat->kind >= MAT_METAL;  // Metal / Glossy / Glass: one fixed lobe
-      if constexpr (F & F_SSS) is_sss = mat->kind == MAT_SUBSURFACE;
       const MatParams mp = material_params<F>(mat, V.node_ops, it.p, it.n, it.uv);
-      if (is_uber) {
-        DRng g = rng_load();
-        if (with_probability(mp.metallic, g)) {
-          bx.kind = BX_CONDUCTOR;
-          bx.roughness = mp.roughness;
-        } else if (with_probability(mp.transmission, g)) {
-          bx.kind = BX_REFR_DIEL;
-          bx.roughness = mp.roughness;
-          bx.ior = mp.ior;
-        } else {
-          bx.kind = BX_DIFF_DIEL;
-          bx.roughness = mp.roughness;
-          bx.ior = mp.ior;
-        }
-        rng_store(g);
-      } else if (is_lobe) {  // material.h:39-78
-        bx.kind = mat->kind == MAT_METAL ? BX_CONDUCTOR : mat->kind == MAT_GLOSSY ? BX_DIFF_DIEL : BX_REFR_DIEL;
-        bx.roughness = pmax(mp.roughness, min_roughness);
-        bx.ior = mp.ior;
-      } else if (is_sss) {
-        const float fr = FrDielectric(dot(wi, it.n), mat->ior);
-        if (sampler_get1d<kSM>(T, sampler) < fr) {
-          bx.kind = BX_REFRACTIVE;
-          bx.roughness = pmax(mp.roughness, min_roughness);
-          bx.ior = mat->ior;
-        } else if (diffused) {
-          bx.kind = BX_DIFFUSE;
-        } else {
-          bx.kind = BX_BSSRDF;
-          bx.ior = mat->ior;
-        }
-      }
+      DBxdf bx;
+      choose_lobe<F, kSM>(mat, mp, wi, it.n, st.diffuse_length() > 0, false, rng_load, rng_store, T, sampler, bx);
       bx.wi = mul(w2l, wi);  // material.h:119
 
       // ---- BSSRDF random walk inside the same shape (bxdf.cpp:329-353, :375-382) ----
@@ -1243,56 +1164,15 @@ path_trace_kernel(DeviceScene S, WorkParams W, const ulonglong2* __restrict__ ck
       // ---- next-event estimation (path.cpp:98-113) ----
       f3 nee = mk3(0.0f);
       if (!bxdf_is_delta<F>(bx)) {
-        // g++ order for LightSampler::sample's arguments (lightsampler.h:27): get2d, then get1d
-        const f2 u2 = sampler_get2d<kSM>(T, sampler);
-        float u1 = sampler_get1d<kSM>(T, sampler);
-        if (S.num_lights > 0) {  // UniformLightSampler::sample lightsampler.cpp:12-26
-          if (S.num_lights != 1) u1 *= float(S.num_lights);  // x * 1.0f == x exactly
-          const int index = int(u1);
-          const DLight* L = &V.lights[index];
-          int lkind = LIGHT_AREA;
-          if constexpr (F & F_LIGHTS) lkind = L->kind;
-          bool lvalid = false;
-          f3 lw = mk3(0.0f), lle = mk3(0.0f);
-          float ldist = 0.0f, lpdf = 0.0f;
-          if (lkind == LIGHT_AREA) {  // AreaLight::sample light.cpp:55-69
-            const DShape* lshape = &V.shapes[L->geom];
-            DShapeSample gs;
-            if (shape_sample<F>(lshape, V.tri_verts, it.p, u2, u1 - float(index), gs)) {
-              lle = material_le(&V.materials[lshape->material], gs.n, -gs.w);
-              lvalid = !is_zero(lle);
-              lw = gs.w;
-              ldist = gs.distance;
-              lpdf = gs.pdf;
-            }
-          } else {
-            if constexpr (F & F_LIGHTS) lvalid = light_sample_other(L, it.p, u2, lw, ldist, lpdf, lle);
-          }
-          const bool ldelta = lkind == LIGHT_POINT || lkind == LIGHT_SPOT || lkind == LIGHT_DIRECTIONAL;  // light.h:111-113
-          if (lvalid) {
-            const float ls_pdf = S.num_lights != 1 ? lpdf / float(S.num_lights) : lpdf;
-            REGION(7);  // shadow ray cast
-            shadow_count++;
-            DRay sr = spawn_ray(it.p, it.n, lw, ldist);
-            int g2, p2;
-            SEC_MARK(5);  // light sampling
-            const bool occluded = scene_traverse<true, F>(V, sr, stack, g2, p2);
-            SEC_MARK(6);  // shadow traversal
-            if (!occluded) {
-              bx.albedo = mp.albedo;
-              bx.albedo_over_pi = mp.albedo_over_pi;
-              const float cosine = absdot(lw, it.n);
-              const f3 wo = mul(w2l, lw);
-              const f3 f = bxdf_f<F>(bx, wo);
-              if (ldelta) {  // path.cpp:104-106: no MIS against a delta light
-                nee = mk3(0.0f) + lle * mk3(1.0f) * cosine * f / ls_pdf;
-              } else {
-                const float mis = balance_heuristic(ls_pdf, bxdf_pdf<F>(bx, wo));
-                nee = mk3(0.0f) + lle * mk3(1.0f) * cosine * f / ls_pdf * mis;
-              }
-            }
-          }
-        }
+        nee = sample_direct<F, kSM>(V, S.num_lights, it, w2l, bx, mp, T, sampler, shadow_count, [&](const DRay& sr) -> bool {
+          REGION(7);  // shadow ray cast
+          DRay r = sr;
+          int g2, p2;
+          SEC_MARK(5);  // light sampling
+          const bool occluded = scene_traverse<true, F>(V, r, stack, g2, p2);
+          SEC_MARK(6);  // shadow traversal
+          return occluded;
+        });
       }
 
       SEC_MARK(7);  // NEE evaluation (and light sampling of lanes without a shadow ray)
@@ -1317,12 +1197,7 @@ path_trace_kernel(DeviceScene S, WorkParams W, const ulonglong2* __restrict__ ck
         st.next_vertex(bs.is_delta);
       } else {
         // no continuation: this vertex resolves now with lo = nee (path.cpp:121)
-        f3 beta = mk3(1.0f);
-        if (beta_channel) {
-          beta = mk3(0.0f);
-          set(beta, beta_channel - 1, 3.0f);
-        }
-        Lo = mk3(0.0f) + vmin(mk3(1.0f) * beta * nee, mk3(8.0f));
+        Lo = clamp_radiance(beta_channel, nee);
         terminal = true;
       }
     }
@@ -1338,28 +1213,13 @@ path_trace_kernel(DeviceScene S, WorkParams W, const ulonglong2* __restrict__ ck
         REGION(9);  // fold level
         float e[8];
         fold_load(level, e);
-        const f3 e_nee{e[0], e[1], e[2]};
-        const f3 e_f{e[3], e[4], e[5]};
-        const float e_cp = e[6], e_pdf = e[7];
-        const float mis = lp_valid ? balance_heuristic(e_pdf, lp) : 1.0f;
-        const f3 lo = e_nee + Li * e_f * (e_cp * mis);
-        f3 beta = mk3(1.0f);
-        if constexpr (F & F_SSS) {
-          const unsigned bc = unsigned(beta_flags >> (2 * level)) & 3u;
-          if (bc) {
-            beta = mk3(0.0f);
-            set(beta, int(bc) - 1, 3.0f);
-          }
-        }
-        Li = mk3(0.0f) + vmin(mk3(1.0f) * beta * lo, mk3(8.0f));
-        lp_valid = false;
+        fold_level<F>(e, beta_flags, level, Li, lp_valid, lp);
       }
       // .w = radiance() invocations of this sample (= depth reached + 1); resolve_kernel sums them
       const int s_now = st.s_cur();
       samples[size_t(sample_base) + size_t(s_now) * 64u] = make_float4(Li.x, Li.y, Li.z, float(pv_length + 1));
       st.v = unsigned(s_now + 1);
-      // item = kspi consecutive samples: a power of two that divides spp, or (another SobolSampler / HaltonSampler count) the whole pixel
-      if ((kspi & (kspi - 1)) == 0 ? ((s_now + 1) & (kspi - 1)) == 0 : s_now + 1 == kspi) have_item = false;
+      if (closes_item(kspi, s_now + 1)) have_item = false;
       alive = false;
     }
     SEC_MARK(9);  // fold + sample store

@@ -16,7 +16,9 @@
 // One workgroup of 1024 threads per CU (all 160 KB of LDS, 16 waves sharing the queues).
 // Per-context cold data (sampler tile slice, RNG, fold stack) lives in L2-resident global memory.
 // Every result is bit-identical to path_trace_kernel and to the oracle: the stages run the same
-// device functions in the same order per path; only the scheduling differs.
+// device functions in the same order per path -- the per-vertex steps of pine_radiance.h, which
+// path_trace_kernel calls too; only the scheduling differs.  What is written here is this kernel's
+// own: queues, contexts, tokens, work hand-out, and the stores that keep a path's state between stages.
 #pragma once
 
 
@@ -130,10 +132,9 @@ __device__ __forceinline__ void path_queue_body(const DeviceScene& S, const Work
 #define kS(FIELD) ([&] { std::remove_cv_t<decltype(S.FIELD)> v_; kload(offsetof(DeviceScene, FIELD), &v_); return v_; }())
 #define kW(FIELD) ([&] { std::remove_cv_t<decltype(W.FIELD)> v_; kload(kWOffset + offsetof(WorkParams, FIELD), &v_); return v_; }())
   constexpr int kSM = kSmLds | ((F & F_SOBOL) ? kSmSobol : 0);  // sampler front mode (pine_device.h)
-  // SobolSampler / HaltonSampler in a scene with Subsurface: the sampler's dimension counter outgrows the nine bits of the packed
-  // state (a BSSRDF walk draws three dimensions per step, SobolSampler's counter never wraps, HaltonSampler's wraps at 1000);
-  // those variants keep it in a free word of the context's global record (float4 1, third word) while the sampler is not BlueSampler
-  constexpr bool kBigDim = (F & F_SSS) != 0 && (F & F_SOBOL) != 0;
+  // the sampler's dimension counter in a free word of the context's global record (float4 1, third word) while the sampler is
+  // not BlueSampler
+  constexpr bool kBigDim = big_sampler_dimension<F>();
   const unsigned tid = threadIdx.x;
   const unsigned lane = tid & 63;
   unsigned* const qctl = reinterpret_cast<unsigned*>(lds_raw + kQOffCtl);
@@ -209,15 +210,7 @@ __device__ __forceinline__ void path_queue_body(const DeviceScene& S, const Work
     for (int i = tid; i < n16; i += kQBlock) dst[i] = S.blob[i];
     const char* base = reinterpret_cast<const char*>(dst);
     V.nodes = reinterpret_cast<const DNode*>(base + S.off_nodes);
-    V.shapes = reinterpret_cast<const DShape*>(base + S.off_shapes);
-    V.materials = reinterpret_cast<const DMaterial*>(base + S.off_materials);
-    V.bvhs = reinterpret_cast<const DBvh*>(base + S.off_bvhs);
-    V.prims = nullptr;
-    V.lights = reinterpret_cast<const DLight*>(base + S.off_lights);
-    V.node_ops = reinterpret_cast<const DNodeOp*>(base + S.off_node_ops);
-    V.leaf = reinterpret_cast<const DShape*>(base + S.off_leaf) - S.top_prim_begin;
-    V.etree = reinterpret_cast<const EmbreeNode*>(base + S.off_etree);
-    V.emesh = reinterpret_cast<const int*>(base + S.off_emesh);
+    view_of_blob(base, S, V);
     if (S.off_rcpps < S.blob_bytes) V.rcpps = reinterpret_cast<const unsigned*>(base + S.off_rcpps);
   } else if constexpr (F & F_LDS_REST) {
     // blob = nodes | shapes | materials | node programs | bvhs | leaf records | lights: everything after the nodes
@@ -229,15 +222,7 @@ __device__ __forceinline__ void path_queue_body(const DeviceScene& S, const Work
     for (int i = tid; i < n16; i += kQBlock) dst[i] = src[i];
     const char* base = reinterpret_cast<const char*>(dst) - S.off_shapes;
     V.nodes = S.nodes;
-    V.shapes = reinterpret_cast<const DShape*>(base + S.off_shapes);
-    V.materials = reinterpret_cast<const DMaterial*>(base + S.off_materials);
-    V.bvhs = reinterpret_cast<const DBvh*>(base + S.off_bvhs);
-    V.prims = nullptr;
-    V.lights = reinterpret_cast<const DLight*>(base + S.off_lights);
-    V.node_ops = reinterpret_cast<const DNodeOp*>(base + S.off_node_ops);
-    V.leaf = reinterpret_cast<const DShape*>(base + S.off_leaf) - S.top_prim_begin;
-    V.etree = reinterpret_cast<const EmbreeNode*>(base + S.off_etree);
-    V.emesh = reinterpret_cast<const int*>(base + S.off_emesh);
+    view_of_blob(base, S, V);
   } else {
     V.leaf = S.leaf;
     V.nodes = S.nodes;
@@ -309,10 +294,7 @@ __device__ __forceinline__ void path_queue_body(const DeviceScene& S, const Work
 
   // samples of a pixel that form one sequential chain (kFork): the whole pixel -- the item itself without tile classes
   const int chain_spi = W.serial_tiles > 0 ? S.spp : W.samples_per_item;
-  // "sample index s closes its chain / item": a chain is a power of two that divides spp, or -- SobolSampler / HaltonSampler with
-  // another count -- the whole pixel (then chain_spi == spp and the chain starts at sample 0)
-  const bool chain_pow2 = (chain_spi & (chain_spi - 1)) == 0;
-  auto chain_ends_at = [&](int s_next) -> bool { return chain_pow2 ? (s_next & (chain_spi - 1)) == 0 : s_next == chain_spi; };
+  auto chain_ends_at = [&](int s_next) -> bool { return closes_item(chain_spi, s_next); };
   SEC_DECL;
   // record a finished closest-hit query in the context and classify the vertex it reaches:
   // emissive / miss / path-length limit -> terminal queue, otherwise -> shade queue
@@ -843,42 +825,16 @@ __device__ __forceinline__ void path_queue_body(const DeviceScene& S, const Work
         T.tile_stride = kStride;
         T.win_lo = wbase * 4;
         T.win_len = (wbase * 4 + 12 <= kLdsSamplerDims ? 12 : kLdsSamplerDims - wbase * 4);
-        DSampler sampler;
-        sampler.px = int(pxy & 0xffffu);
-        sampler.py = int(pxy >> 16);
-        sampler.index = st.s_cur();
-        sampler.dimension = st.dim();
-        if constexpr (kBigDim)
-          if (S.tables.kind != 0) sampler.dimension = int(cg[6]);
+        DSampler sampler = sampler_of<F>(st, pxy, S.tables.kind, [&] { return int(cg[6]); });
         const int pv_length = st.length();
 
         const DShape* shape = &V.shapes[geom];
         const DMaterial* mat = &V.materials[shape->material];
         DSurface it;
-        it.p = it.n = mk3(0.0f);
-        it.uv = f2{0, 0};
-        {
-          const f3 ph = ray_o + ray_tmax * ray_d;
-          bool on_mesh = false;
-          if constexpr (F & F_MESH) on_mesh = shape->kind == SHAPE_MESH;
-          if (on_mesh) {
-            if constexpr (F & F_EMBREE) mesh_surface_info_embree(V.rcpps, V.tri_verts, V.tri_attrs, as_int(shape->f[4]), prim, ray_o, ray_d, it);
-            else mesh_surface_info(V.tri_verts, V.tri_attrs, as_int(shape->f[4]), prim, ph, it);
-          } else shape_surface_info<F>(shape, ph, it);
-        }
+        hit_surface<F>(V, shape, prim, ray_o, ray_d, ray_tmax, it);
         const f3 wi = -ray_d;
         m3 l2w = coordinate_system(it.n);
         m3 w2l = transpose(l2w);
-        const bool diffused = st.diffuse_length() > 0;
-        const float min_roughness = diffused ? 0.6f : 0.0f;
-        DBxdf bx;
-        bx.kind = BX_DIFFUSE;
-        bx.roughness = 0.0f;
-        bx.ior = 1.0f;
-        bool is_uber = false, is_sss = false, is_lobe = false;
-        if constexpr (F & F_UBER) is_uber = mat->kind == MAT_UBER;
-        if constexpr (F & F_UBER) is_lobe = mat->kind >= MAT_METAL;  // Metal / Glossy / Glass: one fixed lobe
-        if constexpr (F & F_SSS) is_sss = mat->kind == MAT_SUBSURFACE;
         const MatParams mp = material_params<F>(mat, V.node_ops, it.p, it.n, it.uv);
         auto rng_load = [&]() -> DRng {
           return DRng{uint64_t(cg[0]) | (uint64_t(cg[1]) << 32), uint64_t(cg[2]) | (uint64_t(cg[3]) << 32)};
@@ -889,43 +845,9 @@ __device__ __forceinline__ void path_queue_body(const DeviceScene& S, const Work
           cg[2] = uint32_t(g.s1);
           cg[3] = uint32_t(g.s1 >> 32);
         };
-        if (is_uber) {
-          DRng g = rng_load();
-          if (with_probability(mp.metallic, g)) {
-            bx.kind = BX_CONDUCTOR;
-            bx.roughness = mp.roughness;
-          } else if (with_probability(mp.transmission, g)) {
-            bx.kind = BX_REFR_DIEL;
-            bx.roughness = mp.roughness;
-            bx.ior = mp.ior;
-          } else {
-            bx.kind = BX_DIFF_DIEL;
-            bx.roughness = mp.roughness;
-            bx.ior = mp.ior;
-          }
-          rng_store(g);
-        } else if (is_lobe) {  // material.h:39-78
-          bx.kind = mat->kind == MAT_METAL ? BX_CONDUCTOR : mat->kind == MAT_GLOSSY ? BX_DIFF_DIEL : BX_REFR_DIEL;
-          bx.roughness = pmax(mp.roughness, min_roughness);
-          bx.ior = mp.ior;
-        } else if (is_sss) {
-          if (st.walk() != kWalkNone) {  // second entry, after the walk: the lobe was chosen (and its draw made) the first time
-            bx.kind = BX_BSSRDF;
-            bx.ior = mat->ior;
-          } else {
-            const float fr = FrDielectric(dot(wi, it.n), mat->ior);
-            if (sampler_get1d<kSM>(T, sampler) < fr) {
-              bx.kind = BX_REFRACTIVE;
-              bx.roughness = pmax(mp.roughness, min_roughness);
-              bx.ior = mat->ior;
-            } else if (diffused) {
-              bx.kind = BX_DIFFUSE;
-            } else {
-              bx.kind = BX_BSSRDF;
-              bx.ior = mat->ior;
-            }
-          }
-        }
+        // (a second entry, after the walk: the lobe was chosen, and its draw made, the first time)
+        DBxdf bx;
+        choose_lobe<F, kSM>(mat, mp, wi, it.n, st.diffuse_length() > 0, st.walk() != kWalkNone, rng_load, rng_store, T, sampler, bx);
         bx.wi = mul(w2l, wi);
         // ---- BSSRDF random walk (bxdf.cpp:329-353, :375-382): started here, stepped by stage W ----
         int beta_channel = 0;
@@ -987,6 +909,7 @@ __device__ __forceinline__ void path_queue_body(const DeviceScene& S, const Work
         bool have_shadow = false;
         DRay shadow_ray{};
         auto shadow_test = [&](const DRay& sr) -> bool {
+          SEC_MARK(2);  // S: sampler draws + light sampling
           if constexpr (kFlat) {
             have_shadow = true;
             shadow_ray = sr;
@@ -995,87 +918,17 @@ __device__ __forceinline__ void path_queue_body(const DeviceScene& S, const Work
             DRay r = sr;
             int g2, p2;
 #if defined(PINE_BAKED_SCENE) && !defined(PINE_BAKED_TOP)
-            return scene_traverse_baked<true, F>(r, g2);
+            const bool occluded = scene_traverse_baked<true, F>(r, g2);
 #else
-            return scene_traverse<true, F, kStride>(V, r, stack, g2, p2);
+            const bool occluded = scene_traverse<true, F, kStride>(V, r, stack, g2, p2);
 #endif
+            SEC_MARK(3);  // S: shadow traversal (the not-X variants)
+            return occluded;
           }
         };
         f3 nee = mk3(0.0f);
-        if (!start_walk && !bxdf_is_delta<F>(bx)) {
-          const f2 u2 = sampler_get2d<kSM>(T, sampler);  // g++ order: get2d first (lightsampler.h:27)
-          float u1 = sampler_get1d<kSM>(T, sampler);
-          if constexpr (F & F_LIGHTS) {
-            // general light list (light.cpp:11-84): area lights, delta lights (no MIS, path.cpp:104-106), Sky
-            if (S.num_lights > 0) {
-              if (S.num_lights != 1) u1 *= float(S.num_lights);
-              const int index = int(u1);
-              const DLight* L = &V.lights[index];
-              const int lkind = L->kind;
-              bool lvalid = false;
-              f3 lw = mk3(0.0f), lle = mk3(0.0f);
-              float ldist = 0.0f, lpdf = 0.0f;
-              if (lkind == LIGHT_AREA) {
-                const DShape* lshape = &V.shapes[L->geom];
-                DShapeSample gs;
-                if (shape_sample<F>(lshape, V.tri_verts, it.p, u2, u1 - float(index), gs)) {
-                  lle = material_le(&V.materials[lshape->material], gs.n, -gs.w);
-                  lvalid = !is_zero(lle);
-                  lw = gs.w;
-                  ldist = gs.distance;
-                  lpdf = gs.pdf;
-                }
-              } else {
-                lvalid = light_sample_other(L, it.p, u2, lw, ldist, lpdf, lle);
-              }
-              const bool ldelta = lkind == LIGHT_POINT || lkind == LIGHT_SPOT || lkind == LIGHT_DIRECTIONAL;
-              if (lvalid) {
-                const float ls_pdf = S.num_lights != 1 ? lpdf / float(S.num_lights) : lpdf;
-                shadow_count++;
-                const DRay sr = spawn_ray(it.p, it.n, lw, ldist);
-                if (!shadow_test(sr)) {
-                  bx.albedo = mp.albedo;
-                  bx.albedo_over_pi = mp.albedo_over_pi;
-                  const float cosine = absdot(lw, it.n);
-                  const f3 wo = mul(w2l, lw);
-                  const f3 f = bxdf_f<F>(bx, wo);
-                  if (ldelta) {
-                    nee = mk3(0.0f) + lle * mk3(1.0f) * cosine * f / ls_pdf;
-                  } else {
-                    const float mis = balance_heuristic(ls_pdf, bxdf_pdf<F>(bx, wo));
-                    nee = mk3(0.0f) + lle * mk3(1.0f) * cosine * f / ls_pdf * mis;
-                  }
-                }
-              }
-            }
-          } else if (S.num_lights > 0) {
-            if (S.num_lights != 1) u1 *= float(S.num_lights);
-            const int index = int(u1);
-            const DShape* lshape = &V.shapes[V.lights[index].geom];  // (no other light kinds in this variant)
-            DShapeSample gs;
-            if (shape_sample<F>(lshape, V.tri_verts, it.p, u2, u1 - float(index), gs)) {
-              const DMaterial* lmat = &V.materials[lshape->material];
-              if (!is_zero(material_le(lmat, gs.n, -gs.w))) {
-                const float ls_pdf = S.num_lights != 1 ? gs.pdf / float(S.num_lights) : gs.pdf;
-                shadow_count++;
-                const DRay sr = spawn_ray(it.p, it.n, gs.w, gs.distance);
-                SEC_MARK(2);  // S: sampler draws + light sampling
-                const bool occluded = shadow_test(sr);
-                SEC_MARK(3);  // S: shadow traversal (the not-X variants)
-                if (!occluded) {
-                  const f3 le = ld3(lmat->color);
-                  bx.albedo = mp.albedo;
-                  bx.albedo_over_pi = mp.albedo_over_pi;
-                  const float cosine = absdot(gs.w, it.n);
-                  const f3 wo = mul(w2l, gs.w);
-                  const f3 f = bxdf_f<F>(bx, wo);
-                  const float mis = balance_heuristic(ls_pdf, bxdf_pdf<F>(bx, wo));
-                  nee = mk3(0.0f) + le * mk3(1.0f) * cosine * f / ls_pdf * mis;
-                }
-              }
-            }
-          }
-        }
+        if (!start_walk && !bxdf_is_delta<F>(bx))
+          nee = sample_direct<F, kSM>(V, S.num_lights, it, w2l, bx, mp, T, sampler, shadow_count, shadow_test);
         SEC_MARK(4);  // S: NEE evaluation
         // ---- BSDF sampling + continuation (path.cpp:114-120) ----
         bx.albedo = mp.albedo;
@@ -1178,12 +1031,7 @@ __device__ __forceinline__ void path_queue_body(const DeviceScene& S, const Work
           }
         } else {
           // no continuation: the vertex resolves with lo = nee (path.cpp:121); stage T folds it
-          f3 beta = mk3(1.0f);
-          if (beta_channel) {
-            beta = mk3(0.0f);
-            set(beta, beta_channel - 1, 3.0f);
-          }
-          const f3 Lo = mk3(0.0f) + vmin(mk3(1.0f) * beta * nee, mk3(8.0f));
+          const f3 Lo = clamp_radiance(beta_channel, nee);
           if (kVlog && W.vertex_log) {
             float4* r = reinterpret_cast<float4*>(vlog(pxy, st.s_cur(), pv_length));
             r[0] = make_float4(3.0f, float(pv_length), nee.x, nee.y);
@@ -1262,13 +1110,7 @@ __device__ __forceinline__ void path_queue_body(const DeviceScene& S, const Work
           const int channel = __float_as_int(a.w);
           DRay wr{f3{a.x, a.y, a.z}, f3{b.x, b.y, b.z}, 0.0f, b.w};
           walk_count++;
-          DSampler sampler;
-          sampler.px = int(pxy & 0xffffu);
-          sampler.py = int(pxy >> 16);
-          sampler.index = st.s_cur();
-          sampler.dimension = st.dim();
-          if constexpr (kBigDim)
-            if (S.tables.kind != 0) sampler.dimension = int(ctx_global(id)[6]);
+          DSampler sampler = sampler_of<F>(st, pxy, S.tables.kind, [&] { return int(ctx_global(id)[6]); });
           bool hh;
           int wprim = 0;
           bool walk_mesh = false;
@@ -1339,40 +1181,17 @@ __device__ __forceinline__ void path_queue_body(const DeviceScene& S, const Work
           float lp = 0.0f;
           if (geom == -2) {
             Lo = f3{cstf[CF_DX * kQCtx + id], cstf[CF_DY * kQCtx + id], cstf[CF_DZ * kQCtx + id]};
-          } else if (geom == -1) {  // miss: the environment light, if any (path.cpp:75-81)
-            if constexpr (F & F_LIGHTS)
-              if (S.env_light >= 0) {
-                const f3 ray_d{cstf[CF_DX * kQCtx + id], cstf[CF_DY * kQCtx + id], cstf[CF_DZ * kQCtx + id]};
-                Lo = mk3(1.0f) * sky_color_of(ld3(V.lights[S.env_light].color), ray_d);
-                if (!st.is_delta()) {
-                  lp_valid = true;
-                  lp = 1 / (4 * kPi);  // Sky::pdf -- not divided by the light count
-                }
-              }
-          } else if (geom >= 0 && (geom & kPrimEmissiveBit) != 0) {
-            const DShape* shape = &V.shapes[geom & kPrimIndexMask];
-            const DMaterial* mat = &V.materials[shape->material];
-            {  // path.cpp:83-87
-              const f3 ray_o{cstf[CF_OX * kQCtx + id], cstf[CF_OY * kQCtx + id], cstf[CF_OZ * kQCtx + id]};
-              const f3 ray_d{cstf[CF_DX * kQCtx + id], cstf[CF_DY * kQCtx + id], cstf[CF_DZ * kQCtx + id]};
-              const float ray_tmax = cstf[CF_TMAX * kQCtx + id];
-              DSurface it;
-              it.p = it.n = mk3(0.0f);
-              it.uv = f2{0, 0};
-              const f3 ph = ray_o + ray_tmax * ray_d;
-              bool on_mesh = false;
-              if constexpr (F & F_MESH) on_mesh = shape->kind == SHAPE_MESH;
-              if (on_mesh) {
-                if constexpr (F & F_EMBREE) mesh_surface_info_embree(V.rcpps, V.tri_verts, V.tri_attrs, as_int(shape->f[4]), int(cstu[CF_PRIM * kQCtx + id]), ray_o, ray_d, it);
-                else mesh_surface_info(V.tri_verts, V.tri_attrs, as_int(shape->f[4]), int(cstu[CF_PRIM * kQCtx + id]), ph, it);
-              } else shape_surface_info<F>(shape, ph, it);
-              Lo = mk3(1.0f) * material_le(mat, it.n, -ray_d);
-              if (!st.is_delta()) {
-                lp_valid = true;
-                const DRay ray{ray_o, ray_d, 0.0f, ray_tmax};
-                lp = shape_pdf<F>(shape, ray, it.n);
-                if (S.num_lights != 1) lp = lp / float(size_t(S.num_lights));
-              }
+          } else if (geom == -1 || (geom & kPrimEmissiveBit) != 0) {  // a miss, or an emissive surface
+            const f3 ray_o{cstf[CF_OX * kQCtx + id], cstf[CF_OY * kQCtx + id], cstf[CF_OZ * kQCtx + id]};
+            const f3 ray_d{cstf[CF_DX * kQCtx + id], cstf[CF_DY * kQCtx + id], cstf[CF_DZ * kQCtx + id]};
+            const float ray_tmax = cstf[CF_TMAX * kQCtx + id];
+            DSurface it;
+            if (geom == -1) {
+              Lo = terminal_radiance<F>(V, S.env_light, S.num_lights, false, nullptr, it, ray_o, ray_d, ray_tmax, st.is_delta(), lp_valid, lp);
+            } else {
+              const DShape* shape = &V.shapes[geom & kPrimIndexMask];
+              hit_surface<F>(V, shape, int(cstu[CF_PRIM * kQCtx + id]), ray_o, ray_d, ray_tmax, it);
+              Lo = terminal_radiance<F>(V, S.env_light, S.num_lights, true, shape, it, ray_o, ray_d, ray_tmax, st.is_delta(), lp_valid, lp);
             }
           }
           // backward fold (path.cpp:114-121)
@@ -1392,21 +1211,8 @@ __device__ __forceinline__ void path_queue_body(const DeviceScene& S, const Work
             r[13] = Lo.x, r[14] = Lo.y, r[15] = Lo.z;
           }
           auto fold_step = [&](const float4& a, const float4& b, int level) {
-            const f3 e_nee{a.x, a.y, a.z};
-            const f3 e_f{a.w, b.x, b.y};
-            const float e_cp = b.z, e_pdf = b.w;
-            const float mis = lp_valid ? balance_heuristic(e_pdf, lp) : 1.0f;
-            const f3 lo = e_nee + Li * e_f * (e_cp * mis);
-            f3 beta = mk3(1.0f);
-            if constexpr (F & F_SSS) {
-              const unsigned bc = unsigned(beta_flags >> (2 * level)) & 3u;
-              if (bc) {
-                beta = mk3(0.0f);
-                set(beta, int(bc) - 1, 3.0f);
-              }
-            }
-            Li = mk3(0.0f) + vmin(mk3(1.0f) * beta * lo, mk3(8.0f));
-            lp_valid = false;
+            const float e[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+            const float mis = fold_level<F>(e, beta_flags, level, Li, lp_valid, lp);
             if (kVlog && W.vertex_log) {
               float* r = vlog(cstu[CF_PXY * kQCtx + id], st.s_cur(), level);
               r[11] = mis;
@@ -1426,10 +1232,7 @@ __device__ __forceinline__ void path_queue_body(const DeviceScene& S, const Work
           s_next = s_now + 1;
           // (sealed: the pixel's next sample went out as a token -- or, with tile classes, the path is a one-sample item
           // of the independent class, which never owned its pixel's chain)
-          // (an item is samples_per_item consecutive samples: a power of two that divides spp, or -- SobolSampler / HaltonSampler
-          //  with another count -- the whole pixel)
-          const int spi = W.samples_per_item;
-          const bool item_done = kFork ? chain_ends_at(s_next) : (spi & (spi - 1)) == 0 ? (s_next & (spi - 1)) == 0 : s_next == spi;
+          const bool item_done = kFork ? chain_ends_at(s_next) : closes_item(W.samples_per_item, s_next);
           if ((kFork && st.sealed()) || item_done) need_item = true;
           else have_path = true;
           if constexpr (kFork)
@@ -1600,16 +1403,11 @@ __device__ __forceinline__ void path_queue_body(const DeviceScene& S, const Work
         DRng g = item_rng;
         if (!fresh_rng)
           g = DRng{uint64_t(rng_words.x) | (uint64_t(rng_words.y) << 32), uint64_t(rng_words.z) | (uint64_t(rng_words.w) << 32)};
-        const float lx = rng_nextf(g);  // g++ argument order: lens sample first, then pixel jitter
-        const float ly = rng_nextf(g);
-        const float jx = rng_nextf(g);
-        const float jy = rng_nextf(g);
-        cg4[0] = make_uint4(uint32_t(g.s0), uint32_t(g.s0 >> 32), uint32_t(g.s1), uint32_t(g.s1 >> 32));
-        if constexpr (kBigDim) ctx_global(id)[6] = S.tables.kind == 2 ? 2u : 0u;  // start_next_sample: dimension = 0 (HaltonSampler: 2)
         const int px = int(pxy & 0xffffu), py = int(pxy >> 16);
         const DCamera cam = kS(cam);
-        const f2 pf{(float(px) + jx) / float(cam.W), (float(py) + jy) / float(cam.H)};
-        const DRay r = camera_gen_ray(cam, pf, f2{lx, ly});
+        const DRay r = camera_sample(cam, px, py, g);
+        cg4[0] = make_uint4(uint32_t(g.s0), uint32_t(g.s0 >> 32), uint32_t(g.s1), uint32_t(g.s1 >> 32));
+        if constexpr (kBigDim) ctx_global(id)[6] = S.tables.kind == 2 ? 2u : 0u;  // start_next_sample: dimension = 0 (HaltonSampler: 2)
         PackedState st{0};
         st.start_sample(s_next);
         if constexpr (kFork)
