@@ -436,6 +436,26 @@ typedef int (*pine_gpu_pass_callback)(void* user, int pass, int pass_count, cons
 int pine_gpu_path_render_passes(pine_gpu_scene*, const pine_gpu_render_params*, int32_t pass_samples, float* film_out_host,
                                 pine_gpu_pass_callback cb, void* user);
 
+/* ---- AOIntegrator ---------------------------------------------------------------------------
+ * AOIntegrator(Accel, Sampler) + render(Scene&): src/pine/impl/integrator/ao.h, ao.cpp, RayIntegrator::render
+ * (src/pine/core/integrator.cpp:83-100), registered program_context.cpp:58-61.  Ambient occlusion: per camera sample one closest-hit
+ * ray and, where it hits, eight any-hit rays of length radius = min_value(scene.get_aabb().diagonal()) / 2 around one random frame;
+ * the sample is the fraction of them that met nothing.  Materials, lights and emissive shapes play no part.  The integrator renders
+ * max(sampler.spp() / 8, 1) samples per pixel (the sampler keeps its own count: tables, index stride); the film is the reference's
+ * bit for bit with Accel = BVH() -- AOIntegrator(BVH(), sampler).  EmbreeAccel answers the eight rays with Embree's PACKET traversal
+ * (rtcOccluded8), which nothing here restates: PINE_GPU_FLAG_ORDER_EMBREE is refused.
+ * prm: spp / sampler / device / shard_rank / shard_world / PINE_GPU_FLAG_TIMING as for PathIntegrator; max_path_length and
+ * samples_per_item are ignored; PINE_GPU_FLAG_FAST, _ORDER_EMBREE, _VERTEX_LOG and _SPECIALIZE are refused.
+ * An AO plan works with pine_gpu_plan_launch (pixels outside the shard are zeros), _stats_get (camera_samples; spp_effective = the
+ * AO count; vertices = primary hits; shadow_rays = any-hit queries = 8 x vertices; trace_ms, grid_blocks, block_threads, lds_bytes),
+ * _check and _destroy; the packed launch, the vertex log and read_samples fail with a message.  Two schedules of the same arithmetic
+ * give the same film: $PINE_GPU_AO_KERNEL=serial (the default: lane = sample, a loop over its eight rays) and =regroup (the wave's
+ * hit points compacted, eight records x eight rays per trip); DESIGN.md 4.11 has the measurements behind the default. */
+int pine_gpu_ao_render(pine_gpu_scene*, const pine_gpu_render_params*, float* film_out_host);
+pine_gpu_plan* pine_gpu_ao_plan_create(pine_gpu_scene*, const pine_gpu_render_params*);
+/* radius, then directions[8] (ao.cpp:6-9) as xyz: host only, no GPU */
+int pine_gpu_ao_constants(pine_gpu_scene*, float out[25]);
+
 /* Host test hook: the reference's partition (src/psl/algorithm.h:394-402) as its sequential swap loop and as the data-parallel
  * formulation of the device BVH build; both permutations out, < 0 if they disagree. */
 int pine_gpu_test_lomuto(const unsigned char* pred, int n, int* perm_sequential, int* perm_parallel);

@@ -176,6 +176,9 @@ SIGNATURES = {
     "pine_gpu_plan_device_bytes": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "pine_gpu_pass_schedule": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int]),
     "pine_gpu_path_render_passes": (C.c_int, [C.c_void_p, C.POINTER(RenderParams), C.c_int32, c_f_p, PASS_CALLBACK, C.c_void_p]),
+    "pine_gpu_ao_render": (C.c_int, [C.c_void_p, C.POINTER(RenderParams), c_f_p]),
+    "pine_gpu_ao_plan_create": (C.c_void_p, [C.c_void_p, C.POINTER(RenderParams)]),
+    "pine_gpu_ao_constants": (C.c_int, [C.c_void_p, c_f_p]),
     "pine_gpu_plan_debug_sections": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "pine_gpu_plan_vertex_log": (C.c_int64, [C.c_void_p, c_f_p, C.c_int64]),
     "pine_gpu_test_lomuto": (C.c_int, [C.POINTER(C.c_uint8), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),

@@ -569,8 +569,12 @@ class Plan:
     """A PathIntegrator bound to a scene with all device state resident (bench / multi-GPU)."""
 
     def __init__(self, scene, spp, max_path_length, device=0, shard_rank=0, shard_world=1,
-                 samples_per_item=0, timing=False, sampler="blue", flags=0, specialize=None, order="pine", pass_samples=None):
-        """spp: an int (BlueSampler(spp), or SobolSampler(spp) with sampler="sobol") or a sampler object.
+                 samples_per_item=0, timing=False, sampler="blue", flags=0, specialize=None, order="pine", pass_samples=None,
+                 integrator="path"):
+        """integrator: "path" -- PathIntegrator; "ao" -- AOIntegrator(BVH(), sampler) (pine_gpu_ao_plan_create: max_path_length,
+        samples_per_item, specialize and pass_samples do not apply; launch / stats / check work, the packed launch and
+        read_samples raise).
+        spp: an int (BlueSampler(spp), or SobolSampler(spp) with sampler="sobol") or a sampler object.
         specialize: None -- the library's default: the scene's own kernel from the cache, else compiled in the background
         while the precompiled kernel renders; True -- PINE_GPU_FLAG_SPECIALIZE: wait for the compiler at plan creation, fail if
         the kernel cannot be built; False -- PINE_GPU_FLAG_NO_SPECIALIZE: precompiled kernels only (stats().specialized tells).
@@ -589,7 +593,15 @@ class Plan:
         self.params = _lib.RenderParams(int(spp), int(max_path_length), int(device), int(shard_rank),
                                         int(shard_world), int(samples_per_item),
                                         (_lib.FLAG_TIMING if timing else 0) | int(flags), kind)
-        if pass_samples is None:
+        if integrator not in ("path", "ao"):
+            raise PineError(f"unknown integrator {integrator!r} (path | ao)")
+        if integrator == "ao":
+            if pass_samples is not None:
+                raise PineError("AOIntegrator: a plan with passes is not available")
+            h = lib.pine_gpu_ao_plan_create(scene._h, C.byref(self.params))
+            if not h:
+                raise PineError("AOIntegrator: " + _lib.last_error())
+        elif pass_samples is None:
             h = lib.pine_gpu_plan_create(scene._h, C.byref(self.params))
         else:
             h = lib.pine_gpu_plan_create_passes(scene._h, C.byref(self.params), int(pass_samples))
@@ -722,5 +734,42 @@ class PathIntegrator:
             film.pixels = out
             return film
         check(lib.pine_gpu_path_render(scene._h, C.byref(prm), out.ctypes.data_as(_lib.c_f_p)), "PathIntegrator.render")
+        film.pixels = out
+        return film
+
+
+# ---- AOIntegrator (program_context.cpp:58-61, src/pine/impl/integrator/ao.h, ao.cpp) ---------------
+def ao_constants(scene):
+    """(radius, directions[8]) of an AOIntegrator render of `scene`, computed on the host (pine_gpu_ao_constants)."""
+    out = np.zeros(25, dtype=np.float32)
+    check(lib.pine_gpu_ao_constants(scene._h, out.ctypes.data_as(_lib.c_f_p)), "AOIntegrator")
+    return out[0], out[1:].reshape(8, 3)
+
+
+class AOIntegrator:
+    """AOIntegrator(BVH(), sampler).render(scene): ambient occlusion -- per camera sample the fraction of eight rays of
+    length min_value(scene.get_aabb().diagonal()) / 2 around the hit point that meet nothing.  The integrator renders
+    max(sampler.spp() / 8, 1) samples per pixel (ao.cpp:13); the sampler keeps its own count.  Materials and lights play no
+    part.  pine-BVH order only: the reference's EmbreeAccel answers the eight rays with Embree's packet traversal, which is
+    not restated."""
+
+    def __init__(self, sampler, device=0, flags=0, order="pine"):
+        if _order_flags(order):
+            raise PineError("AOIntegrator renders in pine-BVH order only: AOIntegrator(BVH(), sampler) "
+                            "(EmbreeAccel's hit8 is Embree's packet traversal, not restated)")
+        self.sampler, self.device, self.flags = sampler, device, int(flags)
+
+    @property
+    def spp(self):
+        """The AO sample count: max(sampler.spp() / 8, 1)."""
+        return max(self.sampler.spp() // 8, 1)
+
+    def render(self, scene):
+        if scene.camera is None:
+            raise PineError("scene has no camera")
+        film = scene.camera.film()
+        prm = _lib.RenderParams(self.sampler.requested, 1, self.device, 0, 1, 0, self.flags, getattr(self.sampler, "kind", 0))
+        out = np.zeros((film.size[1], film.size[0], 4), dtype=np.float32)
+        check(lib.pine_gpu_ao_render(scene._h, C.byref(prm), out.ctypes.data_as(_lib.c_f_p)), "AOIntegrator.render")
         film.pixels = out
         return film

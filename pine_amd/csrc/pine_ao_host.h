@@ -1,0 +1,249 @@
+// pine_amd/csrc/pine_ao_host.h -- the host side of AOIntegrator plans (kernels: pine_ao_kernel.h).  Included by
+// pine_kernels.hip after plan_build's phases, which an AO plan shares: check_params, assemble_scene, upload_sampler_tables,
+// scene_features, the work decomposition's fields, the RNG checkpoint prepass.  An AO plan is a pine_gpu_plan with `ao`
+// set: pine_gpu_plan_launch / _stats_get / _check / _destroy take it as they take any plan.
+
+// The AO sample count (ao.cpp:13) of a sampler whose own count is `sampler_spp`.
+static int ao_effective_spp(int sampler_spp) { return std::max(sampler_spp / 8, 1); }
+
+static int ao_plan_build(pine_gpu_plan* p, pine_gpu_scene* scene, const pine_gpu_render_params* prm_in) {
+  SceneHost& H = scene_host(scene);
+  if (prm_in->flags & (PINE_GPU_FLAG_FAST | PINE_GPU_FLAG_ORDER_EMBREE | PINE_GPU_FLAG_VERTEX_LOG | PINE_GPU_FLAG_SPECIALIZE)) {
+    set_error((prm_in->flags & PINE_GPU_FLAG_ORDER_EMBREE)
+                  ? "AOIntegrator renders in pine-BVH order only, AOIntegrator(BVH(), sampler): EmbreeAccel answers hit8 with Embree's packet "
+                    "traversal, which is not restated (PINE_GPU_FLAG_ORDER_EMBREE refused)"
+                  : "AOIntegrator: PINE_GPU_FLAG_FAST / _VERTEX_LOG / _SPECIALIZE are not available (exact arithmetic, precompiled kernels only)");
+    return -1;
+  }
+  pine_gpu_render_params prm = *prm_in;
+  prm.max_path_length = 1;  // (ignored by AOIntegrator; check_params wants a valid one)
+  prm.samples_per_item = 0;
+  const int sampler_spp = check_params(H, &prm);
+  if (sampler_spp < 0) return -1;
+  const int spp = ao_effective_spp(sampler_spp);
+  TableBlob tables_blob;
+  if (load_tables(tables_blob)) return -1;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+    set_error("no HIP device available: the AOIntegrator hot path requires an AMD GPU (no CPU fallback)");
+    return -1;
+  }
+  HIP_OK(hipSetDevice(prm.device));
+  p->ao = true;
+  p->device = prm.device;
+  p->params = prm;
+  const size_t tally0 = g_alloc_tally;
+  const auto t_build0 = std::chrono::steady_clock::now();
+  if (!H.accel.built) {
+    H.build_on_device = (prm.flags & PINE_GPU_FLAG_DEVICE_BVH) ? prm.device : -1;
+    H.build_accel();
+  }
+  const auto t_build1 = std::chrono::steady_clock::now();
+  p->accel_build_ms = std::chrono::duration<float, std::milli>(t_build1 - t_build0).count();
+  p->accel_on_device = H.built_on_device;
+
+  SceneParts sp;
+  // (the sampler keeps its ORIGINAL count -- BlueSampler's table, SobolSampler's index stride -- only fewer indices are drawn)
+  if (assemble_scene(p, H, &prm, sp) || upload_sampler_tables(p, *tables_blob, &prm, sampler_spp)) return -1;
+  p->S.spp = spp;
+  if (pine_gpu_ao_constants(scene, &p->ao_params.radius)) return -1;
+  static_assert(offsetof(AoParams, dir) == sizeof(float) && sizeof(AoParams) == 26 * sizeof(float), "radius, then directions[8]");
+  p->ao_params.spp = spp;
+
+  // the kernel: the first variant that covers the scene's shape kinds and sampler, in the schedule $PINE_GPU_AO_KERNEL names
+  // (serial, the default: lane = sample; regroup: the wave's occlusion rays regrouped); $PINE_GPU_AO_VARIANT=<index> considers that variant only (tests)
+  const unsigned need = scene_features(sp, &prm) & (kFAoShapes | F_SOBOL);
+  const bool lds_ok = size_t(p->S.blob_bytes) <= 32 * 1024;
+  int count = 0;
+  const PineAoVariant* table = pine_gpu_ao_variants(&count);
+  const char* pin = getenv("PINE_GPU_AO_VARIANT");
+  for (int i = 0; i < count && p->ao_variant < 0; i++) {
+    if (pin && *pin && atoi(pin) != i) continue;
+    const unsigned F = table[i].features;
+    if ((need & ~F) == 0 && (!(F & F_LDS_SCENE) || lds_ok)) p->ao_variant = i;
+  }
+  if (p->ao_variant < 0) {
+    set_error(pin && *pin ? "$PINE_GPU_AO_VARIANT names no AO kernel variant that covers this scene" : "no AO kernel variant covers this scene");
+    return -1;
+  }
+  p->ao_serial = true;  // (the faster of the two on two of the three measured scenes: DESIGN.md 4.11, profiles/ao_speed.txt)
+  if (const char* e = getenv("PINE_GPU_AO_KERNEL")) {
+    if (!strcmp(e, "regroup")) p->ao_serial = false;
+    else if (*e && strcmp(e, "serial")) {
+      set_error("$PINE_GPU_AO_KERNEL is `serial` or `regroup`");
+      return -1;
+    }
+  }
+  const PathKernel kernel = plan_kernel(p);
+  p->lds_bytes = size_t(ao_off_stack(!p->ao_serial)) * 4 + size_t(p->S.stack_total) * kBlock * sizeof(int) +
+                 ((kernel.features & F_LDS_SCENE) ? size_t(p->S.blob_bytes) : 0);
+  if (p->lds_bytes > 160 * 1024) {
+    set_error("AOIntegrator: the traversal stack of this scene does not fit LDS");
+    return -1;
+  }
+  HIP_OK(hipFuncSetAttribute(kernel.fn, hipFuncAttributeMaxDynamicSharedMemorySize, int(p->lds_bytes)));
+
+  // work items: [local tile][chunk of k samples][pixel in tile]; k the largest power of two dividing the AO count that
+  // still leaves 2^20 items (a lane walks its k samples in sequence; the chunks start from RNG checkpoints)
+  WorkParams& W = p->W;
+  p->film_w = H.camera.W, p->film_h = H.camera.H;
+  if (p->film_w > 65535 || p->film_h > 65535) {
+    set_error("film sides above 65535 are not supported");
+    return -1;
+  }
+  W.tiles_x = (p->film_w + kTile - 1) / kTile, W.tiles_y = (p->film_h + kTile - 1) / kTile;
+  W.shard_rank = prm.shard_rank, W.shard_world = prm.shard_world;
+  W.num_local_tiles = (W.tiles_x * W.tiles_y - prm.shard_rank + prm.shard_world - 1) / prm.shard_world;
+  int k = 1;
+  while (spp % (2 * k) == 0 && (unsigned long long)W.num_local_tiles * 64ull * unsigned(spp / (2 * k)) >= (1ull << 20)) k *= 2;
+  W.samples_per_item = k;
+  W.items_per_pixel = spp / k;
+  W.log2_items_per_pixel = 0;
+  while ((1 << W.log2_items_per_pixel) < W.items_per_pixel) W.log2_items_per_pixel++;
+  W.tiles_x_magic = unsigned(((1ull << 32) + unsigned(W.tiles_x) - 1) / unsigned(W.tiles_x));
+  W.total_items = (unsigned long long)W.num_local_tiles * unsigned(W.items_per_pixel) * 64ull;
+  if (W.total_items >= (1ull << 32)) {  // (decode_item's tile-and-chunk number is 32 bits less the pixel's six)
+    set_error("film pixels x AO samples per pixel of one shard must stay below 2^32 (render in several shards)");
+    return -1;
+  }
+  W.tile_order = nullptr;
+  W.serial_tiles = 0;
+  W.pass_first_chunk = 0;
+  W.pass_chunks = W.items_per_pixel;
+  W.pass_chunks_magic = W.pass_chunks > 1 ? unsigned(((1ull << 32) + unsigned(W.pass_chunks) - 1) / unsigned(W.pass_chunks)) : 0u;
+  W.pass_row_stride = spp;
+  W.free_tile_base = 0;
+  W.pass_first_serial_tile = 0;
+  W.debug_force_bail = (prm.flags & PINE_GPU_FLAG_DEBUG_FORCE_BAIL) ? 1 : 0;
+  W.progress = nullptr;
+  W.vertex_log = nullptr;
+  p->pass_plan = PassPlan();
+  p->pass_plan.free_tiles = W.num_local_tiles;
+  if (prm.flags & PINE_GPU_FLAG_PROGRESS) {
+    HIP_OK(hipHostMalloc((void**)&p->h_progress, sizeof(unsigned long long), hipHostMallocMapped));
+    *p->h_progress = 0;
+    HIP_OK(hipHostGetDevicePointer((void**)&W.progress, p->h_progress, 0));
+  }
+  hipDeviceProp_t prop;
+  HIP_OK(hipGetDeviceProperties(&prop, prm.device));
+  int blocks_per_cu = 0;
+  HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, kernel.fn, kBlock, p->lds_bytes));
+  blocks_per_cu = std::min(std::max(blocks_per_cu, 1), 8);
+  p->grid = int(std::min<unsigned long long>((W.total_items + kBlock - 1) / kBlock, (unsigned long long)prop.multiProcessorCount * blocks_per_cu));
+  if (p->grid < 1) p->grid = 1;
+  if (W.items_per_pixel > 1) {
+    p->bytes_ckpt = W.total_items * sizeof(ulonglong2);
+    HIP_OK(POOL_ALLOC(p->d_ckpt, p->bytes_ckpt));
+  }
+  HIP_OK(POOL_ALLOC(p->d_ao_counts, size_t(p->film_w) * p->film_h * sizeof(unsigned)));
+  HIP_OK(POOL_ALLOC(p->d_counters, sizeof(Counters)));
+  p->timed = (prm.flags & PINE_GPU_FLAG_TIMING) != 0;
+  if (p->timed)
+    for (auto& slot : p->ev)
+      for (auto& e : slot) HIP_OK(hipEventCreate(&e));
+  p->bytes_total = g_alloc_tally - tally0;
+  HIP_OK(hipDeviceSynchronize());
+  p->upload_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_build1).count();
+  return 0;
+}
+
+// One AO render into film_dev: counters cleared, checkpoint prepass (first launch), the AO kernel, the film from the counts.
+static int ao_launch(pine_gpu_plan* p, void* film_dev, hipStream_t stream) {
+  HIP_OK(hipSetDevice(p->device));
+  (void)hipGetLastError();
+  g_progress.store(0.0f);
+  WorkParams& W = p->W;
+  const size_t pixels = size_t(p->film_w) * p->film_h;
+  if (W.shard_world > 1) HIP_OK(hipMemsetAsync(film_dev, 0, pixels * sizeof(float4), stream));
+  HIP_OK(hipMemsetAsync(p->d_counters, 0, sizeof(Counters), stream));
+  HIP_OK(hipMemsetAsync(p->d_ao_counts, 0, pixels * sizeof(unsigned), stream));
+  hipEvent_t* ev = p->ev[p->launch_count % pine_gpu_plan::kEvRing];
+  if (p->timed) HIP_OK(hipEventRecord(ev[0], stream));
+  const bool has_work = W.total_items > 0;
+  if (has_work && W.items_per_pixel > 1) {
+    if (!p->ckpt_valid) {
+      const unsigned long long n = (unsigned long long)W.num_local_tiles * 64ull;
+      hipLaunchKernelGGL(rng_checkpoint_kernel, dim3(unsigned((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, W, p->film_w, p->film_h, p->S.spp,
+                         p->d_ckpt, W.num_local_tiles, (ulonglong2*)nullptr);
+      if (!p->ckpt_done) HIP_OK(hipEventCreateWithFlags(&p->ckpt_done, hipEventDisableTiming));
+      HIP_OK(hipEventRecord(p->ckpt_done, stream));
+      p->ckpt_stream = stream;
+      p->ckpt_valid = true;
+    } else if (stream != p->ckpt_stream) {
+      HIP_OK(hipStreamWaitEvent(stream, p->ckpt_done, 0));
+    }
+  }
+  if (p->timed) HIP_OK(hipEventRecord(ev[1], stream));
+  if (has_work) {
+    const PathKernel kernel = plan_kernel(p);
+    const ulonglong2* ckpt = p->d_ckpt;
+    void* args[] = {&p->S, &W, &p->ao_params, &ckpt, &p->d_ao_counts, &p->d_counters};
+    HIP_OK(hipLaunchKernel(kernel.fn, dim3(p->grid), dim3(kBlock), args, p->lds_bytes, stream));
+  }
+  if (p->timed) HIP_OK(hipEventRecord(ev[2], stream));
+  if (W.num_local_tiles > 0) {
+    const unsigned long long n = (unsigned long long)W.num_local_tiles * 64ull;
+    hipLaunchKernelGGL(ao_film_kernel, dim3(unsigned((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, W, p->film_w, p->film_h, p->S.spp,
+                       (const unsigned*)p->d_ao_counts, (float4*)film_dev);
+  }
+  if (p->timed) HIP_OK(hipEventRecord(ev[3], stream));
+  HIP_OK(hipGetLastError());
+  p->launched = true;
+  p->launch_count++;
+  p->last_stream = stream;
+  return 0;
+}
+
+pine_gpu_plan* pine_gpu_ao_plan_create(pine_gpu_scene* scene, const pine_gpu_render_params* prm) {
+  if (!scene || !prm) {
+    set_error("null argument");
+    return nullptr;
+  }
+  pine_gpu_plan* p = new pine_gpu_plan();
+  if (ao_plan_build(p, scene, prm)) {
+    std::string keep = pine_gpu_last_error();
+    pine_gpu_plan_destroy(p);
+    set_error(keep);
+    return nullptr;
+  }
+  return p;
+}
+
+// AOIntegrator(BVH(), sampler).render(scene) in one call: upload, launch, download.  Fails if there is no GPU.
+int pine_gpu_ao_render(pine_gpu_scene* scene, const pine_gpu_render_params* prm, float* film_out) {
+  if (!scene || !prm || !film_out) {
+    set_error("null argument");
+    return -1;
+  }
+  pine_gpu_render_params prm2 = *prm;
+  prm2.flags |= PINE_GPU_FLAG_PROGRESS;
+  pine_gpu_plan* p = pine_gpu_ao_plan_create(scene, &prm2);
+  if (!p) return -1;
+  int rc = -1;
+  void* d_film = nullptr;
+  const size_t bytes = size_t(p->film_w) * p->film_h * 16;
+  do {
+    if (DevicePool::get().alloc(&d_film, bytes) != hipSuccess) {
+      set_error("hipMalloc(film) failed");
+      break;
+    }
+    g_progress_total.store(p->W.total_items);
+    g_progress_base.store(0);
+    g_progress_src.store(p->h_progress);
+    if (pine_gpu_plan_launch(p, d_film, nullptr)) break;
+    if (hipMemcpy(film_out, d_film, bytes, hipMemcpyDeviceToHost) != hipSuccess) {
+      set_error("film download failed");
+      break;
+    }
+    if (pine_gpu_plan_check(p)) break;  // (a launch that gave up leaves an incomplete film: fail)
+    rc = 0;
+  } while (0);
+  g_progress_src.store(nullptr);
+  g_progress.store(rc == 0 ? 1.0f : 0.0f);
+  std::string keep = rc < 0 ? pine_gpu_last_error() : "";
+  if (rc < 0) (void)hipDeviceSynchronize();
+  DevicePool::get().free(d_film);
+  pine_gpu_plan_destroy(p);
+  if (rc < 0) set_error(keep);
+  return rc;
+}

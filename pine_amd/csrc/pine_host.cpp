@@ -1587,6 +1587,47 @@ int pine_gpu_scene_build_accel_device(pine_gpu_scene* s, int device) {
   }
   return int(s->host.accel.nodes.size());
 }
+/* AOIntegrator's host-side constants (ao.h:12, ao.cpp:6-9): radius = min_value(scene.get_aabb().diagonal()) / 2 -- Scene::get_aabb
+ * (scene.cpp:55-62) extends over the geometries' own boxes, a Plane's +-100 one included, a Mesh's over the vertices its
+ * triangles use (geometry.cpp:647-651) -- then directions[8] = uniform_sphere of eight constant pairs, which the reference's
+ * static initialisation evaluates with the host libm (here: the restated sinf / cosf, bit-equal to glibc's). */
+// uniform_sphere (sampling.h:44-50) -- the operations of the device's (pine_device.h, which a plain C++ build of this file cannot include)
+static f3 ao_uniform_sphere(float ux, float uy) {
+  const float phi = ux * kPi * 2;
+  const float cos_theta = 1 - 2 * uy;
+  const float sin_theta = psqrt(1.0f - sqr(cos_theta));
+  float sn, cs;
+  psincos(phi, sn, cs);
+  return f3{sin_theta * cs, sin_theta * sn, cos_theta};
+}
+int pine_gpu_ao_constants(pine_gpu_scene* s, float out[25]) {
+  if (!check(s)) return -1;
+  if (!out) {
+    set_error("null argument");
+    return -1;
+  }
+  const SceneHost& H = s->host;
+  HostAABB box;
+  for (size_t gi = 0; gi < H.geometries.size(); gi++) {
+    if (H.geometries[gi].shape.kind == SHAPE_MESH) {
+      const HostMesh& m = H.meshes[size_t(H.geometries[gi].mesh)];
+      HostAABB mb;
+      for (uint32_t vi : m.indices) mb.extend(ld3(&m.vertices[3 * size_t(vi)]));
+      box.extend(mb);
+    } else {
+      box.extend(H.geometry_aabb(int(gi)));
+    }
+  }
+  const f3 d = box.upper - box.lower;
+  out[0] = pmin(pmin(d.x, d.y), d.z) / 2;
+  static const float kPairs[8][2] = {{0.0f, 0.25f}, {0.25f, 0.25f}, {0.5f, 0.25f}, {0.75f, 0.25f},
+                                     {0.0f, 0.75f}, {0.25f, 0.75f}, {0.5f, 0.75f}, {0.75f, 0.75f}};
+  for (int i = 0; i < 8; i++) {
+    const f3 v = ao_uniform_sphere(kPairs[i][0], kPairs[i][1]);
+    out[1 + 3 * i] = v.x, out[2 + 3 * i] = v.y, out[3 + 3 * i] = v.z;
+  }
+  return 0;
+}
 int64_t pine_gpu_scene_accel_dump(pine_gpu_scene* s, void* nodes_out, int64_t node_cap, int32_t* prims_out,
                                   int64_t prim_cap) {
   if (!check(s)) return -1;

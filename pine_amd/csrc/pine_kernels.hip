@@ -643,6 +643,7 @@ void pine_gpu_plan_destroy(pine_gpu_plan* p) {
   DevicePool::get().free(p->d_rng_carry);
   DevicePool::get().free(p->d_fold);
   DevicePool::get().free(p->d_counters);
+  DevicePool::get().free(p->d_ao_counts);
   p->spec_loaded.reset();  // (the module stays loaded while the process-wide table or another plan holds it)
   if (p->h_progress) (void)hipHostFree(p->h_progress);
   for (auto& slot : p->ev)
@@ -746,6 +747,11 @@ struct PathKernel {
 };
 static_assert(kQBlock != kBlock, "PathKernel::queued tells the two kernels apart by their workgroup size");
 static PathKernel plan_kernel(const pine_gpu_plan* p) {
+  if (p->ao) {
+    int n = 0;
+    const PineAoVariant& V = pine_gpu_ao_variants(&n)[p->ao_variant];
+    return {p->ao_serial ? V.serial : V.regrouped, V.features, kBlock, kBlock};
+  }
   if (p->fast) return {p->fast->fn, p->fast->features, p->fast->ctx, kQBlock};
   if (p->queue_variant >= 0) {
     const PineKernelVariant& V = kQueueVariants[p->queue_variant];
@@ -1532,6 +1538,8 @@ pine_gpu_plan* pine_gpu_plan_create_passes(pine_gpu_scene* scene, const pine_gpu
   return plan_create(scene, prm, pass_samples);
 }
 
+#include "pine_ao_host.h"  // AOIntegrator plans: ao_plan_build, ao_launch and the three pine_gpu_ao_* entry points
+
 // The path kernel of the plan -- the scene's own, or the precompiled one -- over the work decomposition W, its samples going
 // to `samples` (+ sample index * 64, decode_item).
 static int launch_path_kernel(pine_gpu_plan* p, WorkParams& W, float4* samples, int grid, hipStream_t stream) {
@@ -1556,6 +1564,7 @@ static int plan_launch_pass(pine_gpu_plan* p, int j, void* film_dev, hipStream_t
               (p->next_pass > 0 && p->next_pass < PP.n ? " (or 0, which starts the film afresh)" : "") + " is next; nothing was launched");
     return -1;
   }
+  if (p->ao) return packed ? (set_error("an AOIntegrator plan has no packed launch"), -1) : ao_launch(p, film_dev, stream);
   HIP_OK(hipSetDevice(p->device));
   (void)hipGetLastError();  // (HIP's last error is sticky: what the check at the end reports must come from THIS launch's calls)
   // a background build that has finished: this launch and every later one run the scene's own kernel -- between two passes
@@ -1829,6 +1838,10 @@ int64_t pine_gpu_plan_vertex_log(pine_gpu_plan* p, float* out, int64_t capacity)
     set_error("null argument");
     return -1;
   }
+  if (p->ao) {
+    set_error("an AOIntegrator plan has no per-vertex log");
+    return -1;
+  }
   if (p->queue_variant < 0 || !(kQueueVariants[p->queue_variant].features & F_VLOG)) {
     set_error("the per-vertex log needs a plan created with PINE_GPU_FLAG_VERTEX_LOG (stage-queued kernel, the two variants compiled with the hook)");
     return -1;
@@ -1861,6 +1874,10 @@ int64_t pine_gpu_plan_vertex_log(pine_gpu_plan* p, float* out, int64_t capacity)
 int pine_gpu_plan_read_samples(pine_gpu_plan* p, float* out, int64_t capacity) {
   if (!p || !out) {
     set_error("null argument");
+    return -1;
+  }
+  if (p->ao) {
+    set_error("an AOIntegrator plan keeps no per-sample rows (its film is a count per pixel)");
     return -1;
   }
   if (p->pass_plan.n > 1) {

@@ -26,6 +26,7 @@ namespace pine_gpu {
 SceneHost& scene_host(pine_gpu_scene* s);
 }  // namespace pine_gpu
 #include "pine_kernels_device.h"
+#include "pine_ao_kernel.h"
 namespace pine_gpu {
 
 #define HIP_OK(expr)                                                                          \
@@ -290,4 +291,10 @@ struct pine_gpu_plan {
   std::shared_ptr<SpecJob> spec_job;
   std::string spec_async_error;
   float specialize_ms = 0.0f;
+  // An AOIntegrator plan (pine_gpu_ao_plan_create, pine_ao_host.h): S.spp is the AO sample count, the kernel one of
+  // pine_gpu_ao_variants() in the schedule `ao_serial` selects; per film pixel one counter of unoccluded rays.
+  bool ao = false, ao_serial = false;
+  int ao_variant = -1;
+  AoParams ao_params{};
+  unsigned* d_ao_counts = nullptr;
 };

@@ -2,7 +2,7 @@
 //
 // Keeps the names a pine user writes (src/pine/core/program_context.cpp:23-125 and the *_context
 // functions): Scene / add / set, Diffuse, Emissive, Uber, Subsurface, Rect, Box, Sphere, Disk, Cone,
-// Mesh, Film, Uncharted2, ThinLenCamera, BlueSampler, PathIntegrator(sampler, depth).render(scene),
+// Mesh, Film, Uncharted2, ThinLenCamera, BlueSampler, PathIntegrator(sampler, depth).render(scene), AOIntegrator(sampler).render(scene),
 // scene.camera.film().save(...).  Header-only; link with -lpine_gpu.  Errors throw pine::Error where
 // the reference would SEVERE()/abort (src/pine/core/log.h:45-51).
 #pragma once
@@ -285,6 +285,29 @@ class PathIntegrator {
   int max_path_length_, device_;
   int flags_ = 0;
   std::vector<int> devices_;
+};
+
+// AOIntegrator(sampler).render(scene): ambient occlusion (src/pine/impl/integrator/ao.h, ao.cpp) -- what the reference's
+// AOIntegrator(BVH(), sampler) renders, bit for bit: max(sampler.spp() / 8, 1) samples per pixel, each the fraction of eight rays
+// of length min_value(scene.get_aabb().diagonal()) / 2 around the hit point that meet nothing.  Materials and lights play no
+// part.  (pine-BVH order only: EmbreeAccel's hit8 is Embree's packet traversal, which is not reproduced.)
+class AOIntegrator {
+ public:
+  explicit AOIntegrator(Sampler sampler, int device = 0) : sampler_(sampler), device_(device) {}
+  void render(Scene& scene) {
+    pine_gpu_render_params p{};
+    p.spp = sampler_.requested;
+    p.max_path_length = 1;
+    p.device = device_;
+    p.shard_rank = 0;
+    p.shard_world = 1;
+    p.sampler = sampler_.kind;
+    check(pine_gpu_ao_render(scene.handle(), &p, scene.camera.film_.pixels.data()), "AOIntegrator::render");
+  }
+
+ private:
+  Sampler sampler_;
+  int device_;
 };
 
 inline float get_progress() { return pine_gpu_progress(); }

@@ -1989,6 +1989,46 @@ Interp::Interp() {
     in.last_film = f;
     return Value();
   });
+  // AOIntegrator (program_context.cpp:58-61; src/pine/impl/integrator/ao.h, ao.cpp): ambient occlusion.  Its eight occlusion rays
+  // go through Accel::hit8, which EmbreeAccel answers with Embree's PACKET traversal (rtcOccluded8) -- another traverser than the
+  // single-ray one PINE_GPU_FLAG_ORDER_EMBREE restates, pinned by nothing here.  So only pine's own BVH renders: the one-argument
+  // form (EmbreeAccel on real pine, whatever $PINE_PRL_ACCEL says) and Embree() fail and name the form that works.
+  static const char* const kAoNeedsBvh =
+      "`AOIntegrator` renders with pine's own BVH only: write AOIntegrator(BVH(), sampler) -- the one-argument form and Embree() mean "
+      "EmbreeAccel, whose hit8 is Embree's packet traversal (rtcOccluded8), which is not reproduced";
+  r.def("AOIntegrator", {"Accel", "Sampler"}, "AOIntegrator", [](Interp&, std::vector<Cell>& a) {
+    if (a[0]->i[0] != 1) fail(kAoNeedsBvh);
+    auto p = std::make_shared<IntegratorObj>();
+    p->accel = 1;
+    p->spp = a[1]->i[0];
+    p->sampler = a[1]->i[1];
+    return mk_obj("AOIntegrator", p);
+  });
+  r.def("AOIntegrator", {"Sampler"}, "AOIntegrator", [](Interp&, std::vector<Cell>&) -> Value { fail(kAoNeedsBvh); });
+  r.def("render", {"AOIntegrator&", "Scene&"}, "void", [](Interp& in, std::vector<Cell>& a) {
+    auto p = obj<IntegratorObj>(a[0]);
+    auto s = obj<SceneObj>(a[1]);
+    if (!s->camera) fail("AOIntegrator.render: scene has no camera");
+    auto f = obj<CameraObj>(s->camera)->film;
+    if (in.flags & PINE_PRL_DRY_RUN) {
+      in.log(std::string("@render AOIntegrator ") + (p->sampler == PINE_GPU_SAMPLER_SOBOL ? "SobolSampler " : p->sampler == PINE_GPU_SAMPLER_HALTON ? "HaltonSampler " : "BlueSampler ") +
+             std::to_string(p->spp) + "\n");
+      in.log(describe_scene(s->h));
+      in.log("@end\n");
+      return Value();
+    }
+    pine_gpu_render_params prm{};
+    prm.spp = p->spp;
+    prm.max_path_length = 1;
+    prm.device = in.device;
+    prm.shard_rank = 0;
+    prm.shard_world = 1;
+    prm.sampler = p->sampler;
+    f->pixels.assign(size_t(f->w) * f->h * 4, 0.0f);
+    gpu_check(pine_gpu_ao_render(s->h, &prm, f->pixels.data()), "AOIntegrator.render");
+    in.last_film = f;
+    return Value();
+  });
   // quick_render(scene, from, to, filename): 640x480, ThinLenCamera fov 0.5, BlueSampler(4), depth 4, save
   // (program_context.cpp:120-124) -- composed from the functions above
   r.def("quick_render", {"Scene&", "vec3", "vec3", "str"}, "void", [](Interp& in, std::vector<Cell>& a) {
