@@ -4,7 +4,8 @@
 // one random frame -- no materials, no lights, no fold, no recursion.  A sample's value is k / 8, k the rays that met
 // nothing, so a pixel's sum is exact in any order and the kernel counts unoccluded rays per pixel as INTEGERS with plain
 // atomics; ao_film_kernel turns the counts into the film, (count * 0.125f) / spp.  Every building block is the path
-// kernels' (camera_sample, scene_traverse in pine-BVH order, hit_surface, the samplers, spawn_ray): the same bits.
+// kernels' (the prologue of pine_radiance.h -- scene view, LDS staging, sampler slices --, camera_sample, scene_traverse
+// in pine-BVH order, hit_surface, the samplers, spawn_ray): the same bits.
 //
 // Two schedules of the same arithmetic (template parameter REGROUP):
 //   false  lane = camera sample, a loop over its eight occlusion rays ($PINE_GPU_AO_KERNEL=serial, the default: the faster
@@ -51,52 +52,12 @@ __global__ void __launch_bounds__(kBlock) ao_kernel(DeviceScene S, WorkParams W,
   float* const lds_f = reinterpret_cast<float*>(lds_raw);
   uint32_t* const lds_u = reinterpret_cast<uint32_t*>(lds_raw);
   int* const stack = lds_raw + kOffStack + tid;
-  {
-    const uint4* src = reinterpret_cast<const uint4*>(S.tables.sobol);
-    uint4* dst = reinterpret_cast<uint4*>(lds_raw + kAoOffSobol);
-    for (int i = tid; i < kLdsSamplerDims * 256 / 16; i += kBlock) dst[i] = src[i];
-  }
-  DTables T = S.tables;
-  T.lds_sobol = reinterpret_cast<const uint8_t*>(lds_raw + kAoOffSobol);
-  T.lds_tile = lds_u + kAoOffTile + tid;
-  T.lds_scr = lds_u + kAoOffTile + tid + 10 * kLdsLaneStride;
-  T.tile_stride = kLdsLaneStride;
-  T.win_lo = 0;
-  T.win_len = kLdsSamplerDims;
+  stage_sobol_rows(lds_raw + kAoOffSobol, S.tables, tid, kBlock);
+  const DTables T = lane_tables(S.tables, lds_raw + kAoOffSobol, lds_u + kAoOffTile, tid);
   SceneView V;
-  V.tri_verts = S.tri_verts;
-  V.tri_leaf = S.tri_leaf;
-  V.tri_attrs = S.tri_attrs;
-  V.lds_nodes = nullptr;
-  V.lds_node_count = 0;
-  V.lds_tri_entries = nullptr;
-  V.lds_tri_verts = nullptr;
-  V.stack_top = S.stack_top;
-  V.num_shapes = S.num_shapes;
-  V.etree_root = S.etree_root;
-  V.num_emesh = 0;
-  V.rcpps = nullptr;
-  if constexpr (F & F_LDS_SCENE) {
-    uint4* dst = reinterpret_cast<uint4*>(lds_raw + kOffStack + S.stack_total * kBlock);
-    const int n16 = S.blob_bytes >> 4;
-    for (int i = tid; i < n16; i += kBlock) dst[i] = S.blob[i];
-    __syncthreads();
-    const char* base = reinterpret_cast<const char*>(dst);
-    V.nodes = reinterpret_cast<const DNode*>(base + S.off_nodes);
-    view_of_blob(base, S, V);
-  } else {
-    __syncthreads();  // Sobol rows staged above
-    V.etree = nullptr;
-    V.emesh = nullptr;
-    V.leaf = S.leaf;
-    V.nodes = S.nodes;
-    V.shapes = S.shapes;
-    V.materials = S.materials;
-    V.bvhs = S.bvhs;
-    V.prims = nullptr;
-    V.lights = S.lights;
-    V.node_ops = S.node_ops;
-  }
+  if constexpr (F & F_LDS_SCENE) V = scene_view_staged(S, reinterpret_cast<uint4*>(lds_raw + kOffStack + S.stack_total * kBlock), tid, kBlock);
+  else V = scene_view_global(S);
+  __syncthreads();  // Sobol rows (and the scene) staged above
   const int film_w = S.cam.W;
   const int kspi = W.samples_per_item;
   const f3 my_dir = ld3(A.dir + 3 * int(lane & 7u));  // REGROUP: this lane's entry of directions[8]
@@ -121,18 +82,7 @@ __global__ void __launch_bounds__(kBlock) ao_kernel(DeviceScene S, WorkParams W,
     }
     DRng g{0, 0};
     if (valid) {
-      // this lane's sampler slice: 40 ranking bytes + 8 scrambling bytes of the pixel
-      const int pix = (it.px & 127) + (it.py & 127) * 128;
-      const uint2* rsrc = reinterpret_cast<const uint2*>(S.tables.rank + size_t(pix) * 8);
-      const uint2 sc = *reinterpret_cast<const uint2*>(S.tables.scramble + size_t(pix) * 8);
-#pragma unroll
-      for (int j = 0; j < 5; j++) {
-        const uint2 r = rsrc[j];
-        lds_u[kAoOffTile + (2 * j) * kBlock + tid] = r.x;
-        lds_u[kAoOffTile + (2 * j + 1) * kBlock + tid] = r.y;
-      }
-      lds_u[kAoOffTile + 10 * kBlock + tid] = sc.x;
-      lds_u[kAoOffTile + 11 * kBlock + tid] = sc.y;
+      load_lane_slice(S.tables, it.px, it.py, lds_u + kAoOffTile, tid);
       // radiance() draws nothing from the pixel's RNG: the state at sample s is the seed advanced 4 s steps (checkpoints)
       if (W.items_per_pixel == 1) {
         g = rng_seed(hash_pixel(it.px, it.py, 0));

@@ -1,8 +1,8 @@
 // pine_amd/csrc/pine_kernels_device.h -- the device side of the PathIntegrator hot path: types shared by host and
 // kernels (DeviceScene, WorkParams, Counters, PackedState), BVH traversal, the lane-owns-a-path kernel and -- through
 // pine_trav.h / pine_queue_kernel.h -- the stage-queued kernel.  What a path vertex computes (surface, emission, lobe
-// choice, next-event estimation, fold) is written once, in pine_radiance.h; both kernels call it, and that is why their
-// films are the same bits.  Included by pine_kernels.hip (exact arithmetic: the parity build) and by
+// choice, the BSSRDF walk, next-event estimation, fold) is written once, in pine_radiance.h; both kernels call it, and that
+// is why their films are the same bits.  The kernel prologue (scene view, LDS staging, sampler slices) is there too.  Included by pine_kernels.hip (exact arithmetic: the parity build) and by
 // pine_kernels_fast.hip (declared-tolerance arithmetic, under another namespace).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -855,7 +855,7 @@ struct PackedState {
 };
 
 }  // namespace pine_gpu
-#include "pine_radiance.h"  // the per-vertex steps of radiance(): both path kernels run these
+#include "pine_radiance.h"  // the kernel prologue and the per-vertex steps of radiance(): every kernel runs these
 namespace pine_gpu {
 
 template <unsigned F, int WAVES_PER_SIMD>
@@ -868,53 +868,12 @@ path_trace_kernel(DeviceScene S, WorkParams W, const ulonglong2* __restrict__ ck
   float* const lds_f = reinterpret_cast<float*>(lds_raw);
   uint32_t* const lds_u = reinterpret_cast<uint32_t*>(lds_raw);
   int* const stack = lds_raw + kOffStack + tid;
-  {
-    const uint4* src = reinterpret_cast<const uint4*>(S.tables.sobol);
-    uint4* dst = reinterpret_cast<uint4*>(lds_raw + kOffSobol);
-    for (int i = tid; i < kLdsSamplerDims * 256 / 16; i += kBlock) dst[i] = src[i];
-  }
-  DTables T = S.tables;
-  T.lds_sobol = reinterpret_cast<const uint8_t*>(lds_raw + kOffSobol);
-  T.lds_tile = lds_u + kOffTile + tid;
-  T.lds_scr = lds_u + kOffTile + tid + 10 * kLdsLaneStride;
-  T.tile_stride = kLdsLaneStride;
-  T.win_lo = 0;
-  T.win_len = kLdsSamplerDims;
+  stage_sobol_rows(lds_raw + kOffSobol, S.tables, tid, kBlock);
+  const DTables T = lane_tables(S.tables, lds_raw + kOffSobol, lds_u + kOffTile, tid);
   SceneView V;
-  V.tri_verts = S.tri_verts;
-  V.tri_leaf = S.tri_leaf;
-  V.tri_attrs = S.tri_attrs;
-  V.lds_nodes = nullptr;
-  V.lds_node_count = 0;
-  V.lds_tri_entries = nullptr;
-  V.lds_tri_verts = nullptr;
-  V.stack_top = S.stack_top;
-  V.num_shapes = S.num_shapes;
-  V.etree_root = S.etree_root;
-  V.num_emesh = S.num_emesh;
-  V.rcpps = reinterpret_cast<const unsigned*>(reinterpret_cast<const char*>(S.blob) + S.off_rcpps);
-  if constexpr (F & F_LDS_SCENE) {
-    uint4* dst = reinterpret_cast<uint4*>(lds_raw + kOffStack + S.stack_total * kBlock);
-    const int n16 = S.blob_bytes >> 4;
-    for (int i = tid; i < n16; i += kBlock) dst[i] = S.blob[i];
-    __syncthreads();
-    const char* base = reinterpret_cast<const char*>(dst);
-    V.nodes = reinterpret_cast<const DNode*>(base + S.off_nodes);
-    view_of_blob(base, S, V);
-    if (S.off_rcpps < S.blob_bytes) V.rcpps = reinterpret_cast<const unsigned*>(base + S.off_rcpps);
-  } else {
-    __syncthreads();  // Sobol rows staged above
-    V.etree = reinterpret_cast<const EmbreeNode*>(reinterpret_cast<const char*>(S.blob) + S.off_etree);
-    V.emesh = reinterpret_cast<const int*>(reinterpret_cast<const char*>(S.blob) + S.off_emesh);
-    V.leaf = S.leaf;
-    V.nodes = S.nodes;
-    V.shapes = S.shapes;
-    V.materials = S.materials;
-    V.bvhs = S.bvhs;
-    V.prims = nullptr;
-    V.lights = S.lights;
-    V.node_ops = S.node_ops;
-  }
+  if constexpr (F & F_LDS_SCENE) V = scene_view_staged(S, reinterpret_cast<uint4*>(lds_raw + kOffStack + S.stack_total * kBlock), tid, kBlock);
+  else V = scene_view_global(S);
+  __syncthreads();  // Sobol rows (and the scene) staged above
   // Global part of the fold stack: lane-major, one 32-byte entry (two float4) per level, so the
   // bytes a lane touches are only the levels its paths really reach -- the hot set (~2.6 levels x
   // 32 B x resident lanes ~ 22 MB chip-wide, 2.7 MB per XCD) stays in the XCD's 4 MB L2, whereas a
@@ -1020,20 +979,7 @@ path_trace_kernel(DeviceScene S, WorkParams W, const ulonglong2* __restrict__ ck
             pxy = unsigned(it.px) | (unsigned(it.py) << 16);
             st.start_sample(it.chunk * kspi);
             sample_base = unsigned(it.sample_base);
-            {
-              // refresh this lane's sampler slice: 40 ranking bytes + 8 scrambling bytes of the pixel
-              const int pix = (it.px & 127) + (it.py & 127) * 128;
-              const uint2* rsrc = reinterpret_cast<const uint2*>(S.tables.rank + size_t(pix) * 8);
-              const uint2 sc = *reinterpret_cast<const uint2*>(S.tables.scramble + size_t(pix) * 8);
-#pragma unroll
-              for (int j = 0; j < 5; j++) {
-                const uint2 r = rsrc[j];
-                lds_u[kOffTile + (2 * j) * kBlock + tid] = r.x;
-                lds_u[kOffTile + (2 * j + 1) * kBlock + tid] = r.y;
-              }
-              lds_u[kOffTile + 10 * kBlock + tid] = sc.x;
-              lds_u[kOffTile + 11 * kBlock + tid] = sc.y;
-            }
+            load_lane_slice(S.tables, it.px, it.py, lds_u + kOffTile, tid);
             if (W.items_per_pixel == 1) {
               rng_store(rng_seed(hash_pixel(it.px, it.py, 0)));  // Sampler::start_pixel
             } else {
@@ -1119,44 +1065,22 @@ path_trace_kernel(DeviceScene S, WorkParams W, const ulonglong2* __restrict__ ck
       int beta_channel = 0;
       bool do_walk = false;
       if constexpr (F & F_SSS) do_walk = bx.kind == BX_BSSRDF;
-      if (do_walk) {
-        f3 p = it.p;
-        f3 w = -wi;
-        if (Refract(wi, it.n, bx.ior, w, nullptr)) {
-          DRng g = rng_load();
-          const int channel = int(rng_nextf(g) * 3);
-          rng_store(g);
-          const float sigma_t_inv = 1 / mat->sigma_s[channel];
-          const f3 n0 = it.n;
-          for (int i = 0;; i++) {
-            DRay wr = i == 0 ? spawn_ray_raw(p, n0, w) : DRay{p, w, 0.0f, kFloatMax};
-            DSurface sit;
-            sit.p = sit.n = mk3(0.0f);  // non-mesh shapes leave them zero (Appendix A5)
-            bool h;
-            bool walk_mesh = false;
-            if constexpr (F & F_MESH) walk_mesh = shape->kind == SHAPE_MESH;
-            if (walk_mesh) {
-              const DRayOct oct = make_oct(wr);
-              int wprim = 0;
-              h = mesh_traverse<false>(V, V.bvhs[as_int(shape->f[2])], wr, oct, stack, 0, wprim);
-              if (h) mesh_surface_info(V.tri_verts, V.tri_attrs, as_int(shape->f[4]), wprim, ray_at(wr, wr.tmax), sit);
-            } else {
-              h = shape_intersect<F>(shape, wr);
-            }
-            if (!h) break;  // sample_p returns nullopt: nothing changes
-            const float t = -plog(1 - sampler_get1d<kSM>(T, sampler)) * sigma_t_inv;
-            if (wr.tmax < t) {
-              beta_channel = channel + 1;
-              it.p = sit.p;
-              it.n = sit.n;
-              l2w = coordinate_system(it.n);
-              w2l = transpose(l2w);
-              bx.wi = mul(w2l, -w);
-              break;
-            }
-            p = ray_at(wr, t);
-            w = uniform_sphere(sampler_get2d<kSM>(T, sampler));
-          }
+      int channel = 0;
+      DRay wr{};
+      if (do_walk && walk_begin(wi, it, bx, rng_load, rng_store, channel, wr)) {
+        auto inside = [&](DRay& r, int& wprim) -> bool {
+          bool walk_mesh = false;
+          if constexpr (F & F_MESH) walk_mesh = shape->kind == SHAPE_MESH;
+          if (walk_mesh) return mesh_traverse<false>(V, V.bvhs[as_int(shape->f[2])], r, make_oct(r), stack, 0, wprim);
+          return shape_intersect<F>(shape, r);
+        };
+        for (;;) {  // (ends without an exit when a ray finds no surface: sample_p returns nullopt, nothing changes)
+          DRay next;
+          DSurface sit;
+          const unsigned status = walk_step<F, kSM>(V, shape, mat, channel, wr, inside, T, sampler, next, sit);
+          if (status == kWalkExited) walk_exit(sit.p, sit.n, wr.d, channel, it, l2w, w2l, bx, beta_channel);
+          if (status != kWalkRunning) break;
+          wr = next;
         }
       }
 

@@ -16,9 +16,11 @@
 // One workgroup of 1024 threads per CU (all 160 KB of LDS, 16 waves sharing the queues).
 // Per-context cold data (sampler tile slice, RNG, fold stack) lives in L2-resident global memory.
 // Every result is bit-identical to path_trace_kernel and to the oracle: the stages run the same
-// device functions in the same order per path -- the per-vertex steps of pine_radiance.h, which
-// path_trace_kernel calls too; only the scheduling differs.  What is written here is this kernel's
-// own: queues, contexts, tokens, work hand-out, and the stores that keep a path's state between stages.
+// device functions in the same order per path -- the per-vertex steps of pine_radiance.h (the steps
+// of a BSSRDF walk included), which path_trace_kernel calls too; only the scheduling differs.  What
+// is written here is this kernel's own: queues, contexts, tokens, work hand-out, the stores that keep
+// a path's state between stages, and what only this kernel stages in LDS (node cache, triangle
+// packets, records, the per-stage sampler window) on top of pine_radiance.h's scene view.
 #pragma once
 
 
@@ -157,27 +159,8 @@ __device__ __forceinline__ void path_queue_body(const DeviceScene& S, const Work
   StackT* const stack = (F & F_LDS_TOP) ? reinterpret_cast<StackT*>(wave_region) + lane : reinterpret_cast<StackT*>(lds_raw + kQOffStack) + tid;
 
   // ---- one-time staging ----
-  {
-    const uint4* src = reinterpret_cast<const uint4*>(S.tables.sobol);
-    uint4* dst = reinterpret_cast<uint4*>(lds_raw + kQOffSobol);
-    for (int i = tid; i < kLdsSamplerDims * 256 / 16; i += kQBlock) dst[i] = src[i];
-  }
-  SceneView V;
-  V.tri_verts = S.tri_verts;
-  V.tri_leaf = S.tri_leaf;
-  V.tri_attrs = S.tri_attrs;
-  V.lds_nodes = nullptr;
-  V.lds_node_count = 0;
-  V.lds_tri_entries = nullptr;
-  V.lds_tri_verts = nullptr;
-  V.stack_top = S.stack_top;
-  V.num_shapes = S.num_shapes;
-  // (F_EMBREE variants read these; the hierarchy and the mesh list move with the blob when it is staged in LDS)
-  V.etree_root = S.etree_root;
-  V.num_emesh = S.num_emesh;
-  V.rcpps = reinterpret_cast<const unsigned*>(reinterpret_cast<const char*>(S.blob) + S.off_rcpps);
-  V.etree = reinterpret_cast<const EmbreeNode*>(reinterpret_cast<const char*>(S.blob) + S.off_etree);
-  V.emesh = reinterpret_cast<const int*>(reinterpret_cast<const char*>(S.blob) + S.off_emesh);
+  stage_sobol_rows(lds_raw + kQOffSobol, S.tables, tid, kQBlock);
+  SceneView V = scene_view_global(S);  // (what this kernel stages below moves to its LDS copy)
   char* lds_after_stack = nullptr;
   if constexpr (F & F_LDS_TOP) {
     size_t stack_bytes = size_t(S.stack_total) * kQBlock * sizeof(StackT);
@@ -205,13 +188,7 @@ __device__ __forceinline__ void path_queue_body(const DeviceScene& S, const Work
   }
   if constexpr (F & F_LDS_SCENE) {
     static_assert(!(F & F_LDS_TOP), "F_LDS_SCENE already has every node in LDS");
-    uint4* dst = reinterpret_cast<uint4*>(lds_raw + kQOffStack + S.stack_total * kQBlock);
-    const int n16 = S.blob_bytes >> 4;
-    for (int i = tid; i < n16; i += kQBlock) dst[i] = S.blob[i];
-    const char* base = reinterpret_cast<const char*>(dst);
-    V.nodes = reinterpret_cast<const DNode*>(base + S.off_nodes);
-    view_of_blob(base, S, V);
-    if (S.off_rcpps < S.blob_bytes) V.rcpps = reinterpret_cast<const unsigned*>(base + S.off_rcpps);
+    V = scene_view_staged(S, reinterpret_cast<uint4*>(lds_raw + kQOffStack + S.stack_total * kQBlock), tid, kQBlock);
   } else if constexpr (F & F_LDS_REST) {
     // blob = nodes | shapes | materials | node programs | bvhs | leaf records | lights: everything after the nodes
     size_t stack_bytes = size_t(S.stack_total) * kQBlock * sizeof(StackT);
@@ -220,18 +197,7 @@ __device__ __forceinline__ void path_queue_body(const DeviceScene& S, const Work
     const uint4* src = S.blob + (S.off_shapes >> 4);
     const int n16 = (S.blob_bytes - S.off_shapes) >> 4;
     for (int i = tid; i < n16; i += kQBlock) dst[i] = src[i];
-    const char* base = reinterpret_cast<const char*>(dst) - S.off_shapes;
-    V.nodes = S.nodes;
-    view_of_blob(base, S, V);
-  } else {
-    V.leaf = S.leaf;
-    V.nodes = S.nodes;
-    V.shapes = S.shapes;
-    V.materials = S.materials;
-    V.bvhs = S.bvhs;
-    V.prims = nullptr;
-    V.lights = S.lights;
-    V.node_ops = S.node_ops;
+    view_of_blob(reinterpret_cast<const char*>(dst) - S.off_shapes, S, V);  // (the nodes stay where they are)
   }
   // queues: every context starts "fresh" in the terminal queue (stage T hands out work items)
   if (tid < QC_WORDS) qctl[tid] = 0;
@@ -856,12 +822,9 @@ __device__ __forceinline__ void path_queue_body(const DeviceScene& S, const Work
           if (bx.kind == BX_BSSRDF) {
             float4* const cg4 = reinterpret_cast<float4*>(cg);
             if (st.walk() == kWalkNone) {
-              f3 w = -wi;
-              if (Refract(wi, it.n, bx.ior, w, nullptr)) {
-                DRng g = rng_load();
-                const int channel = int(rng_nextf(g) * 3);
-                rng_store(g);
-                const DRay wr = spawn_ray_raw(it.p, it.n, w);  // (later steps start AT the scattering point, with tmax = float max)
+              int channel;
+              DRay wr;
+              if (walk_begin(wi, it, bx, rng_load, rng_store, channel, wr)) {
                 cg4[2] = make_float4(wr.o.x, wr.o.y, wr.o.z, __int_as_float(channel));
                 cg4[3] = make_float4(wr.d.x, wr.d.y, wr.d.z, wr.tmax);
                 st.set_dim(sampler.dimension & 0x1ff);
@@ -891,12 +854,7 @@ __device__ __forceinline__ void path_queue_body(const DeviceScene& S, const Work
             } else if (st.walk() == kWalkExited) {
               // the walk left the shape: bc.it.p / n move to the exit point, wi becomes the reversed last walk direction
               const float4 a = cg4[2], b = cg4[3], c = cg4[4];
-              beta_channel = __float_as_int(a.w) + 1;
-              it.p = f3{a.x, a.y, a.z};
-              it.n = f3{c.x, c.y, c.z};
-              l2w = coordinate_system(it.n);
-              w2l = transpose(l2w);
-              bx.wi = mul(w2l, -f3{b.x, b.y, b.z});
+              walk_exit(f3{a.x, a.y, a.z}, f3{c.x, c.y, c.z}, f3{b.x, b.y, b.z}, __float_as_int(a.w), it, l2w, w2l, bx, beta_channel);
             }  // kWalkFailed: a walk ray found no surface (sample_p returns nullopt): nothing changes
           }
         }
@@ -1108,41 +1066,33 @@ __device__ __forceinline__ void path_queue_body(const DeviceScene& S, const Work
           const DShape* shape = &V.shapes[int(cstu[CF_GEOM * kQCtx + id]) & kPrimIndexMask];
           const DMaterial* mat = &V.materials[shape->material];
           const int channel = __float_as_int(a.w);
-          DRay wr{f3{a.x, a.y, a.z}, f3{b.x, b.y, b.z}, 0.0f, b.w};
+          const DRay wr{f3{a.x, a.y, a.z}, f3{b.x, b.y, b.z}, 0.0f, b.w};
           walk_count++;
           DSampler sampler = sampler_of<F>(st, pxy, S.tables.kind, [&] { return int(ctx_global(id)[6]); });
-          bool hh;
-          int wprim = 0;
-          bool walk_mesh = false;
-          if constexpr (F & F_MESH) walk_mesh = shape->kind == SHAPE_MESH;
-          if (walk_mesh) {
-            const DRayOct oct = make_oct(wr);
-            hh = mesh_traverse<false, kStride, F>(V, V.bvhs[as_int(shape->f[2])], wr, oct, stack, 0, wprim);
-          } else {
-            hh = shape_intersect<F>(shape, wr);
-          }
-          SEC_MARK(12);  // W: closest hit inside the shape
-          if (!hh) {  // sample_p returns nullopt
-            st.set_walk(kWalkFailed);
-            to_shade = true;
-          } else {
-            const float t = -plog(1 - sampler_get1d<kSM & kSmSobol>(S.tables, sampler)) * (1 / mat->sigma_s[channel]);
-            if (wr.tmax < t) {
-              // leaves the shape here: Shape::intersect filled it.p / it.n for meshes only
-              DSurface sit;
-              sit.p = sit.n = mk3(0.0f);
-              if (walk_mesh) mesh_surface_info(V.tri_verts, V.tri_attrs, as_int(shape->f[4]), wprim, ray_at(wr, wr.tmax), sit);
+          auto inside = [&](DRay& r, int& wprim) -> bool {
+            bool hh;
+            bool walk_mesh = false;
+            if constexpr (F & F_MESH) walk_mesh = shape->kind == SHAPE_MESH;
+            if (walk_mesh) hh = mesh_traverse<false, kStride, F>(V, V.bvhs[as_int(shape->f[2])], r, make_oct(r), stack, 0, wprim);
+            else hh = shape_intersect<F>(shape, r);
+            SEC_MARK(12);  // W: closest hit inside the shape
+            return hh;
+          };
+          DRay next;
+          DSurface sit;
+          // (the draws go to the tables themselves: this stage has no sampler window)
+          const unsigned status = walk_step<F, kSM & kSmSobol>(V, shape, mat, channel, wr, inside, S.tables, sampler, next, sit);
+          if (status == kWalkRunning) {
+            cg4[2] = make_float4(next.o.x, next.o.y, next.o.z, a.w);
+            cg4[3] = make_float4(next.d.x, next.d.y, next.d.z, next.tmax);
+            to_walk = true;
+          } else {  // kWalkFailed: sample_p returns nullopt
+            if (status == kWalkExited) {  // the exit point and its normal, for the second pass through stage S
               cg4[2] = make_float4(sit.p.x, sit.p.y, sit.p.z, a.w);
               cg4[4] = make_float4(sit.n.x, sit.n.y, sit.n.z, 0.0f);
-              st.set_walk(kWalkExited);
-              to_shade = true;
-            } else {
-              const f3 p = ray_at(wr, t);
-              const f3 w = uniform_sphere(sampler_get2d<kSM & kSmSobol>(S.tables, sampler));
-              cg4[2] = make_float4(p.x, p.y, p.z, a.w);
-              cg4[3] = make_float4(w.x, w.y, w.z, kFloatMax);
-              to_walk = true;
             }
+            st.set_walk(status);
+            to_shade = true;
           }
           st.set_dim(sampler.dimension & 0x1ff);
           if constexpr (kBigDim) ctx_global(id)[6] = uint32_t(sampler.dimension);

@@ -1,15 +1,26 @@
-// pine_amd/csrc/pine_radiance.h -- the per-vertex steps of radiance() (path.cpp:42-124), written once.
+// pine_amd/csrc/pine_radiance.h -- the kernel prologue and the per-vertex steps of radiance() (path.cpp:42-124), written once.
+//
+// The prologue (scene_view_global / _staged, stage_sobol_rows, lane_tables, load_lane_slice) serves every kernel that
+// traces: the two path kernels, the AO kernel and the traversal test hook.
 //
 // Every film has to match the reference bit for bit: each path vertex runs the same floating-point operations, the same
 // sampler draws and the same RNG draws in the same order as the reference.  That sequence lives HERE; the two path kernels
 // (path_trace_kernel in pine_kernels_device.h, path_queue_body in pine_queue_kernel.h) only decide when a step runs and
-// where its state is kept.  The functions take what they need as arguments -- SceneView, scalar fields of DeviceScene,
+// where its state is kept -- a step of the BSSRDF walk included (walk_begin, walk_step, walk_exit).  The functions take what they need as arguments -- SceneView, scalar fields of DeviceScene,
 // DTables, DSampler&, DRng& or load / store callables -- and know nothing about queues, contexts, LDS layouts or lane
 // state.  All are force-inlined: a caller's constant arguments fold, and a callable costs nothing.
 // Included by pine_kernels_device.h after SceneView, PackedState and material_le.
 #pragma once
 
 namespace pine_gpu {
+
+// ---- the kernel prologue: the scene view and the sampler's LDS front, for every kernel that traces ----
+
+// EmbreeAccel's hierarchy and mesh list (F_EMBREE variants read them) in a scene blob at `base`.
+__device__ __forceinline__ void view_of_embree_order(const char* base, const DeviceScene& S, SceneView& V) {
+  V.etree = reinterpret_cast<const EmbreeNode*>(base + S.off_etree);
+  V.emesh = reinterpret_cast<const int*>(base + S.off_emesh);
+}
 
 // SceneView over a scene blob (DeviceScene::blob and its off_* offsets) staged at `base`.  The nodes and the reciprocal
 // table are the caller's: not every kernel stages them with the rest.
@@ -21,8 +32,83 @@ __device__ __forceinline__ void view_of_blob(const char* base, const DeviceScene
   V.lights = reinterpret_cast<const DLight*>(base + S.off_lights);
   V.node_ops = reinterpret_cast<const DNodeOp*>(base + S.off_node_ops);
   V.leaf = reinterpret_cast<const DShape*>(base + S.off_leaf) - S.top_prim_begin;
-  V.etree = reinterpret_cast<const EmbreeNode*>(base + S.off_etree);
-  V.emesh = reinterpret_cast<const int*>(base + S.off_emesh);
+  view_of_embree_order(base, S, V);
+}
+
+// The scene where the host put it: every field of the view from the DeviceScene's global-memory pointers, nothing in LDS.
+// Every kernel's view starts here, so a new SceneView field is set in this one place.
+__device__ __forceinline__ SceneView scene_view_global(const DeviceScene& S) {
+  SceneView V;
+  V.leaf = S.leaf;
+  V.shapes = S.shapes;
+  V.materials = S.materials;
+  V.nodes = S.nodes;
+  V.prims = nullptr;
+  V.bvhs = S.bvhs;
+  V.lights = S.lights;
+  V.tri_verts = S.tri_verts;
+  V.node_ops = S.node_ops;
+  V.stack_top = S.stack_top;
+  V.num_shapes = S.num_shapes;
+  V.tri_leaf = S.tri_leaf;
+  V.tri_attrs = S.tri_attrs;
+  V.lds_nodes = nullptr;
+  V.lds_node_count = 0;
+  V.lds_tri_entries = nullptr;
+  V.lds_tri_verts = nullptr;
+  view_of_embree_order(reinterpret_cast<const char*>(S.blob), S, V);
+  V.etree_root = S.etree_root;
+  V.num_emesh = S.num_emesh;
+  V.rcpps = reinterpret_cast<const unsigned*>(reinterpret_cast<const char*>(S.blob) + S.off_rcpps);
+  return V;
+}
+
+// F_LDS_SCENE: the workgroup copies the scene blob to `dst` (LDS, 16-byte words, thread tid of nthreads) and gets the view
+// over the copy.  The reciprocal table moves with it when the host put it inside the staged part.  The caller's
+// __syncthreads() comes before the first read.
+__device__ __forceinline__ SceneView scene_view_staged(const DeviceScene& S, uint4* dst, unsigned tid, int nthreads) {
+  const int n16 = S.blob_bytes >> 4;
+  for (int i = tid; i < n16; i += nthreads) dst[i] = S.blob[i];
+  SceneView V = scene_view_global(S);
+  const char* base = reinterpret_cast<const char*>(dst);
+  V.nodes = reinterpret_cast<const DNode*>(base + S.off_nodes);
+  view_of_blob(base, S, V);
+  if (S.off_rcpps < S.blob_bytes) V.rcpps = reinterpret_cast<const unsigned*>(base + S.off_rcpps);
+  return V;
+}
+
+// The transposed Sobol table's rows of the dimensions the LDS front serves, to `dst` (LDS) over the workgroup.
+__device__ __forceinline__ void stage_sobol_rows(int* dst, const DTables& tables, unsigned tid, int nthreads) {
+  const uint4* src = reinterpret_cast<const uint4*>(tables.sobol);
+  for (int i = tid; i < kLdsSamplerDims * 256 / 16; i += nthreads) reinterpret_cast<uint4*>(dst)[i] = src[i];
+}
+
+// The sampler tables as a lane of a 256-thread workgroup sees them: the staged Sobol rows, and the lane's own slice
+// ([dword][lane] from lds_tile_base: 10 dwords of ranking bytes, 2 of scrambling bytes) that load_lane_slice fills.
+__device__ __forceinline__ DTables lane_tables(const DTables& tables, const int* lds_sobol, uint32_t* lds_tile_base, unsigned tid) {
+  DTables T = tables;
+  T.lds_sobol = reinterpret_cast<const uint8_t*>(lds_sobol);
+  T.lds_tile = lds_tile_base + tid;
+  T.lds_scr = lds_tile_base + tid + 10 * kLdsLaneStride;
+  T.tile_stride = kLdsLaneStride;
+  T.win_lo = 0;
+  T.win_len = kLdsSamplerDims;
+  return T;
+}
+
+// This lane's sampler slice for pixel (px, py): its 40 ranking bytes and 8 scrambling bytes.
+__device__ __forceinline__ void load_lane_slice(const DTables& tables, int px, int py, uint32_t* lds_tile_base, unsigned tid) {
+  const int pix = (px & 127) + (py & 127) * 128;
+  const uint2* rsrc = reinterpret_cast<const uint2*>(tables.rank + size_t(pix) * 8);
+  const uint2 sc = *reinterpret_cast<const uint2*>(tables.scramble + size_t(pix) * 8);
+#pragma unroll
+  for (int j = 0; j < 5; j++) {
+    const uint2 r = rsrc[j];
+    lds_tile_base[(2 * j) * kLdsLaneStride + tid] = r.x;
+    lds_tile_base[(2 * j + 1) * kLdsLaneStride + tid] = r.y;
+  }
+  lds_tile_base[10 * kLdsLaneStride + tid] = sc.x;
+  lds_tile_base[11 * kLdsLaneStride + tid] = sc.y;
 }
 
 // SobolSampler / HaltonSampler in a scene with Subsurface: a BSSRDF walk draws three dimensions per step and has no bound on
@@ -156,6 +242,66 @@ __device__ __forceinline__ void choose_lobe(const DMaterial* mat, const MatParam
       }
     }
   }
+}
+
+// ---- the BSSRDF random walk inside the shape that was hit (SeparableBSSRDF::sample_p, bxdf.cpp:329-353, :375-382) ----
+// walk_begin, then walk_step until it answers something other than kWalkRunning, then (kWalkExited) walk_exit.  Where
+// the walk's state lives between steps -- registers of a loop, or a context's record between passes of a stage -- is the
+// kernel's business.  Each function sets ALL its outputs on every path: an output left undefined on one path reaches the
+// kernels' merged control flow as an undefined value, and that cost the queue kernel's Subsurface variants up to 29 spilled
+// VGPRs (profiles/prologue_and_walk_once.txt).
+
+// Refraction into the shape, the colour channel (one draw from the pixel's RNG), the first ray.  false is the reference's
+// nullopt: nothing was drawn, nothing changes, the vertex is shaded where it was hit.
+template <class RngLoad, class RngStore>
+__device__ __forceinline__ bool walk_begin(f3 wi, const DSurface& it, const DBxdf& bx, RngLoad rng_load, RngStore rng_store, int& channel, DRay& first_ray) {
+  channel = 0;
+  first_ray = DRay{};
+  f3 w = -wi;
+  if (!Refract(wi, it.n, bx.ior, w, nullptr)) return false;
+  DRng g = rng_load();
+  channel = int(rng_nextf(g) * 3);
+  rng_store(g);
+  first_ray = spawn_ray_raw(it.p, it.n, w);  // (later rays start AT the scattering point, with tmax = float max)
+  return true;
+}
+
+// One free-flight step along `wr`.  `inside(DRay& wr, int& prim) -> bool` is the closest-hit query against `shape` alone
+// (it shortens wr.tmax); each kernel passes its own traversal call.  Answers a PackedState walk status:
+//   kWalkFailed   the ray found no surface (nullopt: nothing changes);
+//   kWalkExited   the free flight ends beyond the surface: sit.p / .n are the exit point and its normal;
+//   kWalkRunning  scattered: next_ray leaves the scattering point in a uniformly drawn direction.
+// Draws one sampler dimension, and two more when it scatters.
+template <unsigned F, int SM, class Inside>
+__device__ __forceinline__ unsigned walk_step(const SceneView& V, const DShape* shape, const DMaterial* mat, int channel, DRay wr, Inside inside,
+                                              const DTables& T, DSampler& sampler, DRay& next_ray, DSurface& sit) {
+  next_ray = wr;
+  // Shape::intersect fills it.p / it.n for meshes only: non-mesh shapes leave them zero
+  sit.p = sit.n = mk3(0.0f);
+  sit.uv = f2{0, 0};
+  int prim = 0;
+  if (!inside(wr, prim)) return kWalkFailed;
+  const float t = -plog(1 - sampler_get1d<SM>(T, sampler)) * (1 / mat->sigma_s[channel]);
+  if (wr.tmax < t) {
+    bool walk_mesh = false;
+    if constexpr (F & F_MESH) walk_mesh = shape->kind == SHAPE_MESH;
+    if (walk_mesh) mesh_surface_info(V.tri_verts, V.tri_attrs, as_int(shape->f[4]), prim, ray_at(wr, wr.tmax), sit);
+    return kWalkExited;
+  }
+  const f3 p = ray_at(wr, t);
+  next_ray = DRay{p, uniform_sphere(sampler_get2d<SM>(T, sampler)), 0.0f, kFloatMax};
+  return kWalkRunning;
+}
+
+// The walk left the shape in `channel`: the vertex moves to the exit point and is shaded there, its incoming direction the
+// reversed last walk direction (bxdf.cpp:375-382); beta becomes 3 in that channel (clamp_radiance).
+__device__ __forceinline__ void walk_exit(f3 exit_p, f3 exit_n, f3 last_dir, int channel, DSurface& it, m3& l2w, m3& w2l, DBxdf& bx, int& beta_channel) {
+  beta_channel = channel + 1;
+  it.p = exit_p;
+  it.n = exit_n;
+  l2w = coordinate_system(it.n);
+  w2l = transpose(l2w);
+  bx.wi = mul(w2l, -last_dir);
 }
 
 // Next-event estimation (path.cpp:98-113) at a vertex whose lobe is not a delta one: the light sampler's draws, the light

@@ -120,15 +120,7 @@ __global__ void __launch_bounds__(64) test_traverse_kernel(DeviceScene S, const 
   using StackT = typename std::conditional<FLAT, unsigned short, int>::type;
   extern __shared__ __attribute__((aligned(16))) int lds_raw[];
   StackT* const stack = reinterpret_cast<StackT*>(lds_raw) + threadIdx.x;
-  SceneView V;
-  V.tri_verts = S.tri_verts, V.tri_leaf = S.tri_leaf, V.tri_attrs = S.tri_attrs;
-  V.lds_nodes = nullptr, V.lds_node_count = 0, V.lds_tri_entries = nullptr, V.lds_tri_verts = nullptr;
-  V.stack_top = S.stack_top, V.num_shapes = S.num_shapes;
-  V.leaf = S.leaf, V.nodes = S.nodes, V.shapes = S.shapes, V.materials = S.materials, V.bvhs = S.bvhs, V.prims = nullptr;
-  V.lights = S.lights, V.node_ops = S.node_ops;
-  V.etree = reinterpret_cast<const EmbreeNode*>(reinterpret_cast<const char*>(S.blob) + S.off_etree), V.etree_root = S.etree_root;
-  V.emesh = reinterpret_cast<const int*>(reinterpret_cast<const char*>(S.blob) + S.off_emesh), V.num_emesh = S.num_emesh;
-  V.rcpps = reinterpret_cast<const unsigned*>(reinterpret_cast<const char*>(S.blob) + S.off_rcpps);
+  const SceneView V = scene_view_global(S);
   const long long i = blockIdx.x * 64ll + threadIdx.x;
   const bool live = i < nrays;
   const float* q = rays + (live ? i : 0) * 8;

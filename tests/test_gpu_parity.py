@@ -237,11 +237,17 @@ def test_sobol_and_halton_samplers_with_subsurface(oracle, path_kernel, sampler)
     """A BSSRDF walk draws three sampler dimensions per step and has no bound on its steps: SobolSampler's dimension counter never
     wraps (sampler.h:143-155) and HaltonSampler's wraps to 2 at the 1000-prime table's end (:52-63) -- both beyond the nine bits the
     packed path state keeps for BlueSampler (which wraps at 256).  The Subsurface + Sobol variants keep the counter in a word
-    of its own; films equal the CPU restatement's, walks of hundreds of steps included (sigma_s 40 in a sphere of radius 0.4)."""
+    of its own; films equal the CPU restatement's, walks of hundreds of steps included (sigma_s 40 in a sphere of radius 0.4).
+    The third scene walks inside an ANALYTIC shape (a Subsurface Sphere in the room): there the counter of its own meets the
+    exit point that is the reference's zero vector."""
     import pine_amd as pa
     from pine_amd import scenes
     make = pa.SobolSampler if sampler == "sobol" else pa.HaltonSampler
-    for sc, size, spp, depth in ((scenes.sss((32, 32), 2), (32, 32), 8, 6), (scenes.sss((24, 20), 1, camera="committed"), (24, 20), 12, 5)):
+    sph = scenes.cbox((24, 24), "readme", boxes=False)
+    sph.add("skin", pa.Subsurface([0.8, 0.8, 0.7], 0.2, [30.0, 30.0, 30.0]))
+    sph.add(pa.Sphere([0.1, 0.5, 1.0], 0.4), "skin")
+    for sc, size, spp, depth in ((scenes.sss((32, 32), 2), (32, 32), 8, 6), (scenes.sss((24, 20), 1, camera="committed"), (24, 20), 12, 5),
+                                 (sph, (24, 24), 8, 5)):
         film, st = _render(sc, make(spp), depth)
         ref, ost = oracle.render(sc.describe(), size, spp, depth, sampler=sampler)
         assert st.walk_steps > 0 or path_kernel == "mega"

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""usage: tools/kernel_regs.py [lib.so] -- register / spill / scratch table of every path kernel in a built library.
+"""usage: tools/kernel_regs.py [lib.so] -- register / spill / scratch table of every path and AO kernel in a built library.
 Carves the gfx950 code objects out of the library's offload bundles and reads their metadata notes with llvm-readelf."""
 import os
 import re
@@ -44,6 +44,9 @@ def short(name):
     if m:
         ns = "fast " if "pine_gpu_fast" in name else ""
         return f"{ns}{m.group(1)}<{m.group(2)},{m.group(3)}>"
+    m = re.search(r"ao_kernelILj(\d+)ELb(\d)", name)
+    if m:
+        return f"ao_kernel<{m.group(1)},{'regroup' if m.group(2) == '1' else 'serial'}>"
     return None
 print(f"{'kernel':48s} vgpr vgpr_spill sgpr sgpr_spill scratch_bytes_per_lane")
 for r in sorted(rows):
