@@ -528,6 +528,21 @@ int pine_gpu_plan_test_traverse_baked(pine_gpu_plan*, const float* rays_host, in
 int pine_gpu_scene_accel_bvhs(pine_gpu_scene*, int32_t* out, int64_t capacity_words);
 int pine_gpu_test_shapes(pine_gpu_scene*, int device, const float* rays_host, int64_t nrays,
                          float* out_host, int64_t capacity);                        /* layout of oracle_shapes */
+/* The BSDF lobes one call at a time (pine_device.h bxdf_f / bxdf_pdf / bxdf_is_delta / bxdf_sample), for tests/test_sampling_fixtures.py.
+ * One case = 16 floats (integers as exactly representable floats): 0 lobe (BxdfKind order: Diffuse, Conductor, Refractive,
+ * RefractiveDielectric, DiffusiveDielectric, BSSRDF)  1-3 albedo  4 roughness  5 ior  6-8 wi  9-11 wo (local frame)  12 13 sampler
+ * pixel (< 1024)  14 sample index (< 64)  15 calls: bit 0 = f and pdf, bit 1 = sample.  One record = 14 floats: 0-2 f  3 pdf
+ * 4 is_delta  5 sample returned a value  6-8 its wo  9-11 its f  12 its pdf  13 its is_delta; what was not computed is 0.
+ * sample draws from SobolSampler(64) on a 1024 x 1024 image, at that pixel and sample index.  out_host: 2 * n records -- n by the
+ * code built with every feature (F_ALL), then n by the code built with the narrowest feature mask that contains the case's lobe
+ * (none, F_UBER or F_SSS), as the shipped kernel variants are.  device = -1: the host build of the same functions. */
+int pine_gpu_test_bxdf(int device, const float* cases_host, int64_t n, float* out_host);
+/* shape_sample + shape_pdf of every geometry and light_sample_other of every light that is no area light (scene order, the
+ * environment light last) for n queries of 6 floats (o, u2, u1).  out_host: per (geometry, query) 13 floats -- 0 sampled (-1: a
+ * Cylinder, which the reference cannot sample)  1-3 p  4-6 n  7-9 w  10 distance  11 pdf  12 shape_pdf of the ray o -> w with
+ * tmax = distance and that n -- then per (light, query) 9 floats: 0 sampled  1-3 w  4 distance  5 pdf  6-8 le.  Zeros after
+ * a 0 or -1.  device = -1: the host build of the same functions. */
+int pine_gpu_test_light_samples(pine_gpu_scene*, int device, const float* queries_host, int64_t n, float* out_host);
 /* The precompiled path-kernel variants (pine_variants.h) in the order of the host's first-fit search: kind 0 the stage-queued
  * kernel, 1 the megakernel.  Up to `cap` entries of features (F_* bits), ctx (path contexts per workgroup; 0 for the
  * megakernel) and order; any of the arrays may be NULL.  Returns the number of variants, < 0 on error.  Needs no GPU.

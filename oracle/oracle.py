@@ -120,6 +120,26 @@ def shapes(pscene: str, rays: np.ndarray, n_geoms: int):
     return out
 
 
+def bxdf(cases: np.ndarray):
+    """cases[n,16] float32 (layout of `pine_ref bxdf`) -> records[n,14] float32"""
+    cases = np.ascontiguousarray(cases, np.float32).reshape(-1, 16)
+    out = np.zeros((len(cases), 14), np.float32)
+    rc = lib().oracle_bxdf(cases.ctypes.data_as(C.c_void_p), C.c_int64(len(cases)), out.ctypes.data_as(C.c_void_p))
+    assert rc == 0, rc
+    return out
+
+
+def light_samples(pscene: str, queries: np.ndarray, n_geoms: int, n_lights: int):
+    """queries[n,6] float32 -> (shape records[n_geoms,n,13], light records[n_lights,n,9]) in the layout of `pine_ref lightsamples`"""
+    queries = np.ascontiguousarray(queries, np.float32).reshape(-1, 6)
+    n = len(queries)
+    out = np.zeros(n * (13 * n_geoms + 9 * n_lights), np.float32)
+    rc = lib().oracle_light_samples(pscene.encode(), queries.ctypes.data_as(C.c_void_p), C.c_int64(n),
+                                    out.ctypes.data_as(C.c_void_p), C.c_int64(out.size))
+    assert rc == 0, rc
+    return out[:n * 13 * n_geoms].reshape(n_geoms, n, 13), out[n * 13 * n_geoms:].reshape(n_lights, n, 9)
+
+
 def have_ref():
     return os.path.exists(REF_BIN)
 

@@ -2908,18 +2908,26 @@ struct Integrator {
     u1 *= N;
     int index = int(u1);
     const Scene::Light& L = scene->lights[index];
+    if (L.kind == Scene::Light::Area) {
+      const Geometry& g = scene->geometries[L.geom];
+      ShapeSample gs;
+      if (!g.sample(p, u2, u1 - index, gs)) return false;
+      ls.wo = gs.w;
+      ls.pdf = gs.pdf;
+      ls.distance = gs.distance;
+      ls.le = material_le(scene->materials[g.material], gs.n, -ls.wo);
+      if (ls.le.is_zero()) return false;
+    } else if (!sample_other_light(L, p, u2, ls)) {
+      return false;
+    }
+    ls.pdf = ls.pdf / N;
+    ls.is_delta = L.is_delta();
+    return true;
+  }
+  // Light::sample of the lights that are no AreaLight (light.cpp:11-54, 74-81)
+  static bool sample_other_light(const Scene::Light& L, vec3 p, vec2 u2, LightSample& ls) {
     switch (L.kind) {
-      case Scene::Light::Area: {
-        const Geometry& g = scene->geometries[L.geom];
-        ShapeSample gs;
-        if (!g.sample(p, u2, u1 - index, gs)) return false;
-        ls.wo = gs.w;
-        ls.pdf = gs.pdf;
-        ls.distance = gs.distance;
-        ls.le = material_le(scene->materials[g.material], gs.n, -ls.wo);
-        if (ls.le.is_zero()) return false;
-        break;
-      }
+      case Scene::Light::Area: return false;
       case Scene::Light::Point:  // light.cpp:11-17
         ls.wo = normalize(L.position - p, ls.distance);
         ls.pdf = ls.distance * ls.distance;
@@ -2947,8 +2955,6 @@ struct Integrator {
         ls.le = sky_color_of(L.color, ls.wo);
         break;
     }
-    ls.pdf = ls.pdf / N;
-    ls.is_delta = L.is_delta();
     return true;
   }
   static vec3 sky_color_of(vec3 sun_color, vec3 wo) {  // Sky::color light.cpp:71-73, sky_color color.cpp:100-103
@@ -3780,6 +3786,94 @@ int oracle_shapes(const char* pscene, const float* rays, int64_t nrays, float* o
     }
   }
   return 0;
+}
+
+
+int oracle_bxdf(const float* cases, int64_t n, float* out) {
+  for (int64_t i = 0; i < n; i++) {
+    const float* c = cases + i * 16;
+    float* o = out + i * 14;
+    for (int k = 0; k < 14; k++) o[k] = 0.0f;
+    const int lobe = int(c[0]), calls = int(c[15]);
+    if (lobe < 0 || lobe > BX_BSSRDF) {
+      g_error = "oracle_bxdf: unknown lobe";
+      return 2;
+    }
+    BXDF b;
+    b.kind = BxdfKind(lobe);
+    b.albedo = vec3(c[1], c[2], c[3]);
+    b.roughness = c[4];
+    b.ior = c[5];
+    b.wi = vec3(c[6], c[7], c[8]);
+    const vec3 wo(c[9], c[10], c[11]);
+    if (calls & 1) {
+      const vec3 f = b.f(wo);
+      o[0] = f.x, o[1] = f.y, o[2] = f.z;
+      o[3] = b.pdf(wo);
+    }
+    o[4] = b.is_delta() ? 1.0f : 0.0f;
+    if (calls & 2) {
+      Sampler sampler;  // SobolSampler(64) on a 1024 x 1024 image, as `pine_ref bxdf` starts it
+      sampler.kind = SAMPLER_SOBOL;
+      sampler.spp = 64;
+      sampler.init(1024, 1024);
+      sampler.start_pixel(int(c[12]), int(c[13]), 0);
+      for (int k = 0; k < int(c[14]); k++) sampler.start_next_sample();
+      BSDFSample bs;
+      if (b.sample(sampler, bs)) {
+        o[5] = 1.0f;
+        o[6] = bs.wo.x, o[7] = bs.wo.y, o[8] = bs.wo.z;
+        o[9] = bs.f.x, o[10] = bs.f.y, o[11] = bs.f.z;
+        o[12] = bs.pdf;
+        o[13] = bs.is_delta ? 1.0f : 0.0f;
+      }
+    }
+  }
+  return 0;
+}
+
+int oracle_light_samples(const char* pscene, const float* queries, int64_t n, float* out, int64_t capacity) {
+  Scene scene;
+  if (!parse_pscene(pscene, scene)) return 2;
+  int64_t k = 0;
+  for (auto& g : scene.geometries)
+    for (int64_t i = 0; i < n; i++) {
+      if (k + 13 > capacity) return -1;
+      const float* q = queries + i * 6;
+      float* o = out + k;
+      k += 13;
+      for (int j = 0; j < 13; j++) o[j] = 0.0f;
+      if (g.kind == S_CYLINDER) {  // the reference has no Cylinder::sample (geometry.h:148)
+        o[0] = -1.0f;
+        continue;
+      }
+      const vec3 p(q[0], q[1], q[2]);
+      ShapeSample ss;
+      if (!g.sample(p, vec2(q[3], q[4]), q[5], ss)) continue;
+      o[0] = 1.0f;
+      o[1] = ss.p.x, o[2] = ss.p.y, o[3] = ss.p.z;
+      o[4] = ss.n.x, o[5] = ss.n.y, o[6] = ss.n.z;
+      o[7] = ss.w.x, o[8] = ss.w.y, o[9] = ss.w.z;
+      o[10] = ss.distance, o[11] = ss.pdf;
+      o[12] = g.pdf(Ray(p, ss.w, 0.0f, ss.distance), ss.n);
+    }
+  for (auto& L : scene.lights) {  // (the environment light is the last entry)
+    if (L.kind == Scene::Light::Area) continue;
+    for (int64_t i = 0; i < n; i++) {
+      if (k + 9 > capacity) return -1;
+      const float* q = queries + i * 6;
+      float* o = out + k;
+      k += 9;
+      for (int j = 0; j < 9; j++) o[j] = 0.0f;
+      LightSample ls;
+      if (!Integrator::sample_other_light(L, vec3(q[0], q[1], q[2]), vec2(q[3], q[4]), ls)) continue;
+      o[0] = 1.0f;
+      o[1] = ls.wo.x, o[2] = ls.wo.y, o[3] = ls.wo.z;
+      o[4] = ls.distance, o[5] = ls.pdf;
+      o[6] = ls.le.x, o[7] = ls.le.y, o[8] = ls.le.z;
+    }
+  }
+  return k == capacity ? 0 : -1;
 }
 
 }  // extern "C"

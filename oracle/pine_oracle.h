@@ -63,6 +63,11 @@ int oracle_host_math(float* out, int64_t capacity);
 /* Per-shape records in the layout of `pine_ref shapes` (11 floats per (geometry, ray)). */
 int oracle_shapes(const char* pscene, const float* rays, int64_t nrays, float* out,
                   int64_t capacity);
+/* BSDF lobes one call at a time, in the layout of `pine_ref bxdf` (oracle/ref_driver.cpp): 16 floats per case in, 14 out. */
+int oracle_bxdf(const float* cases, int64_t n, float* out);
+/* Shape::sample / Shape::pdf of every geometry and Light::sample of every other light, in the layout of `pine_ref lightsamples`:
+ * 6 floats per query in; 13 floats per (geometry, query), then 9 per (light, query) out.  capacity must be exactly that. */
+int oracle_light_samples(const char* pscene, const float* queries, int64_t n, float* out, int64_t capacity);
 /* libm-compatible sinf/cosf restatement check helpers (see pine_amd/csrc/pine_libm.h). */
 const char* oracle_last_error(void);
 

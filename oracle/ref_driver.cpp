@@ -23,9 +23,15 @@
 //   pine_ref vertices <scene.pscene> <spp> <depth> <out.bin>   per-vertex terms of every path of the film (path.cpp:42-124):
 //                                        radiance() restated around the reference's OWN intersect / light sampler / bxdf
 //                                        objects with a log; the restated loop's film is checked against render()'s
+//   pine_ref bxdf    <cases.bin> <out.bin>   f / pdf / is_delta / sample of the reference's own DiffuseBSDF, ConductorBSDF,
+//                                        RefractiveBSDF, RefractiveDielectricBSDF, DiffusiveDielectricBSDF and BSSRDF objects, one
+//                                        case (16 floats) -> one record (14 floats); the u's of sample() come from a SobolSampler
+//   pine_ref lightsamples <scene.pscene> <queries.bin> <out.bin>   Shape::sample + Shape::pdf of every geometry and Light::sample
+//                                        of every other light for every query (o, u2, u1)
 //   pine_ref prl     <literal>...        psl::stof / stoi / to_string of each literal, and the constant
 //                                        expressions of a cbox-class script evaluated with psl::stof values
 //                                        (pins the PRL front-end's literal and vector arithmetic)
+#include <pine/core/bxdf.h>
 #include <pine/core/fileio.h>
 #include <pine/core/film.h>
 #include <pine/core/lightsampler.h>
@@ -312,6 +318,20 @@ static void write_file(const char* path, const void* p, size_t n) {
     exit(2);
   }
   fclose(f);
+}
+
+static std::vector<float> read_floats(const char* path) {
+  std::ifstream f(path, std::ios::binary);
+  if (!f) {
+    fprintf(stderr, "cannot open %s\n", path);
+    exit(2);
+  }
+  f.seekg(0, std::ios::end);
+  const size_t nbytes = size_t(f.tellg());
+  f.seekg(0);
+  std::vector<float> v(nbytes / 4);
+  f.read((char*)v.data(), std::streamsize(v.size() * 4));
+  return v;
 }
 
 // ---- reading the reference's private BVH members without touching its sources: explicit instantiation may name
@@ -788,6 +808,116 @@ int main(int argc, char** argv) {
     write_file(argv[5], out.data(), out.size() * 4);
     printf("{\"paths\": %d, \"floats\": %zu, \"restated_loop_equals_render\": %s}\n", L.W * L.H * spp, out.size(), same ? "true" : "false");
     return same ? 0 : 3;
+  }
+  if (cmd == "bxdf" && argc == 4) {
+    // One case = 16 floats (integers as exactly representable floats): 0 lobe (BSDF classes in the order of bxdf.h:38-138)
+    // 1-3 albedo  4 roughness  5 ior  6-8 wi  9-11 wo (local frame)  12 13 sampler pixel  14 sample index
+    // 15 calls: bit 0 = f and pdf, bit 1 = sample.  (Conductor / Refractive / RefractiveDielectric f and pdf CHECK
+    // alpha >= 1e-4f and abort below it, bxdf.cpp:67,82,120,136,200,224: such cases carry bit 1 only.)
+    // One record = 14 floats: 0-2 f(wi, wo)  3 pdf(wi, wo)  4 is_delta()  5 sample() returned a value  6-8 its wo
+    // 9-11 its f  12 its pdf  13 its is_delta; what was not computed is 0.
+    // The sampler is SobolSampler(64) on a 1024 x 1024 image, started as PathIntegrator::render starts one: start_pixel(p, 0)
+    // and one start_next_sample() per earlier sample.
+    const std::vector<float> cases = read_floats(argv[2]);
+    std::vector<float> out;
+    for (size_t k = 0; k + 16 <= cases.size(); k += 16) {
+      const float* c = &cases[k];
+      const vec3 albedo(c[1], c[2], c[3]), wi(c[6], c[7], c[8]), wo(c[9], c[10], c[11]);
+      const float roughness = c[4], ior = c[5];
+      const int calls = int(c[15]);
+      float rec[14] = {};
+      auto run = [&](const auto& x) {
+        if (calls & 1) {
+          const vec3 f = x.f(wi, wo);
+          rec[0] = f.x, rec[1] = f.y, rec[2] = f.z;
+          rec[3] = x.pdf(wi, wo);
+        }
+        rec[4] = x.is_delta() ? 1.0f : 0.0f;
+        if (calls & 2) {
+          Sampler sampler = Sampler(SobolSampler(64));
+          sampler.init(vec2i(1024, 1024));
+          sampler.start_pixel(vec2i(int(c[12]), int(c[13])), 0);
+          for (int i = 0; i < int(c[14]); i++) sampler.start_next_sample();
+          if (auto bs = x.sample(wi, sampler)) {
+            rec[5] = 1.0f;
+            rec[6] = bs->wo.x, rec[7] = bs->wo.y, rec[8] = bs->wo.z;
+            rec[9] = bs->f.x, rec[10] = bs->f.y, rec[11] = bs->f.z;
+            rec[12] = bs->pdf;
+            rec[13] = bs->is_delta ? 1.0f : 0.0f;
+          }
+        }
+      };
+      switch (int(c[0])) {
+        case 0: run(DiffuseBSDF(albedo)); break;
+        case 1: run(ConductorBSDF(albedo, roughness)); break;
+        case 2: run(RefractiveBSDF(albedo, roughness, ior)); break;
+        case 3: run(RefractiveDielectricBSDF(albedo, roughness, ior)); break;
+        case 4: run(DiffusiveDielectricBSDF(albedo, roughness, ior)); break;
+        case 5: run(BSSRDF(albedo, ior, vec3(1.0f))); break;
+        default: fprintf(stderr, "bxdf: unknown lobe %d\n", int(c[0])); return 2;
+      }
+      out.insert(out.end(), rec, rec + 14);
+    }
+    write_file(argv[3], out.data(), out.size() * 4);
+    printf("{\"cases\": %zu}\n", cases.size() / 16);
+    return 0;
+  }
+  if (cmd == "lightsamples" && argc == 5) {
+    // One query = 6 floats: o, u2, u1.  For every geometry g (scene order) and query q, 13 floats: 0 Shape::sample returned
+    // a value (-1: the shape has no sample(): Cylinder::sample is PINE_UNREACHABLE, geometry.h:148)  1-3 p  4-6 n  7-9 w
+    // 10 distance  11 pdf  12 Shape::pdf(Ray(o, w, 0, distance), p, n); zeros after a 0 or -1.  Then for every light that is
+    // not an AreaLight (scene order) and last the environment light, per query 9 floats: 0 Light::sample returned a value
+    // 1-3 wo  4 distance  5 pdf  6-8 le.
+    Loaded L;
+    load_pscene(argv[2], L);
+    const std::vector<float> qs = read_floats(argv[3]);
+    const size_t nq = qs.size() / 6;
+    std::vector<float> out;
+    for (auto& g : L.scene.geometries)
+      for (size_t i = 0; i < nq; i++) {
+        const float* q = &qs[i * 6];
+        float rec[13] = {};
+        if (g->shape.is<Cylinder>()) {
+          rec[0] = -1.0f;
+        } else if (auto ss = g->sample(vec3(q[0], q[1], q[2]), vec2(q[3], q[4]), q[5])) {
+          rec[0] = 1.0f;
+          rec[1] = ss->p.x, rec[2] = ss->p.y, rec[3] = ss->p.z;
+          rec[4] = ss->n.x, rec[5] = ss->n.y, rec[6] = ss->n.z;
+          rec[7] = ss->w.x, rec[8] = ss->w.y, rec[9] = ss->w.z;
+          rec[10] = ss->distance, rec[11] = ss->pdf;
+          rec[12] = g->pdf(Ray(vec3(q[0], q[1], q[2]), ss->w, 0.0f, ss->distance), ss->p, ss->n);
+        }
+        out.insert(out.end(), rec, rec + 13);
+      }
+    size_t nl = 0;
+    auto light_record = [&](const psl::optional<LightSample>& ls) {
+      float rec[9] = {};
+      if (ls) {
+        rec[0] = 1.0f;
+        rec[1] = ls->wo.x, rec[2] = ls->wo.y, rec[3] = ls->wo.z;
+        rec[4] = ls->distance, rec[5] = ls->pdf;
+        rec[6] = ls->le.x, rec[7] = ls->le.y, rec[8] = ls->le.z;
+      }
+      out.insert(out.end(), rec, rec + 9);
+    };
+    for (auto& light : L.scene.lights) {
+      if (light.is<AreaLight>()) continue;
+      nl++;
+      for (size_t i = 0; i < nq; i++) {
+        const float* q = &qs[i * 6];
+        light_record(light.sample(vec3(q[0], q[1], q[2]), vec2(q[3], q[4]), q[5]));
+      }
+    }
+    if (L.scene.env_light) {
+      nl++;
+      for (size_t i = 0; i < nq; i++) {
+        const float* q = &qs[i * 6];
+        light_record(L.scene.env_light->sample(vec3(q[0], q[1], q[2]), vec2(q[3], q[4])));
+      }
+    }
+    write_file(argv[4], out.data(), out.size() * 4);
+    printf("{\"queries\": %zu, \"geometries\": %zu, \"lights\": %zu}\n", nq, L.scene.geometries.size(), nl);
+    return 0;
   }
   if (cmd == "shapes" && argc == 5) {
     // For every geometry g in the scene and every ray r (8 floats: o, d, tmin, tmax):

@@ -196,6 +196,8 @@ SIGNATURES = {
     "pine_gpu_test_traverse": (C.c_int, [C.c_void_p, C.c_int, c_f_p, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_uint32)]),
     "pine_gpu_scene_accel_bvhs": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int64]),
     "pine_gpu_test_shapes": (C.c_int, [C.c_void_p, C.c_int, c_f_p, C.c_int64, c_f_p, C.c_int64]),
+    "pine_gpu_test_bxdf": (C.c_int, [C.c_int, c_f_p, C.c_int64, c_f_p]),
+    "pine_gpu_test_light_samples": (C.c_int, [C.c_void_p, C.c_int, c_f_p, C.c_int64, c_f_p]),
     "pine_gpu_test_kernel_variants": (C.c_int, [C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int]),
     "pine_gpu_film_finalize_u8": (C.c_int, [c_f_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8)]),
 }

@@ -222,6 +222,18 @@ PINE_HD uint64_t sobol_index_of(const DTables& t, int px, int py, int index) {  
   const uint64_t morton = (left_shift_64x2(uint32_t(py)) << 1) | left_shift_64x2(uint32_t(px));  // vecmath.h:1243-1245
   return (morton << t.sobol_log2_spp) + uint64_t(uint32_t(index));  // start_pixel ORs sample 0 in, start_next_sample increments
 }
+// SobolSampler(spp) on a w x h image: log2_spp = psl::log2i(spp); init(image_size): nbase4_digits =
+// log2i(roundup2(max(w, h))) + (log2_spp + 1) / 2   (sampler.h:127-129, sampler.cpp:81-84)
+PINE_HD void sobol_sampler_params(DTables& t, int spp, int w, int h) {
+  int l2 = 0;
+  while ((2 << l2) <= spp) l2++;
+  int res = 1;
+  while (res < (w > h ? w : h)) res *= 2;
+  int lr = 0;
+  while ((2 << lr) <= res) lr++;
+  t.sobol_log2_spp = l2;
+  t.sobol_digits = lr + (l2 + 1) / 2;
+}
 PINE_HD uint64_t sobol_compute_sample_index(const DTables& t, uint64_t sobol_index, int dimension) {  // sampler.cpp:86-113
   // the 24 permutations of {0,1,2,3} in the reference's order, one per byte-quadruple: digit d of
   // permutation p is (kPerm[p] >> (2 * d)) & 3

@@ -981,16 +981,7 @@ static int upload_sampler_tables(pine_gpu_plan* p, const std::vector<uint8_t>& t
     HIP_OK(hipMemcpy(p->d_halton + head, ht.perms.data(), ht.perms.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
     T.halton_primes = reinterpret_cast<const int*>(p->d_halton), T.halton_perms = reinterpret_cast<const uint16_t*>(p->d_halton + head);
   }
-  // SobolSampler(spp): log2_spp = psl::log2i(spp); init(image_size): nbase4_digits =
-  // log2i(roundup2(max(w, h))) + (log2_spp + 1) / 2   (sampler.h:127-129, sampler.cpp:81-84)
-  int l2 = 0;
-  while ((2 << l2) <= spp) l2++;
-  int res = 1;
-  while (res < std::max(p->S.cam.W, p->S.cam.H)) res *= 2;
-  int lr = 0;
-  while ((2 << lr) <= res) lr++;
-  T.sobol_log2_spp = l2;
-  T.sobol_digits = lr + (l2 + 1) / 2;
+  sobol_sampler_params(T, spp, p->S.cam.W, p->S.cam.H);
   return 0;
 }
 

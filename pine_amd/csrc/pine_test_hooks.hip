@@ -180,6 +180,90 @@ __global__ void test_shapes_kernel(const DShape* shapes, int num_shapes, const f
   o[6] = it.n.x, o[7] = it.n.y, o[8] = it.n.z;
   o[9] = it.uv.x, o[10] = it.uv.y;
 }
+// pine_gpu_test_bxdf: one BSDF lobe call per case (16 floats in, 14 out: the layout of `pine_ref bxdf`, include/pine_gpu.h).
+// The same body runs on the host (device = -1) and as a kernel; F is the path kernels' feature mask.
+constexpr unsigned kBxdfNarrow[6] = {0u, F_UBER, F_SSS, F_UBER, F_UBER, F_SSS};  // the narrowest mask that contains each lobe
+template <unsigned F>
+PINE_HD void test_bxdf_case(const float* c, float* o) {
+  DBxdf b;
+  b.kind = int(c[0]);
+  b.albedo = ld3(c + 1);
+  b.albedo_over_pi = b.albedo / kPi;
+  b.roughness = c[4];
+  b.ior = c[5];
+  b.wi = ld3(c + 6);
+  const f3 wo = ld3(c + 9);
+  const int calls = int(c[15]);
+  for (int k = 0; k < 14; k++) o[k] = 0.0f;
+  if (calls & 1) {
+    const f3 f = bxdf_f<F>(b, wo);
+    o[0] = f.x, o[1] = f.y, o[2] = f.z;
+    o[3] = bxdf_pdf<F>(b, wo);
+  }
+  o[4] = bxdf_is_delta<F>(b) ? 1.0f : 0.0f;
+  if (calls & 2) {
+    // SobolSampler(64) on a 1024 x 1024 image, set up as a plan sets it up; in this mode nothing is read from the tables
+    DTables T{};
+    T.kind = 1;
+    sobol_sampler_params(T, 64, 1024, 1024);
+    DSampler s;
+    s.px = int(c[12]);
+    s.py = int(c[13]);
+    s.index = int(c[14]);
+    s.dimension = 0;
+    DBsdfSample bs;
+    if (bxdf_sample<F, kSmSobol>(b, T, s, bs)) {
+      o[5] = 1.0f;
+      o[6] = bs.wo.x, o[7] = bs.wo.y, o[8] = bs.wo.z;
+      o[9] = bs.f.x, o[10] = bs.f.y, o[11] = bs.f.z;
+      o[12] = bs.pdf;
+      o[13] = bs.is_delta ? 1.0f : 0.0f;
+    }
+  }
+}
+// one thread per entry of idx (idx = NULL: per case)
+template <unsigned F>
+__global__ void __launch_bounds__(64) test_bxdf_kernel(const float* cases, const int* idx, long long n, float* out) {
+  const long long t = blockIdx.x * 64ll + threadIdx.x;
+  if (t >= n) return;
+  const long long i = idx ? idx[t] : t;
+  test_bxdf_case<F>(cases + i * 16, out + i * 14);
+}
+// pine_gpu_test_light_samples: shape_sample + shape_pdf per (geometry, query), light_sample_other per (light, query)
+PINE_HD void test_shape_sample_case(const DShape* S, const float* tri_verts, const float* q, float* o) {
+  for (int k = 0; k < 13; k++) o[k] = 0.0f;
+  if (S->kind == SHAPE_CYLINDER) {  // the reference has no Cylinder::sample (geometry.h:148)
+    o[0] = -1.0f;
+    return;
+  }
+  const f3 p = ld3(q);
+  DShapeSample ss;
+  if (!shape_sample(S, tri_verts, p, f2{q[3], q[4]}, q[5], ss)) return;
+  o[0] = 1.0f;
+  o[1] = ss.p.x, o[2] = ss.p.y, o[3] = ss.p.z;
+  o[4] = ss.n.x, o[5] = ss.n.y, o[6] = ss.n.z;
+  o[7] = ss.w.x, o[8] = ss.w.y, o[9] = ss.w.z;
+  o[10] = ss.distance, o[11] = ss.pdf;
+  o[12] = shape_pdf(S, DRay{p, ss.w, 0.0f, ss.distance}, ss.n);
+}
+PINE_HD void test_light_sample_case(const DLight* L, const float* q, float* o) {
+  for (int k = 0; k < 9; k++) o[k] = 0.0f;
+  f3 w, le;
+  float distance, pdf;
+  if (!light_sample_other(L, ld3(q), f2{q[3], q[4]}, w, distance, pdf, le)) return;
+  o[0] = 1.0f;
+  o[1] = w.x, o[2] = w.y, o[3] = w.z;
+  o[4] = distance, o[5] = pdf;
+  o[6] = le.x, o[7] = le.y, o[8] = le.z;
+}
+__global__ void __launch_bounds__(64) test_light_samples_kernel(const DShape* shapes, int num_shapes, const float* tri_verts, const DLight* lights,
+                                                               int num_lights, const float* queries, long long n, float* out) {
+  const long long t = blockIdx.x * 64ll + threadIdx.x;
+  if (t >= n * (num_shapes + num_lights)) return;
+  const long long k = t / n, i = t % n;
+  if (k < num_shapes) test_shape_sample_case(&shapes[k], tri_verts, queries + i * 6, out + t * 13);
+  else test_light_sample_case(&lights[k - num_shapes], queries + i * 6, out + n * num_shapes * 13 + (t - n * num_shapes) * 9);
+}
 }  // namespace pine_gpu
 
 using namespace pine_gpu;
@@ -461,6 +545,118 @@ int pine_gpu_test_shapes(pine_gpu_scene* scene, int device, const float* rays, i
   hipFree(dr);
   hipFree(dout);
   return 0;
+}
+
+int pine_gpu_test_bxdf(int device, const float* cases, int64_t n, float* out) {
+  if (!cases || !out || n < 0 || n > (1 << 24)) {
+    set_error("bad argument");
+    return -1;
+  }
+  // the cases of each narrow mask, found here: a lobe its mask excludes never reaches a kernel built without it
+  std::vector<int> idx[3];  // 0: no optional lobe, 1: F_UBER, 2: F_SSS
+  for (int64_t i = 0; i < n; i++) {
+    const float lobe = cases[i * 16];
+    if (!(lobe >= 0 && lobe <= 5 && lobe == float(int(lobe)))) {
+      set_error("pine_gpu_test_bxdf: unknown lobe");
+      return -1;
+    }
+    const unsigned m = kBxdfNarrow[int(lobe)];
+    idx[m == 0 ? 0 : m == F_UBER ? 1 : 2].push_back(int(i));
+  }
+  float* const narrow = out + n * 14;
+  if (device < 0) {
+    for (int64_t i = 0; i < n; i++) test_bxdf_case<F_ALL>(cases + i * 16, out + i * 14);
+    for (int i : idx[0]) test_bxdf_case<0u>(cases + size_t(i) * 16, narrow + size_t(i) * 14);
+    for (int i : idx[1]) test_bxdf_case<F_UBER>(cases + size_t(i) * 16, narrow + size_t(i) * 14);
+    for (int i : idx[2]) test_bxdf_case<F_SSS>(cases + size_t(i) * 16, narrow + size_t(i) * 14);
+    return 0;
+  }
+  if (n == 0) return 0;
+  if (need_device(device)) return -1;
+  float *dc = nullptr, *dout = nullptr;
+  int* didx = nullptr;
+  int rc = -1;
+  do {
+    if (hipMalloc((void**)&dc, n * 64) != hipSuccess || hipMalloc((void**)&dout, n * 2 * 56) != hipSuccess || hipMalloc((void**)&didx, n * 4) != hipSuccess) break;
+    if (hipMemcpy(dc, cases, n * 64, hipMemcpyHostToDevice) != hipSuccess || hipMemset(dout, 0, n * 2 * 56) != hipSuccess) break;
+    size_t at = 0;
+    bool ok = true;
+    for (int g = 0; g < 3 && ok; g++) {
+      if (!idx[g].empty()) ok = hipMemcpy(didx + at, idx[g].data(), idx[g].size() * 4, hipMemcpyHostToDevice) == hipSuccess;
+      at += idx[g].size();
+    }
+    if (!ok) break;
+    const auto blocks = [](size_t m) { return dim3(unsigned((m + 63) / 64)); };
+    hipLaunchKernelGGL(test_bxdf_kernel<F_ALL>, blocks(size_t(n)), dim3(64), 0, 0, dc, (const int*)nullptr, (long long)n, dout);
+    float* const dnarrow = dout + n * 14;
+    const int* di = didx;
+    if (!idx[0].empty()) hipLaunchKernelGGL(test_bxdf_kernel<0u>, blocks(idx[0].size()), dim3(64), 0, 0, dc, di, (long long)idx[0].size(), dnarrow);
+    di += idx[0].size();
+    if (!idx[1].empty()) hipLaunchKernelGGL(test_bxdf_kernel<F_UBER>, blocks(idx[1].size()), dim3(64), 0, 0, dc, di, (long long)idx[1].size(), dnarrow);
+    di += idx[1].size();
+    if (!idx[2].empty()) hipLaunchKernelGGL(test_bxdf_kernel<F_SSS>, blocks(idx[2].size()), dim3(64), 0, 0, dc, di, (long long)idx[2].size(), dnarrow);
+    if (hipGetLastError() != hipSuccess || hipMemcpy(out, dout, n * 2 * 56, hipMemcpyDeviceToHost) != hipSuccess) break;
+    rc = 0;
+  } while (0);
+  if (rc) set_error(std::string("pine_gpu_test_bxdf: ") + hipGetErrorString(hipGetLastError()));
+  (void)hipFree(dc);
+  (void)hipFree(dout);
+  (void)hipFree(didx);
+  return rc;
+}
+
+int pine_gpu_test_light_samples(pine_gpu_scene* scene, int device, const float* queries, int64_t n, float* out) {
+  if (!scene || !queries || !out || n < 0 || n > (1 << 20)) {
+    set_error("bad argument");
+    return -1;
+  }
+  SceneHost& H = scene_host(scene);
+  if (!H.accel.built) H.build_accel();  // (a mesh's first triangle and triangle count are written into its record there)
+  std::vector<DShape> shapes;
+  for (auto& g : H.geometries) shapes.push_back(g.shape);
+  std::vector<DLight> lights;
+  for (auto& l : H.lights)
+    if (l.kind != LIGHT_AREA) lights.push_back(l);
+  if (H.has_env) lights.push_back(H.env);
+  const int ns = int(shapes.size()), nl = int(lights.size());
+  const size_t words = size_t(n) * (size_t(ns) * 13 + size_t(nl) * 9);
+  if (device < 0) {
+    float* o = out;
+    for (int k = 0; k < ns; k++)
+      for (int64_t i = 0; i < n; i++, o += 13) test_shape_sample_case(&shapes[size_t(k)], H.accel.tri_verts.data(), queries + i * 6, o);
+    for (int k = 0; k < nl; k++)
+      for (int64_t i = 0; i < n; i++, o += 9) test_light_sample_case(&lights[size_t(k)], queries + i * 6, o);
+    return 0;
+  }
+  if (words == 0) return 0;
+  if (need_device(device)) return -1;
+  DShape* ds = nullptr;
+  DLight* dl = nullptr;
+  float *dt = nullptr, *dq = nullptr, *dout = nullptr;
+  int rc = -1;
+  do {
+    if (hipMalloc((void**)&ds, std::max<size_t>(shapes.size(), 1) * sizeof(DShape)) != hipSuccess ||
+        hipMalloc((void**)&dl, std::max<size_t>(lights.size(), 1) * sizeof(DLight)) != hipSuccess ||
+        hipMalloc((void**)&dt, std::max<size_t>(H.accel.tri_verts.size(), 1) * 4) != hipSuccess ||
+        hipMalloc((void**)&dq, size_t(n) * 24) != hipSuccess || hipMalloc((void**)&dout, words * 4) != hipSuccess)
+      break;
+    if ((ns && hipMemcpy(ds, shapes.data(), shapes.size() * sizeof(DShape), hipMemcpyHostToDevice) != hipSuccess) ||
+        (nl && hipMemcpy(dl, lights.data(), lights.size() * sizeof(DLight), hipMemcpyHostToDevice) != hipSuccess) ||
+        (!H.accel.tri_verts.empty() && hipMemcpy(dt, H.accel.tri_verts.data(), H.accel.tri_verts.size() * 4, hipMemcpyHostToDevice) != hipSuccess) ||
+        hipMemcpy(dq, queries, size_t(n) * 24, hipMemcpyHostToDevice) != hipSuccess)
+      break;
+    const long long total = (long long)n * (ns + nl);
+    hipLaunchKernelGGL(test_light_samples_kernel, dim3(unsigned((total + 63) / 64)), dim3(64), 0, 0, ds, ns, dt, dl, nl, dq, (long long)n, dout);
+    if (hipGetLastError() != hipSuccess || hipMemcpy(out, dout, words * 4, hipMemcpyDeviceToHost) != hipSuccess) break;
+    rc = 0;
+  } while (0);
+  if (rc) set_error(std::string("pine_gpu_test_light_samples: ") + hipGetErrorString(hipGetLastError()));
+  (void)hipFree(ds);
+  (void)hipFree(dl);
+  (void)hipFree(dt);
+  (void)hipFree(dq);
+  (void)hipFree(dout);
+  return rc;
 }
 
 }  // extern "C"

@@ -6,6 +6,7 @@ and the reference's outputs, no reference source) are committed and travel to th
     python tools/make_golden.py            # everything except the two 640x640 statistics
     python tools/make_golden.py --full     # also C1/C2 whole-image statistics (~1 min of CPU)
     python tools/make_golden.py --bvh --vertices   # the reference's BVH + traversal orders, per-vertex path terms
+    python tools/make_golden.py --sampling # BSDF lobes and shape / light sampling per call (tests/test_sampling_fixtures.py)
     python tools/make_golden.py --live     # the reference's films of the oracle tests' cbox and seeded random scenes
 """
 import hashlib
@@ -238,6 +239,57 @@ def vertex_fixture(tmp):
         print(name, info)
 
 
+def _sampling_cases():
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import test_sampling_fixtures as tsf
+    return tsf
+
+
+def bxdf_fixture(tmp):
+    """tests/golden/bxdf_lobes.npz from `pine_ref bxdf`: the seeded cases of tests/test_sampling_fixtures.py and, per case, f / pdf /
+    is_delta / sample of the reference's own BSDF objects.  The NaN cap and the outcome classes are asserted here, on the
+    reference's records, and again by the test."""
+    tsf = _sampling_cases()
+    cases = tsf.bxdf_cases()
+    cp, op = os.path.join(tmp, "cases.bin"), os.path.join(tmp, "bxdf.bin")
+    cases.tofile(cp)
+    run_ref("bxdf", cp, op)
+    rec = np.fromfile(op, dtype=np.float32).reshape(len(cases), 14)
+    led = tsf.bxdf_ledger(cases, rec)
+    for lobe, row in led.items():
+        print(tsf.LOBES[lobe], row)
+    tsf.check_bxdf_ledger(led)
+    np.savez_compressed(os.path.join(OUT, "bxdf_lobes.npz"), cases=cases, records=rec)
+    print("bxdf_lobes.npz", os.path.getsize(os.path.join(OUT, "bxdf_lobes.npz")), "bytes")
+
+
+def lightsample_fixture(tmp):
+    """tests/golden/lightsamples_<scene>.npz from `pine_ref lightsamples`: Shape::sample / Shape::pdf of every geometry and
+    Light::sample of every other light for the seeded queries of tests/test_sampling_fixtures.py."""
+    tsf = _sampling_cases()
+    total = {}
+    for name, build in tsf.SCENES.items():
+        ps = build(scenes).describe()
+        queries = tsf.light_queries(ps)
+        sp, qp, op = (os.path.join(tmp, f) for f in ("s.pscene", "q.bin", "ls.bin"))
+        open(sp, "w").write(ps)
+        queries.tofile(qp)
+        info = json.loads(run_ref("lightsamples", sp, qp, op).strip().splitlines()[-1])
+        ng, nl, n = info["geometries"], info["lights"], len(queries)
+        assert (ng, nl) == (len(tsf.parse_shapes(ps)[0]), tsf.parse_shapes(ps)[1])
+        out = np.fromfile(op, dtype=np.float32)
+        srec, lrec = out[:n * 13 * ng].reshape(ng, n, 13), out[n * 13 * ng:].reshape(nl, n, 9)
+        for k, row in tsf.shape_ledger(ps, srec).items():
+            t = total.setdefault(k, dict.fromkeys(row, 0))
+            for key, v in row.items():
+                t[key] += v
+        np.savez_compressed(os.path.join(OUT, f"lightsamples_{name}.npz"), pscene=np.array(ps), queries=queries, shape_records=srec, light_records=lrec)
+        print(name, info, os.path.getsize(os.path.join(OUT, f"lightsamples_{name}.npz")), "bytes")
+    for k, row in total.items():
+        print(k, row)
+    tsf.check_shape_ledger(total)
+
+
 def gltf_fixture(tmp):
     """SURVEY.md 8(f)4 mesh import: tests/golden/import_test.glb (tools/make_test_glb.py) through the reference's OWN importer
     (`pine_ref gltf`: load_scene -> scene_from_gltf, fileio.cpp:146-330) and PathIntegrator(BVH) -> whole-film statistics."""
@@ -308,6 +360,11 @@ def main():
     if "--live" in sys.argv:
         with tempfile.TemporaryDirectory() as tmp:
             live_fixture(tmp)
+        return
+    if "--sampling" in sys.argv:
+        with tempfile.TemporaryDirectory() as tmp:
+            bxdf_fixture(tmp)
+            lightsample_fixture(tmp)
         return
     if "--gltf" in sys.argv:
         with tempfile.TemporaryDirectory() as tmp:
