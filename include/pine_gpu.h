@@ -543,6 +543,23 @@ int pine_gpu_test_bxdf(int device, const float* cases_host, int64_t n, float* ou
  * tmax = distance and that n -- then per (light, query) 9 floats: 0 sampled  1-3 w  4 distance  5 pdf  6-8 le.  Zeros after
  * a 0 or -1.  device = -1: the host build of the same functions. */
 int pine_gpu_test_light_samples(pine_gpu_scene*, int device, const float* queries_host, int64_t n, float* out_host);
+/* The shading-node programs of the scene's materials, as plan creation compiles them (needs no GPU): num_materials, num_ops,
+ * then per material prog[4] (index of the first op of the program of albedo, roughness, metallic, transmission / ior; -1: the
+ * parameter is a literal of the record), then per op 4 words: opcode, x, y, z (float bits).  Returns the number of words (they
+ * are written when out is not NULL and capacity_words suffices), or < 0: a node tree needs more than the evaluator's stack. */
+int64_t pine_gpu_test_node_programs(pine_gpu_scene*, int32_t* out, int64_t capacity_words);
+/* The material-to-parameters step, for tests/test_node_fixtures.py: compiles the node programs, then material_params of every
+ * material (scene order) at n queries of 8 floats (p, n, uv).  out_host: per (material, query) 10 floats -- 0-2 albedo
+ * 3-5 albedo / Pi  6 roughness  7 metallic  8 transmission  9 ior.  device = -1: the host build of the same functions. */
+int pine_gpu_test_material_params(pine_gpu_scene*, int device, const float* queries_host, int64_t n, float* out_host);
+/* ... and the parameters-to-lobe step, choose_lobe (device code only: device >= 0).  One case = 16 floats (integers as exactly
+ * representable floats): 0 material index (no Emissive)  1-3 p  4-6 n  7 8 uv  9-11 wi (world)  12 diffused  13 14 sampler
+ * pixel (< 1024)  15 sample index (< 64).  The sampler is SobolSampler(64) on a 1024 x 1024 image at that pixel and sample,
+ * the pixel's RNG is seeded as a render seeds it for that pixel.  out_host: 2 * n records of 8 floats -- n with after_walk = 0
+ * (Material::sample_bxdf of the reference), then n with after_walk = 1 (the vertex resumes after its BSSRDF walk): 0 lobe
+ * (BxdfKind order)  1-3 albedo  4 roughness  5 ior (0 where the lobe has no such member)  6 the sampler's dimension afterwards
+ * 7 the next float of the pixel's RNG afterwards. */
+int pine_gpu_test_choose_lobe(pine_gpu_scene*, int device, const float* cases_host, int64_t n, float* out_host);
 /* The precompiled path-kernel variants (pine_variants.h) in the order of the host's first-fit search: kind 0 the stage-queued
  * kernel, 1 the megakernel.  Up to `cap` entries of features (F_* bits), ctx (path contexts per workgroup; 0 for the
  * megakernel) and order; any of the arrays may be NULL.  Returns the number of variants, < 0 on error.  Needs no GPU.

@@ -140,6 +140,25 @@ def light_samples(pscene: str, queries: np.ndarray, n_geoms: int, n_lights: int)
     return out[:n * 13 * n_geoms].reshape(n_geoms, n, 13), out[n * 13 * n_geoms:].reshape(n_lights, n, 9)
 
 
+def node_evals(pscene: str, queries: np.ndarray, n_materials: int):
+    """queries[n,8] float32 (p, n, uv) -> records[n_materials,n,7] float32 in the layout of `pine_ref nodes`"""
+    queries = np.ascontiguousarray(queries, np.float32).reshape(-1, 8)
+    out = np.zeros((n_materials, len(queries), 7), np.float32)
+    rc = lib().oracle_node_evals(pscene.encode(), queries.ctypes.data_as(C.c_void_p), C.c_int64(len(queries)),
+                                 out.ctypes.data_as(C.c_void_p), C.c_int64(out.size))
+    assert rc == 0, rc
+    return out
+
+
+def lobe_choice(pscene: str, cases: np.ndarray):
+    """cases[n,16] float32 (layout of `pine_ref lobes`) -> records[n,8] float32"""
+    cases = np.ascontiguousarray(cases, np.float32).reshape(-1, 16)
+    out = np.zeros((len(cases), 8), np.float32)
+    rc = lib().oracle_lobe_choice(pscene.encode(), cases.ctypes.data_as(C.c_void_p), C.c_int64(len(cases)), out.ctypes.data_as(C.c_void_p))
+    assert rc == 0, rc
+    return out
+
+
 def have_ref():
     return os.path.exists(REF_BIN)
 

@@ -1904,6 +1904,74 @@ struct Material {
   float ior_at(const NodeEvalCtx& c) const { return n_ior >= 0 ? table->evalf(n_ior, c) : ior; }
 };
 
+// Material::sample_bxdf without the frame (material.h:30-131, material.cpp:9-28): the lobe a material answers with at a
+// surface point.  BxdfSampleCtx (bxdf.h:10-21): min_roughness only once diffused.
+BXDF material_sample_bxdf(const Material& mat, const NodeEvalCtx& nc, vec3 wi, vec3 n, bool diffused, Sampler& sampler) {
+  const float min_roughness = diffused ? 0.6f : 0.0f;
+  BXDF bxdf;
+  switch (mat.kind) {  // material.h:30-131, material.cpp:9-28
+    case M_DIFFUSE:
+      bxdf.kind = BX_DIFFUSE;
+      bxdf.albedo = mat.albedo_at(nc);
+      break;
+    case M_METAL:  // material.h:39-50
+      bxdf.kind = BX_CONDUCTOR;
+      bxdf.albedo = mat.albedo_at(nc);
+      bxdf.roughness = fmax_(mat.roughness_at(nc), min_roughness);
+      break;
+    case M_GLOSSY:  // material.h:52-64
+      bxdf.kind = BX_DIFF_DIEL;
+      bxdf.albedo = mat.albedo_at(nc);
+      bxdf.roughness = fmax_(mat.roughness_at(nc), min_roughness);
+      bxdf.ior = mat.ior_at(nc);
+      break;
+    case M_GLASS:  // material.h:66-78
+      bxdf.kind = BX_REFR_DIEL;
+      bxdf.albedo = mat.albedo_at(nc);
+      bxdf.roughness = fmax_(mat.roughness_at(nc), min_roughness);
+      bxdf.ior = mat.ior_at(nc);
+      break;
+    case M_UBER:
+      if (with_probability(mat.metallic_at(nc), sampler)) {
+        bxdf.kind = BX_CONDUCTOR;
+        bxdf.albedo = mat.albedo_at(nc);
+        bxdf.roughness = mat.roughness_at(nc);
+      } else if (with_probability(mat.transmission_at(nc), sampler)) {
+        bxdf.kind = BX_REFR_DIEL;
+        bxdf.albedo = mat.albedo_at(nc);
+        bxdf.roughness = mat.roughness_at(nc);
+        bxdf.ior = mat.ior;
+      } else {
+        bxdf.kind = BX_DIFF_DIEL;
+        bxdf.albedo = mat.albedo_at(nc);
+        bxdf.roughness = mat.roughness_at(nc);
+        bxdf.ior = mat.ior;
+      }
+      break;
+    case M_SUBSURFACE: {
+      const float ior = 1.4f;  // material.h:110
+      float fr = FrDielectric(dot(wi, n), ior);
+      if (sampler.get1d() < fr) {
+        bxdf.kind = BX_REFRACTIVE;
+        bxdf.albedo = mat.color;
+        bxdf.roughness = fmax_(mat.roughness, min_roughness);
+        bxdf.ior = ior;
+      } else if (diffused) {
+        bxdf.kind = BX_DIFFUSE;
+        bxdf.albedo = mat.color;
+      } else {
+        bxdf.kind = BX_BSSRDF;
+        bxdf.albedo = mat.color;
+        bxdf.ior = ior;
+        bxdf.sigma_s = mat.sigma_s;
+      }
+      break;
+    }
+    default: break;
+  }
+  return bxdf;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Geometry variant + Scene
 // ------------------------------------------------------------------------------------------------
@@ -3031,72 +3099,11 @@ struct Integrator {
     }
     if (pv.length + 1 >= max_path_length) return result;  // path.cpp:89
 
-    // BxdfSampleCtx (bxdf.h:10-21): copies p,n,uv now; min_roughness only once diffused
+    // BxdfSampleCtx (bxdf.h:10-21): copies p,n,uv now
     bool diffused = pv.diffuse_length > 0;
-    float min_roughness = diffused ? 0.6f : 0.0f;
     vec3 bc_p = it.p, bc_n = it.n;
-    BXDF bxdf;
     const NodeEvalCtx nc{it.p, it.n, it.uv};  // BxdfSampleCtx -> NodeEvalCtx(it) (bxdf.h:10-21, node.h:13-20)
-    switch (mat.kind) {  // material.h:30-131, material.cpp:9-28
-      case M_DIFFUSE:
-        bxdf.kind = BX_DIFFUSE;
-        bxdf.albedo = mat.albedo_at(nc);
-        break;
-      case M_METAL:  // material.h:39-50
-        bxdf.kind = BX_CONDUCTOR;
-        bxdf.albedo = mat.albedo_at(nc);
-        bxdf.roughness = fmax_(mat.roughness_at(nc), min_roughness);
-        break;
-      case M_GLOSSY:  // material.h:52-64
-        bxdf.kind = BX_DIFF_DIEL;
-        bxdf.albedo = mat.albedo_at(nc);
-        bxdf.roughness = fmax_(mat.roughness_at(nc), min_roughness);
-        bxdf.ior = mat.ior_at(nc);
-        break;
-      case M_GLASS:  // material.h:66-78
-        bxdf.kind = BX_REFR_DIEL;
-        bxdf.albedo = mat.albedo_at(nc);
-        bxdf.roughness = fmax_(mat.roughness_at(nc), min_roughness);
-        bxdf.ior = mat.ior_at(nc);
-        break;
-      case M_UBER:
-        if (with_probability(mat.metallic_at(nc), sampler)) {
-          bxdf.kind = BX_CONDUCTOR;
-          bxdf.albedo = mat.albedo_at(nc);
-          bxdf.roughness = mat.roughness_at(nc);
-        } else if (with_probability(mat.transmission_at(nc), sampler)) {
-          bxdf.kind = BX_REFR_DIEL;
-          bxdf.albedo = mat.albedo_at(nc);
-          bxdf.roughness = mat.roughness_at(nc);
-          bxdf.ior = mat.ior;
-        } else {
-          bxdf.kind = BX_DIFF_DIEL;
-          bxdf.albedo = mat.albedo_at(nc);
-          bxdf.roughness = mat.roughness_at(nc);
-          bxdf.ior = mat.ior;
-        }
-        break;
-      case M_SUBSURFACE: {
-        const float ior = 1.4f;  // material.h:110
-        float fr = FrDielectric(dot(wi, bc_n), ior);
-        if (sampler.get1d() < fr) {
-          bxdf.kind = BX_REFRACTIVE;
-          bxdf.albedo = mat.color;
-          bxdf.roughness = fmax_(mat.roughness, min_roughness);
-          bxdf.ior = ior;
-        } else if (diffused) {
-          bxdf.kind = BX_DIFFUSE;
-          bxdf.albedo = mat.color;
-        } else {
-          bxdf.kind = BX_BSSRDF;
-          bxdf.albedo = mat.color;
-          bxdf.ior = ior;
-          bxdf.sigma_s = mat.sigma_s;
-        }
-        break;
-      }
-      default: break;
-    }
+    BXDF bxdf = material_sample_bxdf(mat, nc, wi, bc_n, diffused, sampler);
     bxdf.wi = it.to_local(wi);  // material.h:119
 
     vec3 beta(1.0f);
@@ -3874,6 +3881,57 @@ int oracle_light_samples(const char* pscene, const float* queries, int64_t n, fl
     }
   }
   return k == capacity ? 0 : -1;
+}
+
+int oracle_node_evals(const char* pscene, const float* queries, int64_t n, float* out, int64_t capacity) {
+  Scene scene;
+  if (!parse_pscene(pscene, scene)) return 2;
+  if (capacity != int64_t(scene.materials.size()) * n * 7) return -1;
+  float* o = out;
+  for (const Material& m : scene.materials)
+    for (int64_t i = 0; i < n; i++, o += 7) {
+      const float* q = queries + i * 8;
+      const NodeEvalCtx c{vec3(q[0], q[1], q[2]), vec3(q[3], q[4], q[5]), vec2(q[6], q[7])};
+      for (int k = 0; k < 7; k++) o[k] = 0.0f;
+      const vec3 a = m.albedo_at(c);
+      o[0] = a.x, o[1] = a.y, o[2] = a.z;
+      if (m.kind == M_EMISSIVE || m.kind == M_DIFFUSE) continue;
+      o[3] = m.roughness_at(c);
+      if (m.kind == M_UBER) o[4] = m.metallic_at(c), o[5] = m.transmission_at(c), o[6] = m.ior;
+      if (m.kind == M_GLOSSY || m.kind == M_GLASS) o[6] = m.ior_at(c);
+      if (m.kind == M_SUBSURFACE) o[6] = 1.4f;  // material.h:110
+    }
+  return 0;
+}
+
+int oracle_lobe_choice(const char* pscene, const float* cases, int64_t n, float* out) {
+  Scene scene;
+  if (!parse_pscene(pscene, scene)) return 2;
+  for (int64_t i = 0; i < n; i++) {
+    const float* c = cases + i * 16;
+    float* o = out + i * 8;
+    if (!(c[0] >= 0 && c[0] < float(scene.materials.size())) || scene.materials[size_t(c[0])].kind == M_EMISSIVE) {
+      g_error = "oracle_lobe_choice: a case names no material that has a lobe";
+      return 2;
+    }
+    const Material& m = scene.materials[size_t(c[0])];
+    const vec3 nn(c[4], c[5], c[6]);
+    const NodeEvalCtx nc{vec3(c[1], c[2], c[3]), nn, vec2(c[7], c[8])};
+    Sampler sampler;  // SobolSampler(64) on a 1024 x 1024 image, as `pine_ref lobes` starts it
+    sampler.kind = SAMPLER_SOBOL;
+    sampler.spp = 64;
+    sampler.init(1024, 1024);
+    sampler.start_pixel(int(c[13]), int(c[14]), 0);
+    for (int k = 0; k < int(c[15]); k++) sampler.start_next_sample();
+    const BXDF b = material_sample_bxdf(m, nc, vec3(c[9], c[10], c[11]), nn, c[12] != 0.0f, sampler);
+    o[0] = float(b.kind);
+    o[1] = b.albedo.x, o[2] = b.albedo.y, o[3] = b.albedo.z;
+    o[4] = b.kind == BX_DIFFUSE || b.kind == BX_BSSRDF ? 0.0f : b.roughness;
+    o[5] = b.kind == BX_DIFFUSE || b.kind == BX_CONDUCTOR ? 0.0f : b.ior;
+    o[6] = float(sampler.dimension);
+    o[7] = sampler.randf();
+  }
+  return 0;
 }
 
 }  // extern "C"

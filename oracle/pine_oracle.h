@@ -68,6 +68,12 @@ int oracle_bxdf(const float* cases, int64_t n, float* out);
 /* Shape::sample / Shape::pdf of every geometry and Light::sample of every other light, in the layout of `pine_ref lightsamples`:
  * 6 floats per query in; 13 floats per (geometry, query), then 9 per (light, query) out.  capacity must be exactly that. */
 int oracle_light_samples(const char* pscene, const float* queries, int64_t n, float* out, int64_t capacity);
+/* Every node member of every material (description order) at n queries of 8 floats (p, n, uv), in the layout of `pine_ref nodes`:
+ * 7 floats per (material, query) -- albedo, roughness, metallic, transmission, ior; 0 where the material has no such member.
+ * Node trees are evaluated recursively, nothing is folded.  capacity must be exactly materials * n * 7. */
+int oracle_node_evals(const char* pscene, const float* queries, int64_t n, float* out, int64_t capacity);
+/* Material::sample_bxdf per case, in the layout of `pine_ref lobes`: 16 floats per case in, 8 out. */
+int oracle_lobe_choice(const char* pscene, const float* cases, int64_t n, float* out);
 /* libm-compatible sinf/cosf restatement check helpers (see pine_amd/csrc/pine_libm.h). */
 const char* oracle_last_error(void);
 

@@ -28,6 +28,10 @@
 //                                        case (16 floats) -> one record (14 floats); the u's of sample() come from a SobolSampler
 //   pine_ref lightsamples <scene.pscene> <queries.bin> <out.bin>   Shape::sample + Shape::pdf of every geometry and Light::sample
 //                                        of every other light for every query (o, u2, u1)
+//   pine_ref nodes   <scene.pscene> <queries.bin> <out.bin>   every node member of every material (description order), evaluated
+//                                        through Mnode::eval(NodeEvalCtx{p, n, uv}) for every query (8 floats: p, n, uv)
+//   pine_ref lobes   <scene.pscene> <cases.bin> <out.bin>   Material::sample_bxdf(BxdfSampleCtx, sampler) per case: which lobe came
+//                                        back, its members, and what it drew from the sampler and from the pixel's RNG
 //   pine_ref prl     <literal>...        psl::stof / stoi / to_string of each literal, and the constant
 //                                        expressions of a cbox-class script evaluated with psl::stof values
 //                                        (pins the PRL front-end's literal and vector arithmetic)
@@ -56,6 +60,7 @@
 #include <sstream>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 namespace pine {
@@ -77,6 +82,7 @@ static vec3 rd3(std::istream& in) {
 struct Loaded {
   Scene scene;
   int W = 0, H = 0;
+  std::vector<std::string> material_order;  // Scene::materials is a map by name: the description's order is kept here
 };
 
 static void load_pscene(const char* path, Loaded& out) {
@@ -165,6 +171,7 @@ static void load_pscene(const char* path, Loaded& out) {
     } else if (kw == "material") {
       std::string name, kind;
       in >> name >> kind;
+      out.material_order.push_back(name);
       int a, r, m, t, i;
       if (kind == "diffuse_n") {
         in >> a;
@@ -348,6 +355,8 @@ template struct Rob<TagTbvh, &BVH::tbvh>;
 template struct Rob<TagLbvh, &BVH::lbvh>;
 template struct Rob<TagIndices, &BVH::indices>;
 template struct Rob<TagNodes, &BVHImpl::nodes>;
+struct TagSobolDimension { friend constexpr auto rob(TagSobolDimension); };
+template struct Rob<TagSobolDimension, &SobolSampler::dimension>;
 
 // Canonical pre-order stream of one BVHImpl (independent of how nodes are numbered): an inner node is its two child boxes
 // (12 floats: lower, upper of child 0, then of child 1) followed by the two children; a child is either the word
@@ -917,6 +926,87 @@ int main(int argc, char** argv) {
     }
     write_file(argv[4], out.data(), out.size() * 4);
     printf("{\"queries\": %zu, \"geometries\": %zu, \"lights\": %zu}\n", nq, L.scene.geometries.size(), nl);
+    return 0;
+  }
+  if (cmd == "nodes" && argc == 5) {
+    // One query = 8 floats: p, n, uv.  For every material m (description order) and query q, 7 floats: 0-2 albedo (Emissive:
+    // color)  3 roughness  4 metallic  5 transmission  6 ior -- each the material's own public member evaluated at
+    // NodeEvalCtx{p, n, uv} (Uber's and Subsurface's ior are plain floats); a member the material does not have is 0.
+    Loaded L;
+    load_pscene(argv[2], L);
+    const std::vector<float> qs = read_floats(argv[3]);
+    const size_t nq = qs.size() / 8;
+    std::vector<float> out;
+    for (const std::string& name : L.material_order) {
+      const Material& mat = *L.scene.materials[psl::string(name.c_str())];
+      for (size_t i = 0; i < nq; i++) {
+        const float* q = &qs[i * 8];
+        const NodeEvalCtx c(vec3(q[0], q[1], q[2]), vec3(q[3], q[4], q[5]), vec2(q[6], q[7]));
+        float rec[7] = {};
+        mat.dispatch([&](const auto& x) {
+          using T = std::decay_t<decltype(x)>;
+          vec3 a;
+          if constexpr (std::is_same_v<T, EmissiveMaterial>) a = x.color.eval(c);
+          else a = x.albedo.eval(c);
+          rec[0] = a.x, rec[1] = a.y, rec[2] = a.z;
+          if constexpr (requires { x.roughness; }) rec[3] = x.roughness.eval(c);
+          if constexpr (requires { x.metallic; }) rec[4] = x.metallic.eval(c);
+          if constexpr (requires { x.transmission; }) rec[5] = x.transmission.eval(c);
+          if constexpr (requires { x.ior; }) {
+            if constexpr (std::is_same_v<std::decay_t<decltype(x.ior)>, float>) rec[6] = x.ior;
+            else rec[6] = x.ior.eval(c);
+          }
+        });
+        out.insert(out.end(), rec, rec + 7);
+      }
+    }
+    write_file(argv[4], out.data(), out.size() * 4);
+    printf("{\"queries\": %zu, \"materials\": %zu}\n", nq, L.material_order.size());
+    return 0;
+  }
+  if (cmd == "lobes" && argc == 5) {
+    // One case = 16 floats (integers as exactly representable floats): 0 material (description order; no Emissive: its
+    // sample_bxdf is PINE_UNREACHABLE)  1-3 p  4-6 n  7 8 uv  9-11 wi (world)  12 diffused  13 14 sampler pixel  15 sample index.
+    // The sampler is SobolSampler(64) on a 1024 x 1024 image started as in `bxdf`; start_pixel(p, 0) also seeds the pixel's
+    // RNG, as PathIntegrator::render does (path.cpp:32).  One record = 8 floats: 0 the alternative of the BXDF variant
+    // (bxdf.h:140-141)  1-3 its albedo  4 its roughness  5 its ior (0 where the lobe has no such member)  6 the sampler's
+    // dimension afterwards  7 the next randf() of the pixel's RNG afterwards.
+    Loaded L;
+    load_pscene(argv[2], L);
+    const std::vector<float> cases = read_floats(argv[3]);
+    std::vector<float> out;
+    for (size_t k = 0; k + 16 <= cases.size(); k += 16) {
+      const float* c = &cases[k];
+      if (!(c[0] >= 0 && c[0] < float(L.material_order.size()))) {
+        fprintf(stderr, "lobes: case %zu names no material\n", k / 16);
+        return 2;
+      }
+      const Material& mat = *L.scene.materials[psl::string(L.material_order[size_t(c[0])].c_str())];
+      if (mat.is<EmissiveMaterial>()) {
+        fprintf(stderr, "lobes: case %zu names an Emissive material\n", k / 16);
+        return 2;
+      }
+      SurfaceInteraction it(vec3(c[1], c[2], c[3]), vec3(c[4], c[5], c[6]), vec2(c[7], c[8]));
+      auto bc = BxdfSampleCtx(it, vec3(c[9], c[10], c[11]), 0.6f, c[12] != 0.0f);
+      Sampler sampler = Sampler(SobolSampler(64));
+      sampler.init(vec2i(1024, 1024));
+      sampler.start_pixel(vec2i(int(c[13]), int(c[14])), 0);
+      for (int i = 0; i < int(c[15]); i++) sampler.start_next_sample();
+      const BXDF bxdf = mat.sample_bxdf(bc, sampler);
+      float rec[8] = {};
+      rec[0] = bxdf.is<DiffuseBSDF>() ? 0.0f : bxdf.is<ConductorBSDF>() ? 1.0f : bxdf.is<RefractiveBSDF>() ? 2.0f
+               : bxdf.is<RefractiveDielectricBSDF>() ? 3.0f : bxdf.is<DiffusiveDielectricBSDF>() ? 4.0f : 5.0f;
+      bxdf.dispatch([&](const auto& x) {
+        rec[1] = x.albedo.x, rec[2] = x.albedo.y, rec[3] = x.albedo.z;
+        if constexpr (requires { x.roughness; }) rec[4] = x.roughness;
+        if constexpr (requires { x.ior; }) rec[5] = x.ior;
+      });
+      rec[6] = float(sampler.as<SobolSampler>().*rob(TagSobolDimension{}));
+      rec[7] = sampler.randf();
+      out.insert(out.end(), rec, rec + 8);
+    }
+    write_file(argv[4], out.data(), out.size() * 4);
+    printf("{\"cases\": %zu}\n", cases.size() / 16);
     return 0;
   }
   if (cmd == "shapes" && argc == 5) {

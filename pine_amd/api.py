@@ -131,7 +131,12 @@ class Node:
     def __rtruediv__(self, o): return self._bin("/", o, True)
     def __pow__(self, o): return self._bin("^", o)
     def __neg__(self): return Node("un", "-", self, is_vec3=self.is_vec3)
-    def __getitem__(self, n): return Node("comp", self, int(n))
+    def __getitem__(self, n):
+        if not 0 <= int(n) <= 2:  # node.h:181-182 (and what ends an iteration over a node, which would never stop)
+            raise PineError(f"NodeComponent's second parameter should be 0, 1, or 2, but get {int(n)}")
+        if not self.is_vec3:
+            raise PineError("a Node3f is required here")
+        return Node("comp", self, int(n))
 
     def _instantiate(self, scene, memo):
         if id(self) in memo:
@@ -483,6 +488,8 @@ class Scene:
 
     def _add_material(self, name, m):
         n = name.encode()
+        if isinstance(m, (Emissive, Subsurface)) and any(isinstance(x, Node) for x in vars(m).values()):
+            raise PineError(type(m).__name__ + ": a constant colour / albedo / roughness is required (no node-driven entry point)")
         if isinstance(m, Emissive):
             return check(lib.pine_gpu_scene_add_material_emissive(self._h, n, _v3(m.color)), "Emissive")
         memo = {}

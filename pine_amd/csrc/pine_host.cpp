@@ -145,6 +145,56 @@ int SceneHost::find_material(const char* name) const {
   return -1;
 }
 // ---- shading nodes (node.h:13-297) ----------------------------------------------------------------
+static float node_un(char op, float x) {  // NodeUnary::eval node.h:158-175
+  switch (op) {
+    case '-': return -x;
+    case 'a': return fabsf(x);
+    case 's': return x * x;
+    case 'r': return sqrtf(x);
+    default: return x - floorf(x);  // psl::fract math.h:152-154
+  }
+}
+static float node_bin(char op, float x, float y) {  // NodeBinary::eval node.h:134-150
+  switch (op) {
+    case '+': return x + y;
+    case '-': return x - y;
+    case '*': return x * y;
+    case '/': return x / y;
+    default: return powf(x, y);
+  }
+}
+// value of a node whose operands do not read the surface, from their values (floats come back as splats)
+static f3 fold_node(const SceneHost& S, const HostNode& k) {
+  switch (k.kind) {
+    case HostNode::ConstF: return f3{k.f, k.f, k.f};
+    case HostNode::Const3: return k.v;
+    case HostNode::BinF:
+    case HostNode::Bin3: {
+      const f3 x = S.node_fold(k.a), y = S.node_fold(k.b);
+      return f3{node_bin(k.op, x.x, y.x), node_bin(k.op, x.y, y.y), node_bin(k.op, x.z, y.z)};
+    }
+    case HostNode::UnF:
+    case HostNode::Un3: {
+      const f3 x = S.node_fold(k.a);
+      return f3{node_un(k.op, x.x), node_un(k.op, x.y), node_un(k.op, x.z)};
+    }
+    case HostNode::Comp: {
+      const float v = get(S.node_fold(k.a), k.n);
+      return f3{v, v, v};
+    }
+    case HostNode::ToVec3:
+      if (k.b < 0) return S.node_fold(k.a);
+      return f3{S.node_fold(k.a).x, S.node_fold(k.b).x, S.node_fold(k.c).x};
+    case HostNode::Checker: {
+      const f3 q = S.node_fold(k.a);
+      const f3 x{node_un('f', q.x) - k.f, node_un('f', q.y) - k.f, node_un('f', q.z) - k.f};
+      const float v = float(x.x * x.y * x.z > 0);
+      return f3{v, v, v};
+    }
+    case HostNode::Splat: return S.node_fold(k.a);
+    default: return f3{0, 0, 0};
+  }
+}
 int SceneHost::add_node(const HostNode& n) {
   auto ok = [&](int id, bool want_vec3) {
     if (id < 0 || id >= int(nodes.size())) {
@@ -194,68 +244,18 @@ int SceneHost::add_node(const HostNode& n) {
     set_error("node: unknown unary operator");
     return -1;
   }
-  nodes.push_back(n);
+  HostNode k = n;
+  k.reads_surface = k.kind == HostNode::Position || k.kind == HostNode::Normal || k.kind == HostNode::UV;
+  for (int c : {k.a, k.b, k.c})
+    if (c >= 0 && node_reads_surface(c)) k.reads_surface = true;
+  if (!k.reads_surface) k.folded = fold_node(*this, k);
+  nodes.push_back(k);
   return int(nodes.size()) - 1;
 }
-bool SceneHost::node_reads_surface(int id) const {
-  const HostNode& k = nodes[size_t(id)];
-  if (k.kind == HostNode::Position || k.kind == HostNode::Normal || k.kind == HostNode::UV) return true;
-  for (int c : {k.a, k.b, k.c})
-    if (c >= 0 && node_reads_surface(c)) return true;
-  return false;
-}
-static float node_un(char op, float x) {  // NodeUnary::eval node.h:158-175
-  switch (op) {
-    case '-': return -x;
-    case 'a': return fabsf(x);
-    case 's': return x * x;
-    case 'r': return sqrtf(x);
-    default: return x - floorf(x);  // psl::fract math.h:152-154
-  }
-}
-static float node_bin(char op, float x, float y) {  // NodeBinary::eval node.h:134-150
-  switch (op) {
-    case '+': return x + y;
-    case '-': return x - y;
-    case '*': return x * y;
-    case '/': return x / y;
-    default: return powf(x, y);
-  }
-}
-f3 SceneHost::node_fold(int id) const {  // floats come back as splats
-  const HostNode& k = nodes[size_t(id)];
-  switch (k.kind) {
-    case HostNode::ConstF: return f3{k.f, k.f, k.f};
-    case HostNode::Const3: return k.v;
-    case HostNode::BinF:
-    case HostNode::Bin3: {
-      const f3 x = node_fold(k.a), y = node_fold(k.b);
-      return f3{node_bin(k.op, x.x, y.x), node_bin(k.op, x.y, y.y), node_bin(k.op, x.z, y.z)};
-    }
-    case HostNode::UnF:
-    case HostNode::Un3: {
-      const f3 x = node_fold(k.a);
-      return f3{node_un(k.op, x.x), node_un(k.op, x.y), node_un(k.op, x.z)};
-    }
-    case HostNode::Comp: {
-      const float v = get(node_fold(k.a), k.n);
-      return f3{v, v, v};
-    }
-    case HostNode::ToVec3:
-      if (k.b < 0) return node_fold(k.a);
-      return f3{node_fold(k.a).x, node_fold(k.b).x, node_fold(k.c).x};
-    case HostNode::Checker: {
-      const f3 q = node_fold(k.a);
-      const f3 x{node_un('f', q.x) - k.f, node_un('f', q.y) - k.f, node_un('f', q.z) - k.f};
-      const float v = float(x.x * x.y * x.z > 0);
-      return f3{v, v, v};
-    }
-    case HostNode::Splat: return node_fold(k.a);
-    default: return f3{0, 0, 0};
-  }
-}
-// postfix flattening of one node tree; returns the maximum stack depth, or -1
+// postfix flattening of one node tree; returns the maximum stack depth, or -1 -- at once where the tree needs more than
+// kNodeStack slots: every node pushes a value, and a tree of shared operands has exponentially many to walk
 static int emit_program(const SceneHost& S, int id, std::vector<DNodeOp>& ops, int depth) {
+  if (depth >= kNodeStack) return -1;
   const HostNode& k = S.nodes[size_t(id)];
   auto push = [&](int op, float x = 0, float y = 0, float z = 0) { ops.push_back(DNodeOp{op, x, y, z}); };
   if (!S.node_reads_surface(id)) {  // constant subtree: one literal
@@ -272,8 +272,10 @@ static int emit_program(const SceneHost& S, int id, std::vector<DNodeOp>& ops, i
     case HostNode::UV: push(N_UV); break;
     case HostNode::BinF:
     case HostNode::Bin3: {
-      const int m1 = emit_program(S, k.a, ops, depth), m2 = emit_program(S, k.b, ops, depth + 1);
-      if (m1 < 0 || m2 < 0) return -1;
+      const int m1 = emit_program(S, k.a, ops, depth);
+      if (m1 < 0) return -1;
+      const int m2 = emit_program(S, k.b, ops, depth + 1);
+      if (m2 < 0) return -1;
       push(binop(k.op));
       m = std::max(m1, m2);
       break;
@@ -281,25 +283,31 @@ static int emit_program(const SceneHost& S, int id, std::vector<DNodeOp>& ops, i
     case HostNode::UnF:
     case HostNode::Un3:
       m = emit_program(S, k.a, ops, depth);
+      if (m < 0) return -1;
       push(unop(k.op));
       break;
     case HostNode::Comp:
       m = emit_program(S, k.a, ops, depth);
+      if (m < 0) return -1;
       push(N_COMP, float(k.n));
       break;
     case HostNode::ToVec3:
       if (k.b < 0) {
         m = emit_program(S, k.a, ops, depth);  // splat already
       } else {
-        const int m1 = emit_program(S, k.a, ops, depth), m2 = emit_program(S, k.b, ops, depth + 1),
-                  m3 = emit_program(S, k.c, ops, depth + 2);
-        if (m1 < 0 || m2 < 0 || m3 < 0) return -1;
+        const int m1 = emit_program(S, k.a, ops, depth);
+        if (m1 < 0) return -1;
+        const int m2 = emit_program(S, k.b, ops, depth + 1);
+        if (m2 < 0) return -1;
+        const int m3 = emit_program(S, k.c, ops, depth + 2);
+        if (m3 < 0) return -1;
         push(N_TOVEC3);
         m = std::max(m1, std::max(m2, m3));
       }
       break;
     case HostNode::Checker:
       m = emit_program(S, k.a, ops, depth);
+      if (m < 0) return -1;
       push(N_CHECKER, k.f);
       break;
     case HostNode::Splat: m = emit_program(S, k.a, ops, depth); break;

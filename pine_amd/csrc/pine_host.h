@@ -102,6 +102,10 @@ struct HostNode {
   int a = -1, b = -1, c = -1, n = 0;
   float f = 0;
   f3 v{0, 0, 0};
+  // Filled in by SceneHost::add_node, once per node (operands always precede the node, and a script may share one operand
+  // between many nodes): whether the subtree reads the surface and, if it does not, its value (a float as a splat).
+  bool reads_surface = false;
+  f3 folded{0, 0, 0};
   bool is_vec3() const {
     return kind == Const3 || kind == Position || kind == Normal || kind == UV || kind == Bin3 || kind == Un3 || kind == ToVec3 || kind == Splat;
   }
@@ -133,8 +137,8 @@ struct SceneHost {
   FlatAccel accel;
 
   int add_node(const HostNode& n);  // returns the id, or -1 with the error set
-  bool node_reads_surface(int id) const;
-  f3 node_fold(int id) const;       // value of a node subtree that does not read the surface
+  bool node_reads_surface(int id) const { return nodes[size_t(id)].reads_surface; }
+  f3 node_fold(int id) const { return nodes[size_t(id)].folded; }  // value of a node subtree that does not read the surface
   // flatten the programs of every material into `ops`; fills DMaterial::prog / folded literals of `out`
   bool compile_node_programs(std::vector<DMaterial>& out, std::vector<DNodeOp>& ops) const;
   int find_material(const char* name) const;

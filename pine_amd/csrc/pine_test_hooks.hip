@@ -264,6 +264,48 @@ __global__ void __launch_bounds__(64) test_light_samples_kernel(const DShape* sh
   if (k < num_shapes) test_shape_sample_case(&shapes[k], tri_verts, queries + i * 6, out + t * 13);
   else test_light_sample_case(&lights[k - num_shapes], queries + i * 6, out + n * num_shapes * 13 + (t - n * num_shapes) * 9);
 }
+// pine_gpu_test_material_params: material_params<F_ALL> of one material at one query (p, n, uv) -> 10 floats
+PINE_HD void test_material_params_case(const DMaterial* m, const DNodeOp* ops, const float* q, float* o) {
+  const MatParams mp = material_params<F_ALL>(m, ops, ld3(q), ld3(q + 3), f2{q[6], q[7]});
+  o[0] = mp.albedo.x, o[1] = mp.albedo.y, o[2] = mp.albedo.z;
+  o[3] = mp.albedo_over_pi.x, o[4] = mp.albedo_over_pi.y, o[5] = mp.albedo_over_pi.z;
+  o[6] = mp.roughness, o[7] = mp.metallic, o[8] = mp.transmission, o[9] = mp.ior;
+}
+__global__ void __launch_bounds__(64) test_material_params_kernel(const DMaterial* mats, int num_mats, const DNodeOp* ops, const float* queries,
+                                                                 long long n, float* out) {
+  const long long t = blockIdx.x * 64ll + threadIdx.x;
+  if (t >= n * num_mats) return;
+  test_material_params_case(&mats[t / n], ops, queries + (t % n) * 8, out + t * 10);
+}
+// pine_gpu_test_choose_lobe: material_params, then choose_lobe as the path kernels call it, one thread per (after_walk, case).
+// The pixel's RNG lives in a local; the sampler is SobolSampler(64) on a 1024 x 1024 image, as in test_bxdf_case.  A slot the
+// chosen lobe does not have (bxdf.h:38-138: no roughness in Diffuse / BSSRDF, no ior in Diffuse / Conductor) is written as 0.
+__global__ void __launch_bounds__(64) test_choose_lobe_kernel(const DMaterial* mats, const DNodeOp* ops, const float* cases, long long n, float* out) {
+  const long long t = blockIdx.x * 64ll + threadIdx.x;
+  if (t >= 2 * n) return;
+  const float* c = cases + (t % n) * 16;
+  float* o = out + t * 8;
+  const DMaterial* mat = &mats[int(c[0])];  // (checked against the material count on the host)
+  const f3 nn = ld3(c + 4);
+  DTables T{};
+  T.kind = 1;
+  sobol_sampler_params(T, 64, 1024, 1024);
+  DSampler s;
+  s.px = int(c[13]);
+  s.py = int(c[14]);
+  s.index = int(c[15]);
+  s.dimension = 0;
+  DRng g = rng_seed(hash_pixel(s.px, s.py, 0));  // Sampler::start_pixel(p, 0): path.cpp:32
+  const MatParams mp = material_params<F_ALL>(mat, ops, ld3(c + 1), nn, f2{c[7], c[8]});
+  DBxdf bx;
+  choose_lobe<F_ALL, kSmSobol>(mat, mp, ld3(c + 9), nn, c[12] != 0.0f, t >= n, [&]() -> DRng { return g; }, [&](const DRng& x) { g = x; }, T, s, bx);
+  o[0] = float(bx.kind);
+  o[1] = mp.albedo.x, o[2] = mp.albedo.y, o[3] = mp.albedo.z;
+  o[4] = bx.kind == BX_DIFFUSE || bx.kind == BX_BSSRDF ? 0.0f : bx.roughness;
+  o[5] = bx.kind == BX_DIFFUSE || bx.kind == BX_CONDUCTOR ? 0.0f : bx.ior;
+  o[6] = float(s.dimension);
+  o[7] = rng_nextf(g);
+}
 }  // namespace pine_gpu
 
 using namespace pine_gpu;
@@ -655,6 +697,120 @@ int pine_gpu_test_light_samples(pine_gpu_scene* scene, int device, const float* 
   (void)hipFree(dl);
   (void)hipFree(dt);
   (void)hipFree(dq);
+  (void)hipFree(dout);
+  return rc;
+}
+
+int64_t pine_gpu_test_node_programs(pine_gpu_scene* scene, int32_t* out, int64_t capacity_words) {
+  if (!scene) {
+    set_error("null argument");
+    return -1;
+  }
+  std::vector<DMaterial> mats;
+  std::vector<DNodeOp> ops;
+  if (!scene_host(scene).compile_node_programs(mats, ops)) return -1;
+  const int64_t words = 2 + 4 * int64_t(mats.size()) + 4 * int64_t(ops.size());
+  if (out && capacity_words >= words) {
+    int32_t* o = out;
+    *o++ = int32_t(mats.size());
+    *o++ = int32_t(ops.size());
+    for (const DMaterial& m : mats)
+      for (int k = 0; k < 4; k++) *o++ = m.prog[k];
+    if (!ops.empty()) memcpy(o, ops.data(), ops.size() * sizeof(DNodeOp));
+  }
+  return words;
+}
+
+int pine_gpu_test_material_params(pine_gpu_scene* scene, int device, const float* queries, int64_t n, float* out) {
+  if (!scene || !queries || !out || n < 0 || n > (1 << 20)) {
+    set_error("bad argument");
+    return -1;
+  }
+  std::vector<DMaterial> mats;
+  std::vector<DNodeOp> ops;
+  if (!scene_host(scene).compile_node_programs(mats, ops)) return -1;
+  const int nm = int(mats.size());
+  if (device < 0) {
+    for (int k = 0; k < nm; k++)
+      for (int64_t i = 0; i < n; i++) test_material_params_case(&mats[size_t(k)], ops.data(), queries + i * 8, out + (k * n + i) * 10);
+    return 0;
+  }
+  if (n == 0 || nm == 0) return 0;
+  if (need_device(device)) return -1;
+  DMaterial* dm = nullptr;
+  DNodeOp* dops = nullptr;
+  float *dq = nullptr, *dout = nullptr;
+  const size_t words = size_t(n) * size_t(nm) * 10;
+  int rc = -1;
+  do {
+    if (hipMalloc((void**)&dm, mats.size() * sizeof(DMaterial)) != hipSuccess ||
+        hipMalloc((void**)&dops, std::max<size_t>(ops.size(), 1) * sizeof(DNodeOp)) != hipSuccess ||
+        hipMalloc((void**)&dq, size_t(n) * 32) != hipSuccess || hipMalloc((void**)&dout, words * 4) != hipSuccess)
+      break;
+    if (hipMemcpy(dm, mats.data(), mats.size() * sizeof(DMaterial), hipMemcpyHostToDevice) != hipSuccess ||
+        (!ops.empty() && hipMemcpy(dops, ops.data(), ops.size() * sizeof(DNodeOp), hipMemcpyHostToDevice) != hipSuccess) ||
+        hipMemcpy(dq, queries, size_t(n) * 32, hipMemcpyHostToDevice) != hipSuccess)
+      break;
+    const long long total = (long long)n * nm;
+    hipLaunchKernelGGL(test_material_params_kernel, dim3(unsigned((total + 63) / 64)), dim3(64), 0, 0, dm, nm, dops, dq, (long long)n, dout);
+    if (hipGetLastError() != hipSuccess || hipMemcpy(out, dout, words * 4, hipMemcpyDeviceToHost) != hipSuccess) break;
+    rc = 0;
+  } while (0);
+  if (rc) set_error(std::string("pine_gpu_test_material_params: ") + hipGetErrorString(hipGetLastError()));
+  (void)hipFree(dm);
+  (void)hipFree(dops);
+  (void)hipFree(dq);
+  (void)hipFree(dout);
+  return rc;
+}
+
+int pine_gpu_test_choose_lobe(pine_gpu_scene* scene, int device, const float* cases, int64_t n, float* out) {
+  if (!scene || !cases || !out || n < 0 || n > (1 << 20)) {
+    set_error("bad argument");
+    return -1;
+  }
+  if (device < 0) {
+    set_error("pine_gpu_test_choose_lobe: choose_lobe is device code only");
+    return -1;
+  }
+  std::vector<DMaterial> mats;
+  std::vector<DNodeOp> ops;
+  if (!scene_host(scene).compile_node_programs(mats, ops)) return -1;
+  for (int64_t i = 0; i < n; i++) {
+    const float* c = cases + i * 16;
+    const bool whole = c[0] >= 0 && c[0] < float(mats.size()) && c[0] == float(int(c[0]));
+    if (!whole || mats[size_t(c[0])].kind == MAT_EMISSIVE) {  // EmissiveMaterial::sample_bxdf is unreachable (material.h:20)
+      set_error("pine_gpu_test_choose_lobe: a case names no material that has a lobe");
+      return -1;
+    }
+    if (!(c[13] >= 0 && c[13] < 1024 && c[14] >= 0 && c[14] < 1024 && c[15] >= 0 && c[15] < 64)) {
+      set_error("pine_gpu_test_choose_lobe: pixel or sample index out of range");
+      return -1;
+    }
+  }
+  if (n == 0) return 0;
+  if (need_device(device)) return -1;
+  DMaterial* dm = nullptr;
+  DNodeOp* dops = nullptr;
+  float *dc = nullptr, *dout = nullptr;
+  int rc = -1;
+  do {
+    if (hipMalloc((void**)&dm, mats.size() * sizeof(DMaterial)) != hipSuccess ||
+        hipMalloc((void**)&dops, std::max<size_t>(ops.size(), 1) * sizeof(DNodeOp)) != hipSuccess ||
+        hipMalloc((void**)&dc, size_t(n) * 64) != hipSuccess || hipMalloc((void**)&dout, size_t(n) * 64) != hipSuccess)
+      break;
+    if (hipMemcpy(dm, mats.data(), mats.size() * sizeof(DMaterial), hipMemcpyHostToDevice) != hipSuccess ||
+        (!ops.empty() && hipMemcpy(dops, ops.data(), ops.size() * sizeof(DNodeOp), hipMemcpyHostToDevice) != hipSuccess) ||
+        hipMemcpy(dc, cases, size_t(n) * 64, hipMemcpyHostToDevice) != hipSuccess)
+      break;
+    hipLaunchKernelGGL(test_choose_lobe_kernel, dim3(unsigned((2 * n + 63) / 64)), dim3(64), 0, 0, dm, dops, dc, (long long)n, dout);
+    if (hipGetLastError() != hipSuccess || hipMemcpy(out, dout, size_t(n) * 64, hipMemcpyDeviceToHost) != hipSuccess) break;
+    rc = 0;
+  } while (0);
+  if (rc) set_error(std::string("pine_gpu_test_choose_lobe: ") + hipGetErrorString(hipGetLastError()));
+  (void)hipFree(dm);
+  (void)hipFree(dops);
+  (void)hipFree(dc);
   (void)hipFree(dout);
   return rc;
 }

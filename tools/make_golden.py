@@ -7,6 +7,7 @@ and the reference's outputs, no reference source) are committed and travel to th
     python tools/make_golden.py --full     # also C1/C2 whole-image statistics (~1 min of CPU)
     python tools/make_golden.py --bvh --vertices   # the reference's BVH + traversal orders, per-vertex path terms
     python tools/make_golden.py --sampling # BSDF lobes and shape / light sampling per call (tests/test_sampling_fixtures.py)
+    python tools/make_golden.py --nodes    # shading-node programs and the material-to-lobe step per call (tests/test_node_fixtures.py)
     python tools/make_golden.py --live     # the reference's films of the oracle tests' cbox and seeded random scenes
 """
 import hashlib
@@ -239,6 +240,32 @@ def vertex_fixture(tmp):
         print(name, info)
 
 
+def node_fixtures(tmp):
+    """tests/golden/nodes_zoo.pscene, node_evals.npz (`pine_ref nodes`) and lobe_choice.npz (`pine_ref lobes`): the scene, the seeded
+    queries and cases of tests/test_node_fixtures.py and the reference's own answers.  The outcome classes are asserted here, on the
+    reference's records, and again by the test."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import test_node_fixtures as tnf
+    sc, mats = tnf.nodes_zoo()
+    ps = sc.describe()
+    sp, qp, cp, op = (os.path.join(tmp, x) for x in ("zoo.pscene", "queries.bin", "cases.bin", "out.bin"))
+    open(sp, "w").write(ps)
+    open(os.path.join(OUT, "nodes_zoo.pscene"), "w").write(ps)
+    queries = tnf.node_queries()
+    queries.tofile(qp)
+    print(run_ref("nodes", sp, qp, op).strip())
+    rec = np.fromfile(op, dtype=np.float32).reshape(len(mats), len(queries), 7)
+    np.savez_compressed(os.path.join(OUT, "node_evals.npz"), queries=queries, records=rec)
+    cases = tnf.lobe_cases(mats)
+    cases.tofile(cp)
+    print(run_ref("lobes", sp, cp, op).strip())
+    lrec = np.fromfile(op, dtype=np.float32).reshape(len(cases), 8)
+    led = tnf.lobe_ledger(mats, cases, lrec)
+    print(led)
+    tnf.check_lobe_ledger(led)
+    np.savez_compressed(os.path.join(OUT, "lobe_choice.npz"), cases=cases, records=lrec)
+
+
 def _sampling_cases():
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import test_sampling_fixtures as tsf
@@ -360,6 +387,10 @@ def main():
     if "--live" in sys.argv:
         with tempfile.TemporaryDirectory() as tmp:
             live_fixture(tmp)
+        return
+    if "--nodes" in sys.argv:
+        with tempfile.TemporaryDirectory() as tmp:
+            node_fixtures(tmp)
         return
     if "--sampling" in sys.argv:
         with tempfile.TemporaryDirectory() as tmp:
