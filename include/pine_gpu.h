@@ -354,7 +354,8 @@ typedef struct {
   int32_t specialize_source; /* where the scene's kernel came (or will come) from: 0 none; 1 the on-disk cache; 2 compiled at plan
                               * creation (PINE_GPU_FLAG_SPECIALIZE); 3 compiled in the background by this process           */
   int32_t specialize_pending;/* 1: a background build is still running (the precompiled kernel renders meanwhile)             */
-  int32_t reserved;
+  int32_t tiles_in_kernel;   /* 8x8 tiles of the last launch that the path kernel summed itself (its owned tiles); the resolve
+                              * kernel summed the others */
 } pine_gpu_plan_stats;
 /* PINE_GPU_FLAG_SPECIALIZE, host half: the text plan creation would compile for this scene (its BVH as straight-line code,
  * boxes and primitive records as hexadecimal float literals), NUL-terminated into out[0..cap) when it fits; returns its

@@ -59,7 +59,7 @@ class PlanStats(C.Structure):
         ("kernel_features", C.c_uint32),
         ("specialize_source", C.c_int32),
         ("specialize_pending", C.c_int32),
-        ("reserved", C.c_int32),
+        ("tiles_in_kernel", C.c_int32),
     ]
 
 

@@ -124,87 +124,16 @@ static const VariantTables& variant_tables() {
 #define kNumVariants (int(variant_tables().mega.size()))
 #define kNumQueueVariants (int(variant_tables().queue.size()))
 
-// Ordered per-pixel sum: film[p] = (sum_{s=0..spp-1, in order} L_s) / spp  (path.cpp:34-38).
-// One wave per tile, lane = pixel in tile: every sample row is one coalesced 1 KiB read.
-// `packed` != 0: the output is this rank's tile-major slab [local tile][pixel in tile] (multi-GPU gather)
-// instead of the row-major film.
-//
-// The sum is CONTINUED from pass to pass: `sum` holds one float4 per local pixel,
-// (((L_0 + L_1) + ...) + L_{m-1}) of the samples resolved so far -- the partial result of the loop below, so going on from it
-// rounds exactly as one launch over all rows does.  Tiles of the whole-pixel class ([0, whole_tiles) in the plan's tile order)
-// get all spp rows in the pass that renders their slice and none in the others: their film pixel is final from then on and
-// (0, 0, 0, 0) before.  Tiles of the independent class get `free_rows` rows in every pass; their film pixel is the running
-// mean sum / samples_so_far -- after the last pass sum / spp.  A plan of one pass: the slice is the whole class, free_rows =
-// samples_so_far = spp, and `sum` is null -- nothing carried, nothing kept.  W is the PLAN's work decomposition.
-struct ResolvePass {
-  int film_w, film_h, spp;
-  int whole_tiles, slice_first, slice_tiles;  // the whole-pixel class; the slice of it this pass rendered
-  int free_rows;                               // sample rows of this pass per tile of the independent class
-  int first_pass;                              // ... and whether they are the pixel's first (the sum starts from zero)
-  int samples_so_far;                          // ... and the samples of a pixel of that class up to and including this pass
-  int packed;
-};
+// The resolve: one wave per local tile runs resolve_tile (pine_kernels_device.h) -- over every tile that the path kernel has
+// not summed itself (WorkParams::tile_done: the owned tiles of a stage-queued launch).
 __global__ void __launch_bounds__(kBlock) resolve_kernel(WorkParams W, ResolvePass R, const float4* __restrict__ samples,
                                                         float4* __restrict__ sum, float4* __restrict__ film,
                                                         Counters* __restrict__ counters) {
   const unsigned long long t = blockIdx.x * (unsigned long long)kBlock + threadIdx.x;
   const int ltile = int(t >> 6);
   if (ltile >= W.num_local_tiles) return;  // (whole waves: one wave per tile)
-  const int p = int(t & 63);
-  const int tile = film_tile_of(W, ltile);
-  const int px = (tile % W.tiles_x) * kTile + (p & 7), py = (tile / W.tiles_x) * kTile + (p >> 3);
-  const bool inside = px < R.film_w && py < R.film_h;
-  const float4* row = nullptr;
-  int rows = 0;
-  bool carried = false, shown = true;
-  float divisor = float(R.spp);
-  if (ltile < R.whole_tiles) {
-    if (ltile >= R.slice_first && ltile < R.slice_first + R.slice_tiles) {
-      row = samples + (unsigned long long)(ltile - R.slice_first) * (unsigned)R.spp * 64ull + p;
-      rows = R.spp;
-    } else if (ltile < R.slice_first) {
-      carried = true;  // an earlier pass finished it
-    } else {
-      shown = false;
-    }
-  } else {
-    row = samples + ((unsigned long long)R.slice_tiles * (unsigned)R.spp + (unsigned long long)(ltile - R.whole_tiles) * (unsigned)R.free_rows) * 64ull + p;
-    rows = R.free_rows;
-    carried = !R.first_pass;
-    divisor = float(R.samples_so_far);
-  }
-  if (!inside) rows = 0;
-  float4* const acc = sum && inside ? sum + (unsigned long long)ltile * 64ull + p : nullptr;
-  f3 L = mk3(0.0f);
-  if (carried && acc) {
-    const float4 a = *acc;
-    L = f3{a.x, a.y, a.z};
-  }
-  unsigned long long verts = 0;
-  // the sum is sequential in s (path.cpp:34-37), the loads need not be: 8 rows in flight per lane
-  int s = 0;
-  for (; s + 8 <= rows; s += 8) {
-    float4 v[8];
-#pragma unroll
-    for (int j = 0; j < 8; j++) v[j] = row[(unsigned long long)(s + j) * 64ull];
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-      L = L + f3{v[j].x, v[j].y, v[j].z};
-      verts += (unsigned long long)v[j].w;
-    }
-  }
-  for (; s < rows; s++) {
-    const float4 v = row[(unsigned long long)s * 64ull];
-    L = L + f3{v.x, v.y, v.z};
-    verts += (unsigned long long)v.w;
-  }
-  if (inside) {
-    if (acc && rows > 0) *acc = make_float4(L.x, L.y, L.z, 0.0f);
-    const f3 m = L / divisor;
-    // (the slab is tile-major in the shard's NATURAL tile order, whatever order the launch works in: tile_order)
-    const size_t out_index = R.packed ? size_t(tile / W.shard_world) * 64u + size_t(p) : size_t(py) * R.film_w + px;
-    film[out_index] = shown ? make_float4(m.x, m.y, m.z, 1.0f) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-  }
+  if (W.tile_done && W.tile_done[ltile]) return;
+  unsigned long long verts = resolve_tile<8>(W, R, samples, sum, film, ltile, int(t & 63));
   // radiance() invocation count of the launch (the unit of the roofline's algorithmic bytes)
   for (int off = 32; off > 0; off >>= 1) verts += __shfl_down(verts, off);
   if ((threadIdx.x & 63) == 0 && verts) atomicAdd(&counters->vertices, verts);
@@ -389,6 +318,9 @@ struct PlanKnobs {
   // that precompiled variant only (pin_kind 0 / 1; -1 unset, 2 malformed) and the plan never specialises.
   // PINE_GPU_TEST_LDS_NODES=<n>: F_LDS_TOP variants cache at most n BVH nodes in LDS.
   int pin_kind, pin_order, lds_nodes_cap;
+  // PINE_GPU_OWNED_TILES: tiles claimed whole and summed inside the stage-queued kernel (0: none, n: that many, unset: automatic;
+  // size_and_allocate).  Test hook PINE_GPU_TEST_TILE_SLOTS=<n>: a workgroup's table of such tiles in flight has n slots.
+  int owned_tiles, tile_slots;
 };
 static PlanKnobs read_knobs() {
   auto num = [](const char* name) { return getenv(name) ? atoi(getenv(name)) : kUnset; };
@@ -409,7 +341,8 @@ static PlanKnobs read_knobs() {
                    num("PINE_GPU_TRAV_MIN_TRIPS"), num("PINE_GPU_MAX_PIXELS"), num("PINE_GPU_FAIR_PERIOD"), num("PINE_GPU_POOL_ITEMS"),
                    set("PINE_GPU_SPECIALIZE_FORCE"), set("PINE_GPU_NO_LDS_SCENE"), kernel && std::string(kernel) == "mega",
                    set("PINE_GPU_NO_TILE_CLASSES"), set("PINE_GPU_NO_FORK"), ckpt != kUnset && ckpt != 0,
-                   budget && atof(budget) > 0 ? atof(budget) : 30.0, pin_kind, pin_order, num("PINE_GPU_TEST_LDS_NODES")};
+                   budget && atof(budget) > 0 ? atof(budget) : 30.0, pin_kind, pin_order, num("PINE_GPU_TEST_LDS_NODES"),
+                   num("PINE_GPU_OWNED_TILES"), num("PINE_GPU_TEST_TILE_SLOTS")};
 }
 
 static int plan_adopt_kernel(pine_gpu_plan* p, bool compile_here);
@@ -1432,6 +1365,24 @@ static int size_and_allocate(pine_gpu_plan* p, const pine_gpu_render_params* prm
     while (claim < 2048 && (unsigned long long)claim * 2ull <= share) claim *= 2;
     W.pool_items = claim;
   }
+  // Owned tiles (WorkParams::owned_tiles): the plain variants of the stage-queued kernel, plans of one pass in the shard's
+  // natural tile order.  Automatic: every tile but the last two per workgroup -- a whole tile is a large claim (C2: 8192 items,
+  // four of today's), and the end of a launch needs small ones: with two tiles' worth of pool_items claims left per workgroup
+  // the workgroup that takes the last owned tile still finds the others busy when it is done (the claims that "unbalance the
+  // end" above were ALL 8192) -- and none where a tile is a smaller claim than pool_items (that would only multiply the
+  // claims) or has fewer items than a workgroup has contexts (it would hand out several tiles at once and run out of slots).
+  W.owned_tiles = 0;
+  W.pool_items_log2 = 0;
+  while ((1 << W.pool_items_log2) < W.pool_items) W.pool_items_log2++;
+  W.tile_slots = K.tile_slots != kUnset ? std::max(0, std::min(K.tile_slots, kQTileSlots)) : kQTileSlots;
+  const bool can_own = kernel.queued() && !(kernel.features & F_SSS) && !p->fast && PP.n == 1 && W.serial_tiles == 0 && p->tile_order.empty() &&
+                       W.free_tile_base == 0 && (1 << W.pool_items_log2) == W.pool_items && W.total_items > 0;
+  if (can_own) {
+    const long long tile_items = 64ll * W.pass_chunks;
+    long long owned = tile_items >= std::max(W.pool_items, kernel.ctx) ? (long long)W.num_local_tiles - 2ll * p->grid : 0;
+    if (K.owned_tiles != kUnset) owned = K.owned_tiles;
+    W.owned_tiles = int(std::max(0ll, std::min<long long>(owned, W.num_local_tiles)));
+  }
 
   if (W.items_per_pixel > 1) {
     p->bytes_ckpt = (size_t)(W.num_local_tiles - W.serial_tiles) * ckpt_chunks * 64 * sizeof(ulonglong2);
@@ -1460,7 +1411,9 @@ static int size_and_allocate(pine_gpu_plan* p, const pine_gpu_render_params* prm
     const size_t token_dwords = (kernel.features & F_SSS) ? size_t(p->grid) * (kernel.ctx <= 1024 ? 1024 : 2048) * kQTokenDwords : 0;
     HIP_OK(POOL_ALLOC(p->d_ctxg, (size_t(p->grid) * kernel.ctx * q_ctx_global_dwords(kernel.features) + token_dwords) * sizeof(uint32_t)));
   }
-  HIP_OK(POOL_ALLOC(p->d_counters, sizeof(Counters)));
+  // (the owned tiles' done marks sit behind the counters: one clear for both)
+  HIP_OK(POOL_ALLOC(p->d_counters, sizeof(Counters) + (W.owned_tiles > 0 ? size_t(W.num_local_tiles) * sizeof(unsigned) : 0)));
+  W.tile_done = W.owned_tiles > 0 ? reinterpret_cast<unsigned*>(p->d_counters + 1) : nullptr;
   p->timed = (prm->flags & PINE_GPU_FLAG_TIMING) != 0;
   if (p->timed)
     for (auto& slot : p->ev)
@@ -1569,7 +1522,10 @@ static int plan_launch_pass(pine_gpu_plan* p, int j, void* film_dev, hipStream_t
   const size_t film_bytes = size_t(p->film_w) * p->film_h * sizeof(float4);
   if (p->W.shard_world > 1 && !packed) HIP_OK(hipMemsetAsync(film_dev, 0, film_bytes, stream));
   // the counters of the sequence start with pass 0; every pass hands out its own items from zero
-  HIP_OK(hipMemsetAsync(p->d_counters, 0, j == 0 ? sizeof(Counters) : sizeof(unsigned long long), stream));
+  const size_t done_bytes = p->W.tile_done ? size_t(p->W.num_local_tiles) * sizeof(unsigned) : 0;  // (owned tiles: plans of one pass)
+  HIP_OK(hipMemsetAsync(p->d_counters, 0, j == 0 ? sizeof(Counters) + done_bytes : sizeof(unsigned long long), stream));
+  W.film = (float4*)film_dev;
+  W.film_packed = packed ? 1 : 0;
   static_assert(offsetof(Counters, next_item) == 0, "the per-pass reset clears next_item");
   hipEvent_t* ev = p->ev[p->launch_count % pine_gpu_plan::kEvRing];
   if (p->timed) HIP_OK(hipEventRecord(ev[0], stream));
@@ -1746,6 +1702,7 @@ int pine_gpu_plan_stats_get(pine_gpu_plan* p, pine_gpu_plan_stats* out) {
     out->vertices = c.vertices;
     out->shadow_rays = c.shadow_rays;
     out->walk_steps = c.walk_steps;
+    out->tiles_in_kernel = int32_t(c.tiles_summed);
     if (p->timed) {
       // mean over the launches since the previous read (at most the last kEvRing of them)
       unsigned long long first = p->stats_read_upto;

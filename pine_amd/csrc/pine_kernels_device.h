@@ -226,6 +226,17 @@ struct WorkParams {
   int pass_row_stride;         // sample rows a tile of the independent class has in the sample buffer (ordinary launch: spp)
   int free_tile_base;          // ordinary launch: serial_tiles
   int pass_first_serial_tile;  // ordinary launch: 0
+  // Owned tiles (stage-queued kernel, plain variants, plans of one pass): the first `owned_tiles` local tiles are
+  // claimed one whole tile per claim, so that every sample row of such a tile is written by waves of one workgroup, and the wave
+  // that retires the tile's last item sums it (resolve_tile below) instead of resolve_kernel.  The claim counter keeps counting
+  // in units of pool_items = 1 << pool_items_log2: claim number c < owned_tiles is local tile c, the later ones are the usual
+  // runs of pool_items items behind the owned tiles.  0: every claim is pool_items items, every tile is summed by resolve_kernel.
+  int owned_tiles;
+  int pool_items_log2;
+  int tile_slots;         // slots of a workgroup's table of owned tiles in flight (kQTileSlots; fewer: a test knob)
+  int film_packed;        // the launch writes this rank's tile-major slab (ResolvePass::packed)
+  float4* film;           // the launch's film or slab
+  unsigned* tile_done;    // per local tile: summed inside the path kernel (cleared with the counters); null without owned tiles
 };
 constexpr int kVertexLogFloats = 16;
 // get_progress() (integrator.cpp:17-19): every 16th / 64th pool claim posts the claimed-item count to host memory
@@ -784,6 +795,90 @@ static __global__ void __launch_bounds__(kBlock) rng_checkpoint_kernel(WorkParam
 }
 
 // ------------------------------------------------------------------------------------------------
+// Ordered per-pixel sum of one tile: film[p] = (sum_{s=0..spp-1, in order} L_s) / spp  (path.cpp:34-38).
+// One wave per tile, lane = pixel in tile: every sample row is one coalesced 1 KiB read.  Called by resolve_kernel
+// (pine_kernels.hip) and, for the tiles a workgroup owns, by the stage-queued path kernel itself: one text, the same bits.
+// `packed` != 0: the output is this rank's tile-major slab [local tile][pixel in tile] (multi-GPU gather)
+// instead of the row-major film.
+//
+// The sum is CONTINUED from pass to pass: `sum` holds one float4 per local pixel,
+// (((L_0 + L_1) + ...) + L_{m-1}) of the samples resolved so far -- the partial result of the loop below, so going on from it
+// rounds exactly as one launch over all rows does.  Tiles of the whole-pixel class ([0, whole_tiles) in the plan's tile order)
+// get all spp rows in the pass that renders their slice and none in the others: their film pixel is final from then on and
+// (0, 0, 0, 0) before.  Tiles of the independent class get `free_rows` rows in every pass; their film pixel is the running
+// mean sum / samples_so_far -- after the last pass sum / spp.  A plan of one pass: the slice is the whole class, free_rows =
+// samples_so_far = spp, and `sum` is null -- nothing carried, nothing kept.  W is the PLAN's work decomposition.
+// ------------------------------------------------------------------------------------------------
+struct ResolvePass {
+  int film_w, film_h, spp;
+  int whole_tiles, slice_first, slice_tiles;  // the whole-pixel class; the slice of it this pass rendered
+  int free_rows;                               // sample rows of this pass per tile of the independent class
+  int first_pass;                              // ... and whether they are the pixel's first (the sum starts from zero)
+  int samples_so_far;                          // ... and the samples of a pixel of that class up to and including this pass
+  int packed;
+};
+// Returns the lane's radiance() invocation count (the .w of its rows).  ROWS sample rows are in flight per lane.
+template <int ROWS>
+__device__ __forceinline__ unsigned long long resolve_tile(const WorkParams& W, const ResolvePass& R, const float4* samples, float4* sum,
+                                                           float4* film, int ltile, int p) {
+  const int tile = film_tile_of(W, ltile);
+  const int px = (tile % W.tiles_x) * kTile + (p & 7), py = (tile / W.tiles_x) * kTile + (p >> 3);
+  const bool inside = px < R.film_w && py < R.film_h;
+  const float4* row = nullptr;
+  int rows = 0;
+  bool carried = false, shown = true;
+  float divisor = float(R.spp);
+  if (ltile < R.whole_tiles) {
+    if (ltile >= R.slice_first && ltile < R.slice_first + R.slice_tiles) {
+      row = samples + (unsigned long long)(ltile - R.slice_first) * (unsigned)R.spp * 64ull + p;
+      rows = R.spp;
+    } else if (ltile < R.slice_first) {
+      carried = true;  // an earlier pass finished it
+    } else {
+      shown = false;
+    }
+  } else {
+    row = samples + ((unsigned long long)R.slice_tiles * (unsigned)R.spp + (unsigned long long)(ltile - R.whole_tiles) * (unsigned)R.free_rows) * 64ull + p;
+    rows = R.free_rows;
+    carried = !R.first_pass;
+    divisor = float(R.samples_so_far);
+  }
+  if (!inside) rows = 0;
+  float4* const acc = sum && inside ? sum + (unsigned long long)ltile * 64ull + p : nullptr;
+  f3 L = mk3(0.0f);
+  if (carried && acc) {
+    const float4 a = *acc;
+    L = f3{a.x, a.y, a.z};
+  }
+  unsigned long long verts = 0;
+  // the sum is sequential in s (path.cpp:34-37), the loads need not be: ROWS rows in flight per lane
+  int s = 0;
+  for (; s + ROWS <= rows; s += ROWS) {
+    float4 v[ROWS];
+#pragma unroll
+    for (int j = 0; j < ROWS; j++) v[j] = row[(unsigned long long)(s + j) * 64ull];
+#pragma unroll
+    for (int j = 0; j < ROWS; j++) {
+      L = L + f3{v[j].x, v[j].y, v[j].z};
+      verts += (unsigned long long)v[j].w;
+    }
+  }
+  for (; s < rows; s++) {
+    const float4 v = row[(unsigned long long)s * 64ull];
+    L = L + f3{v.x, v.y, v.z};
+    verts += (unsigned long long)v.w;
+  }
+  if (inside) {
+    if (acc && rows > 0) *acc = make_float4(L.x, L.y, L.z, 0.0f);
+    const f3 m = L / divisor;
+    // (the slab is tile-major in the shard's NATURAL tile order, whatever order the launch works in: tile_order)
+    const size_t out_index = R.packed ? size_t(tile / W.shard_world) * 64u + size_t(p) : size_t(py) * R.film_w + px;
+    film[out_index] = shown ? make_float4(m.x, m.y, m.z, 1.0f) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  }
+  return verts;
+}
+
+// ------------------------------------------------------------------------------------------------
 // The path kernel
 // ------------------------------------------------------------------------------------------------
 struct Counters {
@@ -796,6 +891,7 @@ struct Counters {
   unsigned long long bail_count;
   unsigned long long bail_code, bail_a, bail_b;
   unsigned long long walk_steps;  // BSSRDF random-walk steps (stage-queued kernel, F_SSS variants)
+  unsigned long long tiles_summed;  // owned tiles the path kernel summed itself (WorkParams::owned_tiles)
   unsigned long long section_cycles[16];  // diagnostic builds (-DPINE_PROFILE_SECTIONS) only
   unsigned long long t_start, t_pool_dry, t_end;  // ... 100 MHz wall clock: first workgroup in, the work-item pool found empty, last workgroup out
 #ifdef PINE_PROFILE_SECTIONS

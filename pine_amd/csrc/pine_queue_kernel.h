@@ -46,7 +46,11 @@ enum : int { CF_OX, CF_OY, CF_OZ, CF_DX, CF_DY, CF_DZ, CF_TMAX, CF_ST, CF_PXY, C
 constexpr unsigned kStFresh = 0xffffffffu;  // context has no path yet
 // control words: heads at 0..6; tails at 8..14 -- the S and T tails are ONE u64 (8..9) so that a stage reserves
 // slots in both with one atomic
-enum : int { QC_HEAD = 0, QC_TAIL = 8, QC_BUSY = 16, QC_LOCK = 17, QC_EXHAUSTED = 18, QC_PNEXT = 20, QC_PEND = 22, QC_ABORT = 24, QC_PIXELS = 25, QC_WORDS = 32 };
+// ... QC_PSLOT: the slot (+ 1) of the owned tile the workgroup's current block of items is, or 0; QC_TILE / QC_TILE_LEFT: the
+// table of owned tiles in flight ("owned tiles" below)
+enum : int { QC_HEAD = 0, QC_TAIL = 8, QC_BUSY = 16, QC_LOCK = 17, QC_EXHAUSTED = 18, QC_PNEXT = 20, QC_PEND = 22, QC_ABORT = 24, QC_PIXELS = 25, QC_PSLOT = 26,
+             QC_TILE = 32, QC_TILE_LEFT = 36, QC_WORDS = 40 };
+constexpr int kQTileSlots = 4;  // owned tiles a workgroup can have in flight: the one being handed out, and those whose last paths still run
 constexpr int kQTokenDwords = 8;  // a sample token (Subsurface variants): RNG state (4) | pixel, sample-buffer base, sample index, -
 constexpr unsigned kQSpinLimit = 1u << 22;  // every spin loop is bounded: a protocol bug must end the kernel, not hang the GPU
 constexpr int kQWinDwords = 5;  // per-thread sampler window: 3 dwords of ranking bytes (12 dimensions) + 2 of scrambling bytes
@@ -387,6 +391,48 @@ __device__ __forceinline__ void path_queue_body(const DeviceScene& S, const Work
     counters->bail_code = code;
     counters->bail_a = a;
     counters->bail_b = b;
+  };
+
+  // ---- owned tiles (WorkParams::owned_tiles; plain variants) ----
+  // A claim of a whole tile takes a slot of the workgroup's table: QC_TILE = the tile's key (the pixel coordinates of its
+  // corner as CF_PXY packs them, | 1), QC_TILE_LEFT = its items not yet retired.  Every item of the tile is counted off once:
+  // an item outside the film when it is handed out, any other when stage T has stored its last sample -- behind the release
+  // fence that precedes the stage's pushes, so whoever reads the count has the sample rows with it.  The wave whose count-off
+  // reaches zero sums the tile (resolve_tile: the text of resolve_kernel), writes its film pixels and marks it done; rows
+  // and film never leave the workgroup's scope.  A claim that finds no free slot is an ordinary claim the size of a tile:
+  // resolve_kernel sums it.  Nothing here waits.
+  auto tile_sum = [&](unsigned slot) {
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    SEC_MARK(10);
+    const unsigned key = __builtin_amdgcn_readfirstlane(lds_load(&qctl[QC_TILE + slot]));
+    WorkParams Wl;  // (cold: read from the kernel arguments here)
+    kload(kWOffset, &Wl);
+    const int spp = kS(spp);
+    // (owned tiles: no tile order, free_tile_base 0 -- the shard's local tile t is film tile t * shard_world + shard_rank)
+    const int tile = int(key >> 19) * Wl.tiles_x + int((key & 0xffffu) >> 3);
+    const int ltile = tile / Wl.shard_world;
+    const ResolvePass R{kS(cam.W), kS(cam.H), spp, 0, 0, 0, spp, 1, spp, Wl.film_packed};
+    unsigned long long verts = resolve_tile<16>(Wl, R, samples, nullptr, Wl.film, ltile, int(lane));
+    for (int off = 32; off > 0; off >>= 1) verts += __shfl_down(verts, off);
+    if (lane == 0) {
+      if (verts) atomicAdd(&counters->vertices, verts);
+      atomicAdd(&counters->tiles_summed, 1ull);
+      Wl.tile_done[ltile] = 1u;
+      __atomic_store_n(&qctl[QC_TILE + slot], 0u, __ATOMIC_RELAXED);  // the slot is free
+    }
+    SEC_MARK(14);  // T: tile sum
+  };
+  // count off the items of the lanes with `flag` from the tile in `slot`, one LDS atomic for the wave: the slot's bit if
+  // they were its last (wave-uniform) -- this wave then sums the tile at the end of its stage-T pass
+  auto tile_count_off = [&](unsigned slot, bool flag) -> unsigned {
+    const unsigned long long m = __ballot(flag);
+    if (m == 0) return 0u;
+    unsigned last = 0;
+    if (lane == 0) {
+      const unsigned n = unsigned(__popcll(m));
+      last = atomicSub(&qctl[QC_TILE_LEFT + slot], n) == n ? 1u : 0u;
+    }
+    return __builtin_amdgcn_readfirstlane(last) << slot;
   };
 
   // (kFork) contexts with nothing to do wait in the ring F; take up to `count` of them back into stage T (whole wave)
@@ -1112,6 +1158,8 @@ __device__ __forceinline__ void path_queue_body(const DeviceScene& S, const Work
       bool free_item = false;  // (kFork, tile classes) ... and it is an item of the independent class
       bool wake_more = false;  // (kFork, tile classes) independent items are at hand: wake contexts that wait in F
       DRng item_rng{0, 0};
+      unsigned done_slot = 0;  // (owned tiles) this lane's item closed in this pass: the slot (+ 1) of its tile, 0 if none
+      unsigned sum_slots = 0;  // ... the slots whose last item this wave counted off (wave-uniform bits)
       unsigned pxy = 0, sample_base = 0;
       int s_next = 0;
       uint4 rng_words = make_uint4(0, 0, 0, 0);
@@ -1185,6 +1233,13 @@ __device__ __forceinline__ void path_queue_body(const DeviceScene& S, const Work
           const bool item_done = kFork ? chain_ends_at(s_next) : closes_item(W.samples_per_item, s_next);
           if ((kFork && st.sealed()) || item_done) need_item = true;
           else have_path = true;
+          if constexpr (!kFork)
+            if (item_done) {
+              const unsigned key = (pxy & 0xfff8fff8u) | 1u;
+#pragma unroll
+              for (int k = 0; k < kQTileSlots; k++)
+                if (lds_load(&qctl[QC_TILE + k]) == key) done_slot = unsigned(k + 1);
+            }
           if constexpr (kFork)
             if (!st.sealed() && chain_ends_at(s_next)) {
               const unsigned before = atomicSub(&qctl[QC_PIXELS], 1u);
@@ -1211,6 +1266,7 @@ __device__ __forceinline__ void path_queue_body(const DeviceScene& S, const Work
         unsigned got = 0;
         unsigned kbase = 0, kgot = 0;  // (kFork) sample tokens taken: ring positions [kbase, kbase + kgot)
         unsigned want_free = 0;        // (kFork) items wanted beyond the tokens, before the in-flight limit
+        unsigned pslot = 0;            // (owned tiles) the slot (+ 1) of the tile this round's items belong to
         unsigned free_items_left = 0;  // (kFork, tile classes) the workgroup's block still has independent items after this round
         if (lane == 0) {
           unsigned tries = 0;
@@ -1240,7 +1296,20 @@ __device__ __forceinline__ void path_queue_body(const DeviceScene& S, const Work
           unsigned long long nx = (unsigned long long)lds_load(&qctl[QC_PNEXT]) | ((unsigned long long)lds_load(&qctl[QC_PNEXT + 1]) << 32);
           unsigned long long en = (unsigned long long)lds_load(&qctl[QC_PEND]) | ((unsigned long long)lds_load(&qctl[QC_PEND + 1]) << 32);
           if (want != 0u && nx == en && lds_load(&qctl[QC_EXHAUSTED]) == 0u) {
-            const unsigned long long b = atomicAdd(&counters->next_item, (unsigned long long)kW(pool_items));
+            unsigned long long b = atomicAdd(&counters->next_item, (unsigned long long)kW(pool_items));
+            unsigned long long claim_items = (unsigned long long)kW(pool_items);
+            bool owned = false;
+            if constexpr (!kFork) {
+              // owned tiles: the counter counts claims (pool_items each); the first owned_tiles of them are one whole tile each
+              const unsigned long long owned_tiles = (unsigned long long)unsigned(kW(owned_tiles));
+              if (owned_tiles != 0ull) {
+                const unsigned long long c = b >> unsigned(kW(pool_items_log2));
+                const unsigned long long tile_items = 64ull * unsigned(kW(pass_chunks));
+                owned = c < owned_tiles;
+                if (owned) b = c * tile_items, claim_items = tile_items;
+                else b = (c - owned_tiles) * claim_items + owned_tiles * tile_items;
+              }
+            }
             if (b >= kW(total_items)) {
 #ifdef PINE_PROFILE_SECTIONS
               atomicCAS(&counters->t_pool_dry, 0ull, wall_clock64());
@@ -1255,9 +1324,28 @@ __device__ __forceinline__ void path_queue_body(const DeviceScene& S, const Work
               }
 #endif
               nx = b;
-              en = b + kW(pool_items) < kW(total_items) ? b + kW(pool_items) : kW(total_items);
+              en = b + claim_items < kW(total_items) ? b + claim_items : kW(total_items);
+              if constexpr (!kFork) {
+                unsigned slot1 = 0;
+                if (owned) {
+                  const unsigned ltile = unsigned(b / claim_items);
+                  const unsigned tile = ltile * unsigned(kW(shard_world)) + unsigned(kW(shard_rank));
+                  const unsigned tiles_x = unsigned(kW(tiles_x));
+                  const unsigned key = (((tile % tiles_x) * kTile) | (((tile / tiles_x) * kTile) << 16)) | 1u;
+                  const unsigned slots = unsigned(kW(tile_slots));
+                  for (unsigned k = 0; k < unsigned(kQTileSlots) && k < slots; k++)
+                    if (lds_load(&qctl[QC_TILE + k]) == 0u) {
+                      __atomic_store_n(&qctl[QC_TILE_LEFT + k], unsigned(claim_items), __ATOMIC_RELAXED);
+                      __atomic_store_n(&qctl[QC_TILE + k], key, __ATOMIC_RELAXED);
+                      slot1 = k + 1;
+                      break;
+                    }
+                }
+                __atomic_store_n(&qctl[QC_PSLOT], slot1, __ATOMIC_RELAXED);
+              }
             }
           }
+          if constexpr (!kFork) pslot = lds_load(&qctl[QC_PSLOT]);
           const unsigned long long avail = en - nx;
           if constexpr (kFork) {
             // tile classes: the block [nx, en) holds independent one-sample items (no pixel is taken into flight, no limit)
@@ -1280,6 +1368,7 @@ __device__ __forceinline__ void path_queue_body(const DeviceScene& S, const Work
         }
         base = __shfl(base, 0);
         got = __shfl(got, 0);
+        if constexpr (!kFork) pslot = __builtin_amdgcn_readfirstlane(pslot);
         if constexpr (kFork) {
           kbase = __shfl(kbase, 0);
           kgot = __shfl(kgot, 0);
@@ -1317,6 +1406,7 @@ __device__ __forceinline__ void path_queue_body(const DeviceScene& S, const Work
           fresh_rng = true;
         }
         rank -= kgot;  // (wraps for the lanes served above: they no longer need an item)
+        bool off_film = false;  // (owned tiles) this lane's item is a pixel outside the film: retired here
         if (need_item && rank < got) {
           const unsigned long long item = base + rank;
           WorkParams Wl;  // (the work decomposition: cold, read from the kernel arguments here)
@@ -1339,10 +1429,13 @@ __device__ __forceinline__ void path_queue_body(const DeviceScene& S, const Work
             fresh_rng = true;
             if constexpr (kFork) free_item = W.serial_tiles > 0 && !itf.serial;
           } else {
+            off_film = true;
             if constexpr (kFork)
               if (!(W.serial_tiles > 0 && !itf.serial)) atomicSub(&qctl[QC_PIXELS], 1u);  // (counted when claimed)
           }
         }
+        if constexpr (!kFork)
+          if (pslot != 0u) sum_slots |= tile_count_off(pslot - 1u, off_film);
       }
       if constexpr (kFork)
         if (to_free) cstu[CF_ST * kQCtx + id] = kStFresh;  // (woken through stage T as an empty context)
@@ -1377,6 +1470,18 @@ __device__ __forceinline__ void path_queue_body(const DeviceScene& S, const Work
         // tile classes: contexts that went to wait while the workgroup's whole-pixel items were at their in-flight limit
         // are woken by token releases only; once independent items are being handed out they can all work again
         if (wake_more) wake_free(64u);
+      }
+      if constexpr (!kFork) {
+        // owned tiles: the items that closed in this pass are counted off -- behind the release fence above
+        if (__ballot(done_slot != 0u) != 0ull) {
+#pragma unroll
+          for (unsigned k = 0; k < unsigned(kQTileSlots); k++) sum_slots |= tile_count_off(k, done_slot == k + 1u);
+        }
+        while (sum_slots != 0u) {
+          const unsigned k = unsigned(__builtin_ctz(sum_slots));
+          sum_slots &= sum_slots - 1u;
+          tile_sum(k);
+        }
       }
     }
     if (lane == 0) atomicSub(&qctl[QC_BUSY], 1u);

@@ -22,7 +22,7 @@ names = ["loop", "regen", "trav_closest", "surface+terminal", "sample_bxdf", "li
          "nee_eval", "bsdf_sample+push", "fold+store"]
 if queue:
     names = ["pick+pop", "S:load+surface", "S:sampler+light", "S:shadow trav", "S:nee eval", "bsdf+fold store / camera",
-             "closest trav", "T:result+fold", "T:items", "state store", "push", "idle", "W:walk step", "W:store"]
+             "closest trav", "T:result+fold", "T:items", "state store", "push", "idle", "W:walk step", "W:store", "T:tile sum"]
 out = (C.c_uint64 * 16)()
 _lib.check(_lib.lib.pine_gpu_plan_debug_sections(plan._h, out))
 tot = max(1, sum(out[:len(names)]))
