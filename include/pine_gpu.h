@@ -561,6 +561,16 @@ int pine_gpu_test_material_params(pine_gpu_scene*, int device, const float* quer
  * (BxdfKind order)  1-3 albedo  4 roughness  5 ior (0 where the lobe has no such member)  6 the sampler's dimension afterwards
  * 7 the next float of the pixel's RNG afterwards. */
 int pine_gpu_test_choose_lobe(pine_gpu_scene*, int device, const float* cases_host, int64_t n, float* out_host);
+/* The frame table: per face of every Rect (1), AABB and OBB (6: 2 * axis + 1 where the local normal points down
+ * the axis), in geometry order, one entry of 12 floats -- n, t, b, each padded to four -- and per geometry base[g], its first
+ * entry (-1: a kind without faces).  device = -1 (plan NULL): the scene's table as plan creation builds it, on the host.
+ * device >= 0: the table of `plan`, a plan of this scene, copied back from the device; no entries where the plan has none.
+ * generic (or NULL): per entry, in the same layout, what the per-hit code computes at a point of that face (host build of
+ * shape_surface_info and coordinate_system).  faces (or NULL): for nrays rays of 8 floats (pine_gpu_test_shapes) and every
+ * geometry that is no mesh, in that hook's record order, the face the host build reports at the hit; -1 without a hit or a face.
+ * Returns the number of entries, < 0 on error. */
+int64_t pine_gpu_test_frame_table(pine_gpu_scene*, pine_gpu_plan* plan, int device, float* entries, float* generic, int64_t cap_entries,
+                                  int32_t* base, int64_t cap_shapes, const float* rays_host, int64_t nrays, int32_t* faces);
 /* The precompiled path-kernel variants (pine_variants.h) in the order of the host's first-fit search: kind 0 the stage-queued
  * kernel, 1 the megakernel.  Up to `cap` entries of features (F_* bits), ctx (path contexts per workgroup; 0 for the
  * megakernel) and order; any of the arrays may be NULL.  Returns the number of variants, < 0 on error.  Needs no GPU.

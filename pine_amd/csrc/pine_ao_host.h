@@ -44,7 +44,7 @@ static int ao_plan_build(pine_gpu_plan* p, pine_gpu_scene* scene, const pine_gpu
 
   SceneParts sp;
   // (the sampler keeps its ORIGINAL count -- BlueSampler's table, SobolSampler's index stride -- only fewer indices are drawn)
-  if (assemble_scene(p, H, &prm, sp) || upload_sampler_tables(p, *tables_blob, &prm, sampler_spp)) return -1;
+  if (assemble_scene(p, H, &prm, sp, false) || upload_sampler_tables(p, *tables_blob, &prm, sampler_spp)) return -1;
   p->S.spp = spp;
   if (pine_gpu_ao_constants(scene, &p->ao_params.radius)) return -1;
   static_assert(offsetof(AoParams, dir) == sizeof(float) && sizeof(AoParams) == 26 * sizeof(float), "radius, then directions[8]");

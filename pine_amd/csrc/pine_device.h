@@ -789,8 +789,30 @@ PINE_HD bool shape_intersect(const DShape* S, DRay& ray) {
   return shape_intersect<F>(S->kind, S, ray);
 }
 
-// AABB::compute_surface_info bbox.cpp:122-129
-PINE_HD void aabb_surface_info(f3 lo, f3 hi, f3 p, DSurface& it) {
+// ---- faces of flat primitives, and the frame table built from them ----
+// A Rect has one face (0); an AABB or OBB has six: 2 * axis + (1 if the local normal points down the axis).  The world
+// normal and the tangent frame at a hit depend on the shape and the face only, so plan creation evaluates them once per face,
+// on the host, with the functions below -- the ones the kernels would run per hit -- and the kernels look them up.
+// One entry: n, t, b as three float4 (w unused).
+constexpr int kFrameFloats = 12;
+PINE_HD int frame_faces(int kind) { return kind == SHAPE_RECT ? 1 : (kind == SHAPE_AABB || kind == SHAPE_OBB) ? 6 : 0; }
+PINE_HD f3 box_face_normal(int face) {  // as aabb_surface_info leaves it.n
+  f3 n = mk3(0.0f);
+  set(n, face >> 1, (face & 1) ? -1.0f : 1.0f);
+  return n;
+}
+PINE_HD f3 obb_world_normal(const float* f, f3 n_local) { return normalize(mul(transpose(linear(ld34(f + 18))), n_local)); }  // bbox.cpp:176
+PINE_HD void frame_entry(const DShape* S, int face, float* e) {
+  f3 n = S->kind == SHAPE_RECT ? ld3(S->f + 9) : box_face_normal(face);
+  if (S->kind == SHAPE_OBB) n = obb_world_normal(S->f, n);
+  const m3 m = coordinate_system(n);
+  e[0] = n.x, e[1] = n.y, e[2] = n.z, e[3] = 0.0f;
+  e[4] = m.x.x, e[5] = m.x.y, e[6] = m.x.z, e[7] = 0.0f;
+  e[8] = m.y.x, e[9] = m.y.y, e[10] = m.y.z, e[11] = 0.0f;
+}
+
+// AABB::compute_surface_info bbox.cpp:122-129.  Returns the face.
+PINE_HD int aabb_surface_info(f3 lo, f3 hi, f3 p, DSurface& it) {
   it.p = p;
   const f3 pu = (p - (lo + hi) / 2.0f) / (hi - lo);
   const int axis = max_axis(vabs(pu));
@@ -798,12 +820,16 @@ PINE_HD void aabb_surface_info(f3 lo, f3 hi, f3 p, DSurface& it) {
   const bool pos = get(pu, axis) > 0;
   set(it.n, axis, pos ? 1.0f : -1.0f);
   set(it.p, axis, pos ? get(hi, axis) : get(lo, axis));
+  return 2 * axis + (pos ? 0 : 1);
 }
 
+// The surface at p.  Returns the face that was hit (a kind without faces: -1).  `frames`: the frame table, or null; an OBB
+// takes its world normal from there, `base` being its first entry.  (Callers pass a wave-uniform `frames`.)
 template <unsigned F = F_ALL>
-PINE_HD void shape_surface_info(const DShape* S, f3 p, DSurface& it) {
+PINE_HD int shape_surface_info(const DShape* S, f3 p, DSurface& it, const float* frames = nullptr, int base = 0) {
   const float* f = S->f;
   it.uv = f2{0, 0};
+  int face = -1;
   switch (S->kind) {
     case SHAPE_RECT: {  // geometry.cpp:300-307
       const f3 position = ld3(f);
@@ -813,14 +839,24 @@ PINE_HD void shape_surface_info(const DShape* S, f3 p, DSurface& it) {
       it.p = position + f[12] * ld3(f + 3) * u + f[13] * ld3(f + 6) * v;
       it.n = ld3(f + 9);
       it.uv = f2{u, v} + f2{0.5f, 0.5f};
+      face = 0;
       break;
     }
-    case SHAPE_AABB: if constexpr (!(F & F_AABB)) __builtin_unreachable(); else { aabb_surface_info(ld3(f), ld3(f + 3), p, it); } break;
+    case SHAPE_AABB: if constexpr (!(F & F_AABB)) __builtin_unreachable(); else { face = aabb_surface_info(ld3(f), ld3(f + 3), p, it); } break;
     case SHAPE_OBB: if constexpr (!(F & F_OBB)) __builtin_unreachable(); else {  // bbox.cpp:173-177
       const m34 mi = ld34(f + 18);
-      aabb_surface_info(ld3(f), ld3(f + 3), mul_point(mi, p), it);
+      face = aabb_surface_info(ld3(f), ld3(f + 3), mul_point(mi, p), it);
       it.p = mul_point(ld34(f + 6), it.p);
-      it.n = normalize(mul(transpose(linear(mi)), it.n));
+#if defined(PINE_DUP_FRAME) && defined(__HIP_DEVICE_COMPILE__)  /* cost measurement only: the world normal once more on an opaque copy of the local one (same film; the extra time is its cost) */
+      {
+        f3 nl = it.n;
+        asm volatile("" : "+v"(nl.x), "+v"(nl.y), "+v"(nl.z));
+        const f3 nw = obb_world_normal(f, nl);
+        float sink = nw.x + nw.y + nw.z;
+        asm volatile("" : : "v"(sink));
+      }
+#endif
+      it.n = frames ? ld3(frames + (base + face) * kFrameFloats) : obb_world_normal(f, it.n);
       break;
     }
     case SHAPE_SPHERE: if constexpr (!(F & F_SPHERE)) __builtin_unreachable(); else {  // geometry.cpp:94-98
@@ -887,6 +923,7 @@ PINE_HD void shape_surface_info(const DShape* S, f3 p, DSurface& it) {
     }
     default: it.p = p; it.n = mk3(0.0f); break;
   }
+  return face;
 }
 
 // Triangle tests on 9 floats v0,v1,v2 (geometry.cpp:532-565)

@@ -254,7 +254,7 @@ enum : int { kSpecSourceNone = 0, kSpecSourceCache = 1, kSpecSourceCompiledHere 
 namespace pine_gpu {
 AbiFingerprint abi_fingerprint() {
   return AbiFingerprint{sizeof(DeviceScene), sizeof(WorkParams), sizeof(Counters), sizeof(DNode), sizeof(DShape), sizeof(DMaterial), sizeof(DLight),
-                        offsetof(WorkParams, total_items), offsetof(DeviceScene, cam), kQFields, kQWinDwords, int(QC_WORDS), kQTokenDwords,
+                        offsetof(WorkParams, total_items), offsetof(DeviceScene, cam), offsetof(DeviceScene, off_frames), kQFields, kQWinDwords, int(QC_WORDS), kQTokenDwords,
                         kTravRecordDwords, kQCtxGlobalDwordsPlain, kQCtxGlobalDwordsSss};
 }
 }  // namespace pine_gpu
@@ -321,6 +321,7 @@ struct PlanKnobs {
   // PINE_GPU_OWNED_TILES: tiles claimed whole and summed inside the stage-queued kernel (0: none, n: that many, unset: automatic;
   // size_and_allocate).  Test hook PINE_GPU_TEST_TILE_SLOTS=<n>: a workgroup's table of such tiles in flight has n slots.
   int owned_tiles, tile_slots;
+  int frame_table;  // PINE_GPU_FRAME_TABLE (0: plans have no frame table)
 };
 static PlanKnobs read_knobs() {
   auto num = [](const char* name) { return getenv(name) ? atoi(getenv(name)) : kUnset; };
@@ -342,7 +343,7 @@ static PlanKnobs read_knobs() {
                    set("PINE_GPU_SPECIALIZE_FORCE"), set("PINE_GPU_NO_LDS_SCENE"), kernel && std::string(kernel) == "mega",
                    set("PINE_GPU_NO_TILE_CLASSES"), set("PINE_GPU_NO_FORK"), ckpt != kUnset && ckpt != 0,
                    budget && atof(budget) > 0 ? atof(budget) : 30.0, pin_kind, pin_order, num("PINE_GPU_TEST_LDS_NODES"),
-                   num("PINE_GPU_OWNED_TILES"), num("PINE_GPU_TEST_TILE_SLOTS")};
+                   num("PINE_GPU_OWNED_TILES"), num("PINE_GPU_TEST_TILE_SLOTS"), num("PINE_GPU_FRAME_TABLE")};
 }
 
 static int plan_adopt_kernel(pine_gpu_plan* p, bool compile_here);
@@ -708,6 +709,7 @@ struct SceneParts {
   std::vector<int> packed_prims;     // top-level entries: geometry | emissive | kind (pine_types.h)
   std::vector<DLight> lights;        // + the environment light last (lightsampler.cpp:6-10)
   size_t tri_packet_bytes = 0;        // (0: no triangle packets, build_tri_packets)
+  int blob_bytes_plain = 0;           // DeviceScene::blob_bytes without the frame table (equal: the scene has none)
 };
 
 // The samples per pixel the plan renders, or -1.
@@ -752,7 +754,8 @@ static int check_params(const SceneHost& H, const pine_gpu_render_params* prm) {
 
 // The scene's records on the device: the blob of small records, the triangles and their LDS packets; the traversal stack
 // depth, checked with every index before anything is launched.
-static int assemble_scene(pine_gpu_plan* p, SceneHost& H, const pine_gpu_render_params* prm, SceneParts& sp) {
+// `frames`: with the frame table (pine_plan.h build_frame_table) behind everything else that scene-in-LDS variants stage.
+static int assemble_scene(pine_gpu_plan* p, SceneHost& H, const pine_gpu_render_params* prm, SceneParts& sp, bool frames) {
   const FlatAccel& A = H.accel;
   std::vector<DShape>& shapes = sp.shapes;
   for (auto& g : H.geometries) shapes.push_back(g.shape);
@@ -841,6 +844,21 @@ static int assemble_scene(pine_gpu_plan* p, SceneHost& H, const pine_gpu_render_
   const bool table_in_lds = order_embree && blob.size() + sizeof(kRcppsTable) + 64 <= 32 * 1024;
   if (table_in_lds) S.off_rcpps = put(kRcppsTable, sizeof(kRcppsTable));
   blob.resize((blob.size() + 15) & ~size_t(15));
+  sp.blob_bytes_plain = int(blob.size());
+  S.off_frames = S.off_frame_base = 0;
+  // (only stage S reads a frame, and it shades no emissive surface: a scene whose flat shapes are all lamps gets no table)
+  bool shaded_flat = false;
+  for (const DShape& sh : shapes) shaded_flat |= frame_faces(sh.kind) != 0 && H.materials[size_t(sh.material)].kind != MAT_EMISSIVE;
+  if (frames && shaded_flat) {
+    std::vector<float> entries;
+    std::vector<int> base;
+    build_frame_table(shapes, entries, base);
+    {
+      S.off_frames = put(entries.data(), entries.size() * sizeof(float));
+      S.off_frame_base = put(base.data(), base.size() * sizeof(int));
+      blob.resize((blob.size() + 15) & ~size_t(15));
+    }
+  }
   S.blob_bytes = int(blob.size());
   if (order_embree && !table_in_lds) S.off_rcpps = put(kRcppsTable, sizeof(kRcppsTable));
   HIP_OK(POOL_ALLOC(p->d_blob, blob.size()));
@@ -1102,6 +1120,29 @@ static int choose_variants(pine_gpu_plan* p, const FlatAccel& A, const ScenePart
   }
   p->queue_variant = -1;
   return 0;
+}
+
+// The frame table pays where a hit reads it from LDS, so a plan keeps it only where its kernel stages it there with the rest of
+// the blob (F_LDS_SCENE, F_LDS_REST) and is otherwise the kernel the plan would have had: the same variant, the same BVH nodes
+// and triangle packets in LDS.  Everywhere else the plan has no table, and its kernel does no per-hit work for one.
+static int choose_variants_with_frames(pine_gpu_plan* p, const FlatAccel& A, const SceneParts& sp, const pine_gpu_render_params* prm, unsigned need,
+                                       const PlanKnobs& K) {
+  DeviceScene& S = p->S;
+  const int with_table = S.blob_bytes;
+  auto choose = [&](int blob_bytes) {
+    S.blob_bytes = blob_bytes;
+    return choose_variants(p, A, sp, prm, need, K);
+  };
+  if (choose(sp.blob_bytes_plain)) return -1;
+  if (S.off_frames == 0) return 0;
+  const int variant = p->variant, queue_variant = p->queue_variant, lds_nodes = S.lds_nodes, lds_tris = S.lds_tris;
+  const unsigned F = queue_variant >= 0 ? kQueueVariants[queue_variant].features : kVariants[variant].features;
+  if ((F & (F_LDS_SCENE | F_LDS_REST)) != 0 && choose(with_table) == 0 && p->variant == variant && p->queue_variant == queue_variant &&
+      S.lds_nodes == lds_nodes && S.lds_tris == lds_tris)
+    return 0;
+  // (assemble_scene has uploaded the table already: its bytes stay in d_blob behind blob_bytes, read by nobody and staged by no kernel)
+  S.off_frames = S.off_frame_base = 0;
+  return choose(sp.blob_bytes_plain);
 }
 
 // Tile classes (WorkParams::serial_tiles): in a scene whose only in-path RNG consumer is the BSSRDF channel pick and whose other
@@ -1448,10 +1489,12 @@ static int plan_build(pine_gpu_plan* p, pine_gpu_scene* scene, const pine_gpu_re
   const FlatAccel& A = H.accel;
 
   SceneParts sp;
-  if (assemble_scene(p, H, prm, sp) || upload_sampler_tables(p, *tables_blob, prm, spp)) return -1;
+  // (the declared-tolerance kernels keep their own arithmetic for every normal: no table of exact ones)
+  const bool frames = K.frame_table != 0 && !(prm->flags & PINE_GPU_FLAG_FAST);
+  if (assemble_scene(p, H, prm, sp, frames) || upload_sampler_tables(p, *tables_blob, prm, spp)) return -1;
   p->S.spp = spp;
   const unsigned need = scene_features(sp, prm);
-  if (choose_variants(p, A, sp, prm, need, K) || plan_specialize(p, A, sp.shapes, sp.packed_prims, prm, need, K)) return -1;
+  if (choose_variants_with_frames(p, A, sp, prm, need, K) || plan_specialize(p, A, sp.shapes, sp.packed_prims, prm, need, K)) return -1;
   bool uber_rng = false;
   if (choose_items(p, H, sp, prm, spp, K, uber_rng)) return -1;
   schedule_params(p, A, prm, uber_rng, K);

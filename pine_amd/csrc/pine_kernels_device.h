@@ -101,6 +101,9 @@ struct DeviceScene {
   // shape) -- the places in `leaf` of the meshes (num_emesh ints at off_emesh; tested first) and the 2048 RCPPS estimates
   // (off_rcpps: BEHIND blob_bytes, global memory only)
   int off_etree, etree_root, off_emesh, num_emesh, off_rcpps;
+  // The frame table (pine_device.h frame_entry), inside the staged part of the blob: the entries at off_frames
+  // (0: the plan has no table) and, at off_frame_base, one word per shape -- its first entry, or -1 for a kind without faces.
+  int off_frames, off_frame_base;
 };
 
 // (EmbreeNode, kEmbreeNoChild, kEmbreeStackEntries: pine_types.h)
@@ -136,6 +139,9 @@ struct SceneView {
   const int* emesh;
   int num_emesh;
   const unsigned* rcpps;
+  const float* frames;    // DeviceScene::off_frames / off_frame_base; read only where has_frames
+  const int* frame_base;
+  int has_frames;
 };
 
 // One BVH node into registers.  F_LDS_TOP: from the workgroup's LDS copy when the index is below the cached
@@ -914,7 +920,7 @@ __device__ __forceinline__ f3 material_le(const DMaterial* m, f3 n, f3 wo) {  //
 //   RNG state       4 x 256                       per-pixel xoroshiro state (only touched at sample start)
 //   Sobol rows      40 x 256 bytes                transposed table, dimensions < 40
 //   traversal stack stack_total x 256             (runtime depth)
-//   scene blob      blob_bytes                    nodes | shapes | materials | bvhs | prims | lights
+//   scene blob      blob_bytes                    nodes | shapes | materials | bvhs | prims | lights | frame table
 constexpr int kOffFold = 0;
 constexpr int kOffTile = kLdsFoldLevels * 8 * kBlock;
 constexpr int kOffRng = kOffTile + kLdsTileDwords * kBlock;
@@ -1130,6 +1136,7 @@ path_trace_kernel(DeviceScene S, WorkParams W, const ulonglong2* __restrict__ ck
     DSurface it{};
     const DShape* shape = nullptr;
     const DMaterial* mat = nullptr;
+    int frame = -1;  // (hit_surface: the hit's entry of the frame table)
     if (!hit) {
       terminal = true;
       Lo = terminal_radiance<F>(V, S.env_light, S.num_lights, false, shape, it, ray_o, ray_d, ray_tmax, st.is_delta(), has_light_pdf, light_pdf);
@@ -1137,7 +1144,7 @@ path_trace_kernel(DeviceScene S, WorkParams W, const ulonglong2* __restrict__ ck
       REGION(3);  // surface info
       shape = &V.shapes[geom];
       mat = &V.materials[shape->material];
-      hit_surface<F>(V, shape, prim, ray_o, ray_d, ray_tmax, it);
+      frame = hit_surface<F>(V, shape, prim, ray_o, ray_d, ray_tmax, it);
       if (mat->kind == MAT_EMISSIVE) {
         Lo = terminal_radiance<F>(V, S.env_light, S.num_lights, true, shape, it, ray_o, ray_d, ray_tmax, st.is_delta(), has_light_pdf, light_pdf);
         terminal = true;
@@ -1150,7 +1157,7 @@ path_trace_kernel(DeviceScene S, WorkParams W, const ulonglong2* __restrict__ ck
     if (!terminal) {
       REGION(6);  // non-terminal shading
       const f3 wi = -ray_d;
-      m3 l2w = coordinate_system(it.n);  // interaction.h:14-17
+      m3 l2w = surface_frame(V, frame, it.n);
       m3 w2l = transpose(l2w);
       const MatParams mp = material_params<F>(mat, V.node_ops, it.p, it.n, it.uv);
       DBxdf bx;

@@ -207,6 +207,22 @@ static int upload(T*& dptr, const std::vector<T>& v) {
   if (!v.empty()) HIP_OK(hipMemcpy(dptr, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
   return 0;
 }
+// The frame table of a scene's shapes (pine_device.h frame_entry): one entry per face of every Rect, AABB and OBB
+// in geometry order, kFrameFloats floats each; base[g] = the first entry of shape g, or -1 for a kind without faces.
+inline void build_frame_table(const std::vector<DShape>& shapes, std::vector<float>& entries, std::vector<int>& base) {
+  entries.clear();
+  base.assign(shapes.size(), -1);
+  for (size_t g = 0; g < shapes.size(); g++) {
+    const int faces = frame_faces(shapes[g].kind);
+    if (faces == 0) continue;
+    base[g] = int(entries.size() / kFrameFloats);
+    for (int face = 0; face < faces; face++) {
+      entries.resize(entries.size() + kFrameFloats);
+      frame_entry(&shapes[g], face, &entries[entries.size() - kFrameFloats]);
+    }
+  }
+}
+
 static int need_device(int device) {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
@@ -228,7 +244,7 @@ struct pine_gpu_plan {
   WorkParams W{};
   int film_w = 0, film_h = 0;
   // device buffers
-  char* d_blob = nullptr;  // nodes | shapes | materials | bvhs | prims | lights
+  char* d_blob = nullptr;  // nodes | shapes | materials | bvhs | prims | lights | frame table
   float* d_tri = nullptr;
   float* d_tri_leaf = nullptr;
   uint4* d_tri_packets = nullptr;

@@ -843,9 +843,9 @@ __device__ __forceinline__ void path_queue_body(const DeviceScene& S, const Work
         const DShape* shape = &V.shapes[geom];
         const DMaterial* mat = &V.materials[shape->material];
         DSurface it;
-        hit_surface<F>(V, shape, prim, ray_o, ray_d, ray_tmax, it);
+        const int frame = hit_surface<F>(V, shape, prim, ray_o, ray_d, ray_tmax, it);
         const f3 wi = -ray_d;
-        m3 l2w = coordinate_system(it.n);
+        m3 l2w = surface_frame(V, frame, it.n);
         m3 w2l = transpose(l2w);
         const MatParams mp = material_params<F>(mat, V.node_ops, it.p, it.n, it.uv);
         auto rng_load = [&]() -> DRng {

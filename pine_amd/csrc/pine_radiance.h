@@ -33,6 +33,8 @@ __device__ __forceinline__ void view_of_blob(const char* base, const DeviceScene
   V.node_ops = reinterpret_cast<const DNodeOp*>(base + S.off_node_ops);
   V.leaf = reinterpret_cast<const DShape*>(base + S.off_leaf) - S.top_prim_begin;
   view_of_embree_order(base, S, V);
+  V.frames = reinterpret_cast<const float*>(base + S.off_frames);
+  V.frame_base = reinterpret_cast<const int*>(base + S.off_frame_base);
 }
 
 // The scene where the host put it: every field of the view from the DeviceScene's global-memory pointers, nothing in LDS.
@@ -59,6 +61,9 @@ __device__ __forceinline__ SceneView scene_view_global(const DeviceScene& S) {
   view_of_embree_order(reinterpret_cast<const char*>(S.blob), S, V);
   V.etree_root = S.etree_root;
   V.num_emesh = S.num_emesh;
+  V.frames = reinterpret_cast<const float*>(reinterpret_cast<const char*>(S.blob) + S.off_frames);
+  V.frame_base = reinterpret_cast<const int*>(reinterpret_cast<const char*>(S.blob) + S.off_frame_base);
+  V.has_frames = S.off_frames != 0;
   V.rcpps = reinterpret_cast<const unsigned*>(reinterpret_cast<const char*>(S.blob) + S.off_rcpps);
   return V;
 }
@@ -148,18 +153,56 @@ __device__ __forceinline__ DRay camera_sample(const DCamera& cam, int px, int py
   return camera_gen_ray(cam, pf, f2{lx, ly});
 }
 
-// The surface at the hit of ray (ray_o, ray_d) at tmax with primitive `prim` of `shape`.
+// The surface at the hit of ray (ray_o, ray_d) at tmax with primitive `prim` of `shape`.  Returns the index of the frame-table
+// entry of the face that was hit, or a negative number (no table, or a hit that has no entry): surface_frame takes it.
 template <unsigned F>
-__device__ __forceinline__ void hit_surface(const SceneView& V, const DShape* shape, int prim, f3 ray_o, f3 ray_d, float tmax, DSurface& it) {
+__device__ __forceinline__ int hit_surface(const SceneView& V, const DShape* shape, int prim, f3 ray_o, f3 ray_d, float tmax, DSurface& it) {
   it.p = it.n = mk3(0.0f);
   it.uv = f2{0, 0};
   const f3 ph = ray_o + tmax * ray_d;
   bool on_mesh = false;
   if constexpr (F & F_MESH) on_mesh = shape->kind == SHAPE_MESH;
+  int entry = -1;
   if (on_mesh) {
     if constexpr (F & F_EMBREE) mesh_surface_info_embree(V.rcpps, V.tri_verts, V.tri_attrs, as_int(shape->f[4]), prim, ray_o, ray_d, it);
     else mesh_surface_info(V.tri_verts, V.tri_attrs, as_int(shape->f[4]), prim, ph, it);
-  } else shape_surface_info<F>(shape, ph, it);
+  } else {
+    // (has_frames is the same in every lane: a plan without a table does no more here than carry the face along; with one, only
+    //  a Rect, an AABB or an OBB loads its base word.  A face is -1 ... 5, so `kNoFrame + face` stays negative.)
+    constexpr int kNoFrame = -8;
+    const float* frames = nullptr;
+    int base = kNoFrame;
+    if (V.has_frames) {
+      frames = V.frames;
+      if (frame_faces(shape->kind) != 0) base = V.frame_base[shape - V.shapes];
+    }
+    entry = base + shape_surface_info<F>(shape, ph, it, frames, base);
+  }
+  return entry;
+}
+
+// The tangent frame at a surface with normal n (interaction.h:14-17): the table's n, t, b where the hit has an entry
+// (`entry`, from hit_surface), coordinate_system(n) elsewhere -- the same bits, by how the table is built.  A plan without a table
+// runs coordinate_system as if there were no such thing as a table; with one, a wave none of whose lanes lacks an entry only
+// loads, and a mixed wave computes and then loads over the result where a lane has an entry.
+__device__ __forceinline__ m3 surface_frame(const SceneView& V, int entry, f3 n) {
+#ifdef PINE_DUP_FRAME  /* cost measurement only: coordinate_system once more on an opaque copy of n (same film; the extra time is its cost) */
+  {
+    f3 nn = n;
+    asm volatile("" : "+v"(nn.x), "+v"(nn.y), "+v"(nn.z));
+    const m3 d = coordinate_system(nn);
+    float sink = d.x.x + d.x.y + d.x.z + d.y.x + d.y.y + d.y.z;
+    asm volatile("" : : "v"(sink));
+  }
+#endif
+  auto load = [&]() {
+    const float4 *q = reinterpret_cast<const float4*>(V.frames) + (kFrameFloats / 4) * entry, en = q[0], et = q[1], eb = q[2];
+    return m3{f3{et.x, et.y, et.z}, f3{eb.x, eb.y, eb.z}, f3{en.x, en.y, en.z}};
+  };
+  if (V.has_frames && __ballot(entry < 0) == 0) return load();
+  m3 m = coordinate_system(n);
+  if (V.has_frames && entry >= 0) m = load();
+  return m;
 }
 
 // What a path's last vertex returns, and the pdf of having picked it by light sampling (for the MIS weight one level up)

@@ -589,6 +589,85 @@ int pine_gpu_test_shapes(pine_gpu_scene* scene, int device, const float* rays, i
   return 0;
 }
 
+// pine_gpu_test_frame_table: the table as plan creation builds it (device < 0: here, on the host) or as a plan's kernels read it
+// (device >= 0: copied back from the plan's scene blob).  `generic`: per entry what the per-hit code computes at a point of that
+// face; `faces`: the face shape_surface_info reports for caller-given rays.
+static f3 point_on_face(const DShape& sh, int face) {
+  const float* f = sh.f;
+  if (sh.kind == SHAPE_RECT) return ld3(f);
+  const f3 lo = ld3(f), hi = ld3(f + 3);
+  f3 p = (lo + hi) / 2.0f;
+  set(p, face >> 1, (face & 1) ? get(lo, face >> 1) : get(hi, face >> 1));
+  return sh.kind == SHAPE_OBB ? mul_point(ld34(f + 6), p) : p;
+}
+int64_t pine_gpu_test_frame_table(pine_gpu_scene* scene, pine_gpu_plan* plan, int device, float* entries, float* generic, int64_t cap_entries,
+                                  int32_t* base, int64_t cap_shapes, const float* rays, int64_t nrays, int32_t* faces) {
+  if (!scene || (device >= 0) != (plan != nullptr) || (faces && !rays) || nrays < 0) {
+    set_error("pine_gpu_test_frame_table: bad argument (device >= 0 reads a plan's table, device < 0 builds the scene's)");
+    return -1;
+  }
+  SceneHost& H = scene_host(scene);
+  std::vector<DShape> shapes;
+  for (auto& g : H.geometries) shapes.push_back(g.shape);
+  std::vector<float> table;
+  std::vector<int> first;
+  if (plan) {
+    const DeviceScene& S = plan->S;
+    if (size_t(S.num_shapes) != shapes.size()) {
+      set_error("pine_gpu_test_frame_table: the plan is not one of this scene");
+      return -1;
+    }
+    first.assign(shapes.size(), -1);
+    if (S.off_frames != 0) {
+      HIP_OK(hipSetDevice(plan->device));
+      table.resize(size_t(S.off_frame_base - S.off_frames) / sizeof(float));
+      HIP_OK(hipMemcpy(table.data(), plan->d_blob + S.off_frames, table.size() * sizeof(float), hipMemcpyDeviceToHost));
+      HIP_OK(hipMemcpy(first.data(), plan->d_blob + S.off_frame_base, first.size() * sizeof(int), hipMemcpyDeviceToHost));
+      int n = 0;
+      for (const DShape& sh : shapes) n += frame_faces(sh.kind);
+      table.resize(size_t(n) * kFrameFloats);  // (without the section's padding)
+    }
+  } else build_frame_table(shapes, table, first);
+  const int64_t n = int64_t(table.size() / kFrameFloats);
+  if (n > cap_entries || int64_t(shapes.size()) > cap_shapes || !entries || !base) {
+    set_error("pine_gpu_test_frame_table: capacity too small");
+    return -1;
+  }
+  memcpy(entries, table.data(), table.size() * sizeof(float));
+  for (size_t g = 0; g < shapes.size(); g++) base[g] = first[g];
+  if (generic)
+    for (size_t g = 0; g < shapes.size(); g++) {
+      if (first[g] < 0) continue;
+      for (int face = 0; face < frame_faces(shapes[g].kind); face++) {
+        DSurface it;
+        it.p = it.n = mk3(0.0f);
+        it.uv = f2{0, 0};
+        if (shape_surface_info(&shapes[g], point_on_face(shapes[g], face), it) != face) {
+          set_error("pine_gpu_test_frame_table: a point of a face is not reported on that face");
+          return -1;
+        }
+        const m3 m = coordinate_system(it.n);
+        float* e = generic + (size_t(first[g]) + size_t(face)) * kFrameFloats;
+        e[0] = it.n.x, e[1] = it.n.y, e[2] = it.n.z, e[3] = 0.0f;
+        e[4] = m.x.x, e[5] = m.x.y, e[6] = m.x.z, e[7] = 0.0f;
+        e[8] = m.y.x, e[9] = m.y.y, e[10] = m.y.z, e[11] = 0.0f;
+      }
+    }
+  if (faces) {  // (the records' order of pine_gpu_test_shapes: every shape that is no mesh, every ray)
+    int32_t* o = faces;
+    for (const DShape& sh : shapes) {
+      if (sh.kind == SHAPE_MESH) continue;
+      for (int64_t r = 0; r < nrays; r++) {
+        const float* q = rays + r * 8;
+        DRay ray{f3{q[0], q[1], q[2]}, f3{q[3], q[4], q[5]}, q[6], q[7]};
+        DSurface it;
+        *o++ = shape_intersect(&sh, ray) ? shape_surface_info(&sh, ray_at(ray, ray.tmax), it) : -1;
+      }
+    }
+  }
+  return n;
+}
+
 int pine_gpu_test_bxdf(int device, const float* cases, int64_t n, float* out) {
   if (!cases || !out || n < 0 || n > (1 << 24)) {
     set_error("bad argument");
