@@ -4,7 +4,7 @@
 // one random frame -- no materials, no lights, no fold, no recursion.  A sample's value is k / 8, k the rays that met
 // nothing, so a pixel's sum is exact in any order and the kernel counts unoccluded rays per pixel as INTEGERS with plain
 // atomics; ao_film_kernel turns the counts into the film, (count * 0.125f) / spp.  Every building block is the path
-// kernels' (the prologue of pine_radiance.h -- scene view, LDS staging, sampler slices --, camera_sample, scene_traverse
+// kernels' (the prologue of pine_radiance.h -- scene view, LDS staging, sampler slices --, camera_sample, pine_traverse.h's scene_traverse
 // in pine-BVH order, hit_surface, the samplers, spawn_ray): the same bits.
 //
 // Two schedules of the same arithmetic (template parameter REGROUP):

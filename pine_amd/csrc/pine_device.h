@@ -39,7 +39,7 @@ enum : unsigned {
   F_BAKED = 1u << 17,     // scene-specialised builds (pine_specialize.h): the scene's BVH and primitive records are baked into the kernel
                           // (a -DPINE_BAKED_SCENE compile; the bit only makes such a kernel's name its own in profiles)
   F_EMBREE = 1u << 18,    // PINE_GPU_FLAG_ORDER_EMBREE: closest-hit queries hand the shapes to their tests in the order of the reference's
-                          // EmbreeAccel (scene_traverse_embree, pine_kernels_device.h) instead of in pine-BVH order;
+                          // EmbreeAccel (scene_traverse_embree, pine_traverse.h) instead of in pine-BVH order;
                           // a few variants only (pine_variants.h), never chosen without the flag
   F_ALL = 0xffu | F_NODES | F_LIGHTS | F_XSHAPES | F_SOBOL,
 };

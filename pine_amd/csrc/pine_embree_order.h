@@ -1,5 +1,5 @@
 // pine_amd/csrc/pine_embree_order.h -- host side of PINE_GPU_FLAG_ORDER_EMBREE: the hierarchy the reference's DEFAULT accel
-// walks (included by pine_kernels.hip; the device side is scene_traverse_embree in pine_kernels_device.h).
+// walks (included by pine_kernels.hip; the device side is scene_traverse_embree in pine_traverse.h).
 //
 // What is reproduced, and from where.  EmbreeAccel registers every non-mesh shape as ONE Embree user primitive whose bounds and
 // whose intersect callback are pine's own (src/pine/impl/accel/embree.cpp:12-40, :88-99).  So the reference's images depend on

@@ -550,9 +550,7 @@ __device__ __forceinline__ void path_queue_body(const DeviceScene& S, const Work
             ts.done = 0;
             ts.mesh_base = 0;
             ts.mesh_word = kBakedMeshWord;
-            ts.pb = ts.pbn = 0;
-            if (mb.root_count > 0) ts.next = -1, ts.pa = mb.root_start, ts.pan = mb.root_count;
-            else ts.next = mb.root, ts.pa = ts.pan = 0;
+            trav_enter_mesh(ts, mb);
           }
         }
 #endif

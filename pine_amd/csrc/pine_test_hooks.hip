@@ -109,10 +109,11 @@ __global__ void test_rng_kernel(unsigned long long* out) {
   for (int i = 0; i < 16; i++) o[3 + i] = (unsigned long long)(uint32_t)as_int(rng_nextf(g));
 }
 // The primitives a ray's traversal tests, in order, and its result: the nested loops of the scene-in-LDS variants
-// (FLAT = false: scene_traverse / mesh_traverse) or the flat state machine of the F_LDS_TOP variants (pine_trav.h).
+// (FLAT = false: scene_traverse / mesh_traverse, pine_traverse.h) or the flat state machine of the F_LDS_TOP variants (pine_trav.h).
 // One thread per ray, 64 per block; out: per ray `cap` words closest (count, words...), 4 result words (hit, geometry,
 // triangle, tmax bits), `cap` words any-hit, 1 result word.
-// (MODE 2: the closest-hit query in EmbreeAccel's order, PINE_GPU_FLAG_ORDER_EMBREE; the any-hit query is the nested loops')
+// (MODE 2: both queries in EmbreeAccel's order, PINE_GPU_FLAG_ORDER_EMBREE -- scene_traverse_embree for the closest hit,
+//  scene_occluded_embree for the any-hit query; tests/test_embree_order.py compares each with the real Embree's)
 template <int MODE>
 __global__ void __launch_bounds__(64) test_traverse_kernel(DeviceScene S, const float* rays, long long nrays, int cap, unsigned* out) {
   constexpr bool FLAT = MODE == 1;

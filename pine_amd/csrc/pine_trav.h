@@ -1,5 +1,6 @@
 // pine_amd/csrc/pine_trav.h -- the flat BVH traversal of the stage-queued kernel's F_LDS_TOP variants (included by
-// pine_kernels.hip after SceneView / fetch_node; used by pine_queue_kernel.h).
+// pine_kernels_device.h after pine_traverse.h, whose shared steps -- fetch_node, fetch_triangle, load_leaf_record,
+// bvh2_order_children -- it uses; used by pine_queue_kernel.h).
 //
 // Why: in scenes with a real BVH (10 000 cones, triangle meshes) the rays of one wave need wildly
 // different numbers of node visits; with nested node / leaf loops the wave runs until its longest ray
@@ -59,6 +60,19 @@ __device__ __forceinline__ void trav_begin(const SceneView& S, TravState& ts) {
     ts.next = top.root;
   } else {
     ts.done = 1;  // geometries exist but none has primitives
+  }
+}
+// Start on a mesh's BVH (the caller has saved the top-level state and set mesh_base / mesh_word): its root is a leaf
+// (bvh.cpp:331-334) -> that range is pending, else its root is the node to visit.
+__device__ __forceinline__ void trav_enter_mesh(TravState& ts, const DBvh& mb) {
+  ts.pb = ts.pbn = 0;
+  if (mb.root_count > 0) {
+    ts.next = -1;
+    ts.pa = mb.root_start;
+    ts.pan = mb.root_count;
+  } else {
+    ts.next = mb.root;
+    ts.pa = ts.pan = 0;
   }
 }
 
@@ -168,18 +182,7 @@ __device__ __forceinline__ void trav_trips(const SceneView& S, DRay& ray, const 
         else if (ts.pan > 0) ts.pb = nd.child[1], ts.pbn = nd.count[1];
         else ts.pa = nd.child[1], ts.pan = nd.count[1];
       }
-      if (l != -1) {
-        if (r != -1) {
-          if (t0 > t1) {
-            stack[ts.sp * STRIDE] = StackT(l);
-            ts.next = r;
-          } else {
-            stack[ts.sp * STRIDE] = StackT(r);
-            ts.next = l;
-          }
-          ts.sp++;
-        } else ts.next = l;
-      } else ts.next = r;  // (-1 when neither child is an inner node to visit)
+      bvh2_order_children<STRIDE>(l, r, t0, t1, stack, ts.sp, ts.next);  // (-1 when neither child is an inner node to visit)
     }
     }
     // (a node whose child is a leaf: its first primitive is tested in this same trip)
@@ -206,19 +209,7 @@ __device__ __forceinline__ void trav_trips(const SceneView& S, DRay& ray, const 
         }
       } else {
         REGION(ANY ? 7 : 3);
-        const DShape* sh = &S.leaf[i];
-        // The whole 128-byte record is fetched in ONE batch of loads before the kind is looked at: reading the kind word
-        // first and the kind's fields after the dispatch is two dependent round trips per primitive test -- to L2 for the
-        // 10 000-cone scene, whose records live in global memory (C4 7.70 -> 7.11 ms), to LDS elsewhere (C5 134.5 -> 132.1).
-        // (Quads that no kind of the variant reads are dead loads the compiler drops.)
-        DShape rec;
-        {
-          const uint4* src = reinterpret_cast<const uint4*>(sh);
-          uint4* dst = reinterpret_cast<uint4*>(&rec);
-#pragma unroll
-          for (int q = 0; q < 8; q++) dst[q] = src[q];
-          sh = &rec;
-        }
+        const DShape rec = load_leaf_record(&S.leaf[i]), *sh = &rec;
         const int word = sh->kind;  // (the packed word rides in the copy's kind field)
         const int kind = word >> kPrimKindShift;
         bool is_mesh = false;
@@ -231,15 +222,7 @@ __device__ __forceinline__ void trav_trips(const SceneView& S, DRay& ray, const 
             ts.r_next = ts.next, ts.r_pa = ts.pa, ts.r_pan = ts.pan, ts.r_pb = ts.pb, ts.r_pbn = ts.pbn;
             ts.mesh_base = ts.sp;
             ts.mesh_word = word;
-            ts.pb = ts.pbn = 0;
-            if (mb.root_count > 0) {
-              ts.next = -1;
-              ts.pa = mb.root_start;
-              ts.pan = mb.root_count;
-            } else {
-              ts.next = mb.root;
-              ts.pa = ts.pan = 0;
-            }
+            trav_enter_mesh(ts, mb);
           }
         } else if (ANY) {
 #ifdef PINE_DUP_TRAV_PRIMS  /* cost measurement only: the shape test once more on an opaque copy of the ray */

@@ -144,6 +144,24 @@ def sss(size=(640, 640), subdiv=3, camera="readme", skin=None, emissive_mesh=Fal
     return scene
 
 
+def bvh_entry_case(which, size=(16, 16)):
+    """The entry cases of a BVH walk that no larger scene reaches (tests/test_bvh_fixtures.py): "one_sphere" -- the top
+    level's root is itself a leaf; "one_triangle" -- a mesh whose root is a leaf, next to a Rect.  (The third case, geometries
+    none of which has a primitive, has no reference to record: build_sah_binned refuses zero primitives, bvh.cpp:46;
+    tests/test_gpu_parity.py renders such a scene.)"""
+    scene = Scene()
+    scene.add("d", Diffuse([0.8, 0.7, 0.6]))
+    if which == "one_sphere":
+        scene.add(Sphere([0.1, 1.0, 1.0], 0.7), "d")
+    elif which == "one_triangle":
+        scene.add(Rect([0, 0, 1], [2, 0, 0], [0, 0, 2], True), "d")
+        scene.add(Mesh(np.array([[-0.6, 0.4, 1.2], [0.7, 0.5, 0.9], [0.0, 1.6, 1.1]], np.float32), np.array([[0, 1, 2]], np.uint32)), "d")
+    else:
+        raise ValueError(which)
+    scene.set(ThinLenCamera(Film(list(size), Uncharted2()), [0, 1, -4], [0, 1, 0], 0.25))
+    return scene
+
+
 def shapes_zoo(size=(64, 64)):
     """One of every supported analytic shape + materials: used by the per-shape parity fixtures."""
     scene = Scene()

@@ -9,14 +9,16 @@ import pytest
 
 from conftest import GOLDEN
 
-SCENES = ["cbox", "cones10k", "sss_mesh", "zoo"]
+SCENES = ["cbox", "cones10k", "sss_mesh", "zoo", "one_sphere", "one_triangle"]
 
 
 def _scene(name):
     import pine_amd as pa  # noqa: F401
     from pine_amd import scenes
     return {"cbox": lambda: scenes.cbox((64, 64), "readme"), "cones10k": lambda: scenes.classic_cones((720, 360), 100),
-            "sss_mesh": lambda: scenes.sss((64, 64), 2, emissive_mesh=True), "zoo": lambda: scenes.shapes_zoo((48, 48))}[name]()
+            "sss_mesh": lambda: scenes.sss((64, 64), 2, emissive_mesh=True), "zoo": lambda: scenes.shapes_zoo((48, 48)),
+            # the walks' entry cases: the top level's root is a leaf / a mesh's root is a leaf
+            "one_sphere": lambda: scenes.bvh_entry_case(name), "one_triangle": lambda: scenes.bvh_entry_case(name)}[name]()
 
 
 def canonical_tree(sc, device=None):

@@ -182,9 +182,15 @@ def embree_fixtures(tmp):
 
 
 def bvh_scenes():
-    """Scenes of the BVH fixtures (SURVEY.md 8(c) fixture 4): cbox, the 10 000-cone scene of C4, a mesh scene."""
+    """Scenes of the BVH fixtures (SURVEY.md 8(c) fixture 4): cbox, the 10 000-cone scene of C4, a mesh scene, and the two
+    entry cases of a walk that none of those reaches (a leaf as the top level's root, a leaf as a mesh's root; the reference
+    itself refuses a BVH without primitives, bvh.cpp:46)."""
     return {"cbox": scenes.cbox((64, 64), "readme"), "cones10k": scenes.classic_cones((720, 360), 100),
-            "sss_mesh": scenes.sss((64, 64), 2, emissive_mesh=True), "zoo": scenes.shapes_zoo((48, 48))}
+            "sss_mesh": scenes.sss((64, 64), 2, emissive_mesh=True), "zoo": scenes.shapes_zoo((48, 48)),
+            **{name: scenes.bvh_entry_case(name) for name in BVH_ENTRY_CASES}}
+
+
+BVH_ENTRY_CASES = ("one_sphere", "one_triangle")  # 128 rays each
 
 
 def bvh_rays(scene, n, seed):
@@ -212,14 +218,16 @@ def bvh_rays(scene, n, seed):
     return rays
 
 
-def bvh_fixtures(tmp):
+def bvh_fixtures(tmp, only=None):
     """tests/golden/bvh_<scene>.npz from `pine_ref bvh`: the reference's own BVH as a canonical pre-order stream and,
-    for 1000 rays, the primitives BVH::intersect / BVH::hit test in order with their results."""
+    for 1000 rays, the primitives BVH::intersect / BVH::hit test in order with their results.  (--bvh-only=a,b: those scenes)"""
     for i, (name, sc) in enumerate(bvh_scenes().items()):
+        if only is not None and name not in only:
+            continue
         sp, rp, tp, vp = (os.path.join(tmp, f) for f in ("s.pscene", "r.bin", "tree.bin", "trav.bin"))
         ps = sc.describe()
         open(sp, "w").write(ps)
-        rays = bvh_rays(sc, 1000, 77 + i)
+        rays = bvh_rays(sc, 128 if name in BVH_ENTRY_CASES else 1000, 77 + i)
         rays.tofile(rp)
         info = json.loads(run_ref("bvh", sp, rp, tp, vp).strip().splitlines()[-1])
         np.savez_compressed(os.path.join(OUT, f"bvh_{name}.npz"), pscene=ps, rays=rays, tree=np.fromfile(tp, dtype=np.uint32),
@@ -404,7 +412,7 @@ def main():
     if "--bvh" in sys.argv or "--vertices" in sys.argv:
         with tempfile.TemporaryDirectory() as tmp:
             if "--bvh" in sys.argv:
-                bvh_fixtures(tmp)
+                bvh_fixtures(tmp, next((a.split("=", 1)[1].split(",") for a in sys.argv if a.startswith("--bvh-only=")), None))
             if "--vertices" in sys.argv:
                 vertex_fixture(tmp)
         return
