@@ -571,6 +571,11 @@ int pine_gpu_test_choose_lobe(pine_gpu_scene*, int device, const float* cases_ho
  * Returns the number of entries, < 0 on error. */
 int64_t pine_gpu_test_frame_table(pine_gpu_scene*, pine_gpu_plan* plan, int device, float* entries, float* generic, int64_t cap_entries,
                                   int32_t* base, int64_t cap_shapes, const float* rays_host, int64_t nrays, int32_t* faces);
+/* The slab test of the baked scenes' transformed boxes (box_slabs_lean, pine_device.h) beside the one every other caller runs
+ * (box_slabs), both as the host compiles them.  n cases: boxes_host 6 floats each (lo, hi), rays_host 8 floats each (o, d, tmin,
+ * tmax; the ray in the box's frame).  out_host: 6 words per case -- flag, tmin bits, tmax bits of box_slabs, then of the lean
+ * routine (the bounds mean something on a hit only).  Needs no GPU. */
+int pine_gpu_test_box_slabs(const float* boxes_host, const float* rays_host, int64_t n, uint32_t* out_host);
 /* The precompiled path-kernel variants (pine_variants.h) in the order of the host's first-fit search: kind 0 the stage-queued
  * kernel, 1 the megakernel.  Up to `cap` entries of features (F_* bits), ctx (path contexts per workgroup; 0 for the
  * megakernel) and order; any of the arrays may be NULL.  Returns the number of variants, < 0 on error.  Needs no GPU.

@@ -203,6 +203,7 @@ SIGNATURES = {
     "pine_gpu_test_choose_lobe": (C.c_int, [C.c_void_p, C.c_int, c_f_p, C.c_int64, c_f_p]),
     "pine_gpu_test_frame_table": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int, c_f_p, c_f_p, C.c_int64, C.POINTER(C.c_int32), C.c_int64,
                                               c_f_p, C.c_int64, C.POINTER(C.c_int32)]),
+    "pine_gpu_test_box_slabs": (C.c_int, [c_f_p, c_f_p, C.c_int64, C.POINTER(C.c_uint32)]),
     "pine_gpu_test_kernel_variants": (C.c_int, [C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int]),
     "pine_gpu_film_finalize_u8": (C.c_int, [c_f_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8)]),
 }

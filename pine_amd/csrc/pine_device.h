@@ -487,6 +487,62 @@ PINE_HD bool box_slabs(f3 lo, f3 hi, f3 o, f3 d, float& tmin, float& tmax) {
   }
   return ok;
 }
+// box_slabs for the rays the path kernel creates -- finite origin, finite direction with |d| <= 1 that is not all zero,
+// tmin >= 0 -- and a box with finite bounds, lo <= hi: the same flag and, on a hit, the same tmin / tmax, from the same
+// three reciprocals and six products, but the near and far value of an axis taken by min / max instead of by the sign of
+// the reciprocal, the running bounds kept by v_max_f32 / v_min_f32 instead of compare + select, and ONE comparison at the
+// end instead of one per axis (tests/test_obb_slabs.py runs the two side by side).  Why that is the same:
+//  * near / far.  Rounding is monotone, so lo <= hi gives (lo - o) <= (hi - o), and the products by inv are ordered by
+//    inv's sign: the value box_slabs selects as near IS the smaller product, far the larger.  Equal products (lo == hi
+//    on the axis, or two differences that round to one product) are one value, whichever is picked.  They are zeros of
+//    different sign only if a non-zero difference times inv underflows, which |inv| >= 1 excludes; a zero difference
+//    (origin on the face plane) gives a zero of inv's sign in box_slabs and here alike.
+//  * the bounds.  pmax(x, tmin) / pmin(x, tmax) with a right-hand operand that is never NaN is what the hardware's
+//    maximum / minimum computes; tmin only grows and tmax only shrinks from axis to axis, so "no axis saw
+//    ntmin > ntmax" is "the final tmin <= the final tmax" (the callers' own tmin > tmax test included).
+//  * NaN.  A product is NaN only as 0 * inf: a zero difference times the reciprocal of a zero or denormal component,
+//    which is a parallel axis (below, its products are not read), or from a non-finite origin, direction or bound --
+//    those rays and boxes are not given to this function (non-finite rays and records: box_slabs).
+//  * signed zeros.  Where a candidate equals the bound it is compared with and both are zeros, box_slabs keeps the
+//    bound and the hardware returns +0 of (+0, -0) as maximum, -0 as minimum: the device's tmin / tmax can be the other
+//    zero (origin on a face, an edge or a corner of the box with tmin = 0).  Every reader is blind to that: the flag
+//    compares; in o + t * d a zero t of either sign gives o, but for components of o that are zeros themselves, whose
+//    sign then follows; mul_point() carries such a component's sign into zero products only, and a sum changes by the sign
+//    of a zero term only when it is zero itself; distance() squares the differences.  The world distance is the same
+//    float.  (The host build, which the test hook runs against box_slabs, keeps box_slabs' own choice of zero.)
+//  * a parallel axis (|d| < 1e-6) constrains nothing if the origin lies within [lo, hi] and fails the box otherwise:
+//    near / far become -inf / +inf, or +inf / -inf.  That is rare, so it sits behind a per-lane branch, NOT a ballot (the wave-uniform form of such a fallback hung once,
+//    DESIGN.md 7), and holds three compare-and-select groups, not a second copy of box_slabs.
+PINE_HD float slab_max(float x, float bound) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_fmaxf(x, bound);
+#else
+  return pmax(x, bound);
+#endif
+}
+PINE_HD float slab_min(float x, float bound) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_fminf(x, bound);
+#else
+  return pmin(x, bound);
+#endif
+}
+PINE_HD bool box_slabs_lean(f3 lo, f3 hi, f3 o, f3 d, float& tmin, float& tmax) {
+  const f3 inv = f3{prcp(d.x), prcp(d.y), prcp(d.z)};
+  const f3 a = (lo - o) * inv, b = (hi - o) * inv;
+  f3 n = f3{slab_min(a.x, b.x), slab_min(a.y, b.y), slab_min(a.z, b.z)};
+  f3 f = f3{slab_max(a.x, b.x), slab_max(a.y, b.y), slab_max(a.z, b.z)};
+  const f3 ad = f3{pabs(d.x), pabs(d.y), pabs(d.z)};
+  if (__builtin_expect(slab_min(slab_min(ad.x, ad.y), ad.z) < 1e-6f, 0)) {
+    const float inf = __builtin_inff();
+    if (ad.x < 1e-6f) { const bool out = o.x < lo.x || o.x > hi.x; n.x = out ? inf : -inf; f.x = out ? -inf : inf; }
+    if (ad.y < 1e-6f) { const bool out = o.y < lo.y || o.y > hi.y; n.y = out ? inf : -inf; f.y = out ? -inf : inf; }
+    if (ad.z < 1e-6f) { const bool out = o.z < lo.z || o.z > hi.z; n.z = out ? inf : -inf; f.z = out ? -inf : inf; }
+  }
+  tmin = slab_max(n.z, slab_max(n.y, slab_max(n.x, tmin)));
+  tmax = slab_min(f.z, slab_min(f.y, slab_min(f.x, tmax)));
+  return !(tmin > tmax);
+}
 
 // ------------------------------------------------------------------------------------------------
 // Shapes: any-hit, closest-hit (shrinks ray.tmax), surface info.  S is the 128-byte record.
@@ -641,6 +697,67 @@ PINE_HD bool cylinder_solve(const float* f, const DRay& ray, float& t) {
   return true;
 }
 
+// The two tests of a transformed box (a record's f: lo, hi, the matrix at 6, its inverse at 18).  LEAN: the slab test is
+// box_slabs_lean -- the calls generate_baked_scene (pine_specialize.h) emits for records with finite bounds, lo <= hi;
+// the generic dispatch below, the host and the oracle comparison run box_slabs.
+template <bool LEAN>
+PINE_HD bool obb_slabs(const float* f, f3 o, f3 d, float& tmin, float& tmax) {
+  if constexpr (LEAN) return box_slabs_lean(ld3(f), ld3(f + 3), o, d, tmin, tmax);
+  else return box_slabs(ld3(f), ld3(f + 3), o, d, tmin, tmax);
+}
+template <bool LEAN>
+PINE_HD bool obb_hit_once(const float* f, const DRay& ray) {  // OBB::hit bbox.cpp:145-149
+  f3 o, d;
+  obb_local_ray(f, ray.o, ray.d, o, d);
+  float tmin = ray.tmin, tmax = ray.tmax;
+  if constexpr (!LEAN)  // (LEAN: part of the slab test's one comparison)
+    if (tmin > tmax) return false;
+  return obb_slabs<LEAN>(f, o, d, tmin, tmax);
+}
+template <bool LEAN>
+PINE_HD bool obb_intersect_once(const float* f, DRay& ray) {  // bbox.cpp:150-172: endpoints mapped back to world distances
+  f3 o, d;
+  obb_local_ray(f, ray.o, ray.d, o, d);
+  float tmin = ray.tmin, tmax = ray.tmax;
+  if (!obb_slabs<LEAN>(f, o, d, tmin, tmax)) return false;
+  const m34 m = ld34(f + 6);
+  const f3 ps = o + tmin * d;
+  const f3 pe = o + tmax * d;
+  // bbox.cpp:166-171 maps both endpoints back; the far one is only read when the near distance is not
+  // beyond tmin (origin on or inside the box): compute it on demand, the values are the same
+  float tw = distance(mul_point(m, ps), ray.o);
+  if (__builtin_expect(!(tw > ray.tmin), 0)) tw = distance(mul_point(m, pe), ray.o);
+  ray.tmax = tw;
+  return true;
+}
+#if defined(PINE_DUP_OBB) && defined(__HIP_DEVICE_COMPILE__)  /* cost measurement only: a copy of the ray the compiler knows nothing about */
+__device__ __forceinline__ DRay opaque_ray(DRay r) {
+  asm volatile("" : "+v"(r.o.x), "+v"(r.o.y), "+v"(r.o.z), "+v"(r.d.x), "+v"(r.d.y), "+v"(r.d.z), "+v"(r.tmin), "+v"(r.tmax));
+  return r;
+}
+#endif
+template <bool LEAN>
+PINE_HD bool obb_hit(const float* f, const DRay& ray) {
+#if defined(PINE_DUP_OBB) && defined(__HIP_DEVICE_COMPILE__)  /* cost measurement only: the test once more on opaque operands (same film; the extra time is its cost) */
+  {
+    const float sink = obb_hit_once<LEAN>(f, opaque_ray(ray)) ? 1.0f : 0.0f;
+    asm volatile("" : : "v"(sink));
+  }
+#endif
+  return obb_hit_once<LEAN>(f, ray);
+}
+template <bool LEAN>
+PINE_HD bool obb_intersect(const float* f, DRay& ray) {
+#if defined(PINE_DUP_OBB) && defined(__HIP_DEVICE_COMPILE__)
+  {
+    DRay rr = opaque_ray(ray);
+    const float sink = obb_intersect_once<LEAN>(f, rr) ? rr.tmax : 0.0f;
+    asm volatile("" : : "v"(sink));
+  }
+#endif
+  return obb_intersect_once<LEAN>(f, ray);
+}
+
 template <unsigned F = F_ALL>
 PINE_HD bool shape_hit(int kind, const DShape* S, const DRay& ray) {
   const float* f = S->f;
@@ -655,11 +772,7 @@ PINE_HD bool shape_hit(int kind, const DShape* S, const DRay& ray) {
       return box_slabs(ld3(f), ld3(f + 3), ray.o, ray.d, tmin, tmax);
     }
     case SHAPE_OBB: if constexpr (!(F & F_OBB)) __builtin_unreachable(); else {  // OBB::hit bbox.cpp:145-149
-      f3 o, d;
-      obb_local_ray(f, ray.o, ray.d, o, d);
-      float tmin = ray.tmin, tmax = ray.tmax;
-      if (tmin > tmax) return false;
-      return box_slabs(ld3(f), ld3(f + 3), o, d, tmin, tmax);
+      return obb_hit<false>(f, ray);
     }
     case SHAPE_SPHERE: if constexpr (!(F & F_SPHERE)) __builtin_unreachable(); else {  // geometry.cpp:84-87
       const float t = sphere_compute_t(ray.o, ray.d, ray.tmin, ld3(f), f[3]);
@@ -721,19 +834,7 @@ PINE_HD bool shape_intersect(int kind, const DShape* S, DRay& ray) {
       return true;
     }
     case SHAPE_OBB: if constexpr (!(F & F_OBB)) __builtin_unreachable(); else {  // bbox.cpp:150-172: endpoints mapped back to world distances
-      f3 o, d;
-      obb_local_ray(f, ray.o, ray.d, o, d);
-      float tmin = ray.tmin, tmax = ray.tmax;
-      if (!box_slabs(ld3(f), ld3(f + 3), o, d, tmin, tmax)) return false;
-      const m34 m = ld34(f + 6);
-      const f3 ps = o + tmin * d;
-      const f3 pe = o + tmax * d;
-      // bbox.cpp:166-171 maps both endpoints back; the far one is only read when the near distance is not
-      // beyond tmin (origin on or inside the box): compute it on demand, the values are the same
-      float tw = distance(mul_point(m, ps), ray.o);
-      if (__builtin_expect(!(tw > ray.tmin), 0)) tw = distance(mul_point(m, pe), ray.o);
-      ray.tmax = tw;
-      return true;
+      return obb_intersect<false>(f, ray);
     }
     case SHAPE_SPHERE: if constexpr (!(F & F_SPHERE)) __builtin_unreachable(); else {  // geometry.cpp:88-93
       const float t = sphere_compute_t(ray.o, ray.d, ray.tmin, ld3(f), f[3]);

@@ -590,6 +590,27 @@ int pine_gpu_test_shapes(pine_gpu_scene* scene, int device, const float* rays, i
   return 0;
 }
 
+// pine_gpu_test_box_slabs: the host build of box_slabs and of box_slabs_lean (pine_device.h) on caller-given boxes and rays
+int pine_gpu_test_box_slabs(const float* boxes, const float* rays, int64_t n, uint32_t* out) {
+  if (!boxes || !rays || !out || n < 0) {
+    set_error("pine_gpu_test_box_slabs: bad argument");
+    return -1;
+  }
+  for (int64_t i = 0; i < n; i++) {
+    const float *b = boxes + i * 6, *q = rays + i * 8;
+    const f3 lo = ld3(b), hi = ld3(b + 3), o = ld3(q), d = ld3(q + 3);
+    for (int lean = 0; lean < 2; lean++) {
+      float tmin = q[6], tmax = q[7];
+      const bool hit = lean ? box_slabs_lean(lo, hi, o, d, tmin, tmax) : box_slabs(lo, hi, o, d, tmin, tmax);
+      uint32_t* r = out + i * 6 + lean * 3;
+      r[0] = hit ? 1u : 0u;
+      memcpy(r + 1, &tmin, 4);
+      memcpy(r + 2, &tmax, 4);
+    }
+  }
+  return 0;
+}
+
 // pine_gpu_test_frame_table: the table as plan creation builds it (device < 0: here, on the host) or as a plan's kernels read it
 // (device >= 0: copied back from the plan's scene blob).  `generic`: per entry what the per-hit code computes at a point of that
 // face; `faces`: the face shape_surface_info reports for caller-given rays.

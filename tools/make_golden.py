@@ -47,6 +47,7 @@ FILMS = {
     "cbox_committed_64_s16_d4": (lambda: scenes.cbox((64, 64), "committed"), 16, 4),
     "cbox_readme_64_s16_d4": (lambda: scenes.cbox((64, 64), "readme"), 16, 4),
     "cbox_readme_64_s256_d8": (lambda: scenes.cbox((64, 64), "readme"), 256, 8),
+    "cbox_readme_64_s16_d8": (lambda: scenes.cbox((64, 64), "readme"), 16, 8),  # tests/test_obb_slabs.py
     "cbox_rect_readme_64_s64_d5": (lambda: scenes.cbox((64, 64), "readme", False), 64, 5),
     "cbox_committed_ragged_45x37_s8_d3": (lambda: scenes.cbox((45, 37), "committed"), 8, 3),
     "cbox_readme_64_s1_d1": (lambda: scenes.cbox((64, 64), "readme"), 1, 1),
