@@ -77,12 +77,19 @@ int pine_gpu_scene_find_material(pine_gpu_scene*, const char* name);
  * the Sky environment light (added to radiance on a miss, path.cpp:75-81; sampled uniformly over the
  * sphere): src/pine/core/light.h:21-67, light.cpp:11-84.  Lights enter the light sampler's list in
  * add order together with the area lights of emissive geometry; the environment light comes last
- * (lightsampler.cpp:6-10).  Atmosphere and ImageSky are not supported. */
+ * (lightsampler.cpp:6-10).  ImageSky (light.cpp:127-171): an image over the sphere, sampled by the reference's
+ * Distribution2D of its texels' lengths and looked up bilinearly on a miss.  Setting an environment light
+ * replaces the previous one.  Atmosphere is not supported. */
 int pine_gpu_scene_add_light_point(pine_gpu_scene*, const float position[3], const float color[3]);
 int pine_gpu_scene_add_light_spot(pine_gpu_scene*, const float position[3], const float direction[3],
                                   const float color[3], float falloff_radian, float cutoff_additional_radian);
 int pine_gpu_scene_add_light_directional(pine_gpu_scene*, const float direction[3], const float color[3]);
 int pine_gpu_scene_set_env_sky(pine_gpu_scene*, const float sun_color[3]);
+/* ImageSky(image, tint, elevation, rotation): w x h texels of 3 floats, rows top first (a Radiance HDR image as the reference
+ * loads it).  Refused with an error: a texel that is negative or not finite, w or h < 1, more than 2^26 texels. */
+int pine_gpu_scene_set_env_image(pine_gpu_scene*, const float* rgb, int w, int h, const float tint[3], float elevation, float rotation);
+/* ... of an 8-bit image (the reference's vec3u8 images): each texel becomes pow(value / 255, 2.2) here, once. */
+int pine_gpu_scene_set_env_image_u8(pine_gpu_scene*, const uint8_t* rgb, int w, int h, const float tint[3], float elevation, float rotation);
 
 /* Shading nodes (Nodef / Node3f: src/pine/core/node.h:13-297, registered node.cpp:29-116).  A node
  * lives in the scene's node table; each call returns its id (or < 0).  Supported: constants, the
@@ -544,6 +551,15 @@ int pine_gpu_test_bxdf(int device, const float* cases_host, int64_t n, float* ou
  * tmax = distance and that n -- then per (light, query) 9 floats: 0 sampled  1-3 w  4 distance  5 pdf  6-8 le.  Zeros after
  * a 0 or -1.  device = -1: the host build of the same functions. */
 int pine_gpu_test_light_samples(pine_gpu_scene*, int device, const float* queries_host, int64_t n, float* out_host);
+/* The scene's ImageSky one call at a time (pine_device.h image_sky_sample / _color / _pdf), for tests/test_envsky.py.  A query is
+ * 5 floats: u2, then a direction wo.  A record is 13 floats: 0 1 the texel sample(u2) chose (ds.p, as exactly representable
+ * floats)  2 its pdf  3-5 its wo  6-8 its le  9-11 color(wo of the query)  12 pdf(wo of the query).  device = -1: the host build
+ * of the same functions.  An ImageSky is not part of pine_gpu_test_light_samples' records (it reports "not sampled"). */
+int pine_gpu_test_env_light(pine_gpu_scene*, int device, const float* queries_host, int64_t n, float* out_host);
+/* The ImageSky's density tree (the reference's Distribution2D) in pre-order, rebuilt from the flat device layout: per node 7
+ * words -- weight (float bits), split_x, lower.x, lower.y, upper.x, upper.y, leaf.  Returns the number of words (they are
+ * written when out is not NULL and capacity_words suffices), < 0 on error.  Needs no GPU. */
+int64_t pine_gpu_test_env_tree(pine_gpu_scene*, int32_t* out, int64_t capacity_words);
 /* The shading-node programs of the scene's materials, as plan creation compiles them (needs no GPU): num_materials, num_ops,
  * then per material prog[4] (index of the first op of the program of albedo, roughness, metallic, transmission / ior; -1: the
  * parameter is a literal of the record), then per op 4 words: opcode, x, y, z (float bits).  Returns the number of words (they

@@ -262,6 +262,23 @@ class Sky:
         self.sun_color = sun_color
 
 
+class ImageSky:
+    """EnvironmentLight ImageSky(image, tint, elevation, rotation) (light.h:81-94): scene.set(ImageSky(...)).  `image` is an
+    (h, w, 3) float32 array (a Radiance HDR image as the reference loads it), an (h, w, 3) uint8 array (the reference's 8-bit
+    images: each texel is pow(value / 255, 2.2)), rows top first, or the path of a Radiance .hdr file."""
+    def __init__(self, image, tint=(1.0, 1.0, 1.0), elevation=0.0, rotation=0.0):
+        if isinstance(image, (str, bytes)) or hasattr(image, "__fspath__"):
+            from .hdr import read_hdr
+            image = read_hdr(image)
+        image = np.asarray(image)
+        if image.dtype != np.uint8:
+            image = image.astype(np.float32, copy=False)
+        if image.ndim != 3 or image.shape[2] != 3:
+            raise PineError("ImageSky: expected an (h, w, 3) image")
+        self.image = np.ascontiguousarray(image)
+        self.tint, self.elevation, self.rotation = tint, elevation, rotation
+
+
 # ---- shapes (src/pine/core/geometry.cpp:901-946) ------------------------------------------------
 class Shape:
     pass
@@ -475,6 +492,15 @@ class Scene:
     def set(self, camera):
         if isinstance(camera, Sky):
             check(lib.pine_gpu_scene_set_env_sky(self._h, _v3(camera.sun_color)), "scene.set")
+            return camera
+        if isinstance(camera, ImageSky):
+            img = camera.image
+            h, w = img.shape[:2]
+            args = (w, h, _v3(camera.tint), float(camera.elevation), float(camera.rotation))
+            if img.dtype == np.uint8:
+                check(lib.pine_gpu_scene_set_env_image_u8(self._h, img.ctypes.data_as(C.POINTER(C.c_uint8)), *args), "scene.set")
+            else:
+                check(lib.pine_gpu_scene_set_env_image(self._h, img.ctypes.data_as(C.POINTER(C.c_float)), *args), "scene.set")
             return camera
         if not isinstance(camera, ThinLenCamera):
             raise PineError("scene.set: expected a camera")

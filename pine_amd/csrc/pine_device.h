@@ -1369,8 +1369,106 @@ PINE_HD f3 sky_color_of(f3 sun_color, f3 wo) {  // Sky::color light.cpp:71-73, s
   const f3 l = a * (1 - t) + b * t;  // psl::lerp(t, a, b) math.h:118-121
   return sun_color * (l * l);
 }
-PINE_HD bool light_sample_other(const DLight* L, f3 p, f2 u2, f3& w, float& distance, float& pdf, f3& le) {
+// ---- ImageSky (light.cpp:86-92, 127-171; Distribution2D distribution.cpp:77-111; Image image.cpp:7-30) ----
+// The light's DLight record: color = tint, geom = node count of the density tree, pad[0] = "has a rotation", pad[1], pad[2] =
+// image width, height.  Everything else is one global buffer `env` of 4-byte words (SceneHost::EnvImage::words builds it):
+//   [0, 9) l2w, [9, 18) w2l (columns x, y, z)                                                         kEnvHeaderWords
+//   per node of the tree, breadth-first with the two children adjacent, kEnvNodeWords words:
+//     0 weight  1 r = left.weight / weight  2 index of the left child  3 flags (kEnvStop | kEnvSplitX | kEnvLeaf)
+//     4-7 lower.x lower.y upper.x upper.y  8 sample()'s pdf where the descent stops here  9 pdf()'s value at this leaf
+//   per texel one float: pdf()'s value of the leaf the texel lies in -- Distribution2D::pdf(p) as one load
+//   per texel three floats: the image, rows top first
+constexpr int kEnvHeaderWords = 32, kEnvNodeWords = 12;
+constexpr int kEnvStop = 1, kEnvSplitX = 2, kEnvLeaf = 4;
+struct EnvImage {
+  const float* words;
+  const float* pdf;
+  const float* texels;
+  int w, h;
+  long long last;  // index of the last texel
+};
+PINE_HD EnvImage env_image_of(const DLight* L, const float* env) {
+  EnvImage E;
+  E.words = env;
+  E.w = L->pad[1], E.h = L->pad[2];
+  const long long n = (long long)E.w * E.h;
+  E.pdf = env + kEnvHeaderWords + (long long)L->geom * kEnvNodeWords;
+  E.texels = E.pdf + ((n + 3) & ~3ll);
+  E.last = n - 1;
+  return E;
+}
+PINE_HD f3 env_texel(const EnvImage& E, long long i) { return ld3(E.texels + i * 3); }
+// wo -> ic: the optional w2l, y and z swapped, inverse_uniform_sphere (sampling.h:51-54), sc2ic (light.cpp:86-89)
+PINE_HD f2 image_sky_ic(const DLight* L, const EnvImage& E, f3 wo) {
+  if (L->pad[0]) wo = mul(m3{ld3(E.words + 9), ld3(E.words + 12), ld3(E.words + 15)}, wo);
+  const f3 d{wo.x, wo.z, wo.y};
+  float phi = patan2(d.y, d.x);  // phi2pi vecmath.h:1209-1213
+  phi = phi < 0.0f ? kPi * 2 + phi : phi;
+  const f2 sc{phi / (kPi * 2), (1 - d.z) / 2};
+  const f2 ic{sc.x * float(E.w), sc.y * float(E.h)};
+  return f2{pmin(pmax(ic.x, 0.0f), float(E.w) - 1.0f), pmin(pmax(ic.y, 0.0f), float(E.h) - 1.0f)};
+}
+PINE_HD f3 image_sky_color(const DLight* L, const float* env, f3 wo) {  // light.cpp:138-145, Image::filtered image.cpp:18-30
+  const EnvImage E = env_image_of(L, env);
+  const f2 ic = image_sky_ic(L, E, wo);
+  const float fx = floorf(ic.x), fy = floorf(ic.y);
+  const long long x0 = (long long)int(fx), x1 = (long long)int(ceilf(ic.x));
+  const long long y0 = (long long)int(fy) * E.w, y1 = (long long)int(ceilf(ic.y)) * E.w;
+  const f3 c0 = env_texel(E, x0 + y0), c1 = env_texel(E, x1 + y0), c2 = env_texel(E, x0 + y1), c3 = env_texel(E, x1 + y1);
+  const float tx = ic.x - fx, ty = ic.y - fy;
+  const f3 cy0 = c0 * (1.0f - tx) + c1 * tx;  // psl::lerp(t, a, b) math.h:118-121
+  const f3 cy1 = c2 * (1.0f - tx) + c3 * tx;
+  return ld3(L->color) * (cy0 * (1.0f - ty) + cy1 * ty);
+}
+PINE_HD float image_sky_pdf(const DLight* L, const float* env, f3 wo) {  // light.cpp:164-171
+  const EnvImage E = env_image_of(L, env);
+  const f2 ic = image_sky_ic(L, E, wo);
+  return E.pdf[(long long)int(ic.x) + (long long)int(ic.y) * E.w] / (4 * kPi);
+}
+// ImageSky::sample light.cpp:146-163.  px, py: ds.p.
+PINE_HD void image_sky_sample(const DLight* L, const float* env, f2 u2, f3& w, float& pdf, f3& le, int& px, int& py) {
+  const EnvImage E = env_image_of(L, env);
+  const float* node = env + kEnvHeaderWords;
+  // (a tree is at most 21 levels deep; the bound keeps a damaged buffer from looping)
+  for (int level = 0; level < 24; level++) {
+    const int flags = as_int(node[3]);
+    if (flags & kEnvStop) break;
+    const float r = node[1];
+    int child = as_int(node[2]);
+    if (flags & kEnvSplitX) {
+      if (u2.x < r) u2.x = u2.x / r;
+      else u2.x = (u2.x - r) / (1 - r), child++;
+    } else {
+      if (u2.y < r) u2.y = u2.y / r;
+      else u2.y = (u2.y - r) / (1 - r), child++;
+    }
+    node = env + kEnvHeaderWords + (long long)child * kEnvNodeWords;
+  }
+  // lerp(u2, lower, upper) as vec2, then vec2i: the conversion truncates
+  const int lx = as_int(node[4]), ly = as_int(node[5]), ux = as_int(node[6]), uy = as_int(node[7]);
+  px = int(float(lx) * (1.0f - u2.x) + float(ux) * u2.x);
+  py = int(float(ly) * (1.0f - u2.y) + float(uy) * u2.y);
+  const f2 sc{float(px) / float(E.w), float(py) / float(E.h)};
+  const f3 d = uniform_sphere(sc);
+  w = f3{d.x, d.z, d.y};
+  if (L->pad[0]) w = mul(m3{ld3(E.words), ld3(E.words + 3), ld3(E.words + 6)}, w);
+  pdf = node[8] / (4 * kPi);
+  // (a rescaled coordinate that rounded to 1 gives a coordinate equal to `upper`: the reference reads this linear index
+  //  unchecked; here it stays inside the image)
+  long long i = (long long)px + (long long)py * E.w;
+  i = i < 0 ? 0 : i > E.last ? E.last : i;
+  le = ld3(L->color) * env_texel(E, i);
+}
+
+PINE_HD bool light_sample_other(const DLight* L, const float* env, f3 p, f2 u2, f3& w, float& distance, float& pdf, f3& le) {
   switch (L->kind) {
+    case LIGHT_IMAGE_SKY: {
+      if (!env) return false;
+      int px, py;
+      image_sky_sample(L, env, u2, w, pdf, le, px, py);
+      distance = kFloatMax;
+      return true;
+    }
     case LIGHT_POINT:  // light.cpp:11-17
       w = normalize(ld3(L->position) - p, distance);
       pdf = sqr(distance);

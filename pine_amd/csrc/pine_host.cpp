@@ -700,6 +700,222 @@ std::string SceneHost::describe() const {
   return s;
 }
 
+
+// ------------------------------------------------------------------------------------------------
+// ImageSky: Distribution2D(density, 20) (distribution.cpp:18-75) and what the device reads of it
+// ------------------------------------------------------------------------------------------------
+std::string md5_hex(const void* data, size_t bytes) {  // RFC 1321
+  static const uint32_t K[64] = {
+      0xd76aa478, 0xe8c7b756, 0x242070db, 0xc1bdceee, 0xf57c0faf, 0x4787c62a, 0xa8304613, 0xfd469501, 0x698098d8, 0x8b44f7af, 0xffff5bb1,
+      0x895cd7be, 0x6b901122, 0xfd987193, 0xa679438e, 0x49b40821, 0xf61e2562, 0xc040b340, 0x265e5a51, 0xe9b6c7aa, 0xd62f105d, 0x02441453,
+      0xd8a1e681, 0xe7d3fbc8, 0x21e1cde6, 0xc33707d6, 0xf4d50d87, 0x455a14ed, 0xa9e3e905, 0xfcefa3f8, 0x676f02d9, 0x8d2a4c8a, 0xfffa3942,
+      0x8771f681, 0x6d9d6122, 0xfde5380c, 0xa4beea44, 0x4bdecfa9, 0xf6bb4b60, 0xbebfbc70, 0x289b7ec6, 0xeaa127fa, 0xd4ef3085, 0x04881d05,
+      0xd9d4d039, 0xe6db99e5, 0x1fa27cf8, 0xc4ac5665, 0xf4292244, 0x432aff97, 0xab9423a7, 0xfc93a039, 0x655b59c3, 0x8f0ccc92, 0xffeff47d,
+      0x85845dd1, 0x6fa87e4f, 0xfe2ce6e0, 0xa3014314, 0x4e0811a1, 0xf7537e82, 0xbd3af235, 0x2ad7d2bb, 0xeb86d391};
+  static const int R[64] = {7, 12, 17, 22, 7, 12, 17, 22, 7, 12, 17, 22, 7, 12, 17, 22, 5, 9,  14, 20, 5, 9,  14, 20, 5, 9,  14, 20, 5, 9,  14, 20,
+                            4, 11, 16, 23, 4, 11, 16, 23, 4, 11, 16, 23, 4, 11, 16, 23, 6, 10, 15, 21, 6, 10, 15, 21, 6, 10, 15, 21, 6, 10, 15, 21};
+  uint32_t h[4] = {0x67452301, 0xefcdab89, 0x98badcfe, 0x10325476};
+  const unsigned char* src = static_cast<const unsigned char*>(data);
+  const size_t padded = ((bytes + 8) / 64 + 1) * 64;
+  for (size_t at = 0; at < padded; at += 64) {
+    unsigned char block[64];
+    for (size_t i = 0; i < 64; i++) {
+      const size_t j = at + i;
+      block[i] = j < bytes ? src[j] : j == bytes ? 0x80 : 0;
+      if (j >= padded - 8) block[i] = (unsigned char)((uint64_t(bytes) * 8) >> (8 * (j - (padded - 8))));
+    }
+    uint32_t m[16];
+    memcpy(m, block, 64);
+    uint32_t a = h[0], b = h[1], c = h[2], d = h[3];
+    for (int i = 0; i < 64; i++) {
+      uint32_t f;
+      int g;
+      if (i < 16) f = (b & c) | (~b & d), g = i;
+      else if (i < 32) f = (d & b) | (~d & c), g = (5 * i + 1) & 15;
+      else if (i < 48) f = b ^ c ^ d, g = (3 * i + 5) & 15;
+      else f = c ^ (b | ~d), g = (7 * i) & 15;
+      const uint32_t x = a + f + K[i] + m[g];
+      a = d, d = c, c = b;
+      b = b + ((x << R[i]) | (x >> (32 - R[i])));
+    }
+    h[0] += a, h[1] += b, h[2] += c, h[3] += d;
+  }
+  std::string out;
+  for (int i = 0; i < 16; i++) out += fmt("%02x", (h[i / 4] >> (8 * (i % 4))) & 0xffu);
+  return out;
+}
+
+namespace {
+constexpr int kEnvHeaderWords = 32, kEnvNodeWords = 12;  // = pine_device.h, which a plain C++ build of this file cannot include
+constexpr int kEnvStop = 1, kEnvSplitX = 2, kEnvLeaf = 4;
+constexpr int kEnvMaxDepth = 20;  // ImageSky's Distribution2D(density, 20) light.cpp:132
+struct EnvBuildNode {
+  float weight;
+  bool split_x, leaf;
+  int lx, ly, ux, uy;
+  int left = -1, right = -1;
+};
+struct EnvBuilder {
+  const std::vector<float>& density;
+  int w;
+  std::vector<EnvBuildNode> nodes;
+  // Distribution2D::build distribution.cpp:29-75: the sums in double, column by column (or row by row), in the reference's order
+  int build(int lx, int ly, int ux, int uy, double weight, int depth) {
+    const int sx = ux - lx, sy = uy - ly;
+    const int id = int(nodes.size());
+    if (depth >= kEnvMaxDepth || sx == 0 || sy == 0 || (sx == 1 && sy == 1)) {
+      nodes.push_back(EnvBuildNode{float(weight), true, true, lx, ly, ux, uy});
+      return id;
+    }
+    double partial = 0.0;
+    const bool split_x = sx >= sy;
+    int p = 0;
+    if (split_x) {
+      for (int x = lx; x < ux - 1; x++) {
+        double sum = 0.0;
+        for (int y = ly; y < uy; y++) sum += density[size_t(x) + size_t(y) * size_t(w)];
+        partial += sum;
+        if (partial >= weight / 2) {
+          p = x + 1;
+          break;
+        }
+      }
+    } else {
+      for (int y = ly; y < uy - 1; y++) {
+        double sum = 0.0;
+        for (int x = lx; x < ux; x++) sum += density[size_t(x) + size_t(y) * size_t(w)];
+        partial += sum;
+        if (partial >= weight / 2) {
+          p = y + 1;
+          break;
+        }
+      }
+    }
+    if (p == 0) p = split_x ? ux - 1 : uy - 1;
+    nodes.push_back(EnvBuildNode{float(weight), split_x, false, lx, ly, ux, uy});
+    const int left = split_x ? build(lx, ly, p, uy, partial, depth + 1) : build(lx, ly, ux, p, partial, depth + 1);
+    const int right = split_x ? build(p, ly, ux, uy, weight - partial, depth + 1) : build(lx, p, ux, uy, weight - partial, depth + 1);
+    nodes[size_t(id)].left = left, nodes[size_t(id)].right = right;
+    return id;
+  }
+};
+void put_int(float& word, int v) { memcpy(&word, &v, 4); }
+int get_int(float word) {
+  int v;
+  memcpy(&v, &word, 4);
+  return v;
+}
+}  // namespace
+
+bool build_env_image(const float* rgb, int w, int h, const float tint[3], float elevation, float rotation, DLight& L, std::vector<float>& words) {
+  if (w < 1 || h < 1) return set_error("`ImageSky` needs an image of at least 1 x 1 texels"), false;
+  if ((long long)w * h > (1ll << 26)) return set_error("`ImageSky` image has more than 2^26 texels"), false;
+  const size_t n = size_t(w) * size_t(h);
+  std::vector<float> density(n);
+  double weight = 0.0;
+  for (size_t i = 0; i < n; i++) {  // for_2d order: y outer, x inner = the texels' own order
+    const float r = rgb[3 * i], g = rgb[3 * i + 1], b = rgb[3 * i + 2];
+    if (!(r >= 0.0f && g >= 0.0f && b >= 0.0f) || std::isinf(r) || std::isinf(g) || std::isinf(b))
+      return set_error(fmt("`ImageSky` texel (%d, %d) is negative or not finite", int(i % size_t(w)), int(i / size_t(w)))), false;
+    density[i] = std::sqrt(r * r + g * g + b * b);  // length(vec3) vecmath.h:712-725
+    weight += density[i];
+  }
+  EnvBuilder B{density, w, {}};
+  B.build(0, 0, w, h, weight, 0);
+  // breadth-first numbering with the two children adjacent: the levels every query visits share cache lines
+  const size_t count = B.nodes.size();
+  std::vector<int> order, number(count, -1);
+  order.reserve(count);
+  order.push_back(0), number[0] = 0;
+  for (size_t at = 0; at < order.size(); at++) {
+    const EnvBuildNode& nd = B.nodes[size_t(order[at])];
+    if (nd.leaf) continue;
+    number[size_t(nd.left)] = int(order.size()), order.push_back(nd.left);
+    number[size_t(nd.right)] = int(order.size()), order.push_back(nd.right);
+  }
+  const size_t off_pdf = size_t(kEnvHeaderWords) + count * kEnvNodeWords, off_tex = off_pdf + ((n + 3) & ~size_t(3));
+  words.assign(off_tex + n * 3, 0.0f);
+  // the two running products, top down.  sample() (distribution.cpp:77-91): pdf * r or pdf * (1 - r), r = left.weight / weight,
+  // over area where the descent stops -- at a leaf or a node of weight 0.  pdf() (:93-101): pdf_ * child.weight / weight, over
+  // area at a leaf, 0 from a node of weight 0 down.  Both start at area(root) and are functions of the node alone.
+  std::vector<float> ps(count), pp(count);
+  std::vector<char> dead(count, 0);
+  ps[0] = pp[0] = float(w * h);
+  for (size_t k = 0; k < count; k++) {
+    const EnvBuildNode& nd = B.nodes[size_t(order[k])];
+    float* o = &words[size_t(kEnvHeaderWords) + k * kEnvNodeWords];
+    const float area = float((nd.ux - nd.lx) * (nd.uy - nd.ly));
+    const bool zero = nd.weight == 0.0f, off = dead[k] || zero;
+    o[0] = nd.weight;
+    put_int(o[3], ((nd.leaf || zero) ? kEnvStop : 0) | (nd.split_x ? kEnvSplitX : 0) | (nd.leaf ? kEnvLeaf : 0));
+    put_int(o[4], nd.lx), put_int(o[5], nd.ly), put_int(o[6], nd.ux), put_int(o[7], nd.uy);
+    o[8] = ps[k] / area;
+    o[9] = off ? 0.0f : pp[k] / area;
+    if (nd.leaf) {
+      put_int(o[2], 0);
+      for (int y = nd.ly; y < nd.uy; y++)
+        for (int x = nd.lx; x < nd.ux; x++) words[off_pdf + size_t(x) + size_t(y) * size_t(w)] = o[9];
+      continue;
+    }
+    const size_t l = size_t(number[size_t(nd.left)]), r_ = l + 1;
+    put_int(o[2], int(l));
+    const float lw = B.nodes[size_t(nd.left)].weight, rw = B.nodes[size_t(nd.right)].weight;
+    const float r = zero ? 0.0f : lw / nd.weight;
+    o[1] = r;
+    ps[l] = ps[k] * r, ps[r_] = ps[k] * (1 - r);
+    pp[l] = zero ? 0.0f : pp[k] * lw / nd.weight, pp[r_] = zero ? 0.0f : pp[k] * rw / nd.weight;
+    dead[l] = dead[r_] = char(off);
+  }
+  memcpy(&words[off_tex], rgb, n * 12);
+  L = DLight{};
+  L.kind = LIGHT_IMAGE_SKY;
+  memcpy(L.color, tint, 12);
+  L.geom = int(count);
+  L.pad[0] = 0, L.pad[1] = w, L.pad[2] = h;
+  if (elevation != 0.0f || rotation != 0.0f) {  // light.cpp:133-136
+    const Mat4 m = mat4_mul(mat4_rotate_x(elevation * kPi), mat4_rotate_y(rotation * kPi * 2));
+    float a[3][3], inv[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};  // [column][row]; Matrix4 -> Matrix3 vecmath.h:586
+    for (int c = 0; c < 3; c++)
+      for (int r = 0; r < 3; r++) a[c][r] = m.m[c][r];
+    // inverse(mat3) vecmath.cpp:81-103
+    const float det = a[0][0] * (a[1][1] * a[2][2] - a[2][1] * a[1][2]) + a[1][0] * (a[2][1] * a[0][2] - a[0][1] * a[2][2]) +
+                      a[2][0] * (a[0][1] * a[1][2] - a[1][1] * a[0][2]);
+    if (det != 0) {
+      inv[0][0] = a[1][1] * a[2][2] - a[2][1] * a[1][2];
+      inv[0][1] = a[2][1] * a[0][2] - a[0][1] * a[2][2];
+      inv[0][2] = a[0][1] * a[1][2] - a[1][1] * a[0][2];
+      inv[1][0] = a[1][2] * a[2][0] - a[2][2] * a[1][0];
+      inv[1][1] = a[2][2] * a[0][0] - a[0][2] * a[2][0];
+      inv[1][2] = a[0][2] * a[1][0] - a[1][2] * a[0][0];
+      inv[2][0] = a[1][0] * a[2][1] - a[2][0] * a[1][1];
+      inv[2][1] = a[2][0] * a[0][1] - a[0][0] * a[2][1];
+      inv[2][2] = a[0][0] * a[1][1] - a[1][0] * a[0][1];
+      for (int c = 0; c < 3; c++)
+        for (int r = 0; r < 3; r++) inv[c][r] /= det;
+    }
+    for (int c = 0; c < 3; c++)
+      for (int r = 0; r < 3; r++) words[size_t(c * 3 + r)] = a[c][r], words[size_t(9 + c * 3 + r)] = inv[c][r];
+    L.pad[0] = 1;
+  }
+  return true;
+}
+
+bool env_image_valid(const DLight& L, const std::vector<float>& words) {
+  const long long w = L.pad[1], h = L.pad[2], count = L.geom;
+  if (w < 1 || h < 1 || w * h > (1ll << 26) || count < 1 || count > (1ll << 22)) return false;
+  const long long n = w * h, off_pdf = kEnvHeaderWords + count * kEnvNodeWords, off_tex = off_pdf + ((n + 3) & ~3ll);
+  if ((long long)words.size() != off_tex + n * 3) return false;
+  for (long long k = 0; k < count; k++) {
+    const float* o = &words[size_t(kEnvHeaderWords + k * kEnvNodeWords)];
+    const int flags = get_int(o[3]), child = get_int(o[2]);
+    // a descent only moves to higher numbers, so it ends; where it ends the bounds lie inside the image
+    if (!(flags & kEnvStop) && (child <= k || child + 1 >= count)) return false;
+    const int lx = get_int(o[4]), ly = get_int(o[5]), ux = get_int(o[6]), uy = get_int(o[7]);
+    if (lx < 0 || ly < 0 || ux > w || uy > h || lx > ux || ly > uy) return false;
+  }
+  return true;
+}
+
 }  // namespace pine_gpu
 
 // ================================================================================================
@@ -878,7 +1094,30 @@ int pine_gpu_scene_set_env_sky(pine_gpu_scene* s, const float sun_color[3]) {
   s->host.env = L;
   s->host.has_env = true;
   s->host.env_describe = "envlight sky " + hex3(sun_color);
+  s->host.env_words.clear();
+  s->host.env_words.shrink_to_fit();
   return 0;
+}
+int pine_gpu_scene_set_env_image(pine_gpu_scene* s, const float* rgb, int w, int h, const float tint[3], float elevation, float rotation) {
+  if (!check(s, rgb) || !check(s, tint)) return -1;
+  DLight L{};
+  std::vector<float> words;
+  if (!build_env_image(rgb, w, h, tint, elevation, rotation, L, words)) return -1;
+  s->host.env = L;
+  s->host.has_env = true;
+  s->host.env_words.swap(words);
+  s->host.env_describe = fmt("envlight image %d %d ", w, h) + hex3(tint) + fmt(" %a %a ", elevation, rotation) + md5_hex(rgb, size_t(w) * size_t(h) * 12);
+  return 0;
+}
+int pine_gpu_scene_set_env_image_u8(pine_gpu_scene* s, const uint8_t* rgb, int w, int h, const float tint[3], float elevation, float rotation) {
+  if (!check(s, rgb) || !check(s, tint)) return -1;
+  if (w < 1 || h < 1) return set_error("`ImageSky` needs an image of at least 1 x 1 texels"), -1;
+  if ((long long)w * h > (1ll << 26)) return set_error("`ImageSky` image has more than 2^26 texels"), -1;
+  float table[256];  // Image::operator[] of a vec3u8 image image.cpp:10-11: inverse_gamma_correction(value / 255.0f)
+  for (int v = 0; v < 256; v++) table[v] = std::pow(float(v) / 255.0f, 2.2f);
+  std::vector<float> texels(size_t(w) * size_t(h) * 3);
+  for (size_t i = 0; i < texels.size(); i++) texels[i] = table[rgb[i]];
+  return pine_gpu_scene_set_env_image(s, texels.data(), w, h, tint, elevation, rotation);
 }
 
 // ---- shading nodes + node-parameterised materials ----

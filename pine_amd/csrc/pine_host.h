@@ -128,6 +128,9 @@ struct SceneHost {
   DLight env{};                // environment light (appended to the sampler's list at plan build)
   std::vector<std::string> light_describe;
   std::string env_describe;
+  // ImageSky: the words of its device buffer -- rotation, density tree, pdf table, texels (pine_device.h EnvImage) -- built by
+  // build_env_image when the light is set; empty for any other environment light
+  std::vector<float> env_words;
   // what describe() prints after the materials, in add order: (0, geometry index) or (1, light index)
   std::vector<std::pair<int, int>> item_order;
   DCamera camera{};
@@ -152,6 +155,13 @@ struct SceneHost {
 };
 
 void set_error(const std::string& msg);
+
+// ImageSky(image, tint, elevation, rotation) (light.cpp:127-137): the light's record and its device buffer from w x h float
+// texels (3 each, rows top first).  false with the error set: a texel that is negative or not finite, a bad size.
+bool build_env_image(const float* rgb, int w, int h, const float tint[3], float elevation, float rotation, DLight& L, std::vector<float>& words);
+// Every index the device code forms from `words` stays inside it (checked before a plan uploads it).
+bool env_image_valid(const DLight& L, const std::vector<float>& words);
+std::string md5_hex(const void* data, size_t bytes);
 
 // The pass planner: how a render of `spp` samples per pixel is split into launches that keep at most about
 // `pass_samples` sample rows per tile -- one launch with every row (n = 1, P = spp, slice = whole_tiles) when pass_samples

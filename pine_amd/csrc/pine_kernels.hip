@@ -566,6 +566,7 @@ void pine_gpu_plan_destroy(pine_gpu_plan* p) {
   DevicePool::get().free(p->d_tri_packets);
   DevicePool::get().free(p->d_halton);
   DevicePool::get().free(p->d_tri_attrs);
+  DevicePool::get().free(p->d_env);
   DevicePool::get().free(p->d_tables);
   DevicePool::get().free(p->d_ctxg);
   DevicePool::get().free(p->d_ckpt);
@@ -873,13 +874,21 @@ static int assemble_scene(pine_gpu_plan* p, SceneHost& H, const pine_gpu_render_
   }
   sp.tri_packet_bytes = tri_packets.size() * 4;
   if (upload(p->d_tri_attrs, A.tri_attrs)) return -1;
+  S.env = nullptr;
+  if (H.has_env && H.env.kind == LIGHT_IMAGE_SKY) {
+    if (!env_image_valid(H.env, H.env_words)) {
+      set_error("internal: inconsistent ImageSky buffer");
+      return -1;
+    }
+    if (upload(p->d_env, H.env_words)) return -1;
+    S.env = p->d_env;
+  }
 
   S.blob = reinterpret_cast<const uint4*>(p->d_blob);
   S.nodes = reinterpret_cast<const DNode*>(p->d_blob + S.off_nodes);
   S.shapes = reinterpret_cast<const DShape*>(p->d_blob + S.off_shapes);
   S.materials = reinterpret_cast<const DMaterial*>(p->d_blob + S.off_materials);
   S.bvhs = reinterpret_cast<const DBvh*>(p->d_blob + S.off_bvhs);
-  S.prims = nullptr;
   S.leaf = reinterpret_cast<const DShape*>(p->d_blob + S.off_leaf) - S.top_prim_begin;
   S.lights = reinterpret_cast<const DLight*>(p->d_blob + S.off_lights);
   S.node_ops = reinterpret_cast<const DNodeOp*>(p->d_blob + S.off_node_ops);

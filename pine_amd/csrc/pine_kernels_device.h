@@ -67,7 +67,7 @@ struct DeviceScene {
   const DShape* shapes;
   const DMaterial* materials;
   const DNode* nodes;
-  const int* prims;
+  const float* env;  // ImageSky: its rotation, density tree, pdf table and texels (pine_device.h EnvImage), or null; plan-owned
   const DBvh* bvhs;
   const float* tri_verts;
   const DLight* lights;
@@ -120,7 +120,7 @@ struct SceneView {
   const DShape* shapes;
   const DMaterial* materials;
   const DNode* nodes;
-  const int* prims;
+  const float* env;  // DeviceScene::env (global memory, never staged)
   const DBvh* bvhs;
   const DLight* lights;
   const float* tri_verts;

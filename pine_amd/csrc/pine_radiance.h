@@ -28,7 +28,6 @@ __device__ __forceinline__ void view_of_blob(const char* base, const DeviceScene
   V.shapes = reinterpret_cast<const DShape*>(base + S.off_shapes);
   V.materials = reinterpret_cast<const DMaterial*>(base + S.off_materials);
   V.bvhs = reinterpret_cast<const DBvh*>(base + S.off_bvhs);
-  V.prims = nullptr;
   V.lights = reinterpret_cast<const DLight*>(base + S.off_lights);
   V.node_ops = reinterpret_cast<const DNodeOp*>(base + S.off_node_ops);
   V.leaf = reinterpret_cast<const DShape*>(base + S.off_leaf) - S.top_prim_begin;
@@ -45,7 +44,7 @@ __device__ __forceinline__ SceneView scene_view_global(const DeviceScene& S) {
   V.shapes = S.shapes;
   V.materials = S.materials;
   V.nodes = S.nodes;
-  V.prims = nullptr;
+  V.env = S.env;
   V.bvhs = S.bvhs;
   V.lights = S.lights;
   V.tri_verts = S.tri_verts;
@@ -215,10 +214,14 @@ __device__ __forceinline__ f3 terminal_radiance(const SceneView& V, int env_ligh
   if (!hit) {
     if constexpr (F & F_LIGHTS)
       if (env_light >= 0) {
-        Lo = mk3(1.0f) * sky_color_of(ld3(V.lights[env_light].color), ray_d);
+        const DLight* E = &V.lights[env_light];
+        const bool image = E->kind == LIGHT_IMAGE_SKY;
+        if (image) Lo = mk3(1.0f) * image_sky_color(E, V.env, ray_d);
+        else Lo = mk3(1.0f) * sky_color_of(ld3(E->color), ray_d);
         if (!is_delta) {
           has_light_pdf = true;
           light_pdf = 1 / (4 * kPi);  // Sky::pdf -- not divided by the light count
+          if (image) light_pdf = image_sky_pdf(E, V.env, ray_d);  // ImageSky::pdf -- neither
         }
       }
   } else {
@@ -378,8 +381,8 @@ __device__ __forceinline__ f3 sample_direct(const SceneView& V, int num_lights, 
         ldist = gs.distance;
         lpdf = gs.pdf;
       }
-    } else {  // light.cpp:11-84: point, spot, directional, Sky
-      if constexpr (F & F_LIGHTS) lvalid = light_sample_other(L, it.p, u2, lw, ldist, lpdf, lle);
+    } else {  // light.cpp:11-84, 146-163: point, spot, directional, Sky, ImageSky
+      if constexpr (F & F_LIGHTS) lvalid = light_sample_other(L, V.env, it.p, u2, lw, ldist, lpdf, lle);
     }
     const bool ldelta = lkind == LIGHT_POINT || lkind == LIGHT_SPOT || lkind == LIGHT_DIRECTIONAL;  // light.h:111-113
     if (lvalid) {

@@ -251,7 +251,7 @@ PINE_HD void test_light_sample_case(const DLight* L, const float* q, float* o) {
   for (int k = 0; k < 9; k++) o[k] = 0.0f;
   f3 w, le;
   float distance, pdf;
-  if (!light_sample_other(L, ld3(q), f2{q[3], q[4]}, w, distance, pdf, le)) return;
+  if (!light_sample_other(L, nullptr, ld3(q), f2{q[3], q[4]}, w, distance, pdf, le)) return;  // (ImageSky: pine_gpu_test_env_light)
   o[0] = 1.0f;
   o[1] = w.x, o[2] = w.y, o[3] = w.z;
   o[4] = distance, o[5] = pdf;
@@ -264,6 +264,25 @@ __global__ void __launch_bounds__(64) test_light_samples_kernel(const DShape* sh
   const long long k = t / n, i = t % n;
   if (k < num_shapes) test_shape_sample_case(&shapes[k], tri_verts, queries + i * 6, out + t * 13);
   else test_light_sample_case(&lights[k - num_shapes], queries + i * 6, out + n * num_shapes * 13 + (t - n * num_shapes) * 9);
+}
+// pine_gpu_test_env_light: ImageSky::sample(u2), then color(wo) and pdf(wo) of the query's own direction
+PINE_HD void test_env_light_case(const DLight* L, const float* env, const float* q, float* o) {
+  f3 w, le;
+  float pdf;
+  int px, py;
+  image_sky_sample(L, env, f2{q[0], q[1]}, w, pdf, le, px, py);
+  o[0] = float(px), o[1] = float(py), o[2] = pdf;
+  o[3] = w.x, o[4] = w.y, o[5] = w.z;
+  o[6] = le.x, o[7] = le.y, o[8] = le.z;
+  const f3 wo = ld3(q + 2);
+  const f3 c = image_sky_color(L, env, wo);
+  o[9] = c.x, o[10] = c.y, o[11] = c.z;
+  o[12] = image_sky_pdf(L, env, wo);
+}
+__global__ void __launch_bounds__(64) test_env_light_kernel(DLight L, const float* env, const float* queries, long long n, float* out) {
+  const long long t = blockIdx.x * 64ll + threadIdx.x;
+  if (t >= n) return;
+  test_env_light_case(&L, env, queries + t * 5, out + t * 13);
 }
 // pine_gpu_test_material_params: material_params<F_ALL> of one material at one query (p, n, uv) -> 10 floats
 PINE_HD void test_material_params_case(const DMaterial* m, const DNodeOp* ops, const float* q, float* o) {
@@ -800,6 +819,70 @@ int pine_gpu_test_light_samples(pine_gpu_scene* scene, int device, const float* 
   (void)hipFree(dq);
   (void)hipFree(dout);
   return rc;
+}
+
+int pine_gpu_test_env_light(pine_gpu_scene* scene, int device, const float* queries, int64_t n, float* out) {
+  if (!scene || !queries || !out || n < 0 || n > (1 << 20)) {
+    set_error("bad argument");
+    return -1;
+  }
+  SceneHost& H = scene_host(scene);
+  if (!H.has_env || H.env.kind != LIGHT_IMAGE_SKY || !env_image_valid(H.env, H.env_words)) {
+    set_error("pine_gpu_test_env_light: the scene's environment light is no ImageSky");
+    return -1;
+  }
+  if (device < 0) {
+    for (int64_t i = 0; i < n; i++) test_env_light_case(&H.env, H.env_words.data(), queries + i * 5, out + i * 13);
+    return 0;
+  }
+  if (n == 0) return 0;
+  if (need_device(device)) return -1;
+  float *de = nullptr, *dq = nullptr, *dout = nullptr;
+  int rc = -1;
+  do {
+    if (hipMalloc((void**)&de, H.env_words.size() * 4) != hipSuccess || hipMalloc((void**)&dq, size_t(n) * 20) != hipSuccess ||
+        hipMalloc((void**)&dout, size_t(n) * 52) != hipSuccess)
+      break;
+    if (hipMemcpy(de, H.env_words.data(), H.env_words.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(dq, queries, size_t(n) * 20, hipMemcpyHostToDevice) != hipSuccess)
+      break;
+    hipLaunchKernelGGL(test_env_light_kernel, dim3(unsigned((n + 63) / 64)), dim3(64), 0, 0, H.env, de, dq, (long long)n, dout);
+    if (hipGetLastError() != hipSuccess || hipMemcpy(out, dout, size_t(n) * 52, hipMemcpyDeviceToHost) != hipSuccess) break;
+    rc = 0;
+  } while (0);
+  if (rc) set_error(std::string("pine_gpu_test_env_light: ") + hipGetErrorString(hipGetLastError()));
+  (void)hipFree(de);
+  (void)hipFree(dq);
+  (void)hipFree(dout);
+  return rc;
+}
+
+int64_t pine_gpu_test_env_tree(pine_gpu_scene* scene, int32_t* out, int64_t capacity_words) {
+  if (!scene) {
+    set_error("null argument");
+    return -1;
+  }
+  SceneHost& H = scene_host(scene);
+  if (!H.has_env || H.env.kind != LIGHT_IMAGE_SKY || !env_image_valid(H.env, H.env_words)) {
+    set_error("pine_gpu_test_env_tree: the scene's environment light is no ImageSky");
+    return -1;
+  }
+  const int64_t words = int64_t(H.env.geom) * 7;
+  if (!out || capacity_words < words) return words;
+  const int32_t* base = reinterpret_cast<const int32_t*>(H.env_words.data()) + kEnvHeaderWords;
+  std::vector<int> todo{0};  // pre-order: a node, its left subtree, its right subtree
+  int32_t* o = out;
+  while (!todo.empty()) {
+    const int k = todo.back();
+    todo.pop_back();
+    const int32_t* nd = base + int64_t(k) * kEnvNodeWords;
+    *o++ = nd[0];
+    *o++ = (nd[3] & kEnvSplitX) ? 1 : 0;
+    *o++ = nd[4], *o++ = nd[5], *o++ = nd[6], *o++ = nd[7];
+    *o++ = (nd[3] & kEnvLeaf) ? 1 : 0;
+    if (!(nd[3] & kEnvLeaf)) todo.push_back(nd[2] + 1), todo.push_back(nd[2]);
+  }
+  return words;
 }
 
 int64_t pine_gpu_test_node_programs(pine_gpu_scene* scene, int32_t* out, int64_t capacity_words) {

@@ -17,6 +17,7 @@
 
 #include "../../include/pine_gpu.h"
 #include "gltf_import.hpp"
+#include "hdr_read.hpp"
 
 namespace pine {
 
@@ -153,6 +154,41 @@ struct Sampler {  // the variant PathIntegrator takes (sampler.h:275-; UniformSa
   Sampler(HaltonSampler s) : requested(s.requested), kind(PINE_GPU_SAMPLER_HALTON) {}
 };
 
+// An image as ImageSky takes it (image.h:11-30): float texels (a Radiance HDR file, or an array), or 8-bit texels that the
+// library converts as the reference's vec3u8 images are read (pow(value / 255, 2.2)).  Rows top first, 3 values per texel.
+struct Image {
+  vec2i size;
+  std::vector<float> rgb;
+  std::vector<uint8_t> u8;
+  Image(vec2i size, std::vector<float> texels) : size(size), rgb(std::move(texels)) { expect(rgb.size()); }
+  Image(vec2i size, std::vector<uint8_t> texels) : size(size), u8(std::move(texels)) { expect(u8.size()); }
+  explicit Image(vec3 color) : size{1, 1}, rgb{color.x, color.y, color.z} {}  // ImagePtr(vec3): the reference's 1 x 1 image
+  explicit Image(const std::string& hdr_file) {
+    try {
+      HdrImage f = read_hdr(hdr_file);
+      size = vec2i{f.w, f.h};
+      rgb = std::move(f.rgb);
+    } catch (const std::runtime_error& e) {
+      throw Error(e.what());
+    }
+  }
+
+ private:
+  void expect(size_t values) const {
+    if (size.x < 0 || size.y < 0 || values != size_t(size.x) * size_t(size.y) * 3) throw Error("Image: size and texel count disagree");
+  }
+};
+using ImagePtr = std::shared_ptr<Image>;
+struct ImageSky {  // light.h:81-94
+  ImagePtr image;
+  vec3 tint{1, 1, 1};
+  float elevation = 0.0f, rotation = 0.0f;
+  ImageSky(ImagePtr image, vec3 tint = vec3{1, 1, 1}, float elevation = 0.0f, float rotation = 0.0f)
+      : image(std::move(image)), tint(tint), elevation(elevation), rotation(rotation) {
+    if (!this->image) throw Error("ImageSky: no image");
+  }
+};
+
 class Scene {
  public:
   Scene() : h_(pine_gpu_scene_create()) {}
@@ -184,6 +220,22 @@ class Scene {
   }
   int add(DirectionalLight l) { return check(pine_gpu_scene_add_light_directional(h_, l.direction.data(), l.color.data()), "DirectionalLight"); }
   void set(Sky sky) { check(pine_gpu_scene_set_env_sky(h_, sky.sun_color.data()), "scene.set(Sky)"); }
+  // the scene as .pscene text (the exchange format of the tests and the reference driver)
+  std::string describe() const {
+    const long long n = pine_gpu_scene_describe(h_, nullptr, 0);
+    if (n < 0) throw Error(std::string("describe: ") + pine_gpu_last_error());
+    std::string text(size_t(n) + 1, '\0');
+    pine_gpu_scene_describe(h_, &text[0], n + 1);
+    text.resize(size_t(n));
+    return text;
+  }
+  void set(const ImageSky& sky) {
+    const Image& im = *sky.image;
+    if (!im.u8.empty())
+      check(pine_gpu_scene_set_env_image_u8(h_, im.u8.data(), im.size.x, im.size.y, sky.tint.data(), sky.elevation, sky.rotation), "scene.set(ImageSky)");
+    else
+      check(pine_gpu_scene_set_env_image(h_, im.rgb.data(), im.size.x, im.size.y, sky.tint.data(), sky.elevation, sky.rotation), "scene.set(ImageSky)");
+  }
   // scene.add(shape, "material name") and scene.add(shape, Material)
   template <class S, class = std::enable_if_t<is_shape<S>::value>>
   int add(const S& shape, const std::string& material) {

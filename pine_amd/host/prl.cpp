@@ -36,6 +36,7 @@
 #include "../../include/pine_gpu.h"
 #include "../../include/pine_prl.h"
 #include "gltf_import.hpp"
+#include "hdr_read.hpp"
 #include "png_writer.hpp"
 
 namespace prl {
@@ -148,10 +149,15 @@ struct SceneObj : Object {
   SceneObj() : h(pine_gpu_scene_create()) {}
   ~SceneObj() override { pine_gpu_scene_destroy(h); }
 };
+struct ImageObj : Object {  // ImagePtr: float texels, 3 each, rows top first
+  int w = 0, h = 0;
+  std::vector<float> rgb;
+};
 struct LightObj : Object {
-  std::string kind;  // PointLight | SpotLight | DirectionalLight | Sky
+  std::string kind;  // PointLight | SpotLight | DirectionalLight | Sky | ImageSky
   float a[3] = {0, 0, 0}, b[3] = {0, 0, 0}, c[3] = {0, 0, 0};
-  float falloff = 0, extra = 0;
+  float falloff = 0, extra = 0;  // (ImageSky: c = tint, falloff = elevation, extra = rotation)
+  std::shared_ptr<ImageObj> image;
 };
 struct IntegratorObj : Object {
   int spp = 0, depth = 0, sampler = 0;
@@ -1838,6 +1844,40 @@ Interp::Interp() {
     return mk_obj("Sky", l);
   });
   r.convert("Sky", "EnvironmentLight", [](const Value& v) { return retype(v, "EnvironmentLight"); });
+  // ImagePtr(str) / load_image(str): a Radiance .hdr file; ImagePtr(vec3): the reference's 1 x 1 image (image.cpp:49-61)
+  auto image_file = [](Interp&, std::vector<Cell>& a) {
+    auto im = std::make_shared<ImageObj>();
+    try {
+      pine::HdrImage f = pine::read_hdr(a[0]->s);
+      im->w = f.w, im->h = f.h, im->rgb = std::move(f.rgb);
+    } catch (const std::runtime_error& e) {
+      fail(std::string("Unable to load `") + a[0]->s + "`: " + e.what());
+    }
+    return mk_obj("ImagePtr", im);
+  };
+  r.def("ImagePtr", {"str_view"}, "ImagePtr", image_file);
+  r.def("load_image", {"str_view"}, "ImagePtr", image_file);
+  r.def("ImagePtr", {"vec3"}, "ImagePtr", [](Interp&, std::vector<Cell>& a) {
+    auto im = std::make_shared<ImageObj>();
+    im->w = im->h = 1;
+    im->rgb.assign(a[0]->f, a[0]->f + 3);
+    return mk_obj("ImagePtr", im);
+  });
+  for (int full = 0; full < 2; full++) {  // ImageSky(ImagePtr) and ImageSky(ImagePtr, vec3, f32, f32) light.cpp:182-184
+    std::vector<std::string> pt{"ImagePtr"};
+    if (full) pt.insert(pt.end(), {"vec3", "f32", "f32"});
+    r.def("ImageSky", pt, "ImageSky", [=](Interp&, std::vector<Cell>& a) {
+      auto l = light("ImageSky");
+      l->image = obj<ImageObj>(a[0]);
+      l->c[0] = l->c[1] = l->c[2] = 1.0f;
+      if (full) {
+        memcpy(l->c, a[1]->f, 12);
+        l->falloff = a[2]->f[0], l->extra = a[3]->f[0];
+      }
+      return mk_obj("ImageSky", l);
+    });
+  }
+  r.convert("ImageSky", "EnvironmentLight", [](const Value& v) { return retype(v, "EnvironmentLight"); });
   r.def("add", {"Scene&", "Light"}, "void", [](Interp&, std::vector<Cell>& a) {  // Scene::add_light scene.cpp:29-34
     auto s = obj<SceneObj>(a[0]);
     auto l = obj<LightObj>(a[1]);
@@ -1849,7 +1889,12 @@ Interp::Interp() {
     return Value();
   });
   r.def("set", {"Scene&", "EnvironmentLight"}, "void", [](Interp&, std::vector<Cell>& a) {  // Scene::set_env_light scene.cpp:44-46
-    gpu_check(pine_gpu_scene_set_env_sky(obj<SceneObj>(a[0])->h, obj<LightObj>(a[1])->c), "scene.set(environment light)");
+    auto l = obj<LightObj>(a[1]);
+    if (l->kind == "ImageSky")
+      gpu_check(pine_gpu_scene_set_env_image(obj<SceneObj>(a[0])->h, l->image->rgb.data(), l->image->w, l->image->h, l->c, l->falloff, l->extra),
+                "scene.set(environment light)");
+    else
+      gpu_check(pine_gpu_scene_set_env_sky(obj<SceneObj>(a[0])->h, l->c), "scene.set(environment light)");
     return Value();
   });
 

@@ -80,6 +80,8 @@ int pine_gpu_test_math_sweep(int device, int fn, uint32_t fixed_bits, int swept_
 int pine_gpu_test_shapes(pine_gpu_scene*, int, const float*, int64_t, float*, int64_t) { return fail(); }
 int pine_gpu_test_bxdf(int, const float*, int64_t, float*) { return fail(); }
 int pine_gpu_test_light_samples(pine_gpu_scene*, int, const float*, int64_t, float*) { return fail(); }
+int pine_gpu_test_env_light(pine_gpu_scene*, int, const float*, int64_t, float*) { return fail(); }
+int64_t pine_gpu_test_env_tree(pine_gpu_scene*, int32_t*, int64_t) { return fail(); }
 int64_t pine_gpu_test_node_programs(pine_gpu_scene*, int32_t*, int64_t) { return fail(); }
 int pine_gpu_test_material_params(pine_gpu_scene*, int, const float*, int64_t, float*) { return fail(); }
 int pine_gpu_test_choose_lobe(pine_gpu_scene*, int, const float*, int64_t, float*) { return fail(); }
