@@ -79,7 +79,8 @@ int pine_gpu_scene_find_material(pine_gpu_scene*, const char* name);
  * add order together with the area lights of emissive geometry; the environment light comes last
  * (lightsampler.cpp:6-10).  ImageSky (light.cpp:127-171): an image over the sphere, sampled by the reference's
  * Distribution2D of its texels' lengths and looked up bilinearly on a miss.  Setting an environment light
- * replaces the previous one.  Atmosphere is not supported. */
+ * replaces the previous one.  Atmosphere (light.cpp:94-125): the single-scattering Rayleigh / Mie sky of color.cpp:41-98 with a
+ * sun disc, sampled by the Distribution2D of its own colours over an image_size grid and evaluated per ray on a miss. */
 int pine_gpu_scene_add_light_point(pine_gpu_scene*, const float position[3], const float color[3]);
 int pine_gpu_scene_add_light_spot(pine_gpu_scene*, const float position[3], const float direction[3],
                                   const float color[3], float falloff_radian, float cutoff_additional_radian);
@@ -90,6 +91,12 @@ int pine_gpu_scene_set_env_sky(pine_gpu_scene*, const float sun_color[3]);
 int pine_gpu_scene_set_env_image(pine_gpu_scene*, const float* rgb, int w, int h, const float tint[3], float elevation, float rotation);
 /* ... of an 8-bit image (the reference's vec3u8 images): each texel becomes pow(value / 255, 2.2) here, once. */
 int pine_gpu_scene_set_env_image_u8(pine_gpu_scene*, const uint8_t* rgb, int w, int h, const float tint[3], float elevation, float rotation);
+/* Atmosphere(sun_direction, sun_color, image_size): the reference's image_size is 1024 x 1024 (scripts cannot change it).  The
+ * light's tables -- its colour at every grid point, about 100 expf each -- are computed by a kernel on `device`, or, device = -1,
+ * by the same function on host threads (at most min(16, $OMP_NUM_THREADS, hardware threads)): the same bytes either way.
+ * Refused with an error: a sun direction that is zero or not finite, a sun colour that is not finite, image_w or image_h < 1,
+ * more than 2^22 texels, device >= 0 where there is no such device. */
+int pine_gpu_scene_set_env_atmosphere(pine_gpu_scene*, const float sun_direction[3], const float sun_color[3], int image_w, int image_h, int device);
 
 /* Shading nodes (Nodef / Node3f: src/pine/core/node.h:13-297, registered node.cpp:29-116).  A node
  * lives in the scene's node table; each call returns its id (or < 0).  Supported: constants, the
@@ -479,7 +486,7 @@ int pine_gpu_test_atan(int device, const float* y_host, const float* x_host, int
 /* Scalar math of pine_math.h / pine_libm.h over bit patterns, for the sweeps of tests/test_device_math.py.  fn names the
  * function f(a[, b[, c]]) and the reference it must equal bit for bit:
  *   SQRT psqrt(a) / RCP prcp(a) / DIV a / b      host IEEE sqrtf, 1.0f / a, a / b (correctly rounded)
- *   SIN COS LOG ACOS psin pcos plog pacos (a)     glibc sinf cosf logf acosf
+ *   SIN COS LOG ACOS EXP psin pcos plog pacos pexp (a)   glibc sinf cosf logf acosf expf
  *   SINCOS psincos(a): two results (sin, cos)     glibc sinf, cosf
  *   ATAN2 patan2(a, b) / POW ppow(a, b)           glibc atan2f, powf
  *   MIN pmin(a, b) / MAX pmax(a, b) / CLAMP pclamp(a, b, c)   the same comparison expressions on the host
@@ -502,7 +509,8 @@ enum {
   PINE_GPU_MATH_MIN = 10,
   PINE_GPU_MATH_MAX = 11,
   PINE_GPU_MATH_CLAMP = 12,
-  PINE_GPU_MATH_COUNT = 13
+  PINE_GPU_MATH_EXP = 13,
+  PINE_GPU_MATH_COUNT = 14
 };
 /* got[i] = fn(a[i], b[i], c[i]) (SINCOS: got[2i], got[2i+1]) by the device build on HIP device `device`, or by the host
  * build of the same functions for device = -1.  b and c may be NULL when fn does not read them. */
@@ -551,15 +559,28 @@ int pine_gpu_test_bxdf(int device, const float* cases_host, int64_t n, float* ou
  * tmax = distance and that n -- then per (light, query) 9 floats: 0 sampled  1-3 w  4 distance  5 pdf  6-8 le.  Zeros after
  * a 0 or -1.  device = -1: the host build of the same functions. */
 int pine_gpu_test_light_samples(pine_gpu_scene*, int device, const float* queries_host, int64_t n, float* out_host);
-/* The scene's ImageSky one call at a time (pine_device.h image_sky_sample / _color / _pdf), for tests/test_envsky.py.  A query is
+/* The scene's ImageSky or Atmosphere one call at a time (pine_device.h image_sky_sample / _color / _pdf, atmosphere_sample /
+ * atmosphere_sky_color), for tests/test_envsky.py and tests/test_atmosphere.py.  A query is
  * 5 floats: u2, then a direction wo.  A record is 13 floats: 0 1 the texel sample(u2) chose (ds.p, as exactly representable
  * floats)  2 its pdf  3-5 its wo  6-8 its le  9-11 color(wo of the query)  12 pdf(wo of the query).  device = -1: the host build
  * of the same functions.  An ImageSky is not part of pine_gpu_test_light_samples' records (it reports "not sampled"). */
 int pine_gpu_test_env_light(pine_gpu_scene*, int device, const float* queries_host, int64_t n, float* out_host);
-/* The ImageSky's density tree (the reference's Distribution2D) in pre-order, rebuilt from the flat device layout: per node 7
+/* The ImageSky's or Atmosphere's density tree (the reference's Distribution2D) in pre-order, rebuilt from the flat device layout: per node 7
  * words -- weight (float bits), split_x, lower.x, lower.y, upper.x, upper.y, leaf.  Returns the number of words (they are
  * written when out is not NULL and capacity_words suffices), < 0 on error.  Needs no GPU. */
 int64_t pine_gpu_test_env_tree(pine_gpu_scene*, int32_t* out, int64_t capacity_words);
+/* The environment light as the light sampler calls it: light_sample_other (pine_device.h) with the light's buffer.  A query is 5
+ * floats, p then u2; a record the 9 floats of pine_gpu_test_light_samples: 0 sampled  1-3 w  4 distance  5 pdf  6-8 le.  For an
+ * ImageSky or an Atmosphere; device = -1: the host build. */
+int pine_gpu_test_env_light_sample(pine_gpu_scene*, int device, const float* queries_host, int64_t n, float* out_host);
+/* atmosphere_color(direction, sun_dir, 8, flag) (pine_atmosphere.h) one call at a time: a query is 7 floats -- direction, sun
+ * direction (taken as given), flag (non-zero: with the sun disc) -- and gives 3.  device = -1: the host build. */
+int pine_gpu_test_atmosphere_color(int device, const float* queries_host, int64_t n, float* out_host);
+/* The tables of the scene's Atmosphere: w * h densities, then (w + 1) * (h + 1) colours of 3 floats (row by row; row h and column
+ * w are the grid points a sample can reach when a rescaled u rounds to 1).  The colours are the light's own; the densities,
+ * which the scene does not keep, are computed again where the light's were.  Returns the number of floats (they are written when
+ * out is not NULL and capacity suffices), < 0 on error. */
+int64_t pine_gpu_test_env_table(pine_gpu_scene*, float* out, int64_t capacity);
 /* The shading-node programs of the scene's materials, as plan creation compiles them (needs no GPU): num_materials, num_ops,
  * then per material prog[4] (index of the first op of the program of albedo, roughness, metallic, transmission / ior; -1: the
  * parameter is a literal of the record), then per op 4 words: opcode, x, y, z (float bits).  Returns the number of words (they

@@ -114,6 +114,7 @@ SIGNATURES = {
     "pine_gpu_scene_set_env_sky": (C.c_int, [C.c_void_p, f3]),
     "pine_gpu_scene_set_env_image": (C.c_int, [C.c_void_p, c_f_p, C.c_int, C.c_int, f3, C.c_float, C.c_float]),
     "pine_gpu_scene_set_env_image_u8": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.c_int, C.c_int, f3, C.c_float, C.c_float]),
+    "pine_gpu_scene_set_env_atmosphere": (C.c_int, [C.c_void_p, f3, f3, C.c_int, C.c_int, C.c_int]),
     "pine_gpu_scene_node_constf": (C.c_int, [C.c_void_p, C.c_float]),
     "pine_gpu_scene_node_const3": (C.c_int, [C.c_void_p, f3]),
     "pine_gpu_scene_node_input": (C.c_int, [C.c_void_p, C.c_int]),
@@ -202,6 +203,9 @@ SIGNATURES = {
     "pine_gpu_test_light_samples": (C.c_int, [C.c_void_p, C.c_int, c_f_p, C.c_int64, c_f_p]),
     "pine_gpu_test_env_light": (C.c_int, [C.c_void_p, C.c_int, c_f_p, C.c_int64, c_f_p]),
     "pine_gpu_test_env_tree": (C.c_int64, [C.c_void_p, C.POINTER(C.c_int32), C.c_int64]),
+    "pine_gpu_test_atmosphere_color": (C.c_int, [C.c_int, c_f_p, C.c_int64, c_f_p]),
+    "pine_gpu_test_env_light_sample": (C.c_int, [C.c_void_p, C.c_int, c_f_p, C.c_int64, c_f_p]),
+    "pine_gpu_test_env_table": (C.c_int64, [C.c_void_p, c_f_p, C.c_int64]),
     "pine_gpu_test_node_programs": (C.c_int64, [C.c_void_p, C.POINTER(C.c_int32), C.c_int64]),
     "pine_gpu_test_material_params": (C.c_int, [C.c_void_p, C.c_int, c_f_p, C.c_int64, c_f_p]),
     "pine_gpu_test_choose_lobe": (C.c_int, [C.c_void_p, C.c_int, c_f_p, C.c_int64, c_f_p]),

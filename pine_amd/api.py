@@ -279,6 +279,17 @@ class ImageSky:
         self.tint, self.elevation, self.rotation = tint, elevation, rotation
 
 
+class Atmosphere:
+    """EnvironmentLight Atmosphere(sun_direction, sun_color) (light.h:69-79): scene.set(Atmosphere(...)).  A single-scattering
+    Rayleigh / Mie sky with a sun disc.  image_size is the grid its importance sampling is tabulated on -- the reference's is
+    1024 x 1024, and its scripts cannot change it.  device: the HIP device that computes the light's tables when it is set
+    (None: host threads; the same bytes either way)."""
+    def __init__(self, sun_direction, sun_color, image_size=(1024, 1024), device=None):
+        self.sun_direction, self.sun_color = sun_direction, sun_color
+        self.image_size = (int(image_size[0]), int(image_size[1]))
+        self.device = device
+
+
 # ---- shapes (src/pine/core/geometry.cpp:901-946) ------------------------------------------------
 class Shape:
     pass
@@ -501,6 +512,11 @@ class Scene:
                 check(lib.pine_gpu_scene_set_env_image_u8(self._h, img.ctypes.data_as(C.POINTER(C.c_uint8)), *args), "scene.set")
             else:
                 check(lib.pine_gpu_scene_set_env_image(self._h, img.ctypes.data_as(C.POINTER(C.c_float)), *args), "scene.set")
+            return camera
+        if isinstance(camera, Atmosphere):
+            device = -1 if camera.device is None else int(camera.device)
+            check(lib.pine_gpu_scene_set_env_atmosphere(self._h, _v3(camera.sun_direction), _v3(camera.sun_color), camera.image_size[0],
+                                                        camera.image_size[1], device), "scene.set")
             return camera
         if not isinstance(camera, ThinLenCamera):
             raise PineError("scene.set: expected a camera")

@@ -7,6 +7,7 @@
 // point: binary32, no contraction, operand order of the reference; sin/cos via pine_libm.h.
 #pragma once
 #include "pine_math.h"
+#include "pine_atmosphere.h"
 #include "pine_types.h"
 
 namespace pine_gpu {
@@ -381,14 +382,7 @@ PINE_HD f3 cosine_weighted_hemisphere(f2 u) {
   const float z = psqrt(pmax(1.0f - d.x * d.x - d.y * d.y, 0.0f));
   return f3{d.x, d.y, z};
 }
-PINE_HD f3 uniform_sphere(f2 u) {
-  const float phi = u.x * kPi * 2;
-  const float cos_theta = 1 - 2 * u.y;
-  const float sin_theta = psqrt(1.0f - sqr(cos_theta));
-  float sn, cs;
-  psincos(phi, sn, cs);
-  return f3{sin_theta * cs, sin_theta * sn, cos_theta};
-}
+// (uniform_sphere: pine_math.h)
 PINE_HD float balance_heuristic(float pF, float pG) { return pF / (pF + pG); }
 
 // ------------------------------------------------------------------------------------------------
@@ -562,17 +556,7 @@ PINE_HD bool intersect_quadratic(float a, float b, float c, float tmin, float& t
   tmax = t;
   return true;
 }
-PINE_HD float sphere_compute_t(f3 ro, f3 rd, float tmin, f3 p, float r) {  // geometry.cpp:73-83
-  const f3 ro_p = ro - p;
-  const float b = dot(ro_p, rd);
-  const float c = dot(ro_p, ro_p) - r * r;
-  float d = b * b - c;
-  if (d <= 0.0f) return -1.0f;
-  d = psqrt(d);
-  float t = -b - d;
-  if (t < tmin) t = -b + d;
-  return t;
-}
+// (sphere_compute_t: pine_math.h)
 
 // Rect::hit / Rect::intersect share the plane + extent test (geometry.cpp:275-299)
 PINE_HD bool rect_test(const float* f, const DRay& ray, float& t_out) {
@@ -1425,9 +1409,8 @@ PINE_HD float image_sky_pdf(const DLight* L, const float* env, f3 wo) {  // ligh
   const f2 ic = image_sky_ic(L, E, wo);
   return E.pdf[(long long)int(ic.x) + (long long)int(ic.y) * E.w] / (4 * kPi);
 }
-// ImageSky::sample light.cpp:146-163.  px, py: ds.p.
-PINE_HD void image_sky_sample(const DLight* L, const float* env, f2 u2, f3& w, float& pdf, f3& le, int& px, int& py) {
-  const EnvImage E = env_image_of(L, env);
+// Distribution2D::sample (distribution.cpp:77-91) on the flat tree: the node the descent stops at, and ds.p in px, py.
+PINE_HD const float* env_tree_sample(const float* env, f2 u2, int& px, int& py) {
   const float* node = env + kEnvHeaderWords;
   // (a tree is at most 21 levels deep; the bound keeps a damaged buffer from looping)
   for (int level = 0; level < 24; level++) {
@@ -1448,6 +1431,12 @@ PINE_HD void image_sky_sample(const DLight* L, const float* env, f2 u2, f3& w, f
   const int lx = as_int(node[4]), ly = as_int(node[5]), ux = as_int(node[6]), uy = as_int(node[7]);
   px = int(float(lx) * (1.0f - u2.x) + float(ux) * u2.x);
   py = int(float(ly) * (1.0f - u2.y) + float(uy) * u2.y);
+  return node;
+}
+// ImageSky::sample light.cpp:146-163.  px, py: ds.p.
+PINE_HD void image_sky_sample(const DLight* L, const float* env, f2 u2, f3& w, float& pdf, f3& le, int& px, int& py) {
+  const EnvImage E = env_image_of(L, env);
+  const float* node = env_tree_sample(env, u2, px, py);
   const f2 sc{float(px) / float(E.w), float(py) / float(E.h)};
   const f3 d = uniform_sphere(sc);
   w = f3{d.x, d.z, d.y};
@@ -1460,12 +1449,42 @@ PINE_HD void image_sky_sample(const DLight* L, const float* env, f2 u2, f3& w, f
   le = ld3(L->color) * env_texel(E, i);
 }
 
+// ---- Atmosphere (light.cpp:94-125; atmosphere_color: pine_atmosphere.h) ----
+// The light's DLight record: color = sun_color, direction = the normalised sun direction, geom = node count, pad[0] = 0,
+// pad[1], pad[2] = image width, height.  Its `env` buffer is ImageSky's with another last part: header (unused), the tree
+// of Distribution2D(density, 15), the per-texel pdf table, then (w + 1) x (h + 1) colours of 3 floats, row by row:
+// atmosphere_color(wo(p), sun, 8, true) at grid point p -- sample()'s le is a function of ds.p alone, and a coordinate of
+// ds.p may equal w or h (a rescaled u that rounded to 1), where the reference evaluates the colour at sc = 1.
+// pdf(wo) (light.cpp:120-125) is image_sky_pdf: the record has no rotation.
+PINE_HD f3 atmosphere_sky_color(const DLight* L, f3 wo) {  // light.cpp:106-108
+  return ld3(L->color) * atmosphere_color_of(wo, ld3(L->direction), false);
+}
+// Atmosphere::sample light.cpp:109-119.  px, py: ds.p.
+PINE_HD void atmosphere_sample(const DLight* L, const float* env, f2 u2, f3& w, float& pdf, f3& le, int& px, int& py) {
+  const EnvImage E = env_image_of(L, env);
+  const float* node = env_tree_sample(env, u2, px, py);
+  w = atmosphere_texel_direction(px, py, E.w, E.h);
+  pdf = node[8] / (4 * kPi);
+  // (ds.p lies on the grid but where the descent divided 0 by 0: a rescaled u that rounded to 1 meets a node whose right half
+  //  weighs nothing, r = 1, and (1 - r) / (1 - r) is a NaN, whose conversion to int is whatever the machine gives -- the
+  //  reference then evaluates the colour at a direction without meaning; here the load stays inside the table)
+  const long long x = px < 0 ? 0 : px > E.w ? E.w : px, y = py < 0 ? 0 : py > E.h ? E.h : py;
+  le = ld3(L->color) * env_texel(E, x + y * (E.w + 1));
+}
+
 PINE_HD bool light_sample_other(const DLight* L, const float* env, f3 p, f2 u2, f3& w, float& distance, float& pdf, f3& le) {
   switch (L->kind) {
     case LIGHT_IMAGE_SKY: {
       if (!env) return false;
       int px, py;
       image_sky_sample(L, env, u2, w, pdf, le, px, py);
+      distance = kFloatMax;
+      return true;
+    }
+    case LIGHT_ATMOSPHERE: {
+      if (!env) return false;
+      int px, py;
+      atmosphere_sample(L, env, u2, w, pdf, le, px, py);
       distance = kFloatMax;
       return true;
     }

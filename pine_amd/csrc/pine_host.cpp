@@ -5,6 +5,7 @@
 #include "pine_bvh_build.h"
 #include "pine_embree_order.h"
 #include "pine_math_check.h"
+#include "pine_atmosphere.h"
 
 #include <algorithm>
 #include <cmath>
@@ -12,6 +13,7 @@
 #include <cstdio>
 #include <cstring>
 #include <limits>
+#include <thread>
 
 #include "../../include/pine_gpu.h"
 
@@ -748,7 +750,6 @@ std::string md5_hex(const void* data, size_t bytes) {  // RFC 1321
 namespace {
 constexpr int kEnvHeaderWords = 32, kEnvNodeWords = 12;  // = pine_device.h, which a plain C++ build of this file cannot include
 constexpr int kEnvStop = 1, kEnvSplitX = 2, kEnvLeaf = 4;
-constexpr int kEnvMaxDepth = 20;  // ImageSky's Distribution2D(density, 20) light.cpp:132
 struct EnvBuildNode {
   float weight;
   bool split_x, leaf;
@@ -758,12 +759,13 @@ struct EnvBuildNode {
 struct EnvBuilder {
   const std::vector<float>& density;
   int w;
+  int max_depth;  // Distribution2D(density, max_depth): 20 for ImageSky (light.cpp:132), 15 for Atmosphere (:104)
   std::vector<EnvBuildNode> nodes;
   // Distribution2D::build distribution.cpp:29-75: the sums in double, column by column (or row by row), in the reference's order
   int build(int lx, int ly, int ux, int uy, double weight, int depth) {
     const int sx = ux - lx, sy = uy - ly;
     const int id = int(nodes.size());
-    if (depth >= kEnvMaxDepth || sx == 0 || sy == 0 || (sx == 1 && sy == 1)) {
+    if (depth >= max_depth || sx == 0 || sy == 0 || (sx == 1 && sy == 1)) {
       nodes.push_back(EnvBuildNode{float(weight), true, true, lx, ly, ux, uy});
       return id;
     }
@@ -807,20 +809,13 @@ int get_int(float word) {
 }
 }  // namespace
 
-bool build_env_image(const float* rgb, int w, int h, const float tint[3], float elevation, float rotation, DLight& L, std::vector<float>& words) {
-  if (w < 1 || h < 1) return set_error("`ImageSky` needs an image of at least 1 x 1 texels"), false;
-  if ((long long)w * h > (1ll << 26)) return set_error("`ImageSky` image has more than 2^26 texels"), false;
+// Distribution2D(density, max_depth) of a w x h density (its weight: the sum in the texels' own order) as the device reads it:
+// the header left zero, the nodes, the per-texel pdf table, then `tail_words` zero words for the caller.  Returns the tail's
+// offset; count = the number of nodes.
+static size_t build_env_tree(const std::vector<float>& density, int w, int h, double weight, int max_depth, size_t tail_words, std::vector<float>& words,
+                             size_t& count_out) {
   const size_t n = size_t(w) * size_t(h);
-  std::vector<float> density(n);
-  double weight = 0.0;
-  for (size_t i = 0; i < n; i++) {  // for_2d order: y outer, x inner = the texels' own order
-    const float r = rgb[3 * i], g = rgb[3 * i + 1], b = rgb[3 * i + 2];
-    if (!(r >= 0.0f && g >= 0.0f && b >= 0.0f) || std::isinf(r) || std::isinf(g) || std::isinf(b))
-      return set_error(fmt("`ImageSky` texel (%d, %d) is negative or not finite", int(i % size_t(w)), int(i / size_t(w)))), false;
-    density[i] = std::sqrt(r * r + g * g + b * b);  // length(vec3) vecmath.h:712-725
-    weight += density[i];
-  }
-  EnvBuilder B{density, w, {}};
+  EnvBuilder B{density, w, max_depth, {}};
   B.build(0, 0, w, h, weight, 0);
   // breadth-first numbering with the two children adjacent: the levels every query visits share cache lines
   const size_t count = B.nodes.size();
@@ -834,7 +829,7 @@ bool build_env_image(const float* rgb, int w, int h, const float tint[3], float 
     number[size_t(nd.right)] = int(order.size()), order.push_back(nd.right);
   }
   const size_t off_pdf = size_t(kEnvHeaderWords) + count * kEnvNodeWords, off_tex = off_pdf + ((n + 3) & ~size_t(3));
-  words.assign(off_tex + n * 3, 0.0f);
+  words.assign(off_tex + tail_words, 0.0f);
   // the two running products, top down.  sample() (distribution.cpp:77-91): pdf * r or pdf * (1 - r), r = left.weight / weight,
   // over area where the descent stops -- at a leaf or a node of weight 0.  pdf() (:93-101): pdf_ * child.weight / weight, over
   // area at a leaf, 0 from a node of weight 0 down.  Both start at area(root) and are functions of the node alone.
@@ -866,6 +861,25 @@ bool build_env_image(const float* rgb, int w, int h, const float tint[3], float 
     pp[l] = zero ? 0.0f : pp[k] * lw / nd.weight, pp[r_] = zero ? 0.0f : pp[k] * rw / nd.weight;
     dead[l] = dead[r_] = char(off);
   }
+  count_out = count;
+  return off_tex;
+}
+
+bool build_env_image(const float* rgb, int w, int h, const float tint[3], float elevation, float rotation, DLight& L, std::vector<float>& words) {
+  if (w < 1 || h < 1) return set_error("`ImageSky` needs an image of at least 1 x 1 texels"), false;
+  if ((long long)w * h > (1ll << 26)) return set_error("`ImageSky` image has more than 2^26 texels"), false;
+  const size_t n = size_t(w) * size_t(h);
+  std::vector<float> density(n);
+  double weight = 0.0;
+  for (size_t i = 0; i < n; i++) {  // for_2d order: y outer, x inner = the texels' own order
+    const float r = rgb[3 * i], g = rgb[3 * i + 1], b = rgb[3 * i + 2];
+    if (!(r >= 0.0f && g >= 0.0f && b >= 0.0f) || std::isinf(r) || std::isinf(g) || std::isinf(b))
+      return set_error(fmt("`ImageSky` texel (%d, %d) is negative or not finite", int(i % size_t(w)), int(i / size_t(w)))), false;
+    density[i] = std::sqrt(r * r + g * g + b * b);  // length(vec3) vecmath.h:712-725
+    weight += density[i];
+  }
+  size_t count = 0;
+  const size_t off_tex = build_env_tree(density, w, h, weight, 20, n * 3, words, count);
   memcpy(&words[off_tex], rgb, n * 12);
   L = DLight{};
   L.kind = LIGHT_IMAGE_SKY;
@@ -900,11 +914,61 @@ bool build_env_image(const float* rgb, int w, int h, const float tint[3], float 
   return true;
 }
 
+// Atmosphere(sun_direction, sun_color, image_size) (light.cpp:94-105) from its tables (pine_atmosphere.h): `colors` the
+// (w + 1) x (h + 1) grid of atmosphere_color(wo(p), sun, 8, true), `density` the w x h lengths of its texels.
+bool build_env_atmosphere(const float sun_dir[3], const float sun_color[3], int w, int h, const std::vector<float>& colors, const std::vector<float>& density,
+                          DLight& L, std::vector<float>& words) {
+  const size_t n = size_t(w) * size_t(h), grid = size_t(w + 1) * size_t(h + 1);
+  if (w < 1 || h < 1 || density.size() != n || colors.size() != grid * 3) return set_error("internal: inconsistent Atmosphere tables"), false;
+  double weight = 0.0;
+  for (size_t i = 0; i < n; i++) {
+    // (the integral of a finite direction is finite; a density that is not would make the tree's sums meaningless)
+    if (!(density[i] >= 0.0f) || std::isinf(density[i])) return set_error(fmt("`Atmosphere` density of texel (%d, %d) is not finite", int(i % size_t(w)), int(i / size_t(w)))), false;
+    weight += density[i];
+  }
+  size_t count = 0;
+  const size_t off_colors = build_env_tree(density, w, h, weight, 15, grid * 3, words, count);
+  memcpy(&words[off_colors], colors.data(), grid * 12);
+  L = DLight{};
+  L.kind = LIGHT_ATMOSPHERE;
+  memcpy(L.direction, sun_dir, 12);
+  memcpy(L.color, sun_color, 12);
+  L.geom = int(count);
+  L.pad[0] = 0, L.pad[1] = w, L.pad[2] = h;
+  return true;
+}
+
+// the Atmosphere tables on host threads: rows of the (w + 1) x (h + 1) grid, each entry by the function the device runs
+static void atmosphere_table_host(f3 sun, int w, int h, float* colors, float* density) {
+  const int rows = h + 1, nt = std::max(1, std::min(math_check::threads(), rows));
+  auto part = [=](int t) {
+    for (int y = int((long long)rows * t / nt); y < int((long long)rows * (t + 1) / nt); y++)
+      for (int x = 0; x <= w; x++) atmosphere_table_entry(x, y, w, h, sun, colors, density);
+  };
+  std::vector<std::thread> th;
+  int started = 0;
+  try {
+    th.reserve(size_t(nt));
+    for (; started < nt - 1; started++) th.emplace_back(part, started);
+  } catch (const std::exception&) {  // (no more threads to be had: the parts not handed out run here -- nothing leaves the C ABI)
+  }
+  for (int t = started; t < nt; t++) part(t);
+  for (auto& x : th) x.join();
+}
+int atmosphere_tables(int device, const float sun_dir[3], int w, int h, float* colors, float* density) {
+  if (device >= 0) return atmosphere_table_device(device, sun_dir, w, h, colors, density);
+  atmosphere_table_host(ld3(sun_dir), w, h, colors, density);
+  return 0;
+}
+
 bool env_image_valid(const DLight& L, const std::vector<float>& words) {
+  const bool atmosphere = L.kind == LIGHT_ATMOSPHERE;
   const long long w = L.pad[1], h = L.pad[2], count = L.geom;
-  if (w < 1 || h < 1 || w * h > (1ll << 26) || count < 1 || count > (1ll << 22)) return false;
+  if (w < 1 || h < 1 || w * h > (1ll << (atmosphere ? 22 : 26)) || count < 1 || count > (1ll << 22)) return false;
+  if (atmosphere && L.pad[0]) return false;  // (no rotation: its pdf() goes through image_sky_ic)
   const long long n = w * h, off_pdf = kEnvHeaderWords + count * kEnvNodeWords, off_tex = off_pdf + ((n + 3) & ~3ll);
-  if ((long long)words.size() != off_tex + n * 3) return false;
+  // the last part: ImageSky's texels, or Atmosphere's colours at the (w + 1) x (h + 1) grid points
+  if ((long long)words.size() != off_tex + (atmosphere ? (w + 1) * (h + 1) : n) * 3) return false;
   for (long long k = 0; k < count; k++) {
     const float* o = &words[size_t(kEnvHeaderWords + k * kEnvNodeWords)];
     const int flags = get_int(o[3]), child = get_int(o[2]);
@@ -1118,6 +1182,31 @@ int pine_gpu_scene_set_env_image_u8(pine_gpu_scene* s, const uint8_t* rgb, int w
   std::vector<float> texels(size_t(w) * size_t(h) * 3);
   for (size_t i = 0; i < texels.size(); i++) texels[i] = table[rgb[i]];
   return pine_gpu_scene_set_env_image(s, texels.data(), w, h, tint, elevation, rotation);
+}
+
+int pine_gpu_scene_set_env_atmosphere(pine_gpu_scene* s, const float sun_direction[3], const float sun_color[3], int image_w, int image_h, int device) {
+  if (!check(s, sun_direction) || !check(s, sun_color)) return -1;
+  for (int k = 0; k < 3; k++) {
+    if (!std::isfinite(sun_direction[k])) return set_error("`Atmosphere` sun direction is not finite"), -1;
+    if (!std::isfinite(sun_color[k])) return set_error("`Atmosphere` sun colour is not finite"), -1;
+  }
+  const f3 sun = normalize(ld3(sun_direction));  // light.cpp:95
+  if (is_zero(ld3(sun_direction)) || !std::isfinite(sun.x) || !std::isfinite(sun.y) || !std::isfinite(sun.z) || is_zero(sun))
+    return set_error("`Atmosphere` sun direction is zero (or its length is not representable)"), -1;
+  if (image_w < 1 || image_h < 1) return set_error("`Atmosphere` needs an image size of at least 1 x 1 texels"), -1;
+  if ((long long)image_w * image_h > (1ll << 22)) return set_error("`Atmosphere` image size has more than 2^22 texels"), -1;
+  std::vector<float> colors(size_t(image_w + 1) * size_t(image_h + 1) * 3), density(size_t(image_w) * size_t(image_h));
+  const float sun_dir[3] = {sun.x, sun.y, sun.z};
+  if (atmosphere_tables(device, sun_dir, image_w, image_h, colors.data(), density.data()) < 0) return -1;
+  DLight L{};
+  std::vector<float> words;
+  if (!build_env_atmosphere(sun_dir, sun_color, image_w, image_h, colors, density, L, words)) return -1;
+  s->host.env = L;
+  s->host.has_env = true;
+  s->host.env_words.swap(words);
+  s->host.env_table_device = device < 0 ? -1 : device;
+  s->host.env_describe = "envlight atmosphere " + hex3(sun_direction) + " " + hex3(sun_color) + fmt(" %d %d", image_w, image_h);
+  return 0;
 }
 
 // ---- shading nodes + node-parameterised materials ----

@@ -128,9 +128,10 @@ struct SceneHost {
   DLight env{};                // environment light (appended to the sampler's list at plan build)
   std::vector<std::string> light_describe;
   std::string env_describe;
-  // ImageSky: the words of its device buffer -- rotation, density tree, pdf table, texels (pine_device.h EnvImage) -- built by
-  // build_env_image when the light is set; empty for any other environment light
+  // ImageSky, Atmosphere: the words of the device buffer -- rotation, density tree, pdf table, texels or colours (pine_device.h
+  // EnvImage) -- built by build_env_image / build_env_atmosphere when the light is set; empty for any other environment light
   std::vector<float> env_words;
+  int env_table_device = -1;  // Atmosphere: where its tables were computed (-1: on host threads)
   // what describe() prints after the materials, in add order: (0, geometry index) or (1, light index)
   std::vector<std::pair<int, int>> item_order;
   DCamera camera{};
@@ -159,7 +160,16 @@ void set_error(const std::string& msg);
 // ImageSky(image, tint, elevation, rotation) (light.cpp:127-137): the light's record and its device buffer from w x h float
 // texels (3 each, rows top first).  false with the error set: a texel that is negative or not finite, a bad size.
 bool build_env_image(const float* rgb, int w, int h, const float tint[3], float elevation, float rotation, DLight& L, std::vector<float>& words);
-// Every index the device code forms from `words` stays inside it (checked before a plan uploads it).
+// Atmosphere(sun_direction, sun_color, image_size) (light.cpp:94-105): the record and the buffer from the light's tables,
+// (w + 1) x (h + 1) colours and w x h densities (pine_atmosphere.h atmosphere_table_entry), whoever computed them.
+bool build_env_atmosphere(const float sun_dir[3], const float sun_color[3], int w, int h, const std::vector<float>& colors, const std::vector<float>& density,
+                          DLight& L, std::vector<float>& words);
+// The tables themselves, on `device` or (device < 0) on host threads: the same bytes.  < 0 with the error set when it cannot.
+int atmosphere_tables(int device, const float sun_dir[3], int w, int h, float* colors, float* density);
+// ... computed by atmosphere_table_kernel on `device` (pine_kernels.hip); < 0 with the error set when it cannot
+int atmosphere_table_device(int device, const float sun_dir[3], int w, int h, float* colors, float* density);
+// Every index the device code forms from the `words` of an ImageSky or an Atmosphere stays inside it (checked before a plan
+// uploads it).
 bool env_image_valid(const DLight& L, const std::vector<float>& words);
 std::string md5_hex(const void* data, size_t bytes);
 

@@ -31,6 +31,43 @@
 #include "../data/rcpps_table.h"
 namespace pine_gpu {
 
+// ---- the Atmosphere light's tables (pine_atmosphere.h): one thread per grid point of the (w + 1) x (h + 1) grid ----
+__global__ void __launch_bounds__(256) atmosphere_table_kernel(f3 sun, int w, int h, float* __restrict__ colors, float* __restrict__ density) {
+  const long long t = blockIdx.x * 256ll + threadIdx.x;
+  if (t >= (long long)(w + 1) * (h + 1)) return;
+  atmosphere_table_entry(int(t % (w + 1)), int(t / (w + 1)), w, h, sun, colors, density);
+}
+int atmosphere_table_device(int device, const float sun_dir[3], int w, int h, float* colors, float* density) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+    (void)hipGetLastError();
+    set_error("no HIP device available: the Atmosphere tables were asked of a device (device = -1 builds them on the host)");
+    return -1;
+  }
+  if (device >= ndev || w < 1 || h < 1 || (long long)w * h > (1ll << 22)) {
+    set_error("bad argument");
+    return -1;
+  }
+  const size_t grid = size_t(w + 1) * size_t(h + 1), n = size_t(w) * size_t(h);
+  float *d_colors = nullptr, *d_density = nullptr;
+  int rc = -1, keep = 0;
+  (void)hipGetDevice(&keep);  // (the caller's current device is the caller's)
+  hipError_t first = hipSuccess;  // the first failure: asking again for the last error would find it cleared
+  auto bad = [&](hipError_t e) { return e != hipSuccess && (first = e, true); };
+  do {
+    if (bad(hipSetDevice(device)) || bad(hipMalloc((void**)&d_colors, grid * 12)) || bad(hipMalloc((void**)&d_density, n * 4))) break;
+    hipLaunchKernelGGL(atmosphere_table_kernel, dim3(unsigned((grid + 255) / 256)), dim3(256), 0, 0, ld3(sun_dir), w, h, d_colors, d_density);
+    if (bad(hipGetLastError()) || bad(hipMemcpy(colors, d_colors, grid * 12, hipMemcpyDeviceToHost)) || bad(hipMemcpy(density, d_density, n * 4, hipMemcpyDeviceToHost)))
+      break;
+    rc = 0;
+  } while (0);
+  if (rc) set_error(std::string("Atmosphere tables on the device: ") + hipGetErrorString(first));
+  (void)hipFree(d_colors);
+  (void)hipFree(d_density);
+  (void)hipSetDevice(keep);
+  return rc;
+}
+
 // ---- the BVH build on the device: host orchestration (one decide / scan / split triple per level) ----
 static int device_build(std::vector<BuildPrim>& prims, const std::vector<BuildTask>& roots, FlatAccel& A, int device) {
   int ndev = 0;
@@ -875,9 +912,9 @@ static int assemble_scene(pine_gpu_plan* p, SceneHost& H, const pine_gpu_render_
   sp.tri_packet_bytes = tri_packets.size() * 4;
   if (upload(p->d_tri_attrs, A.tri_attrs)) return -1;
   S.env = nullptr;
-  if (H.has_env && H.env.kind == LIGHT_IMAGE_SKY) {
+  if (H.has_env && (H.env.kind == LIGHT_IMAGE_SKY || H.env.kind == LIGHT_ATMOSPHERE)) {
     if (!env_image_valid(H.env, H.env_words)) {
-      set_error("internal: inconsistent ImageSky buffer");
+      set_error("internal: inconsistent environment light buffer");
       return -1;
     }
     if (upload(p->d_env, H.env_words)) return -1;

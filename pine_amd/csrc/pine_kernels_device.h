@@ -67,7 +67,7 @@ struct DeviceScene {
   const DShape* shapes;
   const DMaterial* materials;
   const DNode* nodes;
-  const float* env;  // ImageSky: its rotation, density tree, pdf table and texels (pine_device.h EnvImage), or null; plan-owned
+  const float* env;  // ImageSky, Atmosphere: rotation, density tree, pdf table and texels / colours (pine_device.h EnvImage), or null; plan-owned
   const DBvh* bvhs;
   const float* tri_verts;
   const DLight* lights;

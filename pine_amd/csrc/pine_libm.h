@@ -383,6 +383,37 @@ PINE_HD float powf_glibc(float x, float y) {
   }
   return powf_exp2_inline(ylogx, sign_bias);
 }
+// e_expf.c: x * 32 / ln 2 = k + r, exp(x) = 2^(k / 32) * 2^(r / 32) through exp2f_tab and the cubic of exp2f with its
+// coefficients scaled by 1 / 32.  In the -mfma build the product InvLn2N * x is contracted into BOTH of its uses (the
+// rounding add of the shift and the subtraction that leaves r): with a separately rounded product two arguments of the
+// 2^32 differ from the host's expf, with the two fused operations none does.  Atmosphere's optical depths are its callers.
+PINE_HD float expf_glibc(float x) {
+  const uint32_t ix = asuint(x);
+  const uint32_t abstop = abstop12(x);
+  if (abstop >= 0x42bu) {  // |x| >= 88 or x is nan
+    if (ix == 0xff800000u) return 0.0f;
+    if (abstop >= 0x7f8u) return x + x;
+    if (x > 0x1.62e42ep6f) return __builtin_inff();  // x > log(0x1p128): overflow
+    if (x < -0x1.9fe368p6f) return 0.0f;             // x < log(0x1p-150): underflow to zero
+    if (x < -0x1.9d1d9ep6f) return 0x1p-149f;        // x < log(0x1p-149): __math_may_uflowf, 0x1.4p-75f squared
+  }
+  const double xd = double(x);
+  const double InvLn2N = 0x1.71547652b82fep+5, shift = 0x1.8p+52;
+  double kd = __builtin_fma(InvLn2N, xd, shift);
+  const uint64_t ki = asuint64(kd);
+  kd -= shift;
+  const double r = __builtin_fma(InvLn2N, xd, -kd);
+  uint64_t t = exp2f_tab(unsigned(ki % 32));
+  t += ki << (52 - 5);
+  const double s = asdouble(t);
+  const double C0 = 0x1.c6af84b912394p-20, C1 = 0x1.ebfce50fac4f3p-13, C2 = 0x1.62e42ff0c52d6p-6;  // poly_scaled
+  const double z = __builtin_fma(C0, r, C1);
+  const double r2 = r * r;
+  double y = __builtin_fma(C2, r, 1.0);
+  y = __builtin_fma(z, r2, y);
+  y = y * s;
+  return float(y);
+}
 PINE_HD float logf_glibc(float x) {  // e_logf.c
   uint32_t ix = asuint(x);
   if (ix == 0x3f800000u) return 0.0f;

@@ -72,6 +72,7 @@ PINE_HD float psin(float v) { return __sinf(v); }
 PINE_HD float pcos(float v) { return __cosf(v); }
 PINE_HD float ppow(float a, float b) { return __powf(a, b); }
 PINE_HD float plog(float v) { return __logf(v); }
+PINE_HD float pexp(float v) { return __expf(v); }
 PINE_HD void psincos(float v, float& sn, float& cs) {
   sn = __sinf(v);
   cs = __cosf(v);
@@ -84,6 +85,8 @@ PINE_HD float pcos(float v) { return pine_libm::cosf_glibc(v); }
 // libm-exact pow / log (pine_libm.h): psl::pow == std::pow (src/psl/math.h:201-202), psl::log == std::log
 PINE_HD float ppow(float a, float b) { return pine_libm::powf_glibc(a, b); }
 PINE_HD float plog(float v) { return pine_libm::logf_glibc(v); }
+// libm-exact exp: psl::exp == std::exp (src/psl/math.h:272-273), of a float and per component of a vec3 (vecmath.h:943-945)
+PINE_HD float pexp(float v) { return pine_libm::expf_glibc(v); }
 PINE_HD void psincos(float v, float& sn, float& cs) {
   pine_libm::sincosf_glibc(v, sn, cs);
 }
@@ -224,6 +227,28 @@ PINE_HD int32_t as_int(float f) {
   int32_t i;
   memcpy(&i, &f, 4);
   return i;
+}
+
+// Two functions of the kernels that the host build of the Atmosphere table (pine_atmosphere.h) needs as well:
+// uniform_sphere (sampling.h:44-50) and Sphere::compute_t.
+PINE_HD f3 uniform_sphere(f2 u) {
+  const float phi = u.x * kPi * 2;
+  const float cos_theta = 1 - 2 * u.y;
+  const float sin_theta = psqrt(1.0f - sqr(cos_theta));
+  float sn, cs;
+  psincos(phi, sn, cs);
+  return f3{sin_theta * cs, sin_theta * sn, cos_theta};
+}
+PINE_HD float sphere_compute_t(f3 ro, f3 rd, float tmin, f3 p, float r) {  // geometry.cpp:73-83
+  const f3 ro_p = ro - p;
+  const float b = dot(ro_p, rd);
+  const float c = dot(ro_p, ro_p) - r * r;
+  float d = b * b - c;
+  if (d <= 0.0f) return -1.0f;
+  d = psqrt(d);
+  float t = -b - d;
+  if (t < tmin) t = -b + d;
+  return t;
 }
 
 }  // namespace pine_gpu

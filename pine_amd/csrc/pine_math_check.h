@@ -25,7 +25,7 @@
 namespace pine_gpu {
 
 constexpr int math_width(int fn) { return fn == PINE_GPU_MATH_SINCOS ? 2 : 1; }
-constexpr int math_arity(int fn) { return fn == PINE_GPU_MATH_CLAMP ? 3 : fn >= PINE_GPU_MATH_ATAN2 ? 2 : 1; }
+constexpr int math_arity(int fn) { return fn == PINE_GPU_MATH_CLAMP ? 3 : fn == PINE_GPU_MATH_EXP ? 1 : fn >= PINE_GPU_MATH_ATAN2 ? 2 : 1; }
 
 // out[0] (SINCOS: out[0], out[1]) = FN(a, b, c) by the production functions.  One instantiation per function, so that
 // a kernel inlines only the function under test.
@@ -50,6 +50,7 @@ PINE_HD void math_eval(uint32_t ua, uint32_t ub, uint32_t uc, uint32_t* out) {
   else if constexpr (FN == PINE_GPU_MATH_MIN) r = pmin(a, b);
   else if constexpr (FN == PINE_GPU_MATH_MAX) r = pmax(a, b);
   else if constexpr (FN == PINE_GPU_MATH_CLAMP) r = pclamp(a, b, c);
+  else if constexpr (FN == PINE_GPU_MATH_EXP) r = pexp(a);
   out[0] = pine_libm::asuint(r);
 }
 
@@ -93,6 +94,7 @@ inline uint32_t reference(int fn, int k, uint32_t ua, uint32_t ub, uint32_t uc) 
       r = t < c ? t : c;
       break;
     }
+    case PINE_GPU_MATH_EXP: r = ::expf(a); break;
   }
   return pine_libm::asuint(r);
 }

@@ -250,7 +250,7 @@ struct pine_gpu_plan {
   uint4* d_tri_packets = nullptr;
   uint8_t* d_halton = nullptr;
   float* d_tri_attrs = nullptr;
-  float* d_env = nullptr;  // ImageSky: SceneHost::env_words (null: another environment light, or none)
+  float* d_env = nullptr;  // ImageSky, Atmosphere: SceneHost::env_words (null: another environment light, or none)
   uint8_t* d_tables = nullptr;
   int variant = -1;
   int queue_variant = -1;   // >= 0: the stage-queued kernel is used instead of path_trace_kernel

@@ -215,13 +215,14 @@ __device__ __forceinline__ f3 terminal_radiance(const SceneView& V, int env_ligh
     if constexpr (F & F_LIGHTS)
       if (env_light >= 0) {
         const DLight* E = &V.lights[env_light];
-        const bool image = E->kind == LIGHT_IMAGE_SKY;
+        const bool image = E->kind == LIGHT_IMAGE_SKY, atmosphere = E->kind == LIGHT_ATMOSPHERE;
         if (image) Lo = mk3(1.0f) * image_sky_color(E, V.env, ray_d);
+        else if (atmosphere) Lo = mk3(1.0f) * atmosphere_sky_color(E, ray_d);
         else Lo = mk3(1.0f) * sky_color_of(ld3(E->color), ray_d);
         if (!is_delta) {
           has_light_pdf = true;
           light_pdf = 1 / (4 * kPi);  // Sky::pdf -- not divided by the light count
-          if (image) light_pdf = image_sky_pdf(E, V.env, ray_d);  // ImageSky::pdf -- neither
+          if (image || atmosphere) light_pdf = image_sky_pdf(E, V.env, ray_d);  // ImageSky::pdf, Atmosphere::pdf -- neither
         }
       }
   } else {
@@ -381,7 +382,7 @@ __device__ __forceinline__ f3 sample_direct(const SceneView& V, int num_lights, 
         ldist = gs.distance;
         lpdf = gs.pdf;
       }
-    } else {  // light.cpp:11-84, 146-163: point, spot, directional, Sky, ImageSky
+    } else {  // light.cpp:11-84, 109-119, 146-163: point, spot, directional, Sky, Atmosphere, ImageSky
       if constexpr (F & F_LIGHTS) lvalid = light_sample_other(L, V.env, it.p, u2, lw, ldist, lpdf, lle);
     }
     const bool ldelta = lkind == LIGHT_POINT || lkind == LIGHT_SPOT || lkind == LIGHT_DIRECTIONAL;  // light.h:111-113

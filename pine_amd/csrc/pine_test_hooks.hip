@@ -265,19 +265,48 @@ __global__ void __launch_bounds__(64) test_light_samples_kernel(const DShape* sh
   if (k < num_shapes) test_shape_sample_case(&shapes[k], tri_verts, queries + i * 6, out + t * 13);
   else test_light_sample_case(&lights[k - num_shapes], queries + i * 6, out + n * num_shapes * 13 + (t - n * num_shapes) * 9);
 }
-// pine_gpu_test_env_light: ImageSky::sample(u2), then color(wo) and pdf(wo) of the query's own direction
+// pine_gpu_test_env_light: ImageSky's or Atmosphere's sample(u2), then color(wo) and pdf(wo) of the query's own direction
 PINE_HD void test_env_light_case(const DLight* L, const float* env, const float* q, float* o) {
   f3 w, le;
   float pdf;
   int px, py;
-  image_sky_sample(L, env, f2{q[0], q[1]}, w, pdf, le, px, py);
+  const bool atmosphere = L->kind == LIGHT_ATMOSPHERE;
+  if (atmosphere) atmosphere_sample(L, env, f2{q[0], q[1]}, w, pdf, le, px, py);
+  else image_sky_sample(L, env, f2{q[0], q[1]}, w, pdf, le, px, py);
   o[0] = float(px), o[1] = float(py), o[2] = pdf;
   o[3] = w.x, o[4] = w.y, o[5] = w.z;
   o[6] = le.x, o[7] = le.y, o[8] = le.z;
   const f3 wo = ld3(q + 2);
-  const f3 c = image_sky_color(L, env, wo);
+  const f3 c = atmosphere ? atmosphere_sky_color(L, wo) : image_sky_color(L, env, wo);
   o[9] = c.x, o[10] = c.y, o[11] = c.z;
   o[12] = image_sky_pdf(L, env, wo);
+}
+// pine_gpu_test_atmosphere_color: atmosphere_color(direction, sun_dir, 8, flag) of a query of 7 floats
+PINE_HD void test_atmosphere_color_case(const float* q, float* o) {
+  const f3 c = atmosphere_color_of(ld3(q), ld3(q + 3), q[6] != 0.0f);
+  o[0] = c.x, o[1] = c.y, o[2] = c.z;
+}
+__global__ void __launch_bounds__(64) test_atmosphere_color_kernel(const float* queries, long long n, float* out) {
+  const long long t = blockIdx.x * 64ll + threadIdx.x;
+  if (t >= n) return;
+  test_atmosphere_color_case(queries + t * 7, out + t * 3);
+}
+// pine_gpu_test_env_light_sample: the light sampler's own call for the environment light -- light_sample_other with the plan's
+// env buffer -- as pine_gpu_test_light_samples' 9-float record
+PINE_HD void test_env_light_sample_case(const DLight* L, const float* env, const float* q, float* o) {
+  for (int k = 0; k < 9; k++) o[k] = 0.0f;
+  f3 w, le;
+  float distance, pdf;
+  if (!light_sample_other(L, env, ld3(q), f2{q[3], q[4]}, w, distance, pdf, le)) return;
+  o[0] = 1.0f;
+  o[1] = w.x, o[2] = w.y, o[3] = w.z;
+  o[4] = distance, o[5] = pdf;
+  o[6] = le.x, o[7] = le.y, o[8] = le.z;
+}
+__global__ void __launch_bounds__(64) test_env_light_sample_kernel(DLight L, const float* env, const float* queries, long long n, float* out) {
+  const long long t = blockIdx.x * 64ll + threadIdx.x;
+  if (t >= n) return;
+  test_env_light_sample_case(&L, env, queries + t * 5, out + t * 9);
 }
 __global__ void __launch_bounds__(64) test_env_light_kernel(DLight L, const float* env, const float* queries, long long n, float* out) {
   const long long t = blockIdx.x * 64ll + threadIdx.x;
@@ -827,8 +856,8 @@ int pine_gpu_test_env_light(pine_gpu_scene* scene, int device, const float* quer
     return -1;
   }
   SceneHost& H = scene_host(scene);
-  if (!H.has_env || H.env.kind != LIGHT_IMAGE_SKY || !env_image_valid(H.env, H.env_words)) {
-    set_error("pine_gpu_test_env_light: the scene's environment light is no ImageSky");
+  if (!H.has_env || (H.env.kind != LIGHT_IMAGE_SKY && H.env.kind != LIGHT_ATMOSPHERE) || !env_image_valid(H.env, H.env_words)) {
+    set_error("pine_gpu_test_env_light: the scene's environment light is no ImageSky and no Atmosphere");
     return -1;
   }
   if (device < 0) {
@@ -857,14 +886,104 @@ int pine_gpu_test_env_light(pine_gpu_scene* scene, int device, const float* quer
   return rc;
 }
 
+int pine_gpu_test_atmosphere_color(int device, const float* queries, int64_t n, float* out) {
+  if (!queries || !out || n < 0 || n > (1 << 20)) {
+    set_error("bad argument");
+    return -1;
+  }
+  if (device < 0) {
+    for (int64_t i = 0; i < n; i++) test_atmosphere_color_case(queries + i * 7, out + i * 3);
+    return 0;
+  }
+  if (n == 0) return 0;
+  if (need_device(device)) return -1;
+  float *dq = nullptr, *dout = nullptr;
+  int rc = -1;
+  hipError_t first = hipSuccess;  // the first failure: asking again for the last error would find it cleared
+  auto bad = [&](hipError_t e) { return e != hipSuccess && (first = e, true); };
+  do {
+    if (bad(hipMalloc((void**)&dq, size_t(n) * 28)) || bad(hipMalloc((void**)&dout, size_t(n) * 12))) break;
+    if (bad(hipMemcpy(dq, queries, size_t(n) * 28, hipMemcpyHostToDevice))) break;
+    hipLaunchKernelGGL(test_atmosphere_color_kernel, dim3(unsigned((n + 63) / 64)), dim3(64), 0, 0, dq, (long long)n, dout);
+    if (bad(hipGetLastError()) || bad(hipMemcpy(out, dout, size_t(n) * 12, hipMemcpyDeviceToHost))) break;
+    rc = 0;
+  } while (0);
+  if (rc) set_error(std::string("pine_gpu_test_atmosphere_color: ") + hipGetErrorString(first));
+  (void)hipFree(dq);
+  (void)hipFree(dout);
+  return rc;
+}
+
+int pine_gpu_test_env_light_sample(pine_gpu_scene* scene, int device, const float* queries, int64_t n, float* out) {
+  if (!scene || !queries || !out || n < 0 || n > (1 << 20)) {
+    set_error("bad argument");
+    return -1;
+  }
+  SceneHost& H = scene_host(scene);
+  if (!H.has_env || (H.env.kind != LIGHT_IMAGE_SKY && H.env.kind != LIGHT_ATMOSPHERE) || !env_image_valid(H.env, H.env_words)) {
+    set_error("pine_gpu_test_env_light_sample: the scene's environment light is no ImageSky and no Atmosphere");
+    return -1;
+  }
+  if (device < 0) {
+    for (int64_t i = 0; i < n; i++) test_env_light_sample_case(&H.env, H.env_words.data(), queries + i * 5, out + i * 9);
+    return 0;
+  }
+  if (n == 0) return 0;
+  if (need_device(device)) return -1;
+  float *de = nullptr, *dq = nullptr, *dout = nullptr;
+  int rc = -1;
+  hipError_t first = hipSuccess;
+  auto bad = [&](hipError_t e) { return e != hipSuccess && (first = e, true); };
+  do {
+    if (bad(hipMalloc((void**)&de, H.env_words.size() * 4)) || bad(hipMalloc((void**)&dq, size_t(n) * 20)) || bad(hipMalloc((void**)&dout, size_t(n) * 36))) break;
+    if (bad(hipMemcpy(de, H.env_words.data(), H.env_words.size() * 4, hipMemcpyHostToDevice)) || bad(hipMemcpy(dq, queries, size_t(n) * 20, hipMemcpyHostToDevice))) break;
+    hipLaunchKernelGGL(test_env_light_sample_kernel, dim3(unsigned((n + 63) / 64)), dim3(64), 0, 0, H.env, de, dq, (long long)n, dout);
+    if (bad(hipGetLastError()) || bad(hipMemcpy(out, dout, size_t(n) * 36, hipMemcpyDeviceToHost))) break;
+    rc = 0;
+  } while (0);
+  if (rc) set_error(std::string("pine_gpu_test_env_light_sample: ") + hipGetErrorString(first));
+  (void)hipFree(de);
+  (void)hipFree(dq);
+  (void)hipFree(dout);
+  return rc;
+}
+
+int64_t pine_gpu_test_env_table(pine_gpu_scene* scene, float* out, int64_t capacity) {
+  if (!scene) {
+    set_error("null argument");
+    return -1;
+  }
+  SceneHost& H = scene_host(scene);
+  if (!H.has_env || H.env.kind != LIGHT_ATMOSPHERE || !env_image_valid(H.env, H.env_words)) {
+    set_error("pine_gpu_test_env_table: the scene's environment light is no Atmosphere");
+    return -1;
+  }
+  const int w = H.env.pad[1], h = H.env.pad[2];
+  const int64_t n = int64_t(w) * h, grid = int64_t(w + 1) * (h + 1), floats = n + grid * 3;
+  if (!out || capacity < floats) return floats;
+  // The scene keeps the colours (they are part of the light's buffer) and not the densities, which only the tree build read:
+  // they are computed again here, where the light's own were (H.env_table_device), and the colours that come with them must be
+  // the ones the light holds.
+  std::vector<float> colors(size_t(grid) * 3), density(static_cast<size_t>(n));
+  if (atmosphere_tables(H.env_table_device, H.env.direction, w, h, colors.data(), density.data()) < 0) return -1;
+  const float* held = H.env_words.data() + (H.env_words.size() - size_t(grid) * 3);
+  if (memcmp(colors.data(), held, size_t(grid) * 12) != 0) {
+    set_error("pine_gpu_test_env_table: the tables computed again differ from the light's");
+    return -1;
+  }
+  memcpy(out, density.data(), size_t(n) * 4);
+  memcpy(out + n, held, size_t(grid) * 12);
+  return floats;
+}
+
 int64_t pine_gpu_test_env_tree(pine_gpu_scene* scene, int32_t* out, int64_t capacity_words) {
   if (!scene) {
     set_error("null argument");
     return -1;
   }
   SceneHost& H = scene_host(scene);
-  if (!H.has_env || H.env.kind != LIGHT_IMAGE_SKY || !env_image_valid(H.env, H.env_words)) {
-    set_error("pine_gpu_test_env_tree: the scene's environment light is no ImageSky");
+  if (!H.has_env || (H.env.kind != LIGHT_IMAGE_SKY && H.env.kind != LIGHT_ATMOSPHERE) || !env_image_valid(H.env, H.env_words)) {
+    set_error("pine_gpu_test_env_tree: the scene's environment light is no ImageSky and no Atmosphere");
     return -1;
   }
   const int64_t words = int64_t(H.env.geom) * 7;

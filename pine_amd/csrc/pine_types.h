@@ -127,16 +127,17 @@ struct DCamera {
 // One entry of the light sampler's list (UniformLightSampler::build lightsampler.cpp:6-10): Scene::lights
 // in add order -- an area light per emissive geometry, Point / Spot / Directional lights -- then the
 // environment light, if any, last.  light.h:21-67.
-enum LightKind : int { LIGHT_AREA = 0, LIGHT_POINT = 1, LIGHT_SPOT = 2, LIGHT_DIRECTIONAL = 3, LIGHT_SKY = 4, LIGHT_IMAGE_SKY = 5 };
+enum LightKind : int { LIGHT_AREA = 0, LIGHT_POINT = 1, LIGHT_SPOT = 2, LIGHT_DIRECTIONAL = 3, LIGHT_SKY = 4, LIGHT_IMAGE_SKY = 5, LIGHT_ATMOSPHERE = 6 };
 struct alignas(16) DLight {
   float position[3];
   int kind;
-  float direction[3];  // normalised (Spot, Directional)
-  int geom;            // LIGHT_AREA: geometry index; ImageSky: node count of its density tree
-  float color[3];      // Point / Spot / Directional: colour; Sky: sun_color; ImageSky: tint
+  float direction[3];  // normalised (Spot, Directional; Atmosphere: the sun's)
+  int geom;            // LIGHT_AREA: geometry index; ImageSky, Atmosphere: node count of the density tree
+  float color[3];      // Point / Spot / Directional: colour; Sky, Atmosphere: sun_color; ImageSky: tint
   float falloff_cos;
   float cutoff_cos;
-  int pad[3];          // ImageSky: 1 where it has a rotation (l2w / w2l), image width, image height (pine_device.h EnvImage)
+  int pad[3];          // ImageSky: 1 where it has a rotation (l2w / w2l), image width, image height (pine_device.h EnvImage);
+                       // Atmosphere: 0, image width, image height
 };
 static_assert(sizeof(DLight) == 64, "DLight must be 64 bytes");
 

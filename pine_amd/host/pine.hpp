@@ -188,6 +188,13 @@ struct ImageSky {  // light.h:81-94
     if (!this->image) throw Error("ImageSky: no image");
   }
 };
+struct Atmosphere {  // light.h:69-79; image_size: the grid of its importance sampling (the reference's scripts always get 1024 x 1024)
+  vec3 sun_direction, sun_color;
+  vec2i image_size{1024, 1024};
+  int device = -1;  // the HIP device that computes the light's tables when it is set; -1: host threads (the same bytes)
+  Atmosphere(vec3 sun_direction, vec3 sun_color, vec2i image_size = vec2i{1024, 1024}, int device = -1)
+      : sun_direction(sun_direction), sun_color(sun_color), image_size(image_size), device(device) {}
+};
 
 class Scene {
  public:
@@ -228,6 +235,10 @@ class Scene {
     pine_gpu_scene_describe(h_, &text[0], n + 1);
     text.resize(size_t(n));
     return text;
+  }
+  void set(const Atmosphere& sky) {
+    check(pine_gpu_scene_set_env_atmosphere(h_, sky.sun_direction.data(), sky.sun_color.data(), sky.image_size.x, sky.image_size.y, sky.device),
+          "scene.set(Atmosphere)");
   }
   void set(const ImageSky& sky) {
     const Image& im = *sky.image;

@@ -154,7 +154,7 @@ struct ImageObj : Object {  // ImagePtr: float texels, 3 each, rows top first
   std::vector<float> rgb;
 };
 struct LightObj : Object {
-  std::string kind;  // PointLight | SpotLight | DirectionalLight | Sky | ImageSky
+  std::string kind;  // PointLight | SpotLight | DirectionalLight | Sky | ImageSky | Atmosphere (b = sun direction, c = sun colour)
   float a[3] = {0, 0, 0}, b[3] = {0, 0, 0}, c[3] = {0, 0, 0};
   float falloff = 0, extra = 0;  // (ImageSky: c = tint, falloff = elevation, extra = rotation)
   std::shared_ptr<ImageObj> image;
@@ -1844,6 +1844,13 @@ Interp::Interp() {
     return mk_obj("Sky", l);
   });
   r.convert("Sky", "EnvironmentLight", [](const Value& v) { return retype(v, "EnvironmentLight"); });
+  r.def("Atmosphere", {"vec3", "vec3"}, "Atmosphere", [=](Interp&, std::vector<Cell>& a) {  // light.cpp:181: image_size stays 1024 x 1024
+    auto l = light("Atmosphere");
+    memcpy(l->b, a[0]->f, 12);
+    memcpy(l->c, a[1]->f, 12);
+    return mk_obj("Atmosphere", l);
+  });
+  r.convert("Atmosphere", "EnvironmentLight", [](const Value& v) { return retype(v, "EnvironmentLight"); });
   // ImagePtr(str) / load_image(str): a Radiance .hdr file; ImagePtr(vec3): the reference's 1 x 1 image (image.cpp:49-61)
   auto image_file = [](Interp&, std::vector<Cell>& a) {
     auto im = std::make_shared<ImageObj>();
@@ -1888,9 +1895,12 @@ Interp::Interp() {
     gpu_check(rc, "scene.add(light)");
     return Value();
   });
-  r.def("set", {"Scene&", "EnvironmentLight"}, "void", [](Interp&, std::vector<Cell>& a) {  // Scene::set_env_light scene.cpp:44-46
+  r.def("set", {"Scene&", "EnvironmentLight"}, "void", [](Interp& in, std::vector<Cell>& a) {  // Scene::set_env_light scene.cpp:44-46
     auto l = obj<LightObj>(a[1]);
-    if (l->kind == "ImageSky")
+    if (l->kind == "Atmosphere")  // (its tables: on the render device; a dry run has none, the host builds the same ones)
+      gpu_check(pine_gpu_scene_set_env_atmosphere(obj<SceneObj>(a[0])->h, l->b, l->c, 1024, 1024, (in.flags & PINE_PRL_DRY_RUN) ? -1 : in.device),
+                "scene.set(environment light)");
+    else if (l->kind == "ImageSky")
       gpu_check(pine_gpu_scene_set_env_image(obj<SceneObj>(a[0])->h, l->image->rgb.data(), l->image->w, l->image->h, l->c, l->falloff, l->extra),
                 "scene.set(environment light)");
     else

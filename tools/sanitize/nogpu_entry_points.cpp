@@ -26,6 +26,8 @@ static int fail() {
   set_error(kNoDevice);
   return -1;
 }
+// (the Atmosphere tables on a device: pine_kernels.hip; the host build of them, device = -1, is the real thing in pine_host.cpp)
+int pine_gpu::atmosphere_table_device(int, const float*, int, int, float*, float*) { return fail(); }
 
 extern "C" {
 float pine_gpu_progress(void) { return 0.0f; }
@@ -82,6 +84,9 @@ int pine_gpu_test_bxdf(int, const float*, int64_t, float*) { return fail(); }
 int pine_gpu_test_light_samples(pine_gpu_scene*, int, const float*, int64_t, float*) { return fail(); }
 int pine_gpu_test_env_light(pine_gpu_scene*, int, const float*, int64_t, float*) { return fail(); }
 int64_t pine_gpu_test_env_tree(pine_gpu_scene*, int32_t*, int64_t) { return fail(); }
+int pine_gpu_test_atmosphere_color(int, const float*, int64_t, float*) { return fail(); }
+int64_t pine_gpu_test_env_table(pine_gpu_scene*, float*, int64_t) { return fail(); }
+int pine_gpu_test_env_light_sample(pine_gpu_scene*, int, const float*, int64_t, float*) { return fail(); }
 int64_t pine_gpu_test_node_programs(pine_gpu_scene*, int32_t*, int64_t) { return fail(); }
 int pine_gpu_test_material_params(pine_gpu_scene*, int, const float*, int64_t, float*) { return fail(); }
 int pine_gpu_test_choose_lobe(pine_gpu_scene*, int, const float*, int64_t, float*) { return fail(); }
