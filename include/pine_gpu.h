@@ -618,6 +618,11 @@ int pine_gpu_test_box_slabs(const float* boxes_host, const float* rays_host, int
  * megakernel) and order; any of the arrays may be NULL.  Returns the number of variants, < 0 on error.  Needs no GPU.
  * With $PINE_GPU_TEST_VARIANT=queue:<order> / mega:<order> plan creation considers that variant only (tests/test_kernel_matrix.py). */
 int pine_gpu_test_kernel_variants(int kind, uint32_t* features, int32_t* ctx, int32_t* order, int cap);
+/* Who holds device resources right now.  out[0]: the handles the library's owners hold -- device blocks, pinned host memory,
+ * events and streams of live plans and of calls in flight, all kinds counted together; a call that has returned, a plan that
+ * has been destroyed or was never created holds none.  out[1]: the blocks the device memory pool keeps for the next plan
+ * (pine_gpu_release_cached_memory frees them).  Reads two counters and launches nothing; returns 0. */
+int pine_gpu_test_live_device_blocks(int64_t out[2]);
 
 /* ---- Film (host side, after the hot path) ----------------------------------------------------
  * Film::finalize + tone mapping + to_uint8_array: src/pine/core/film.cpp:12-27,66-68,

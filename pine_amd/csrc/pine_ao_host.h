@@ -120,10 +120,11 @@ static int ao_plan_build(pine_gpu_plan* p, pine_gpu_scene* scene, const pine_gpu
   p->pass_plan = PassPlan();
   p->pass_plan.free_tiles = W.num_local_tiles;
   if (prm.flags & PINE_GPU_FLAG_PROGRESS) {
-    HIP_OK(hipHostMalloc((void**)&p->h_progress, sizeof(unsigned long long), hipHostMallocMapped));
-    *p->h_progress = 0;
-    HIP_OK(hipHostGetDevicePointer((void**)&W.progress, p->h_progress, 0));
+    if (alloc_pinned(p->h_progress, 1, hipHostMallocMapped, "plan creation: the progress word")) return -1;
+    p->h_progress[0] = 0;
+    HIP_OK(hipHostGetDevicePointer((void**)&W.progress, p->h_progress.get(), 0));
   }
+  const char* const what = "plan creation: the launch buffers";
   hipDeviceProp_t prop;
   HIP_OK(hipGetDeviceProperties(&prop, prm.device));
   int blocks_per_cu = 0;
@@ -133,14 +134,14 @@ static int ao_plan_build(pine_gpu_plan* p, pine_gpu_scene* scene, const pine_gpu
   if (p->grid < 1) p->grid = 1;
   if (W.items_per_pixel > 1) {
     p->bytes_ckpt = W.total_items * sizeof(ulonglong2);
-    HIP_OK(POOL_ALLOC(p->d_ckpt, p->bytes_ckpt));
+    if (p->d_ckpt.alloc(W.total_items, what)) return -1;
   }
-  HIP_OK(POOL_ALLOC(p->d_ao_counts, size_t(p->film_w) * p->film_h * sizeof(unsigned)));
-  HIP_OK(POOL_ALLOC(p->d_counters, sizeof(Counters)));
+  if (p->d_ao_counts.alloc(size_t(p->film_w) * p->film_h, what) || p->d_counters.alloc(1, what)) return -1;
   p->timed = (prm.flags & PINE_GPU_FLAG_TIMING) != 0;
   if (p->timed)
     for (auto& slot : p->ev)
-      for (auto& e : slot) HIP_OK(hipEventCreate(&e));
+      for (auto& e : slot)
+        if (create_event(e, hipEventDefault, "plan creation: the timing events")) return -1;
   p->bytes_total = g_alloc_tally - tally0;
   HIP_OK(hipDeviceSynchronize());
   p->upload_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_build1).count();
@@ -157,36 +158,38 @@ static int ao_launch(pine_gpu_plan* p, void* film_dev, hipStream_t stream) {
   if (W.shard_world > 1) HIP_OK(hipMemsetAsync(film_dev, 0, pixels * sizeof(float4), stream));
   HIP_OK(hipMemsetAsync(p->d_counters, 0, sizeof(Counters), stream));
   HIP_OK(hipMemsetAsync(p->d_ao_counts, 0, pixels * sizeof(unsigned), stream));
-  hipEvent_t* ev = p->ev[p->launch_count % pine_gpu_plan::kEvRing];
-  if (p->timed) HIP_OK(hipEventRecord(ev[0], stream));
+  const EventOwner* ev = p->ev[p->launch_count % pine_gpu_plan::kEvRing];
+  if (p->timed) HIP_OK(hipEventRecord(ev[0].get(), stream));
   const bool has_work = W.total_items > 0;
   if (has_work && W.items_per_pixel > 1) {
     if (!p->ckpt_valid) {
       const unsigned long long n = (unsigned long long)W.num_local_tiles * 64ull;
       hipLaunchKernelGGL(rng_checkpoint_kernel, dim3(unsigned((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, W, p->film_w, p->film_h, p->S.spp,
                          p->d_ckpt, W.num_local_tiles, (ulonglong2*)nullptr);
-      if (!p->ckpt_done) HIP_OK(hipEventCreateWithFlags(&p->ckpt_done, hipEventDisableTiming));
-      HIP_OK(hipEventRecord(p->ckpt_done, stream));
+      if (!p->ckpt_done && create_event(p->ckpt_done, hipEventDisableTiming, "launch: the checkpoint event")) return -1;
+      HIP_OK(hipEventRecord(p->ckpt_done.get(), stream));
       p->ckpt_stream = stream;
       p->ckpt_valid = true;
     } else if (stream != p->ckpt_stream) {
-      HIP_OK(hipStreamWaitEvent(stream, p->ckpt_done, 0));
+      HIP_OK(hipStreamWaitEvent(stream, p->ckpt_done.get(), 0));
     }
   }
-  if (p->timed) HIP_OK(hipEventRecord(ev[1], stream));
+  if (p->timed) HIP_OK(hipEventRecord(ev[1].get(), stream));
   if (has_work) {
     const PathKernel kernel = plan_kernel(p);
     const ulonglong2* ckpt = p->d_ckpt;
-    void* args[] = {&p->S, &W, &p->ao_params, &ckpt, &p->d_ao_counts, &p->d_counters};
+    unsigned* counts = p->d_ao_counts;
+    Counters* counters = p->d_counters;
+    void* args[] = {&p->S, &W, &p->ao_params, &ckpt, &counts, &counters};
     HIP_OK(hipLaunchKernel(kernel.fn, dim3(p->grid), dim3(kBlock), args, p->lds_bytes, stream));
   }
-  if (p->timed) HIP_OK(hipEventRecord(ev[2], stream));
+  if (p->timed) HIP_OK(hipEventRecord(ev[2].get(), stream));
   if (W.num_local_tiles > 0) {
     const unsigned long long n = (unsigned long long)W.num_local_tiles * 64ull;
     hipLaunchKernelGGL(ao_film_kernel, dim3(unsigned((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, W, p->film_w, p->film_h, p->S.spp,
-                       (const unsigned*)p->d_ao_counts, (float4*)film_dev);
+                       p->d_ao_counts.get(), (float4*)film_dev);
   }
-  if (p->timed) HIP_OK(hipEventRecord(ev[3], stream));
+  if (p->timed) HIP_OK(hipEventRecord(ev[3].get(), stream));
   HIP_OK(hipGetLastError());
   p->launched = true;
   p->launch_count++;
@@ -219,31 +222,9 @@ int pine_gpu_ao_render(pine_gpu_scene* scene, const pine_gpu_render_params* prm,
   prm2.flags |= PINE_GPU_FLAG_PROGRESS;
   pine_gpu_plan* p = pine_gpu_ao_plan_create(scene, &prm2);
   if (!p) return -1;
-  int rc = -1;
-  void* d_film = nullptr;
-  const size_t bytes = size_t(p->film_w) * p->film_h * 16;
-  do {
-    if (DevicePool::get().alloc(&d_film, bytes) != hipSuccess) {
-      set_error("hipMalloc(film) failed");
-      break;
-    }
-    g_progress_total.store(p->W.total_items);
-    g_progress_base.store(0);
-    g_progress_src.store(p->h_progress);
-    if (pine_gpu_plan_launch(p, d_film, nullptr)) break;
-    if (hipMemcpy(film_out, d_film, bytes, hipMemcpyDeviceToHost) != hipSuccess) {
-      set_error("film download failed");
-      break;
-    }
-    if (pine_gpu_plan_check(p)) break;  // (a launch that gave up leaves an incomplete film: fail)
-    rc = 0;
-  } while (0);
-  g_progress_src.store(nullptr);
-  g_progress.store(rc == 0 ? 1.0f : 0.0f);
-  std::string keep = rc < 0 ? pine_gpu_last_error() : "";
-  if (rc < 0) (void)hipDeviceSynchronize();
-  DevicePool::get().free(d_film);
-  pine_gpu_plan_destroy(p);
-  if (rc < 0) set_error(keep);
-  return rc;
+  return one_shot_render(p, p->W.total_items, [&](float4* d_film, size_t bytes) {
+    if (pine_gpu_plan_launch(p, d_film, nullptr)) return -1;
+    if (const hipError_t e = hipMemcpy(film_out, d_film, bytes, hipMemcpyDeviceToHost)) return hip_error("film download", e);
+    return pine_gpu_plan_check(p);  // (a launch that gave up leaves an incomplete film: fail)
+  });
 }

@@ -49,21 +49,17 @@ int atmosphere_table_device(int device, const float sun_dir[3], int w, int h, fl
     return -1;
   }
   const size_t grid = size_t(w + 1) * size_t(h + 1), n = size_t(w) * size_t(h);
-  float *d_colors = nullptr, *d_density = nullptr;
-  int rc = -1, keep = 0;
+  int keep = 0;
   (void)hipGetDevice(&keep);  // (the caller's current device is the caller's)
-  hipError_t first = hipSuccess;  // the first failure: asking again for the last error would find it cleared
-  auto bad = [&](hipError_t e) { return e != hipSuccess && (first = e, true); };
-  do {
-    if (bad(hipSetDevice(device)) || bad(hipMalloc((void**)&d_colors, grid * 12)) || bad(hipMalloc((void**)&d_density, n * 4))) break;
-    hipLaunchKernelGGL(atmosphere_table_kernel, dim3(unsigned((grid + 255) / 256)), dim3(256), 0, 0, ld3(sun_dir), w, h, d_colors, d_density);
-    if (bad(hipGetLastError()) || bad(hipMemcpy(colors, d_colors, grid * 12, hipMemcpyDeviceToHost)) || bad(hipMemcpy(density, d_density, n * 4, hipMemcpyDeviceToHost)))
-      break;
-    rc = 0;
-  } while (0);
-  if (rc) set_error(std::string("Atmosphere tables on the device: ") + hipGetErrorString(first));
-  (void)hipFree(d_colors);
-  (void)hipFree(d_density);
+  const int rc = [&] {
+    const char* const what = "Atmosphere tables on the device";
+    if (const hipError_t e = hipSetDevice(device)) return hip_error(what, e);
+    DeviceBuffer<float> d_colors, d_density;
+    if (d_colors.alloc(grid * 3, what) || d_density.alloc(n, what)) return -1;
+    hipLaunchKernelGGL(atmosphere_table_kernel, dim3(unsigned((grid + 255) / 256)), dim3(256), 0, 0, ld3(sun_dir), w, h, d_colors.get(), d_density.get());
+    if (hip_launch_check(what) || d_colors.download(colors, grid * 3, what) || d_density.download(density, n, what)) return -1;
+    return 0;
+  }();
   (void)hipSetDevice(keep);
   return rc;
 }
@@ -77,59 +73,43 @@ static int device_build(std::vector<BuildPrim>& prims, const std::vector<BuildTa
   }
   if (hipSetDevice(device) != hipSuccess) return -1;
   const size_t n = prims.size();
-  BuildPrim *d_prims = nullptr, *d_scratch = nullptr;
-  BuildTask *d_tasks[2] = {nullptr, nullptr};
-  BuildDecision* d_dec = nullptr;
-  int *d_rank = nullptr, *d_perm = nullptr, *d_src = nullptr, *d_counts = nullptr;
-  unsigned char* d_pred = nullptr;
-  DNode* d_nodes = nullptr;
-  DBvh* d_bvhs = nullptr;
-  int rc = -1;
-  auto ok = [](hipError_t e) { return e == hipSuccess; };
-  do {
-    const size_t max_tasks = std::max<size_t>(n, roots.size()) + 2;
-    if (!ok(hipMalloc((void**)&d_prims, n * sizeof(BuildPrim))) || !ok(hipMalloc((void**)&d_scratch, n * sizeof(BuildPrim))) ||
-        !ok(hipMalloc((void**)&d_tasks[0], max_tasks * sizeof(BuildTask))) || !ok(hipMalloc((void**)&d_tasks[1], max_tasks * sizeof(BuildTask))) ||
-        !ok(hipMalloc((void**)&d_dec, max_tasks * sizeof(BuildDecision))) || !ok(hipMalloc((void**)&d_rank, max_tasks * sizeof(int))) ||
-        !ok(hipMalloc((void**)&d_perm, n * sizeof(int))) || !ok(hipMalloc((void**)&d_src, n * sizeof(int))) || !ok(hipMalloc((void**)&d_pred, n)) || !ok(hipMalloc((void**)&d_nodes, (n + 1) * sizeof(DNode))) ||
-        !ok(hipMalloc((void**)&d_bvhs, A.bvhs.size() * sizeof(DBvh))) || !ok(hipMalloc((void**)&d_counts, 4 * sizeof(int))))
-      break;
-    if (!ok(hipMemcpy(d_prims, prims.data(), n * sizeof(BuildPrim), hipMemcpyHostToDevice)) ||
-        !ok(hipMemcpy(d_tasks[0], roots.data(), roots.size() * sizeof(BuildTask), hipMemcpyHostToDevice)) ||
-        !ok(hipMemcpy(d_bvhs, A.bvhs.data(), A.bvhs.size() * sizeof(DBvh), hipMemcpyHostToDevice)))
-      break;
-    int counts[4] = {0, 0, 0, 0};  // nodes so far | tasks of the next level | largest range of the next level
-    int ntasks = int(roots.size()), node_base = 0, max_n = 0;
-    for (const BuildTask& t : roots) max_n = std::max(max_n, t.end - t.begin);
-    if (!ok(hipFuncSetAttribute((const void*)bvh_split_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kBuildLdsPrims * 9 + 16))) break;
-    bool failed = false;
-    for (int cur = 0; ntasks > 0; cur ^= 1) {
-      if (!ok(hipMemcpy(d_counts, counts, sizeof counts, hipMemcpyHostToDevice))) { failed = true; break; }
-      hipLaunchKernelGGL(bvh_decide_kernel, dim3(ntasks), dim3(kBuildWave), 0, 0, d_prims, d_tasks[cur], ntasks, d_dec);
-      hipLaunchKernelGGL(bvh_scan_kernel, dim3(1), dim3(1024), 0, 0, d_tasks[cur], ntasks, d_dec, d_rank, d_nodes, d_bvhs, d_counts);
-      const int lds_prims = std::min(max_n, kBuildLdsPrims);
-      hipLaunchKernelGGL(bvh_split_kernel, dim3(ntasks), dim3(kSplitBlock), size_t(lds_prims) * 8 + ((size_t(lds_prims) + 15) & ~size_t(15)), 0, d_prims, d_scratch,
-                         d_tasks[cur], ntasks, d_dec, d_rank, node_base, d_nodes, d_tasks[cur ^ 1], d_perm, d_src, d_pred, lds_prims, d_counts + 2);
-      if (!ok(hipGetLastError()) || !ok(hipMemcpy(counts, d_counts, sizeof counts, hipMemcpyDeviceToHost))) { failed = true; break; }
-      node_base = counts[0];
-      ntasks = counts[1];
-      max_n = counts[2];
-      counts[1] = counts[2] = 0;
-      if (size_t(node_base) > n || size_t(ntasks) > max_tasks) { failed = true; break; }  // (cannot happen: a binary tree over n leaves)
-    }
-    if (failed) break;
-    A.nodes.resize(size_t(node_base));
-    if (node_base && !ok(hipMemcpy(A.nodes.data(), d_nodes, size_t(node_base) * sizeof(DNode), hipMemcpyDeviceToHost))) break;
-    if (!ok(hipMemcpy(prims.data(), d_prims, n * sizeof(BuildPrim), hipMemcpyDeviceToHost)) ||
-        !ok(hipMemcpy(A.bvhs.data(), d_bvhs, A.bvhs.size() * sizeof(DBvh), hipMemcpyDeviceToHost)))
-      break;
-    rc = 0;
-  } while (0);
-  (void)hipGetLastError();
-  for (void* q : {(void*)d_prims, (void*)d_scratch, (void*)d_tasks[0], (void*)d_tasks[1], (void*)d_dec, (void*)d_rank, (void*)d_perm, (void*)d_src, (void*)d_pred,
-                  (void*)d_nodes, (void*)d_bvhs, (void*)d_counts})
-    if (q) (void)hipFree(q);
-  return rc;
+  // (every failure is silent -- no error text: the host build takes over)
+  const size_t max_tasks = std::max<size_t>(n, roots.size()) + 2;
+  DeviceBuffer<BuildPrim> d_prims, d_scratch;
+  DeviceBuffer<BuildTask> d_tasks[2];
+  DeviceBuffer<BuildDecision> d_dec;
+  DeviceBuffer<int> d_rank, d_perm, d_src, d_counts;
+  DeviceBuffer<unsigned char> d_pred;
+  DeviceBuffer<DNode> d_nodes;
+  DeviceBuffer<DBvh> d_bvhs;
+  if (d_prims.upload(prims, nullptr) || d_scratch.alloc(n, nullptr) || d_tasks[0].alloc(max_tasks, nullptr) || d_tasks[0].write(roots.data(), roots.size(), nullptr) ||
+      d_tasks[1].alloc(max_tasks, nullptr) || d_dec.alloc(max_tasks, nullptr) || d_rank.alloc(max_tasks, nullptr) || d_perm.alloc(n, nullptr) ||
+      d_src.alloc(n, nullptr) || d_pred.alloc(n, nullptr) || d_nodes.alloc(n + 1, nullptr) || d_bvhs.upload(A.bvhs, nullptr) || d_counts.alloc(4, nullptr))
+    return -1;
+  int counts[4] = {0, 0, 0, 0};  // nodes so far | tasks of the next level | largest range of the next level
+  int ntasks = int(roots.size()), node_base = 0, max_n = 0;
+  for (const BuildTask& t : roots) max_n = std::max(max_n, t.end - t.begin);
+  if (const hipError_t e = hipFuncSetAttribute((const void*)bvh_split_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kBuildLdsPrims * 9 + 16))
+    return hip_error(nullptr, e);
+  for (int cur = 0; ntasks > 0; cur ^= 1) {
+    if (d_counts.write(counts, 4, nullptr)) return -1;
+    hipLaunchKernelGGL(bvh_decide_kernel, dim3(ntasks), dim3(kBuildWave), 0, 0, d_prims.get(), d_tasks[cur].get(), ntasks, d_dec.get());
+    hipLaunchKernelGGL(bvh_scan_kernel, dim3(1), dim3(1024), 0, 0, d_tasks[cur].get(), ntasks, d_dec.get(), d_rank.get(), d_nodes.get(), d_bvhs.get(), d_counts.get());
+    const int lds_prims = std::min(max_n, kBuildLdsPrims);
+    hipLaunchKernelGGL(bvh_split_kernel, dim3(ntasks), dim3(kSplitBlock), size_t(lds_prims) * 8 + ((size_t(lds_prims) + 15) & ~size_t(15)), 0, d_prims.get(), d_scratch.get(),
+                       d_tasks[cur].get(), ntasks, d_dec.get(), d_rank.get(), node_base, d_nodes.get(), d_tasks[cur ^ 1].get(), d_perm.get(), d_src.get(), d_pred.get(), lds_prims,
+                       d_counts.get() + 2);
+    if (hip_launch_check(nullptr) || d_counts.download(counts, 4, nullptr)) return -1;
+    node_base = counts[0];
+    ntasks = counts[1];
+    max_n = counts[2];
+    counts[1] = counts[2] = 0;
+    if (size_t(node_base) > n || size_t(ntasks) > max_tasks) return -1;  // (cannot happen: a binary tree over n leaves)
+  }
+  A.nodes.resize(size_t(node_base));
+  if (d_nodes.download(A.nodes.data(), size_t(node_base), nullptr) || d_prims.download(prims.data(), n, nullptr) || d_bvhs.download(A.bvhs.data(), A.bvhs.size(), nullptr))
+    return -1;
+  return 0;
 }
 static const bool g_device_builder_installed = (g_device_builder = &device_build, true);
 
@@ -534,6 +514,36 @@ static int plan_check_counters(const Counters& c) {
   return -1;
 }
 
+// The launch side of a one-shot render (create, launch, download, destroy), which the path and the AO render share: a film from
+// the pool, `run(film, bytes)` -- launches, downloads, checks; 0, PINE_GPU_RENDER_STOPPED or -1 -- while get_progress() follows
+// the plan's progress word over `total_items`, the error kept across the cleanup.  After a failure a launch may still be
+// running: nothing of it may touch a block the pool hands out again, so the device is synchronised before any goes back.
+template <class Run>
+static int one_shot_render(pine_gpu_plan* plan, unsigned long long total_items, Run run) {
+  PlanOwner p(plan);
+  int rc = -1;
+  std::string keep;
+  {
+    DeviceBuffer<float4> film(kFromPool);
+    if (film.alloc(size_t(p->film_w) * p->film_h, "one-shot render: the film") == 0) {
+      g_progress_total.store(total_items);
+      g_progress_base.store(0);
+      g_progress_src.store(p->h_progress.get());
+      rc = run(film.get(), size_t(p->film_w) * p->film_h * sizeof(float4));
+    }
+    g_progress_src.store(nullptr);
+    g_progress_base.store(0);
+    g_progress.store(rc == 0 ? 1.0f : 0.0f);
+    if (rc < 0) {
+      keep = pine_gpu_last_error();
+      (void)hipDeviceSynchronize();
+    }
+  }
+  p.reset();
+  if (rc < 0) set_error(keep);
+  return rc;
+}
+
 extern "C" {
 
 float pine_gpu_progress(void) {
@@ -594,33 +604,9 @@ void pine_gpu_plan_destroy(pine_gpu_plan* p) {
     p->spec_job.reset();
   }
   (void)hipSetDevice(p->device);
-  // the plan's buffers go back to the pool, which hands them to the next plan without the device-wide synchronisation hipFree
-  // implies: the plan's last launch must have finished first
+  // the plan's buffers go back to the pool (its members' destructors), which hands them to the next plan without the device-wide
+  // synchronisation hipFree implies: the plan's last launch must have finished first
   if (p->launched) (void)hipStreamSynchronize(p->last_stream);
-  DevicePool::get().free(p->d_blob);
-  DevicePool::get().free(p->d_tri);
-  DevicePool::get().free(p->d_tri_leaf);
-  DevicePool::get().free(p->d_tri_packets);
-  DevicePool::get().free(p->d_halton);
-  DevicePool::get().free(p->d_tri_attrs);
-  DevicePool::get().free(p->d_env);
-  DevicePool::get().free(p->d_tables);
-  DevicePool::get().free(p->d_ctxg);
-  DevicePool::get().free(p->d_ckpt);
-  if (p->ckpt_done) (void)hipEventDestroy(p->ckpt_done);
-  DevicePool::get().free(p->d_tile_order);
-  DevicePool::get().free(p->d_vertex_log);
-  DevicePool::get().free(p->d_samples);
-  DevicePool::get().free(p->d_sum);
-  DevicePool::get().free(p->d_rng_carry);
-  DevicePool::get().free(p->d_fold);
-  DevicePool::get().free(p->d_counters);
-  DevicePool::get().free(p->d_ao_counts);
-  p->spec_loaded.reset();  // (the module stays loaded while the process-wide table or another plan holds it)
-  if (p->h_progress) (void)hipHostFree(p->h_progress);
-  for (auto& slot : p->ev)
-    for (auto& e : slot)
-      if (e) (void)hipEventDestroy(e);
   delete p;
 }
 
@@ -899,29 +885,27 @@ static int assemble_scene(pine_gpu_plan* p, SceneHost& H, const pine_gpu_render_
   }
   S.blob_bytes = int(blob.size());
   if (order_embree && !table_in_lds) S.off_rcpps = put(kRcppsTable, sizeof(kRcppsTable));
-  HIP_OK(POOL_ALLOC(p->d_blob, blob.size()));
-  HIP_OK(hipMemcpy(p->d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice));
-  if (upload(p->d_tri, A.tri_verts)) return -1;
-  if (upload(p->d_tri_leaf, A.tri_leaf)) return -1;
+  const char* const what = "plan creation: the scene's records";
+  if (p->d_blob.alloc(blob.size(), what) || p->d_blob.write(blob.data(), blob.size(), what)) return -1;
+  if (p->d_tri.upload(A.tri_verts, what) || p->d_tri_leaf.upload(A.tri_leaf, what)) return -1;
   std::vector<uint32_t> tri_packets;
   int tri_packet_entries = 0, tri_packet_verts = 0;
   if (build_tri_packets(A, tri_packets, tri_packet_entries, tri_packet_verts)) {
-    HIP_OK(POOL_ALLOC(p->d_tri_packets, tri_packets.size() * 4));
-    HIP_OK(hipMemcpy(p->d_tri_packets, tri_packets.data(), tri_packets.size() * 4, hipMemcpyHostToDevice));
+    if (p->d_tri_packets.upload(tri_packets, what)) return -1;
   }
   sp.tri_packet_bytes = tri_packets.size() * 4;
-  if (upload(p->d_tri_attrs, A.tri_attrs)) return -1;
+  if (p->d_tri_attrs.upload(A.tri_attrs, what)) return -1;
   S.env = nullptr;
   if (H.has_env && (H.env.kind == LIGHT_IMAGE_SKY || H.env.kind == LIGHT_ATMOSPHERE)) {
     if (!env_image_valid(H.env, H.env_words)) {
       set_error("internal: inconsistent environment light buffer");
       return -1;
     }
-    if (upload(p->d_env, H.env_words)) return -1;
+    if (p->d_env.upload(H.env_words, what)) return -1;
     S.env = p->d_env;
   }
 
-  S.blob = reinterpret_cast<const uint4*>(p->d_blob);
+  S.blob = reinterpret_cast<const uint4*>(p->d_blob.get());
   S.nodes = reinterpret_cast<const DNode*>(p->d_blob + S.off_nodes);
   S.shapes = reinterpret_cast<const DShape*>(p->d_blob + S.off_shapes);
   S.materials = reinterpret_cast<const DMaterial*>(p->d_blob + S.off_materials);
@@ -929,8 +913,8 @@ static int assemble_scene(pine_gpu_plan* p, SceneHost& H, const pine_gpu_render_
   S.leaf = reinterpret_cast<const DShape*>(p->d_blob + S.off_leaf) - S.top_prim_begin;
   S.lights = reinterpret_cast<const DLight*>(p->d_blob + S.off_lights);
   S.node_ops = reinterpret_cast<const DNodeOp*>(p->d_blob + S.off_node_ops);
-  S.tri_verts = p->d_tri, S.tri_leaf = reinterpret_cast<const float4*>(p->d_tri_leaf), S.tri_attrs = p->d_tri_attrs;
-  S.tri_packets = p->d_tri_packets, S.tri_packet_entries = tri_packet_entries, S.tri_packet_verts = tri_packet_verts;
+  S.tri_verts = p->d_tri, S.tri_leaf = reinterpret_cast<const float4*>(p->d_tri_leaf.get()), S.tri_attrs = p->d_tri_attrs;
+  S.tri_packets = reinterpret_cast<const uint4*>(p->d_tri_packets.get()), S.tri_packet_entries = tri_packet_entries, S.tri_packet_verts = tri_packet_verts;
   S.lds_nodes = 0, S.lds_tris = 0;
   S.num_lights = int(sp.lights.size()), S.env_light = H.has_env ? int(sp.lights.size()) - 1 : -1, S.num_shapes = int(shapes.size());
   S.cam = H.camera;
@@ -956,11 +940,8 @@ static int upload_sampler_tables(pine_gpu_plan* p, const std::vector<uint8_t>& t
   if (sobol) k = 0;  // (SobolSampler reads no table; any variant keeps the BlueSampler window loads in bounds)
   // device layout: sobolT 64 KiB | scramble 128 KiB | rank 128 KiB | 64 bytes = rank[0..63] again, so
   // a pixel's 40 consecutive ranking bytes never need the reference's modulo wrap
-  HIP_OK(POOL_ALLOC(p->d_tables, 65536 + 262144 + 64));
-  {
-    const std::vector<uint8_t> st = transposed_sobol(tables);
-    HIP_OK(hipMemcpy(p->d_tables, st.data(), 65536, hipMemcpyHostToDevice));
-  }
+  const char* const what = "plan creation: the sampler's tables";
+  if (p->d_tables.alloc(65536 + 262144 + 64, what) || p->d_tables.write(transposed_sobol(tables).data(), 65536, what)) return -1;
   HIP_OK(hipMemcpy(p->d_tables + 65536, tables.data() + 65536 + size_t(k) * 262144, 262144, hipMemcpyHostToDevice));
   HIP_OK(hipMemcpy(p->d_tables + 65536 + 262144, tables.data() + 65536 + size_t(k) * 262144 + 131072, 64,
                    hipMemcpyHostToDevice));
@@ -973,10 +954,10 @@ static int upload_sampler_tables(pine_gpu_plan* p, const std::vector<uint8_t>& t
   if (halton) {
     const HaltonHostTables& ht = halton_host_tables();
     const size_t head = size_t(2 * kHaltonDims) * sizeof(int), bytes = head + ht.perms.size() * sizeof(uint16_t);
-    HIP_OK(POOL_ALLOC(p->d_halton, bytes));
+    if (p->d_halton.alloc(bytes, what)) return -1;
     HIP_OK(hipMemcpy(p->d_halton, ht.primes_and_sums.data(), head, hipMemcpyHostToDevice));
     HIP_OK(hipMemcpy(p->d_halton + head, ht.perms.data(), ht.perms.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-    T.halton_primes = reinterpret_cast<const int*>(p->d_halton), T.halton_perms = reinterpret_cast<const uint16_t*>(p->d_halton + head);
+    T.halton_primes = reinterpret_cast<const int*>(p->d_halton.get()), T.halton_perms = reinterpret_cast<const uint16_t*>(p->d_halton + head);
   }
   sobol_sampler_params(T, spp, p->S.cam.W, p->S.cam.H);
   return 0;
@@ -1412,11 +1393,12 @@ static void schedule_params(pine_gpu_plan* p, const FlatAccel& A, const pine_gpu
 
 // The launch shape (grid, work-item claims) and every buffer the launches use.
 static int size_and_allocate(pine_gpu_plan* p, const pine_gpu_render_params* prm, int spp, const PlanKnobs& K) {
+  const char* const what = "plan creation: the launch buffers";
   WorkParams& W = p->W;
   if (prm->flags & PINE_GPU_FLAG_PROGRESS) {
-    HIP_OK(hipHostMalloc((void**)&p->h_progress, sizeof(unsigned long long), hipHostMallocMapped));
-    *p->h_progress = 0;
-    HIP_OK(hipHostGetDevicePointer((void**)&W.progress, p->h_progress, 0));
+    if (alloc_pinned(p->h_progress, 1, hipHostMallocMapped, "plan creation: the progress word")) return -1;
+    p->h_progress[0] = 0;
+    HIP_OK(hipHostGetDevicePointer((void**)&W.progress, p->h_progress.get(), 0));
   }
   hipDeviceProp_t prop;
   HIP_OK(hipGetDeviceProperties(&prop, prm->device));
@@ -1473,38 +1455,38 @@ static int size_and_allocate(pine_gpu_plan* p, const pine_gpu_render_params* prm
 
   if (W.items_per_pixel > 1) {
     p->bytes_ckpt = (size_t)(W.num_local_tiles - W.serial_tiles) * ckpt_chunks * 64 * sizeof(ulonglong2);
-    HIP_OK(POOL_ALLOC(p->d_ckpt, p->bytes_ckpt));
+    if (p->d_ckpt.alloc(p->bytes_ckpt / sizeof(ulonglong2), what)) return -1;
     if (PP.n > 1) {
       p->bytes_carry = (size_t)PP.free_tiles * 64 * sizeof(ulonglong2);
-      HIP_OK(POOL_ALLOC(p->d_rng_carry, p->bytes_carry));
+      if (p->d_rng_carry.alloc((size_t)PP.free_tiles * 64, what)) return -1;
     }
   }
   if (PP.n > 1) {
-    HIP_OK(POOL_ALLOC(p->d_sum, (size_t)W.num_local_tiles * 64 * sizeof(float4)));
+    if (p->d_sum.alloc((size_t)W.num_local_tiles * 64, what)) return -1;
     p->bytes_carry += (size_t)W.num_local_tiles * 64 * sizeof(float4);
   }
   p->ckpt_every_launch = K.ckpt_every_launch;
   if (!p->tile_order.empty()) {
-    HIP_OK(POOL_ALLOC(p->d_tile_order, p->tile_order.size() * sizeof(int)));
-    HIP_OK(hipMemcpy(p->d_tile_order, p->tile_order.data(), p->tile_order.size() * sizeof(int), hipMemcpyHostToDevice));
+    if (p->d_tile_order.upload(p->tile_order, what)) return -1;
     W.tile_order = p->d_tile_order;
   }
   p->bytes_samples = size_t(sample_rows) * 64 * sizeof(float4);
-  HIP_OK(POOL_ALLOC(p->d_samples, p->bytes_samples));
+  if (p->d_samples.alloc(size_t(sample_rows) * 64, what)) return -1;
   const size_t fold_slots = size_t(p->grid) * kernel.ctx;
-  HIP_OK(POOL_ALLOC(p->d_fold, size_t(prm->max_path_length) * 8 * fold_slots * sizeof(float)));
+  if (p->d_fold.alloc(size_t(prm->max_path_length) * 8 * fold_slots, what)) return -1;
   if (kernel.queued()) {
     // per-context records, then (Subsurface variants) every workgroup's ring of sample-token slots
     const size_t token_dwords = (kernel.features & F_SSS) ? size_t(p->grid) * (kernel.ctx <= 1024 ? 1024 : 2048) * kQTokenDwords : 0;
-    HIP_OK(POOL_ALLOC(p->d_ctxg, (size_t(p->grid) * kernel.ctx * q_ctx_global_dwords(kernel.features) + token_dwords) * sizeof(uint32_t)));
+    if (p->d_ctxg.alloc(size_t(p->grid) * kernel.ctx * q_ctx_global_dwords(kernel.features) + token_dwords, what)) return -1;
   }
   // (the owned tiles' done marks sit behind the counters: one clear for both)
-  HIP_OK(POOL_ALLOC(p->d_counters, sizeof(Counters) + (W.owned_tiles > 0 ? size_t(W.num_local_tiles) * sizeof(unsigned) : 0)));
+  if (p->d_counters.alloc_bytes(sizeof(Counters) + (W.owned_tiles > 0 ? size_t(W.num_local_tiles) * sizeof(unsigned) : 0), what)) return -1;
   W.tile_done = W.owned_tiles > 0 ? reinterpret_cast<unsigned*>(p->d_counters + 1) : nullptr;
   p->timed = (prm->flags & PINE_GPU_FLAG_TIMING) != 0;
   if (p->timed)
     for (auto& slot : p->ev)
-      for (auto& e : slot) HIP_OK(hipEventCreate(&e));
+      for (auto& e : slot)
+        if (create_event(e, hipEventDefault, "plan creation: the timing events")) return -1;
   return 0;
 }
 
@@ -1577,10 +1559,13 @@ pine_gpu_plan* pine_gpu_plan_create_passes(pine_gpu_scene* scene, const pine_gpu
 // to `samples` (+ sample index * 64, decode_item).
 static int launch_path_kernel(pine_gpu_plan* p, WorkParams& W, float4* samples, int grid, hipStream_t stream) {
   const ulonglong2* ckpt = p->d_ckpt;
+  float* fold = p->d_fold;
+  uint32_t* ctxg = p->d_ctxg;
+  Counters* counters = p->d_counters;
   const PathKernel kernel = plan_kernel(p);
   // (the kernels of the other translation units: same argument layout, launched untyped; the megakernel has no context records)
-  void* queue_args[] = {&p->S, &W, &ckpt, &samples, &p->d_fold, &p->d_ctxg, &p->d_counters};
-  void* mega_args[] = {&p->S, &W, &ckpt, &samples, &p->d_fold, &p->d_counters};
+  void* queue_args[] = {&p->S, &W, &ckpt, &samples, &fold, &ctxg, &counters};
+  void* mega_args[] = {&p->S, &W, &ckpt, &samples, &fold, &counters};
   if (p->spec_fn)
     HIP_OK(hipModuleLaunchKernel(p->spec_fn, unsigned(grid), 1, 1, kQBlock, 1, 1, unsigned(p->lds_bytes), stream, queue_args, nullptr));
   else
@@ -1616,8 +1601,8 @@ static int plan_launch_pass(pine_gpu_plan* p, int j, void* film_dev, hipStream_t
   W.film = (float4*)film_dev;
   W.film_packed = packed ? 1 : 0;
   static_assert(offsetof(Counters, next_item) == 0, "the per-pass reset clears next_item");
-  hipEvent_t* ev = p->ev[p->launch_count % pine_gpu_plan::kEvRing];
-  if (p->timed) HIP_OK(hipEventRecord(ev[0], stream));
+  const EventOwner* ev = p->ev[p->launch_count % pine_gpu_plan::kEvRing];
+  if (p->timed) HIP_OK(hipEventRecord(ev[0].get(), stream));
   // (a shard can own no tile at all -- more ranks than 8x8 tiles: nothing to launch, the film / slab stays zero)
   const bool has_work = W.total_items > 0;
   if (has_work && p->W.items_per_pixel > 1 && PP.free_tiles > 0) {
@@ -1627,16 +1612,16 @@ static int plan_launch_pass(pine_gpu_plan* p, int j, void* film_dev, hipStream_t
       hipLaunchKernelGGL(rng_checkpoint_kernel, dim3(unsigned((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, W, p->film_w, p->film_h,
                          spp, p->d_ckpt, PP.free_tiles, p->d_rng_carry);
       if (PP.n == 1) {
-        if (!p->ckpt_done) HIP_OK(hipEventCreateWithFlags(&p->ckpt_done, hipEventDisableTiming));
-        HIP_OK(hipEventRecord(p->ckpt_done, stream));
+        if (!p->ckpt_done && create_event(p->ckpt_done, hipEventDisableTiming, "launch: the checkpoint event")) return -1;
+        HIP_OK(hipEventRecord(p->ckpt_done.get(), stream));
         p->ckpt_stream = stream;
         p->ckpt_valid = true;
       }
     } else if (stream != p->ckpt_stream) {
-      HIP_OK(hipStreamWaitEvent(stream, p->ckpt_done, 0));
+      HIP_OK(hipStreamWaitEvent(stream, p->ckpt_done.get(), 0));
     }
   }
-  if (p->timed) HIP_OK(hipEventRecord(ev[1], stream));
+  if (p->timed) HIP_OK(hipEventRecord(ev[1].get(), stream));
   if (has_work) {
     // (the largest pass fills p->grid: the only pass of a plan of one)
     const int ctx = plan_kernel(p).ctx;
@@ -1645,7 +1630,7 @@ static int plan_launch_pass(pine_gpu_plan* p, int j, void* film_dev, hipStream_t
     float4* const samples = p->d_samples - size_t(W.pass_first_chunk) * size_t(W.samples_per_item) * 64u;
     if (launch_path_kernel(p, W, samples, grid, stream)) return -1;
   }
-  if (p->timed) HIP_OK(hipEventRecord(ev[2], stream));
+  if (p->timed) HIP_OK(hipEventRecord(ev[2].get(), stream));
   if (p->W.num_local_tiles > 0) {
     ResolvePass R;
     R.film_w = p->film_w, R.film_h = p->film_h, R.spp = spp;
@@ -1656,7 +1641,7 @@ static int plan_launch_pass(pine_gpu_plan* p, int j, void* film_dev, hipStream_t
     hipLaunchKernelGGL(resolve_kernel, dim3(unsigned((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, p->W, R, p->d_samples, p->d_sum,
                        (float4*)film_dev, p->d_counters);
   }
-  if (p->timed) HIP_OK(hipEventRecord(ev[3], stream));
+  if (p->timed) HIP_OK(hipEventRecord(ev[3].get(), stream));
   HIP_OK(hipGetLastError());
   p->launched = true;
   p->launch_count++;
@@ -1803,11 +1788,11 @@ int pine_gpu_plan_stats_get(pine_gpu_plan* p, pine_gpu_plan_stats* out) {
       if (np > 1) first = p->launch_count - std::min<unsigned long long>({np, p->launch_count, (unsigned long long)pine_gpu_plan::kEvRing});
       double a = 0, b = 0, c3 = 0;
       for (unsigned long long i = first; i < p->launch_count; i++) {
-        hipEvent_t* ev = p->ev[i % pine_gpu_plan::kEvRing];
+        const EventOwner* ev = p->ev[i % pine_gpu_plan::kEvRing];
         float x = 0, y = 0, z = 0;
-        HIP_OK(hipEventElapsedTime(&x, ev[0], ev[1]));
-        HIP_OK(hipEventElapsedTime(&y, ev[1], ev[2]));
-        HIP_OK(hipEventElapsedTime(&z, ev[2], ev[3]));
+        HIP_OK(hipEventElapsedTime(&x, ev[0].get(), ev[1].get()));
+        HIP_OK(hipEventElapsedTime(&y, ev[1].get(), ev[2].get()));
+        HIP_OK(hipEventElapsedTime(&z, ev[2].get(), ev[3].get()));
         a += x, b += y, c3 += z;
       }
       const double n = np > 1 ? double(p->launch_count - first) / double(np) : double(p->launch_count - first);
@@ -1894,7 +1879,7 @@ int64_t pine_gpu_plan_vertex_log(pine_gpu_plan* p, float* out, int64_t capacity)
   }
   HIP_OK(hipSetDevice(p->device));
   if (!out) {  // switch the log on: the NEXT launches fill it
-    if (!p->d_vertex_log) HIP_OK(POOL_ALLOC(p->d_vertex_log, size_t(n) * 4));
+    if (!p->d_vertex_log && p->d_vertex_log.alloc(size_t(n), "pine_gpu_plan_vertex_log")) return -1;
     HIP_OK(hipMemset(p->d_vertex_log, 0, size_t(n) * 4));
     p->W.vertex_log = p->d_vertex_log;
     return n;
@@ -1956,45 +1941,21 @@ int pine_gpu_path_render_passes(pine_gpu_scene* scene, const pine_gpu_render_par
   prm2.flags |= PINE_GPU_FLAG_PROGRESS;  // the reference's CLI polls get_progress() while render() runs (src/cli/pine.cpp:36-40)
   pine_gpu_plan* p = pine_gpu_plan_create_passes(scene, &prm2, pass_samples);
   if (!p) return -1;
-  int rc = -1;
-  void* d_film = nullptr;
-  const size_t bytes = size_t(p->film_w) * p->film_h * 16;
   const int n = p->pass_plan.n;
-  do {
-    if (DevicePool::get().alloc(&d_film, bytes) != hipSuccess) {
-      set_error("hipMalloc(film) failed");
-      break;
-    }
-    // get_progress() over the whole sequence: the items of the passes done + those the running pass has claimed
-    unsigned long long total = 0;
-    for (int j = 0; j < n; j++) total += pass_work(p, j).total_items;
-    g_progress_total.store(total);
-    g_progress_base.store(0);
-    g_progress_src.store(p->h_progress);
-    bool ok = true;
-    for (int j = 0; j < n && ok && rc < 0; j++) {
-      ok = pine_gpu_plan_launch_pass(p, j, d_film, nullptr) == 0;
-      if (ok && hipMemcpy(film_out, d_film, bytes, hipMemcpyDeviceToHost) != hipSuccess) {
-        set_error("film download failed");
-        ok = false;
-      }
-      if (ok) ok = pine_gpu_plan_check(p) == 0;  // a bailed-out path kernel leaves an incomplete film: fail, do not return it as a result
-      if (!ok) break;
-      *p->h_progress = 0;  // (the pass has finished: nothing writes the word until the next launch)
+  // get_progress() over the whole sequence: the items of the passes done + those the running pass has claimed
+  unsigned long long total = 0;
+  for (int j = 0; j < n; j++) total += pass_work(p, j).total_items;
+  return one_shot_render(p, total, [&](float4* d_film, size_t bytes) {
+    for (int j = 0; j < n; j++) {
+      if (pine_gpu_plan_launch_pass(p, j, d_film, nullptr)) return -1;
+      if (const hipError_t e = hipMemcpy(film_out, d_film, bytes, hipMemcpyDeviceToHost)) return hip_error("film download", e);
+      if (pine_gpu_plan_check(p)) return -1;  // a bailed-out path kernel leaves an incomplete film: fail, do not return it as a result
+      p->h_progress[0] = 0;  // (the pass has finished: nothing writes the word until the next launch)
       g_progress_base.fetch_add(pass_work(p, j).total_items);
-      if (cb && cb(user, j, n, film_out) != 0) rc = PINE_GPU_RENDER_STOPPED;
+      if (cb && cb(user, j, n, film_out) != 0) return PINE_GPU_RENDER_STOPPED;
     }
-    if (ok && rc < 0) rc = 0;
-  } while (0);
-  g_progress_src.store(nullptr);
-  g_progress_base.store(0);
-  g_progress.store(rc == 0 ? 1.0f : 0.0f);
-  std::string keep = rc < 0 ? pine_gpu_last_error() : "";
-  if (rc < 0) (void)hipDeviceSynchronize();  // (a failed launch may still be running: nothing of it may touch a block the pool hands out again)
-  DevicePool::get().free(d_film);
-  pine_gpu_plan_destroy(p);
-  if (rc < 0) set_error(keep);
-  return rc;
+    return 0;
+  });
 }
 
 int pine_gpu_path_render(pine_gpu_scene* scene, const pine_gpu_render_params* prm, float* film_out) {
@@ -2029,84 +1990,60 @@ int pine_gpu_path_render_devices(pine_gpu_scene* scene, const pine_gpu_render_pa
       set_error("device ordinal out of range");
       return -1;
     }
-  std::vector<pine_gpu_plan*> plans(size_t(num_devices), nullptr);
-  std::vector<void*> slabs(size_t(num_devices), nullptr);
-  std::vector<hipStream_t> streams(size_t(num_devices), nullptr);
-  void *gathered = nullptr, *d_film = nullptr;
   int rc = -1;
-  std::string err;
-  do {
-    bool ok = true;
-    for (int r = 0; r < num_devices && ok; r++) {
-      pine_gpu_render_params p = *prm;
-      p.device = devices[r];
-      p.shard_rank = r;
-      p.shard_world = num_devices;
-      plans[size_t(r)] = pine_gpu_plan_create(scene, &p);
-      ok = plans[size_t(r)] != nullptr;
-    }
-    if (!ok) break;
-    const int w = plans[0]->film_w, h = plans[0]->film_h;
-    const int64_t slab_floats = pine_gpu_packed_slab_floats(w, h, num_devices);
-    const size_t slab_bytes = size_t(slab_floats) * 4, film_bytes = size_t(w) * h * 16;
-    if (hipSetDevice(devices[0]) != hipSuccess || hipMalloc(&gathered, slab_bytes * size_t(num_devices)) != hipSuccess ||
-        hipMalloc(&d_film, film_bytes) != hipSuccess) {
-      set_error("device allocation failed");
-      break;
-    }
-    for (int r = 0; r < num_devices && ok; r++) {
-      ok = hipSetDevice(devices[r]) == hipSuccess && hipStreamCreateWithFlags(&streams[size_t(r)], hipStreamNonBlocking) == hipSuccess &&
-           hipMalloc(&slabs[size_t(r)], slab_bytes) == hipSuccess;
-      if (ok && devices[r] != devices[0]) {
-        int can = 0;
-        (void)hipDeviceCanAccessPeer(&can, devices[r], devices[0]);
-        if (can) (void)hipDeviceEnablePeerAccess(devices[0], 0);  // (already enabled is fine; without peer access the copy is staged)
-        (void)hipGetLastError();
+  std::string keep;
+  {
+    // (destroyed in reverse: the plans first -- each waits for its stream, the slab copy on it included -- then slabs and streams)
+    DeviceBuffer<char> gathered, d_film;
+    std::vector<StreamOwner> streams(static_cast<size_t>(num_devices));
+    std::vector<DeviceBuffer<char>> slabs(static_cast<size_t>(num_devices));
+    std::vector<PlanOwner> plans(static_cast<size_t>(num_devices));
+    rc = [&]() -> int {
+      for (int r = 0; r < num_devices; r++) {
+        pine_gpu_render_params p = *prm;
+        p.device = devices[r];
+        p.shard_rank = r;
+        p.shard_world = num_devices;
+        plans[size_t(r)].reset(pine_gpu_plan_create(scene, &p));
+        if (!plans[size_t(r)]) return -1;
       }
-    }
-    if (!ok) {
-      set_error("per-device setup failed");
-      break;
-    }
-    // all devices render concurrently; each slab goes to devices[0] on the rendering device's own stream as soon as it is ready
-    for (int r = 0; r < num_devices && ok; r++) {
-      char* dst = static_cast<char*>(gathered) + size_t(r) * slab_bytes;
-      ok = pine_gpu_plan_launch_packed(plans[size_t(r)], slabs[size_t(r)], streams[size_t(r)]) == 0;
-      if (!ok) break;
-      // (a peer copy between a device and itself is refused: "invalid device ordinal")
-      const hipError_t e = devices[r] == devices[0]
-                               ? hipMemcpyAsync(dst, slabs[size_t(r)], slab_bytes, hipMemcpyDeviceToDevice, streams[size_t(r)])
-                               : hipMemcpyPeerAsync(dst, devices[0], slabs[size_t(r)], devices[r], slab_bytes, streams[size_t(r)]);
-      if (e != hipSuccess) {
-        (void)hipGetLastError();
-        set_error(std::string("slab copy to the first device failed: ") + hipGetErrorString(e));
-        err = "copy";
-        ok = false;
+      const int w = plans[0]->film_w, h = plans[0]->film_h;
+      const int64_t slab_floats = pine_gpu_packed_slab_floats(w, h, num_devices);
+      const size_t slab_bytes = size_t(slab_floats) * 4, film_bytes = size_t(w) * h * 16;
+      if (const hipError_t e = hipSetDevice(devices[0])) return hip_error("device allocation", e);
+      if (gathered.alloc(slab_bytes * size_t(num_devices), "device allocation") || d_film.alloc(film_bytes, "device allocation")) return -1;
+      for (int r = 0; r < num_devices; r++) {
+        if (const hipError_t e = hipSetDevice(devices[r])) return hip_error("per-device setup", e);
+        if (create_stream(streams[size_t(r)], hipStreamNonBlocking, "per-device setup") || slabs[size_t(r)].alloc(slab_bytes, "per-device setup")) return -1;
+        if (devices[r] != devices[0]) {
+          int can = 0;
+          (void)hipDeviceCanAccessPeer(&can, devices[r], devices[0]);
+          if (can) (void)hipDeviceEnablePeerAccess(devices[0], 0);  // (already enabled is fine; without peer access the copy is staged)
+          (void)hipGetLastError();
+        }
       }
-    }
-    if (!ok) {
-      if (err.empty()) set_error(std::string("launch failed: ") + pine_gpu_last_error());
-      break;
-    }
-    for (int r = 0; r < num_devices && ok; r++) ok = pine_gpu_plan_check(plans[size_t(r)]) == 0;  // waits for the stream, reports bail-outs
-    if (!ok) break;
-    if (pine_gpu_film_unpack(w, h, num_devices, devices[0], gathered, d_film, nullptr)) break;
-    if (hipMemcpy(film_out, d_film, film_bytes, hipMemcpyDeviceToHost) != hipSuccess) {
-      set_error("film download failed");
-      break;
-    }
-    rc = 0;
-  } while (0);
-  const std::string keep = rc ? pine_gpu_last_error() : "";
-  for (int r = 0; r < num_devices; r++) {
-    (void)hipSetDevice(devices[r]);
-    if (plans[size_t(r)]) pine_gpu_plan_destroy(plans[size_t(r)]);
-    if (slabs[size_t(r)]) (void)hipFree(slabs[size_t(r)]);
-    if (streams[size_t(r)]) (void)hipStreamDestroy(streams[size_t(r)]);
+      // all devices render concurrently; each slab goes to devices[0] on the rendering device's own stream as soon as it is ready
+      for (int r = 0; r < num_devices; r++) {
+        char* dst = gathered + size_t(r) * slab_bytes;
+        hipStream_t stream = streams[size_t(r)].get();
+        if (pine_gpu_plan_launch_packed(plans[size_t(r)].get(), slabs[size_t(r)], stream)) {
+          set_error(std::string("launch failed: ") + pine_gpu_last_error());
+          return -1;
+        }
+        // (a peer copy between a device and itself is refused: "invalid device ordinal")
+        const hipError_t e = devices[r] == devices[0] ? hipMemcpyAsync(dst, slabs[size_t(r)], slab_bytes, hipMemcpyDeviceToDevice, stream)
+                                                      : hipMemcpyPeerAsync(dst, devices[0], slabs[size_t(r)], devices[r], slab_bytes, stream);
+        if (e != hipSuccess) return hip_error("slab copy to the first device failed", e);
+      }
+      for (int r = 0; r < num_devices; r++)
+        if (pine_gpu_plan_check(plans[size_t(r)].get())) return -1;  // waits for the stream, reports bail-outs
+      if (pine_gpu_film_unpack(w, h, num_devices, devices[0], gathered, d_film, nullptr)) return -1;
+      if (const hipError_t e = hipMemcpy(film_out, d_film, film_bytes, hipMemcpyDeviceToHost)) return hip_error("film download", e);
+      return 0;
+    }();
+    if (rc) keep = pine_gpu_last_error();
   }
   (void)hipSetDevice(devices[0]);
-  if (gathered) (void)hipFree(gathered);
-  if (d_film) (void)hipFree(d_film);
   if (rc) set_error(keep);
   return rc;
 }

@@ -1,6 +1,8 @@
 // pine_amd/csrc/pine_plan.h -- what the host side of the two kernel translation units shares: the plan record
 // (struct pine_gpu_plan), HIP_OK, the sampler-table loader, the device memory pool and need_device.  Included by
 // pine_kernels.hip (plans, launches) and pine_test_hooks.hip (the device unit-test hooks).
+// Device memory, pinned memory, events and streams are held by the owners of pine_device_buffer.h: a plan owns what its members
+// hold and gives it back when it is deleted, a hook or a builder when it returns.  DeviceScene / WorkParams keep raw views.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -12,6 +14,7 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include <dlfcn.h>
@@ -197,16 +200,10 @@ struct DevicePool {
     (void)hipSetDevice(keep);
   }
 };
-#define POOL_ALLOC(ptr, bytes) DevicePool::get().alloc((void**)&(ptr), (bytes))
+}  // namespace pine_gpu
+#include "pine_device_buffer.h"
+namespace pine_gpu {
 
-template <class T>
-static int upload(T*& dptr, const std::vector<T>& v) {
-  dptr = nullptr;
-  size_t bytes = std::max<size_t>(v.size(), 1) * sizeof(T);
-  HIP_OK(POOL_ALLOC(dptr, bytes));
-  if (!v.empty()) HIP_OK(hipMemcpy(dptr, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-  return 0;
-}
 // The frame table of a scene's shapes (pine_device.h frame_entry): one entry per face of every Rect, AABB and OBB
 // in geometry order, kFrameFloats floats each; base[g] = the first entry of shape g, or -1 for a kind without faces.
 inline void build_frame_table(const std::vector<DShape>& shapes, std::vector<float>& entries, std::vector<int>& base) {
@@ -243,41 +240,41 @@ struct pine_gpu_plan {
   DeviceScene S{};
   WorkParams W{};
   int film_w = 0, film_h = 0;
-  // device buffers
-  char* d_blob = nullptr;  // nodes | shapes | materials | bvhs | prims | lights | frame table
-  float* d_tri = nullptr;
-  float* d_tri_leaf = nullptr;
-  uint4* d_tri_packets = nullptr;
-  uint8_t* d_halton = nullptr;
-  float* d_tri_attrs = nullptr;
-  float* d_env = nullptr;  // ImageSky, Atmosphere: SceneHost::env_words (null: another environment light, or none)
-  uint8_t* d_tables = nullptr;
+  // device buffers: blocks of the pool (the plan's last launch has finished before `delete` gives them back: pine_gpu_plan_destroy)
+  DeviceBuffer<char> d_blob{kFromPool};  // nodes | shapes | materials | bvhs | prims | lights | frame table
+  DeviceBuffer<float> d_tri{kFromPool};
+  DeviceBuffer<float> d_tri_leaf{kFromPool};
+  DeviceBuffer<uint32_t> d_tri_packets{kFromPool};  // (DeviceScene::tri_packets views it as uint4)
+  DeviceBuffer<uint8_t> d_halton{kFromPool};
+  DeviceBuffer<float> d_tri_attrs{kFromPool};
+  DeviceBuffer<float> d_env{kFromPool};  // ImageSky, Atmosphere: SceneHost::env_words (null: another environment light, or none)
+  DeviceBuffer<uint8_t> d_tables{kFromPool};
   int variant = -1;
   int queue_variant = -1;   // >= 0: the stage-queued kernel is used instead of path_trace_kernel
   const PineFastVariant* fast = nullptr;  // PINE_GPU_FLAG_FAST: the declared-tolerance variant that runs instead (pine_kernels_fast.hip)
-  uint32_t* d_ctxg = nullptr;
-  ulonglong2* d_ckpt = nullptr;
+  DeviceBuffer<uint32_t> d_ctxg{kFromPool};
+  DeviceBuffer<ulonglong2> d_ckpt{kFromPool};
   // The RNG checkpoints are a function of the film partition and the sample counts alone: the FIRST launch of a plan of one pass
   // computes them, later launches reuse the table (they wait for `ckpt_done` when they run on another stream).
   // $PINE_GPU_CKPT_EVERY_LAUNCH=1: as before round 4, every launch recomputes it (measurement aid).  A plan of several passes
   // keeps the checkpoints of one pass only: each pass computes its own from the carried states.
   bool ckpt_valid = false, ckpt_every_launch = false;
-  hipEvent_t ckpt_done = nullptr;
+  EventOwner ckpt_done;
   hipStream_t ckpt_stream = nullptr;
-  float* d_vertex_log = nullptr;        // test hook (pine_gpu_plan_vertex_log)
-  int* d_tile_order = nullptr;          // tile classes (WorkParams::tile_order), or null
-  std::vector<int> tile_order;          // ... its host copy (empty: local tile t is film tile t * shard_world + shard_rank)
-  float4* d_samples = nullptr;
+  DeviceBuffer<float> d_vertex_log{kFromPool};  // test hook (pine_gpu_plan_vertex_log)
+  DeviceBuffer<int> d_tile_order{kFromPool};    // tile classes (WorkParams::tile_order), or null
+  std::vector<int> tile_order;                  // ... its host copy (empty: local tile t is film tile t * shard_world + shard_rank)
+  DeviceBuffer<float4> d_samples{kFromPool};
   // Passes: every launch is a pass of pass_plan (pass_plan.n == 1: an ordinary plan, none of the buffers below).  The running sum is
   // one float4 per local pixel ([local tile][pixel in tile], .w unused); the carried RNG states one per pixel of the independent class.
   int pass_samples_req = 0;
   PassPlan pass_plan;
   int next_pass = 0;                        // the pass that may be launched next (0 may always be)
-  float4* d_sum = nullptr;
-  ulonglong2* d_rng_carry = nullptr;
+  DeviceBuffer<float4> d_sum{kFromPool};
+  DeviceBuffer<ulonglong2> d_rng_carry{kFromPool};
   size_t bytes_samples = 0, bytes_ckpt = 0, bytes_carry = 0, bytes_total = 0;
-  float* d_fold = nullptr;
-  Counters* d_counters = nullptr;
+  DeviceBuffer<float> d_fold{kFromPool};
+  DeviceBuffer<Counters> d_counters{kFromPool};
   int grid = 0;
   size_t lds_bytes = 0;
   bool serial_rng = false;
@@ -285,12 +282,12 @@ struct pine_gpu_plan {
   // kEvRing launches: reading them (stats_get) averages over the launches since the previous read,
   // so a timed loop never has to synchronise inside
   static constexpr int kEvRing = 64;
-  hipEvent_t ev[kEvRing][4] = {};
+  EventOwner ev[kEvRing][4];
   unsigned long long launch_count = 0, stats_read_upto = 0;
   bool timed = false;
   bool launched = false;
   hipStream_t last_stream = nullptr;
-  unsigned long long* h_progress = nullptr;  // host-mapped progress word (PINE_GPU_FLAG_PROGRESS)
+  PinnedOwner<unsigned long long> h_progress;  // host-mapped progress word (PINE_GPU_FLAG_PROGRESS)
   float accel_build_ms = 0.0f, upload_ms = 0.0f;  // host-side cost of plan creation (reported by stats_get)
   bool accel_on_device = false;
   // PINE_GPU_FLAG_SPECIALIZE: the queue kernel compiled for this scene (pine_specialize.h); null: the precompiled variant
@@ -313,5 +310,10 @@ struct pine_gpu_plan {
   bool ao = false, ao_serial = false;
   int ao_variant = -1;
   AoParams ao_params{};
-  unsigned* d_ao_counts = nullptr;
+  DeviceBuffer<unsigned> d_ao_counts{kFromPool};
 };
+// A plan held for the length of a call (the one-shot renders, the multi-device render, pine_gpu_test_traverse).
+struct PlanDeleter {
+  void operator()(pine_gpu_plan* p) const { pine_gpu_plan_destroy(p); }
+};
+using PlanOwner = std::unique_ptr<pine_gpu_plan, PlanDeleter>;

@@ -373,75 +373,40 @@ int pine_gpu_plan_test_traverse_baked(pine_gpu_plan* p, const float* rays, int64
   HIP_OK(hipSetDevice(p->device));
   hipFunction_t fn;
   HIP_OK(hipModuleGetFunction(&fn, p->spec_module, "pine_baked_traverse_test"));
-  float* dr = nullptr;
-  unsigned* dout = nullptr;
-  int rc = -1;
-  do {
-    if (hipMalloc((void**)&dr, size_t(nrays) * 32) != hipSuccess || hipMalloc((void**)&dout, size_t(nrays) * 16) != hipSuccess) break;
-    if (hipMemcpy(dr, rays, size_t(nrays) * 32, hipMemcpyHostToDevice) != hipSuccess) break;
-    long long n = nrays;
-    void* args[] = {&dr, &n, &dout};
-    if (hipModuleLaunchKernel(fn, unsigned((nrays + 63) / 64), 1, 1, 64, 1, 1, 0, nullptr, args, nullptr) != hipSuccess) break;
-    if (hipMemcpy(out, dout, size_t(nrays) * 16, hipMemcpyDeviceToHost) != hipSuccess) break;
-    rc = 0;
-  } while (0);
-  if (rc) set_error(std::string("pine_gpu_plan_test_traverse_baked: ") + hipGetErrorString(hipGetLastError()));
-  (void)hipFree(dr);
-  (void)hipFree(dout);
-  return rc;
+  DeviceBuffer<float> dr;
+  DeviceBuffer<unsigned> dout;
+  if (dr.upload(rays, size_t(nrays) * 8, __func__) || dout.alloc(size_t(nrays) * 4, __func__)) return -1;
+  float* rays_dev = dr;
+  unsigned* out_dev = dout;
+  long long n = nrays;
+  void* args[] = {&rays_dev, &n, &out_dev};
+  if (const hipError_t e = hipModuleLaunchKernel(fn, unsigned((nrays + 63) / 64), 1, 1, 64, 1, 1, 0, nullptr, args, nullptr)) return hip_error(__func__, e);
+  return dout.download(out, size_t(nrays) * 4, __func__);
 }
 
 // ---- device unit-test hooks -------------------------------------------------------------------
+// Every hook below reads: validate the arguments, build the inputs, upload them, allocate the outputs, launch, check the launch,
+// download.  Its buffers are locals (pine_device_buffer.h); the first failing HIP call is reported under the hook's own name.
 int pine_gpu_test_sincos(int device, const float* x, int64_t n, float* s, float* c) {
   if (need_device(device)) return -1;
-  float *dx, *ds, *dc;
-  HIP_OK(hipMalloc((void**)&dx, n * 4));
-  HIP_OK(hipMalloc((void**)&ds, n * 4));
-  HIP_OK(hipMalloc((void**)&dc, n * 4));
-  HIP_OK(hipMemcpy(dx, x, n * 4, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(test_sincos_kernel, dim3(unsigned((n + 255) / 256)), dim3(256), 0, 0, dx, (long long)n, ds, dc);
-  HIP_OK(hipMemcpy(s, ds, n * 4, hipMemcpyDeviceToHost));
-  HIP_OK(hipMemcpy(c, dc, n * 4, hipMemcpyDeviceToHost));
-  hipFree(dx);
-  hipFree(ds);
-  hipFree(dc);
-  return 0;
+  DeviceBuffer<float> dx, ds, dc;
+  if (dx.upload(x, n, __func__) || ds.alloc(n, __func__) || dc.alloc(n, __func__)) return -1;
+  if (n > 0) hipLaunchKernelGGL(test_sincos_kernel, dim3(unsigned((n + 255) / 256)), dim3(256), 0, 0, dx.get(), (long long)n, ds.get(), dc.get());
+  return hip_launch_check(__func__) || ds.download(s, n, __func__) || dc.download(c, n, __func__) ? -1 : 0;
 }
 int pine_gpu_test_powlog(int device, const float* x, const float* y, int64_t n, float* pw, float* lg) {
   if (need_device(device)) return -1;
-  float *dx, *dy, *dp, *dl;
-  HIP_OK(hipMalloc((void**)&dx, n * 4));
-  HIP_OK(hipMalloc((void**)&dy, n * 4));
-  HIP_OK(hipMalloc((void**)&dp, n * 4));
-  HIP_OK(hipMalloc((void**)&dl, n * 4));
-  HIP_OK(hipMemcpy(dx, x, n * 4, hipMemcpyHostToDevice));
-  HIP_OK(hipMemcpy(dy, y, n * 4, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(test_powlog_kernel, dim3(unsigned((n + 255) / 256)), dim3(256), 0, 0, dx, dy, (long long)n, dp, dl);
-  HIP_OK(hipMemcpy(pw, dp, n * 4, hipMemcpyDeviceToHost));
-  HIP_OK(hipMemcpy(lg, dl, n * 4, hipMemcpyDeviceToHost));
-  hipFree(dx);
-  hipFree(dy);
-  hipFree(dp);
-  hipFree(dl);
-  return 0;
+  DeviceBuffer<float> dx, dy, dp, dl;
+  if (dx.upload(x, n, __func__) || dy.upload(y, n, __func__) || dp.alloc(n, __func__) || dl.alloc(n, __func__)) return -1;
+  if (n > 0) hipLaunchKernelGGL(test_powlog_kernel, dim3(unsigned((n + 255) / 256)), dim3(256), 0, 0, dx.get(), dy.get(), (long long)n, dp.get(), dl.get());
+  return hip_launch_check(__func__) || dp.download(pw, n, __func__) || dl.download(lg, n, __func__) ? -1 : 0;
 }
 int pine_gpu_test_atan(int device, const float* y, const float* x, int64_t n, float* at2, float* ac) {
   if (need_device(device)) return -1;
-  float *dy, *dx, *da, *dc;
-  HIP_OK(hipMalloc((void**)&dy, n * 4));
-  HIP_OK(hipMalloc((void**)&dx, n * 4));
-  HIP_OK(hipMalloc((void**)&da, n * 4));
-  HIP_OK(hipMalloc((void**)&dc, n * 4));
-  HIP_OK(hipMemcpy(dy, y, n * 4, hipMemcpyHostToDevice));
-  HIP_OK(hipMemcpy(dx, x, n * 4, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(test_atan_kernel, dim3(unsigned((n + 255) / 256)), dim3(256), 0, 0, dy, dx, (long long)n, da, dc);
-  HIP_OK(hipMemcpy(at2, da, n * 4, hipMemcpyDeviceToHost));
-  HIP_OK(hipMemcpy(ac, dc, n * 4, hipMemcpyDeviceToHost));
-  hipFree(dy);
-  hipFree(dx);
-  hipFree(da);
-  hipFree(dc);
-  return 0;
+  DeviceBuffer<float> dy, dx, da, dc;
+  if (dy.upload(y, n, __func__) || dx.upload(x, n, __func__) || da.alloc(n, __func__) || dc.alloc(n, __func__)) return -1;
+  if (n > 0) hipLaunchKernelGGL(test_atan_kernel, dim3(unsigned((n + 255) / 256)), dim3(256), 0, 0, dy.get(), dx.get(), (long long)n, da.get(), dc.get());
+  return hip_launch_check(__func__) || da.download(at2, n, __func__) || dc.download(ac, n, __func__) ? -1 : 0;
 }
 
 // ---- pine_gpu_test_math_*: the scalar functions over bit patterns against their references (pine_math_check.h) -----
@@ -474,24 +439,16 @@ int pine_gpu_test_math_eval(int device, int fn, const uint32_t* a, const uint32_
   if (need_device(device)) return -1;
   const int w = math_width(fn), ar = math_arity(fn);
   const int64_t m = std::max<int64_t>(1, std::min(n, math_check::kChunk));
-  uint32_t* d[4] = {nullptr, nullptr, nullptr, nullptr};
-  int rc = 0;
-  for (int k = 0; k < 4 && !rc; k++)
-    if ((k < ar || k == 3) && hipMalloc((void**)&d[k], m * 4 * (k == 3 ? w : 1)) != hipSuccess) rc = -1;
-  const uint32_t* src[3] = {a, b, c};
-  for (int64_t i0 = 0; i0 < n && !rc; i0 += m) {
-    const int64_t len = std::min(m, n - i0);
-    for (int k = 0; k < ar && !rc; k++)
-      if (hipMemcpy(d[k], src[k] + i0, len * 4, hipMemcpyHostToDevice) != hipSuccess) rc = -1;
-    if (rc) break;
-    kMathLaunch[size_t(fn)](d[0], d[1], d[2], 0u, 0, 0u, 0u, (long long)len, d[3]);
-    if (hipGetLastError() != hipSuccess || hipMemcpy(got + i0 * w, d[3], len * 4 * w, hipMemcpyDeviceToHost) != hipSuccess) rc = -1;
-  }
+  DeviceBuffer<uint32_t> d[4];  // a, b, c as the arity needs; the results
   for (int k = 0; k < 4; k++)
-    if (d[k]) hipFree(d[k]);
-  if (rc) {
-    set_error(std::string("pine_gpu_test_math_eval: ") + hipGetErrorString(hipGetLastError()));
-    return -1;
+    if ((k < ar || k == 3) && d[k].alloc(size_t(m) * (k == 3 ? w : 1), __func__)) return -1;
+  const uint32_t* src[3] = {a, b, c};
+  for (int64_t i0 = 0; i0 < n; i0 += m) {
+    const int64_t len = std::min(m, n - i0);
+    for (int k = 0; k < ar; k++)
+      if (d[k].write(src[k] + i0, size_t(len), __func__)) return -1;
+    kMathLaunch[size_t(fn)](d[0], d[1], d[2], 0u, 0, 0u, 0u, (long long)len, d[3]);
+    if (hip_launch_check(__func__) || d[3].download(got + i0 * w, size_t(len) * w, __func__)) return -1;
   }
   return 0;
 }
@@ -502,26 +459,15 @@ int pine_gpu_test_math_sweep(int device, int fn, uint32_t fixed_bits, int swept_
   if (math_check::bad_sweep_args(fn, swept_arg, count, stats, examples, cap) || need_device(device)) return -1;
   const int w = math_width(fn);
   const int64_t m = std::max<int64_t>(1, std::min<int64_t>(int64_t(count), math_check::kChunk));
-  uint32_t* h = nullptr;  // one chunk's results, pinned for the copies
-  uint32_t* d = nullptr;
-  HIP_OK(hipHostMalloc((void**)&h, m * w * 4, hipHostMallocDefault));
-  if (hipMalloc((void**)&d, m * w * 4) != hipSuccess) {
-    hipHostFree(h);
-    set_error("pine_gpu_test_math_sweep: out of device memory");
-    return -1;
-  }
+  PinnedOwner<uint32_t> h;  // one chunk's results, pinned for the copies
+  DeviceBuffer<uint32_t> d;
+  if (alloc_pinned(h, size_t(m) * w, hipHostMallocDefault, __func__) || d.alloc(size_t(m) * w, __func__)) return -1;
+  const char* const me = __func__;
   const math_check::ChunkEval on_device = [&](uint32_t start, int64_t len, uint32_t* out) {
     kMathLaunch[size_t(fn)](nullptr, nullptr, nullptr, fixed_bits, swept_arg, start, stride, (long long)len, d);
-    if (hipGetLastError() != hipSuccess || hipMemcpy(out, d, len * w * 4, hipMemcpyDeviceToHost) != hipSuccess) {
-      set_error(std::string("pine_gpu_test_math_sweep: ") + hipGetErrorString(hipGetLastError()));
-      return -1;
-    }
-    return 0;
+    return hip_launch_check(me) || d.download(out, size_t(len) * w, me) ? -1 : 0;
   };
-  const int rc = math_check::sweep(fn, fixed_bits, swept_arg, first, count, stride, on_device, h, stats, examples, cap);
-  hipFree(d);
-  hipHostFree(h);
-  return rc;
+  return math_check::sweep(fn, fixed_bits, swept_arg, first, count, stride, on_device, h.get(), stats, examples, cap);
 }
 
 int pine_gpu_test_sampler(int device, int spp_req, float* out, int64_t capacity) {
@@ -537,21 +483,13 @@ int pine_gpu_test_sampler(int device, int spp_req, float* out, int64_t capacity)
   }
   int k = 0;
   while ((1 << k) < spp) k++;
-  uint8_t* dt;
-  float* dout;
-  HIP_OK(hipMalloc((void**)&dt, 65536 + 262144));
-  {
-    const std::vector<uint8_t> st = transposed_sobol(g_tables);
-    HIP_OK(hipMemcpy(dt, st.data(), 65536, hipMemcpyHostToDevice));
-  }
-  HIP_OK(hipMemcpy(dt + 65536, g_tables.data() + 65536 + size_t(k) * 262144, 262144, hipMemcpyHostToDevice));
-  HIP_OK(hipMalloc((void**)&dout, need * 4));
+  DeviceBuffer<uint8_t> dt;
+  DeviceBuffer<float> dout;
+  if (dt.alloc(65536 + 262144, __func__) || dt.write(transposed_sobol(g_tables).data(), 65536, __func__) || dout.alloc(size_t(need), __func__)) return -1;
+  if (const hipError_t e = hipMemcpy(dt + 65536, g_tables.data() + 65536 + size_t(k) * 262144, 262144, hipMemcpyHostToDevice)) return hip_error(__func__, e);
   DTables T{dt, dt + 65536, dt + 65536 + 131072, nullptr, nullptr, 0};
-  hipLaunchKernelGGL(test_sampler_kernel, dim3(6), dim3(64), 0, 0, T, spp, dout);
-  HIP_OK(hipMemcpy(out, dout, need * 4, hipMemcpyDeviceToHost));
-  hipFree(dt);
-  hipFree(dout);
-  return 0;
+  hipLaunchKernelGGL(test_sampler_kernel, dim3(6), dim3(64), 0, 0, T, spp, dout.get());
+  return hip_launch_check(__func__) || dout.download(out, size_t(need), __func__) ? -1 : 0;
 }
 int pine_gpu_test_rng(int device, uint64_t* out, int64_t capacity) {
   if (need_device(device)) return -1;
@@ -559,12 +497,11 @@ int pine_gpu_test_rng(int device, uint64_t* out, int64_t capacity) {
     set_error("capacity too small");
     return -1;
   }
-  unsigned long long* d;
-  HIP_OK(hipMalloc((void**)&d, 6 * 19 * 8));
-  hipLaunchKernelGGL(test_rng_kernel, dim3(1), dim3(64), 0, 0, d);
-  HIP_OK(hipMemcpy(out, d, 6 * 19 * 8, hipMemcpyDeviceToHost));
-  hipFree(d);
-  return 0;
+  DeviceBuffer<unsigned long long> d;
+  if (d.alloc(6 * 19, __func__)) return -1;
+  hipLaunchKernelGGL(test_rng_kernel, dim3(1), dim3(64), 0, 0, d.get());
+  static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "the stream is read back in place");
+  return hip_launch_check(__func__) || d.download(reinterpret_cast<unsigned long long*>(out), 6 * 19, __func__) ? -1 : 0;
 }
 int pine_gpu_test_traverse(pine_gpu_scene* scene, int device, const float* rays, int64_t nrays, int flat, int cap, uint32_t* out) {
   if (!scene || !rays || !out || cap < 2 || nrays < 0) {
@@ -576,33 +513,24 @@ int pine_gpu_test_traverse(pine_gpu_scene* scene, int device, const float* rays,
   pine_gpu_render_params prm{};
   prm.spp = 1, prm.max_path_length = 2, prm.device = device, prm.shard_rank = 0, prm.shard_world = 1;
   prm.flags = PINE_GPU_FLAG_NO_SPECIALIZE | (flat == 2 ? PINE_GPU_FLAG_ORDER_EMBREE : 0);
-  pine_gpu_plan* p = pine_gpu_plan_create(scene, &prm);
+  const PlanOwner p(pine_gpu_plan_create(scene, &prm));
   if (!p) return -1;
-  int rc = -1;
-  float* dr = nullptr;
-  unsigned* dout = nullptr;
+  if (flat == 1 && p->S.stack_total > 0 && scene_host(scene).accel.nodes.size() > 65535) {
+    set_error("the flat traversal keeps 16-bit node ids");
+    return -1;
+  }
   const size_t words = size_t(nrays) * (2 * size_t(cap) + 5);
-  do {
-    if (flat == 1 && p->S.stack_total > 0 && scene_host(scene).accel.nodes.size() > 65535) {
-      set_error("the flat traversal keeps 16-bit node ids");
-      break;
-    }
-    if (hipMalloc((void**)&dr, std::max<int64_t>(nrays, 1) * 32) != hipSuccess || hipMalloc((void**)&dout, std::max<size_t>(words, 1) * 4) != hipSuccess) break;
-    if (hipMemcpy(dr, rays, nrays * 32, hipMemcpyHostToDevice) != hipSuccess || hipMemset(dout, 0, std::max<size_t>(words, 1) * 4) != hipSuccess) break;
-    const size_t lds = size_t(std::max(1, p->S.stack_total)) * 64 * (flat == 1 ? sizeof(unsigned short) : sizeof(int));
-    if (nrays > 0) {
-      if (flat == 1) hipLaunchKernelGGL(test_traverse_kernel<1>, dim3(unsigned((nrays + 63) / 64)), dim3(64), lds, 0, p->S, dr, (long long)nrays, cap, dout);
-      else if (flat == 2) hipLaunchKernelGGL(test_traverse_kernel<2>, dim3(unsigned((nrays + 63) / 64)), dim3(64), lds, 0, p->S, dr, (long long)nrays, cap, dout);
-      else hipLaunchKernelGGL(test_traverse_kernel<0>, dim3(unsigned((nrays + 63) / 64)), dim3(64), lds, 0, p->S, dr, (long long)nrays, cap, dout);
-    }
-    if (hipMemcpy(out, dout, words * 4, hipMemcpyDeviceToHost) != hipSuccess) break;
-    rc = 0;
-  } while (0);
-  if (rc) set_error(std::string("pine_gpu_test_traverse: ") + hipGetErrorString(hipGetLastError()));
-  (void)hipFree(dr);
-  (void)hipFree(dout);
-  pine_gpu_plan_destroy(p);
-  return rc;
+  DeviceBuffer<float> dr;
+  DeviceBuffer<unsigned> dout;
+  if (dr.upload(rays, size_t(nrays) * 8, __func__) || dout.alloc(std::max<size_t>(words, 1), __func__)) return -1;
+  if (const hipError_t e = hipMemset(dout, 0, std::max<size_t>(words, 1) * 4)) return hip_error(__func__, e);
+  const size_t lds = size_t(std::max(1, p->S.stack_total)) * 64 * (flat == 1 ? sizeof(unsigned short) : sizeof(int));
+  if (nrays > 0) {
+    if (flat == 1) hipLaunchKernelGGL(test_traverse_kernel<1>, dim3(unsigned((nrays + 63) / 64)), dim3(64), lds, 0, p->S, dr.get(), (long long)nrays, cap, dout.get());
+    else if (flat == 2) hipLaunchKernelGGL(test_traverse_kernel<2>, dim3(unsigned((nrays + 63) / 64)), dim3(64), lds, 0, p->S, dr.get(), (long long)nrays, cap, dout.get());
+    else hipLaunchKernelGGL(test_traverse_kernel<0>, dim3(unsigned((nrays + 63) / 64)), dim3(64), lds, 0, p->S, dr.get(), (long long)nrays, cap, dout.get());
+  }
+  return hip_launch_check(__func__) || dout.download(out, words, __func__) ? -1 : 0;
 }
 
 int pine_gpu_test_shapes(pine_gpu_scene* scene, int device, const float* rays, int64_t nrays, float* out,
@@ -621,21 +549,13 @@ int pine_gpu_test_shapes(pine_gpu_scene* scene, int device, const float* rays, i
     set_error("capacity too small");
     return -1;
   }
-  DShape* ds;
-  float *dr, *dout;
-  if (upload(ds, shapes)) return -1;
-  HIP_OK(hipMalloc((void**)&dr, nrays * 32));
-  HIP_OK(hipMemcpy(dr, rays, nrays * 32, hipMemcpyHostToDevice));
-  HIP_OK(hipMalloc((void**)&dout, std::max<int64_t>(need, 1) * 4));
+  DeviceBuffer<DShape> ds;
+  DeviceBuffer<float> dr, dout;
+  if (ds.upload(shapes, __func__) || dr.upload(rays, size_t(nrays) * 8, __func__) || dout.alloc(size_t(std::max<int64_t>(need, 1)), __func__)) return -1;
   const long long total = (long long)shapes.size() * nrays;
   if (total > 0)
-    hipLaunchKernelGGL(test_shapes_kernel, dim3(unsigned((total + 255) / 256)), dim3(256), 0, 0, ds,
-                       int(shapes.size()), dr, (long long)nrays, dout);
-  HIP_OK(hipMemcpy(out, dout, need * 4, hipMemcpyDeviceToHost));
-  hipFree(ds);
-  hipFree(dr);
-  hipFree(dout);
-  return 0;
+    hipLaunchKernelGGL(test_shapes_kernel, dim3(unsigned((total + 255) / 256)), dim3(256), 0, 0, ds.get(), int(shapes.size()), dr.get(), (long long)nrays, dout.get());
+  return hip_launch_check(__func__) || dout.download(out, size_t(need), __func__) ? -1 : 0;
 }
 
 // pine_gpu_test_box_slabs: the host build of box_slabs and of box_slabs_lean (pine_device.h) on caller-given boxes and rays
@@ -764,36 +684,22 @@ int pine_gpu_test_bxdf(int device, const float* cases, int64_t n, float* out) {
   }
   if (n == 0) return 0;
   if (need_device(device)) return -1;
-  float *dc = nullptr, *dout = nullptr;
-  int* didx = nullptr;
-  int rc = -1;
-  do {
-    if (hipMalloc((void**)&dc, n * 64) != hipSuccess || hipMalloc((void**)&dout, n * 2 * 56) != hipSuccess || hipMalloc((void**)&didx, n * 4) != hipSuccess) break;
-    if (hipMemcpy(dc, cases, n * 64, hipMemcpyHostToDevice) != hipSuccess || hipMemset(dout, 0, n * 2 * 56) != hipSuccess) break;
-    size_t at = 0;
-    bool ok = true;
-    for (int g = 0; g < 3 && ok; g++) {
-      if (!idx[g].empty()) ok = hipMemcpy(didx + at, idx[g].data(), idx[g].size() * 4, hipMemcpyHostToDevice) == hipSuccess;
-      at += idx[g].size();
-    }
-    if (!ok) break;
-    const auto blocks = [](size_t m) { return dim3(unsigned((m + 63) / 64)); };
-    hipLaunchKernelGGL(test_bxdf_kernel<F_ALL>, blocks(size_t(n)), dim3(64), 0, 0, dc, (const int*)nullptr, (long long)n, dout);
-    float* const dnarrow = dout + n * 14;
-    const int* di = didx;
-    if (!idx[0].empty()) hipLaunchKernelGGL(test_bxdf_kernel<0u>, blocks(idx[0].size()), dim3(64), 0, 0, dc, di, (long long)idx[0].size(), dnarrow);
-    di += idx[0].size();
-    if (!idx[1].empty()) hipLaunchKernelGGL(test_bxdf_kernel<F_UBER>, blocks(idx[1].size()), dim3(64), 0, 0, dc, di, (long long)idx[1].size(), dnarrow);
-    di += idx[1].size();
-    if (!idx[2].empty()) hipLaunchKernelGGL(test_bxdf_kernel<F_SSS>, blocks(idx[2].size()), dim3(64), 0, 0, dc, di, (long long)idx[2].size(), dnarrow);
-    if (hipGetLastError() != hipSuccess || hipMemcpy(out, dout, n * 2 * 56, hipMemcpyDeviceToHost) != hipSuccess) break;
-    rc = 0;
-  } while (0);
-  if (rc) set_error(std::string("pine_gpu_test_bxdf: ") + hipGetErrorString(hipGetLastError()));
-  (void)hipFree(dc);
-  (void)hipFree(dout);
-  (void)hipFree(didx);
-  return rc;
+  DeviceBuffer<float> dc, dout;
+  DeviceBuffer<int> didx;
+  std::vector<int> order;  // the three groups one after the other
+  for (const std::vector<int>& g : idx) order.insert(order.end(), g.begin(), g.end());
+  if (dc.upload(cases, size_t(n) * 16, __func__) || dout.alloc(size_t(n) * 2 * 14, __func__) || didx.upload(order, __func__)) return -1;
+  if (const hipError_t e = hipMemset(dout, 0, size_t(n) * 2 * 56)) return hip_error(__func__, e);
+  const auto blocks = [](size_t m) { return dim3(unsigned((m + 63) / 64)); };
+  hipLaunchKernelGGL(test_bxdf_kernel<F_ALL>, blocks(size_t(n)), dim3(64), 0, 0, dc.get(), (const int*)nullptr, (long long)n, dout.get());
+  float* const dnarrow = dout + n * 14;
+  const int* di = didx;
+  if (!idx[0].empty()) hipLaunchKernelGGL(test_bxdf_kernel<0u>, blocks(idx[0].size()), dim3(64), 0, 0, dc.get(), di, (long long)idx[0].size(), dnarrow);
+  di += idx[0].size();
+  if (!idx[1].empty()) hipLaunchKernelGGL(test_bxdf_kernel<F_UBER>, blocks(idx[1].size()), dim3(64), 0, 0, dc.get(), di, (long long)idx[1].size(), dnarrow);
+  di += idx[1].size();
+  if (!idx[2].empty()) hipLaunchKernelGGL(test_bxdf_kernel<F_SSS>, blocks(idx[2].size()), dim3(64), 0, 0, dc.get(), di, (long long)idx[2].size(), dnarrow);
+  return hip_launch_check(__func__) || dout.download(out, size_t(n) * 2 * 14, __func__) ? -1 : 0;
 }
 
 int pine_gpu_test_light_samples(pine_gpu_scene* scene, int device, const float* queries, int64_t n, float* out) {
@@ -821,69 +727,46 @@ int pine_gpu_test_light_samples(pine_gpu_scene* scene, int device, const float* 
   }
   if (words == 0) return 0;
   if (need_device(device)) return -1;
-  DShape* ds = nullptr;
-  DLight* dl = nullptr;
-  float *dt = nullptr, *dq = nullptr, *dout = nullptr;
-  int rc = -1;
-  do {
-    if (hipMalloc((void**)&ds, std::max<size_t>(shapes.size(), 1) * sizeof(DShape)) != hipSuccess ||
-        hipMalloc((void**)&dl, std::max<size_t>(lights.size(), 1) * sizeof(DLight)) != hipSuccess ||
-        hipMalloc((void**)&dt, std::max<size_t>(H.accel.tri_verts.size(), 1) * 4) != hipSuccess ||
-        hipMalloc((void**)&dq, size_t(n) * 24) != hipSuccess || hipMalloc((void**)&dout, words * 4) != hipSuccess)
-      break;
-    if ((ns && hipMemcpy(ds, shapes.data(), shapes.size() * sizeof(DShape), hipMemcpyHostToDevice) != hipSuccess) ||
-        (nl && hipMemcpy(dl, lights.data(), lights.size() * sizeof(DLight), hipMemcpyHostToDevice) != hipSuccess) ||
-        (!H.accel.tri_verts.empty() && hipMemcpy(dt, H.accel.tri_verts.data(), H.accel.tri_verts.size() * 4, hipMemcpyHostToDevice) != hipSuccess) ||
-        hipMemcpy(dq, queries, size_t(n) * 24, hipMemcpyHostToDevice) != hipSuccess)
-      break;
-    const long long total = (long long)n * (ns + nl);
-    hipLaunchKernelGGL(test_light_samples_kernel, dim3(unsigned((total + 63) / 64)), dim3(64), 0, 0, ds, ns, dt, dl, nl, dq, (long long)n, dout);
-    if (hipGetLastError() != hipSuccess || hipMemcpy(out, dout, words * 4, hipMemcpyDeviceToHost) != hipSuccess) break;
-    rc = 0;
-  } while (0);
-  if (rc) set_error(std::string("pine_gpu_test_light_samples: ") + hipGetErrorString(hipGetLastError()));
-  (void)hipFree(ds);
-  (void)hipFree(dl);
-  (void)hipFree(dt);
-  (void)hipFree(dq);
-  (void)hipFree(dout);
-  return rc;
+  DeviceBuffer<DShape> ds;
+  DeviceBuffer<DLight> dl;
+  DeviceBuffer<float> dt, dq, dout;
+  if (ds.upload(shapes, __func__) || dl.upload(lights, __func__) || dt.upload(H.accel.tri_verts, __func__) || dq.upload(queries, size_t(n) * 6, __func__) ||
+      dout.alloc(words, __func__))
+    return -1;
+  const long long total = (long long)n * (ns + nl);
+  hipLaunchKernelGGL(test_light_samples_kernel, dim3(unsigned((total + 63) / 64)), dim3(64), 0, 0, ds.get(), ns, dt.get(), dl.get(), nl, dq.get(), (long long)n, dout.get());
+  return hip_launch_check(__func__) || dout.download(out, words, __func__) ? -1 : 0;
 }
 
-int pine_gpu_test_env_light(pine_gpu_scene* scene, int device, const float* queries, int64_t n, float* out) {
+// pine_gpu_test_env_light and pine_gpu_test_env_light_sample: per query of 5 floats a record of `rec` floats, from `host_case`
+// (device < 0) or from `kernel`
+static int env_light_hook(const char* me, pine_gpu_scene* scene, int device, const float* queries, int64_t n, float* out, int rec,
+                          void (*host_case)(const DLight*, const float*, const float*, float*), void (*kernel)(DLight, const float*, const float*, long long, float*)) {
   if (!scene || !queries || !out || n < 0 || n > (1 << 20)) {
     set_error("bad argument");
     return -1;
   }
   SceneHost& H = scene_host(scene);
   if (!H.has_env || (H.env.kind != LIGHT_IMAGE_SKY && H.env.kind != LIGHT_ATMOSPHERE) || !env_image_valid(H.env, H.env_words)) {
-    set_error("pine_gpu_test_env_light: the scene's environment light is no ImageSky and no Atmosphere");
+    set_error(std::string(me) + ": the scene's environment light is no ImageSky and no Atmosphere");
     return -1;
   }
   if (device < 0) {
-    for (int64_t i = 0; i < n; i++) test_env_light_case(&H.env, H.env_words.data(), queries + i * 5, out + i * 13);
+    for (int64_t i = 0; i < n; i++) host_case(&H.env, H.env_words.data(), queries + i * 5, out + i * rec);
     return 0;
   }
   if (n == 0) return 0;
   if (need_device(device)) return -1;
-  float *de = nullptr, *dq = nullptr, *dout = nullptr;
-  int rc = -1;
-  do {
-    if (hipMalloc((void**)&de, H.env_words.size() * 4) != hipSuccess || hipMalloc((void**)&dq, size_t(n) * 20) != hipSuccess ||
-        hipMalloc((void**)&dout, size_t(n) * 52) != hipSuccess)
-      break;
-    if (hipMemcpy(de, H.env_words.data(), H.env_words.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(dq, queries, size_t(n) * 20, hipMemcpyHostToDevice) != hipSuccess)
-      break;
-    hipLaunchKernelGGL(test_env_light_kernel, dim3(unsigned((n + 63) / 64)), dim3(64), 0, 0, H.env, de, dq, (long long)n, dout);
-    if (hipGetLastError() != hipSuccess || hipMemcpy(out, dout, size_t(n) * 52, hipMemcpyDeviceToHost) != hipSuccess) break;
-    rc = 0;
-  } while (0);
-  if (rc) set_error(std::string("pine_gpu_test_env_light: ") + hipGetErrorString(hipGetLastError()));
-  (void)hipFree(de);
-  (void)hipFree(dq);
-  (void)hipFree(dout);
-  return rc;
+  DeviceBuffer<float> de, dq, dout;
+  if (de.upload(H.env_words, me) || dq.upload(queries, size_t(n) * 5, me) || dout.alloc(size_t(n) * rec, me)) return -1;
+  hipLaunchKernelGGL(kernel, dim3(unsigned((n + 63) / 64)), dim3(64), 0, 0, H.env, de.get(), dq.get(), (long long)n, dout.get());
+  return hip_launch_check(me) || dout.download(out, size_t(n) * rec, me) ? -1 : 0;
+}
+int pine_gpu_test_env_light(pine_gpu_scene* scene, int device, const float* queries, int64_t n, float* out) {
+  return env_light_hook(__func__, scene, device, queries, n, out, 13, test_env_light_case, test_env_light_kernel);
+}
+int pine_gpu_test_env_light_sample(pine_gpu_scene* scene, int device, const float* queries, int64_t n, float* out) {
+  return env_light_hook(__func__, scene, device, queries, n, out, 9, test_env_light_sample_case, test_env_light_sample_kernel);
 }
 
 int pine_gpu_test_atmosphere_color(int device, const float* queries, int64_t n, float* out) {
@@ -897,55 +780,10 @@ int pine_gpu_test_atmosphere_color(int device, const float* queries, int64_t n, 
   }
   if (n == 0) return 0;
   if (need_device(device)) return -1;
-  float *dq = nullptr, *dout = nullptr;
-  int rc = -1;
-  hipError_t first = hipSuccess;  // the first failure: asking again for the last error would find it cleared
-  auto bad = [&](hipError_t e) { return e != hipSuccess && (first = e, true); };
-  do {
-    if (bad(hipMalloc((void**)&dq, size_t(n) * 28)) || bad(hipMalloc((void**)&dout, size_t(n) * 12))) break;
-    if (bad(hipMemcpy(dq, queries, size_t(n) * 28, hipMemcpyHostToDevice))) break;
-    hipLaunchKernelGGL(test_atmosphere_color_kernel, dim3(unsigned((n + 63) / 64)), dim3(64), 0, 0, dq, (long long)n, dout);
-    if (bad(hipGetLastError()) || bad(hipMemcpy(out, dout, size_t(n) * 12, hipMemcpyDeviceToHost))) break;
-    rc = 0;
-  } while (0);
-  if (rc) set_error(std::string("pine_gpu_test_atmosphere_color: ") + hipGetErrorString(first));
-  (void)hipFree(dq);
-  (void)hipFree(dout);
-  return rc;
-}
-
-int pine_gpu_test_env_light_sample(pine_gpu_scene* scene, int device, const float* queries, int64_t n, float* out) {
-  if (!scene || !queries || !out || n < 0 || n > (1 << 20)) {
-    set_error("bad argument");
-    return -1;
-  }
-  SceneHost& H = scene_host(scene);
-  if (!H.has_env || (H.env.kind != LIGHT_IMAGE_SKY && H.env.kind != LIGHT_ATMOSPHERE) || !env_image_valid(H.env, H.env_words)) {
-    set_error("pine_gpu_test_env_light_sample: the scene's environment light is no ImageSky and no Atmosphere");
-    return -1;
-  }
-  if (device < 0) {
-    for (int64_t i = 0; i < n; i++) test_env_light_sample_case(&H.env, H.env_words.data(), queries + i * 5, out + i * 9);
-    return 0;
-  }
-  if (n == 0) return 0;
-  if (need_device(device)) return -1;
-  float *de = nullptr, *dq = nullptr, *dout = nullptr;
-  int rc = -1;
-  hipError_t first = hipSuccess;
-  auto bad = [&](hipError_t e) { return e != hipSuccess && (first = e, true); };
-  do {
-    if (bad(hipMalloc((void**)&de, H.env_words.size() * 4)) || bad(hipMalloc((void**)&dq, size_t(n) * 20)) || bad(hipMalloc((void**)&dout, size_t(n) * 36))) break;
-    if (bad(hipMemcpy(de, H.env_words.data(), H.env_words.size() * 4, hipMemcpyHostToDevice)) || bad(hipMemcpy(dq, queries, size_t(n) * 20, hipMemcpyHostToDevice))) break;
-    hipLaunchKernelGGL(test_env_light_sample_kernel, dim3(unsigned((n + 63) / 64)), dim3(64), 0, 0, H.env, de, dq, (long long)n, dout);
-    if (bad(hipGetLastError()) || bad(hipMemcpy(out, dout, size_t(n) * 36, hipMemcpyDeviceToHost))) break;
-    rc = 0;
-  } while (0);
-  if (rc) set_error(std::string("pine_gpu_test_env_light_sample: ") + hipGetErrorString(first));
-  (void)hipFree(de);
-  (void)hipFree(dq);
-  (void)hipFree(dout);
-  return rc;
+  DeviceBuffer<float> dq, dout;
+  if (dq.upload(queries, size_t(n) * 7, __func__) || dout.alloc(size_t(n) * 3, __func__)) return -1;
+  hipLaunchKernelGGL(test_atmosphere_color_kernel, dim3(unsigned((n + 63) / 64)), dim3(64), 0, 0, dq.get(), (long long)n, dout.get());
+  return hip_launch_check(__func__) || dout.download(out, size_t(n) * 3, __func__) ? -1 : 0;
 }
 
 int64_t pine_gpu_test_env_table(pine_gpu_scene* scene, float* out, int64_t capacity) {
@@ -1040,31 +878,14 @@ int pine_gpu_test_material_params(pine_gpu_scene* scene, int device, const float
   }
   if (n == 0 || nm == 0) return 0;
   if (need_device(device)) return -1;
-  DMaterial* dm = nullptr;
-  DNodeOp* dops = nullptr;
-  float *dq = nullptr, *dout = nullptr;
+  DeviceBuffer<DMaterial> dm;
+  DeviceBuffer<DNodeOp> dops;
+  DeviceBuffer<float> dq, dout;
   const size_t words = size_t(n) * size_t(nm) * 10;
-  int rc = -1;
-  do {
-    if (hipMalloc((void**)&dm, mats.size() * sizeof(DMaterial)) != hipSuccess ||
-        hipMalloc((void**)&dops, std::max<size_t>(ops.size(), 1) * sizeof(DNodeOp)) != hipSuccess ||
-        hipMalloc((void**)&dq, size_t(n) * 32) != hipSuccess || hipMalloc((void**)&dout, words * 4) != hipSuccess)
-      break;
-    if (hipMemcpy(dm, mats.data(), mats.size() * sizeof(DMaterial), hipMemcpyHostToDevice) != hipSuccess ||
-        (!ops.empty() && hipMemcpy(dops, ops.data(), ops.size() * sizeof(DNodeOp), hipMemcpyHostToDevice) != hipSuccess) ||
-        hipMemcpy(dq, queries, size_t(n) * 32, hipMemcpyHostToDevice) != hipSuccess)
-      break;
-    const long long total = (long long)n * nm;
-    hipLaunchKernelGGL(test_material_params_kernel, dim3(unsigned((total + 63) / 64)), dim3(64), 0, 0, dm, nm, dops, dq, (long long)n, dout);
-    if (hipGetLastError() != hipSuccess || hipMemcpy(out, dout, words * 4, hipMemcpyDeviceToHost) != hipSuccess) break;
-    rc = 0;
-  } while (0);
-  if (rc) set_error(std::string("pine_gpu_test_material_params: ") + hipGetErrorString(hipGetLastError()));
-  (void)hipFree(dm);
-  (void)hipFree(dops);
-  (void)hipFree(dq);
-  (void)hipFree(dout);
-  return rc;
+  if (dm.upload(mats, __func__) || dops.upload(ops, __func__) || dq.upload(queries, size_t(n) * 8, __func__) || dout.alloc(words, __func__)) return -1;
+  const long long total = (long long)n * nm;
+  hipLaunchKernelGGL(test_material_params_kernel, dim3(unsigned((total + 63) / 64)), dim3(64), 0, 0, dm.get(), nm, dops.get(), dq.get(), (long long)n, dout.get());
+  return hip_launch_check(__func__) || dout.download(out, words, __func__) ? -1 : 0;
 }
 
 int pine_gpu_test_choose_lobe(pine_gpu_scene* scene, int device, const float* cases, int64_t n, float* out) {
@@ -1093,29 +914,25 @@ int pine_gpu_test_choose_lobe(pine_gpu_scene* scene, int device, const float* ca
   }
   if (n == 0) return 0;
   if (need_device(device)) return -1;
-  DMaterial* dm = nullptr;
-  DNodeOp* dops = nullptr;
-  float *dc = nullptr, *dout = nullptr;
-  int rc = -1;
-  do {
-    if (hipMalloc((void**)&dm, mats.size() * sizeof(DMaterial)) != hipSuccess ||
-        hipMalloc((void**)&dops, std::max<size_t>(ops.size(), 1) * sizeof(DNodeOp)) != hipSuccess ||
-        hipMalloc((void**)&dc, size_t(n) * 64) != hipSuccess || hipMalloc((void**)&dout, size_t(n) * 64) != hipSuccess)
-      break;
-    if (hipMemcpy(dm, mats.data(), mats.size() * sizeof(DMaterial), hipMemcpyHostToDevice) != hipSuccess ||
-        (!ops.empty() && hipMemcpy(dops, ops.data(), ops.size() * sizeof(DNodeOp), hipMemcpyHostToDevice) != hipSuccess) ||
-        hipMemcpy(dc, cases, size_t(n) * 64, hipMemcpyHostToDevice) != hipSuccess)
-      break;
-    hipLaunchKernelGGL(test_choose_lobe_kernel, dim3(unsigned((2 * n + 63) / 64)), dim3(64), 0, 0, dm, dops, dc, (long long)n, dout);
-    if (hipGetLastError() != hipSuccess || hipMemcpy(out, dout, size_t(n) * 64, hipMemcpyDeviceToHost) != hipSuccess) break;
-    rc = 0;
-  } while (0);
-  if (rc) set_error(std::string("pine_gpu_test_choose_lobe: ") + hipGetErrorString(hipGetLastError()));
-  (void)hipFree(dm);
-  (void)hipFree(dops);
-  (void)hipFree(dc);
-  (void)hipFree(dout);
-  return rc;
+  DeviceBuffer<DMaterial> dm;
+  DeviceBuffer<DNodeOp> dops;
+  DeviceBuffer<float> dc, dout;
+  if (dm.upload(mats, __func__) || dops.upload(ops, __func__) || dc.upload(cases, size_t(n) * 16, __func__) || dout.alloc(size_t(n) * 16, __func__)) return -1;
+  hipLaunchKernelGGL(test_choose_lobe_kernel, dim3(unsigned((2 * n + 63) / 64)), dim3(64), 0, 0, dm.get(), dops.get(), dc.get(), (long long)n, dout.get());
+  return hip_launch_check(__func__) || dout.download(out, size_t(n) * 16, __func__) ? -1 : 0;
+}
+
+// The handles the owners of pine_device_buffer.h hold right now (device blocks, pinned memory, events, streams: those of live plans
+// and of calls in flight) and the blocks the pool keeps for the next plan.  Reads two counters; launches nothing.
+int pine_gpu_test_live_device_blocks(int64_t out[2]) {
+  if (!out) {
+    set_error("null argument");
+    return -1;
+  }
+  out[0] = g_live_handles.load();
+  std::lock_guard<std::mutex> lock(DevicePool::get().mu);
+  out[1] = int64_t(DevicePool::get().free_blocks.size());
+  return 0;
 }
 
 }  // extern "C"
