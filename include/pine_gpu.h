@@ -613,6 +613,16 @@ int64_t pine_gpu_test_frame_table(pine_gpu_scene*, pine_gpu_plan* plan, int devi
  * tmax; the ray in the box's frame).  out_host: 6 words per case -- flag, tmin bits, tmax bits of box_slabs, then of the lean
  * routine (the bounds mean something on a hit only).  Needs no GPU. */
 int pine_gpu_test_box_slabs(const float* boxes_host, const float* rays_host, int64_t n, uint32_t* out_host);
+/* The baked traversal's short division and short normalisation (pine_math.h "division") beside the compiler's
+ * own, bit by bit, on the device.  kind 0: per case a numerator and a denominator -- n / d against what a site of the traversal
+ * computes (window test, quotient from the refined reciprocal, plain division outside the window).  kind 1: per case a vector of
+ * three -- normalize() and prcp() of its components against local_direction_lean.  The cases: gen 0, n cases of 2 (3) words at
+ * in_host; gen 1 (kind 0), the numerator p1 over the n denominators p0, p0 + 1, ...; gen 2, n pseudo-random cases from the seed
+ * p0, every sign and mantissa, biased exponents p1 ... p2.  stats[4]: cases, mismatches, cases that took the short form, and of
+ * those the ones with an operand outside the window (asked of the operand's bits).  examples: the first `cap` mismatches, 8
+ * words each -- the operands (3), the index of the differing output, wanted, got, whether the short form was taken, 0. */
+int pine_gpu_test_short_div(int device, int kind, int gen, const uint32_t* in_host, uint32_t p0, uint32_t p1, uint32_t p2, int64_t n,
+                            int64_t stats[4], uint32_t* examples, int cap);
 /* The precompiled path-kernel variants (pine_variants.h) in the order of the host's first-fit search: kind 0 the stage-queued
  * kernel, 1 the megakernel.  Up to `cap` entries of features (F_* bits), ctx (path contexts per workgroup; 0 for the
  * megakernel) and order; any of the arrays may be NULL.  Returns the number of variants, < 0 on error.  Needs no GPU.

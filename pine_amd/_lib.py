@@ -212,6 +212,8 @@ SIGNATURES = {
     "pine_gpu_test_frame_table": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int, c_f_p, c_f_p, C.c_int64, C.POINTER(C.c_int32), C.c_int64,
                                               c_f_p, C.c_int64, C.POINTER(C.c_int32)]),
     "pine_gpu_test_box_slabs": (C.c_int, [c_f_p, c_f_p, C.c_int64, C.POINTER(C.c_uint32)]),
+    "pine_gpu_test_short_div": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_uint32, C.c_int64,
+                                          C.POINTER(C.c_int64), C.POINTER(C.c_uint32), C.c_int]),
     "pine_gpu_test_kernel_variants": (C.c_int, [C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int]),
     "pine_gpu_test_live_device_blocks": (C.c_int, [C.POINTER(C.c_int64)]),
     "pine_gpu_film_finalize_u8": (C.c_int, [c_f_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8)]),

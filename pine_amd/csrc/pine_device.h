@@ -438,6 +438,35 @@ PINE_HD DRayOct make_oct(const DRay& r) {
   o.neg = (r.d.x < 0 ? 1 : 0) | (r.d.y < 0 ? 2 : 0) | (r.d.z < 0 ? 4 : 0);
   return o;
 }
+// The baked traversal's one range test per ray (pine_math.h, "division"): every direction component
+// within [kRayLo, kRayHi] in magnitude, every origin component at most kRayHi.  (The origin needs no floor: it enters
+// the Rects' numerators as `literal - o`, whose floor each site tests itself.)  NaN compares false, so a ray with a
+// component that is not finite is not ordinary.  Kept per lane; every site that reads it falls back to the plain
+// code behind a per-lane branch.
+PINE_HD bool ray_ordinary(const DRay& r) {
+#if defined(PINE_SHORT_DIV)
+  const float dlo = __builtin_fminf(__builtin_fminf(pabs(r.d.x), pabs(r.d.y)), pabs(r.d.z));
+  const float dhi = __builtin_fmaxf(__builtin_fmaxf(pabs(r.d.x), pabs(r.d.y)), pabs(r.d.z));
+  const float ohi = __builtin_fmaxf(__builtin_fmaxf(pabs(r.o.x), pabs(r.o.y)), pabs(r.o.z));
+  // (minimum / maximum ignore a NaN operand, so NaN is asked for by name: a sum is unordered with itself when a term
+  //  is NaN; infinite terms fail the bounds above)
+  const float s = ((r.d.x + r.d.y) + (r.d.z + r.o.x)) + (r.o.y + r.o.z);
+  return dlo >= kRayLo && __builtin_fmaxf(dhi, ohi) <= kRayHi && s == s;
+#else
+  (void)r;
+  return false;
+#endif
+}
+// make_oct for a ray whose flag is known: an ordinary ray's reciprocals need neither prcp's guard nor safe_rcp's
+// zero case (the same values: prcp_core is prcp's own sequence)
+PINE_HD DRayOct make_oct(const DRay& r, bool ordinary) {
+  DRayOct o;
+  o.dir_inv = f3{prcp_core(r.d.x), prcp_core(r.d.y), prcp_core(r.d.z)};
+  if (__builtin_expect(!ordinary, 0)) o.dir_inv = f3{safe_rcp(r.d.x), safe_rcp(r.d.y), safe_rcp(r.d.z)};
+  o.org_div_dir = r.o * o.dir_inv;
+  o.neg = (r.d.x < 0 ? 1 : 0) | (r.d.y < 0 ? 2 : 0) | (r.d.z < 0 ? 4 : 0);
+  return o;
+}
 // AABB::hit(RayOctant, tmin, tmax&) bbox.h:59-72
 PINE_HD bool box_hit_oct(const float* lo, const float* hi, const DRayOct& r, float tmin, float& tmax) {
   const bool nx = r.neg & 1, ny = r.neg & 2, nz = r.neg & 4;
@@ -521,8 +550,8 @@ PINE_HD float slab_min(float x, float bound) {
   return pmin(x, bound);
 #endif
 }
-PINE_HD bool box_slabs_lean(f3 lo, f3 hi, f3 o, f3 d, float& tmin, float& tmax) {
-  const f3 inv = f3{prcp(d.x), prcp(d.y), prcp(d.z)};
+// (`inv`: the reciprocals of d's components, prcp's values -- the caller may hold them from a shorter sequence)
+PINE_HD bool box_slabs_lean(f3 lo, f3 hi, f3 o, f3 d, f3 inv, float& tmin, float& tmax) {
   const f3 a = (lo - o) * inv, b = (hi - o) * inv;
   f3 n = f3{slab_min(a.x, b.x), slab_min(a.y, b.y), slab_min(a.z, b.z)};
   f3 f = f3{slab_max(a.x, b.x), slab_max(a.y, b.y), slab_max(a.z, b.z)};
@@ -536,6 +565,9 @@ PINE_HD bool box_slabs_lean(f3 lo, f3 hi, f3 o, f3 d, float& tmin, float& tmax) 
   tmin = slab_max(n.z, slab_max(n.y, slab_max(n.x, tmin)));
   tmax = slab_min(f.z, slab_min(f.y, slab_min(f.x, tmax)));
   return !(tmin > tmax);
+}
+PINE_HD bool box_slabs_lean(f3 lo, f3 hi, f3 o, f3 d, float& tmin, float& tmax) {
+  return box_slabs_lean(lo, hi, o, d, f3{prcp(d.x), prcp(d.y), prcp(d.z)}, tmin, tmax);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -582,6 +614,43 @@ PINE_HD void obb_local_ray(const float* f, f3 o, f3 d, f3& lo_o, f3& lo_d) {
   const m34 mi = ld34(f + 18);
   lo_o = mul_point(mi, o);
   lo_d = normalize(mul(linear(mi), d));
+}
+// normalize(v) and the reciprocals of its components (prcp's values), as the lean calls below need them of the local
+// direction v = M^-1 d.  When all of |v.x|, |v.y|, |v.z| lie within [kRayLo, kRayHi] -- one minimum and one maximum
+// of three -- the short normalize applies (pine_math.h), and each component of the result is |v.k| / len with
+// len < 2^41, so it lies in [2^-81, 1]: inside prcp's range, the three reciprocals need no guard either.  Anything
+// else (a component that is zero, tiny, huge or not finite -- NaN fails the test through `s == s`) redoes all of it
+// with the guarded forms behind a per-lane branch.  Returns whether the short forms were taken.
+PINE_HD bool local_direction_lean(f3 v, f3& dir, f3& inv) {
+#if defined(PINE_SHORT_DIV)
+  const float vlo = __builtin_fminf(__builtin_fminf(pabs(v.x), pabs(v.y)), pabs(v.z));
+  const float vhi = __builtin_fmaxf(__builtin_fmaxf(pabs(v.x), pabs(v.y)), pabs(v.z));
+  const float s = v.x + v.y + v.z;
+  const bool tame = vlo >= kRayLo && vhi <= kRayHi && s == s;
+  dir = normalize_short(v);
+  inv = f3{prcp_core(dir.x), prcp_core(dir.y), prcp_core(dir.z)};
+  if (__builtin_expect(!tame, 0)) {
+    dir = normalize(v);
+    inv = f3{prcp(dir.x), prcp(dir.y), prcp(dir.z)};
+  }
+  return tame;
+#else
+  dir = normalize(v);
+  inv = f3{prcp(dir.x), prcp(dir.y), prcp(dir.z)};
+  return false;
+#endif
+}
+PINE_HD void obb_local_ray_lean(const float* f, f3 o, f3 d, f3& lo_o, f3& lo_d, f3& inv) {
+  const m34 mi = ld34(f + 18);
+  lo_o = mul_point(mi, o);
+  const f3 v = mul(linear(mi), d);
+#if defined(PINE_DUP_DIV) && defined(__HIP_DEVICE_COMPILE__)  /* cost measurement only: the normalisation's three divisions once more */
+  {
+    const float len = length(v);
+    dup_div(v.x, len), dup_div(v.y, len), dup_div(v.z, len);
+  }
+#endif
+  local_direction_lean(v, lo_d, inv);
 }
 PINE_HD bool cone_quadratic(const float* f, const DRay& ray, float& tmax, float& side) {  // geometry.cpp:415-434
   const f3 p = ld3(f), n = ld3(f + 3);
@@ -684,26 +753,32 @@ PINE_HD bool cylinder_solve(const float* f, const DRay& ray, float& t) {
 // The two tests of a transformed box (a record's f: lo, hi, the matrix at 6, its inverse at 18).  LEAN: the slab test is
 // box_slabs_lean -- the calls generate_baked_scene (pine_specialize.h) emits for records with finite bounds, lo <= hi;
 // the generic dispatch below, the host and the oracle comparison run box_slabs.
+// (LEAN: the local ray comes with its direction's reciprocals, from the short forms where the direction allows them --
+//  local_direction_lean above; the way back to a world distance keeps distance()'s guarded psqrt: nothing bounds its argument.)
 template <bool LEAN>
-PINE_HD bool obb_slabs(const float* f, f3 o, f3 d, float& tmin, float& tmax) {
-  if constexpr (LEAN) return box_slabs_lean(ld3(f), ld3(f + 3), o, d, tmin, tmax);
-  else return box_slabs(ld3(f), ld3(f + 3), o, d, tmin, tmax);
+PINE_HD bool obb_local_slabs(const float* f, const DRay& ray, f3& o, f3& d, float& tmin, float& tmax) {
+  if constexpr (LEAN) {
+    f3 inv;
+    obb_local_ray_lean(f, ray.o, ray.d, o, d, inv);
+    return box_slabs_lean(ld3(f), ld3(f + 3), o, d, inv, tmin, tmax);
+  } else {
+    obb_local_ray(f, ray.o, ray.d, o, d);
+    return box_slabs(ld3(f), ld3(f + 3), o, d, tmin, tmax);
+  }
 }
 template <bool LEAN>
 PINE_HD bool obb_hit_once(const float* f, const DRay& ray) {  // OBB::hit bbox.cpp:145-149
   f3 o, d;
-  obb_local_ray(f, ray.o, ray.d, o, d);
   float tmin = ray.tmin, tmax = ray.tmax;
   if constexpr (!LEAN)  // (LEAN: part of the slab test's one comparison)
     if (tmin > tmax) return false;
-  return obb_slabs<LEAN>(f, o, d, tmin, tmax);
+  return obb_local_slabs<LEAN>(f, ray, o, d, tmin, tmax);
 }
 template <bool LEAN>
 PINE_HD bool obb_intersect_once(const float* f, DRay& ray) {  // bbox.cpp:150-172: endpoints mapped back to world distances
   f3 o, d;
-  obb_local_ray(f, ray.o, ray.d, o, d);
   float tmin = ray.tmin, tmax = ray.tmax;
-  if (!obb_slabs<LEAN>(f, o, d, tmin, tmax)) return false;
+  if (!obb_local_slabs<LEAN>(f, ray, o, d, tmin, tmax)) return false;
   const m34 m = ld34(f + 6);
   const f3 ps = o + tmin * d;
   const f3 pe = o + tmax * d;

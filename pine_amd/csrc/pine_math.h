@@ -99,7 +99,88 @@ PINE_HD float pacos(float v) { return pine_libm::acosf_glibc(v); }
 // `a / b` in device code is hipcc's IEEE-correct expansion (v_div_scale x2, v_rcp, 5 fma/mul, v_div_fmas,
 // v_div_fixup).  A guarded short form (shared refined reciprocal + two residual steps, full expansion
 // outside a safe exponent range) was built, verified bit for bit on 1e11 operand pairs, and measured
-// SLOWER in the path kernel; it is not kept.  Plain division everywhere.
+// SLOWER in the path kernel: each call paid range compares and a rare branch of its own.  It is
+// not kept, and every division is plain -- but for the baked traversal (generate_baked_scene, pine_specialize.h;
+// DESIGN.md 7.3f), where ONE range test of the ray answers for all divisions of a traversal and the reciprocal
+// is one the traversal holds anyway.  Its pieces are the *_core functions and pdiv_short below.
+//
+// Why pdiv_short is `n / d`.  The compiler's expansion of n / d is
+//     ds = v_div_scale(d, d, n)    ns = v_div_scale(n, d, n)
+//     r0 = v_rcp(ds)   e0 = fma(-ds, r0, 1)   r1 = fma(e0, r0, r0)
+//     q  = ns * r1     rem = fma(-ds, q, ns)   q1 = fma(rem, r1, q)   rem2 = fma(-ds, q1, ns)
+//     q2 = v_div_fmas(rem2, r1, q1)            result = v_div_fixup(q2, d, n)
+// By the ISA reference's pseudo-code, v_div_scale_f32 returns its operand unchanged and leaves VCC clear unless
+// an operand is zero, denormal, infinite or NaN, the exponents of n and d differ by 96 or more, n has a biased
+// exponent of 23 or less, or 1 / d or n / d is denormal; with VCC clear v_div_fmas_f32 is fma(rem2, r1, q1); and
+// v_div_fixup_f32 returns its first operand with the sign of n * d unless an operand is zero, infinite or NaN or
+// the quotient over- or underflows.  For |n| and |d| in [2^-42, 2^42] (kDivLo, kDivHi: biased exponents 85 to
+// 169, difference at most 84, quotient and 1 / d in [2^-84, 2^84]) none of these conditions holds, so the
+// quotient is the core alone: r1 -- which IS prcp_core(d), the same three instructions -- then one product and
+// four fma.  The sign: the core's result is non-zero there and has the sign of n * d already.  A ZERO numerator
+// is outside the window for a reason: the core returns fma(+0, r1, q1) with q1 = -0 as +0, the wrong zero.
+// Negation commutes with every step (v_rcp is odd, fma(-a, -b, c) == fma(a, b, c), rounding is symmetric), so
+// prcp_core(-d) == -prcp_core(d) and the quotient by -d is pdiv_short(n, -d, -r1).
+// This is an argument from the instruction descriptions; what decides is tests/test_short_division.py, which
+// runs n / d beside the short form on the GPU over every denominator mantissa, the window's edges and 2^26 pairs.
+// The window of a RAY's components (kRayLo, kRayHi) lies strictly inside it, so that a difference of a ray
+// component and a literal of at most 2^40 (< 2^41) and the length of a vector of three such components
+// (< 2^41) are in the division's window as well.
+// -DPINE_NO_SHORT_DIV (through PINE_GPU_SPECIALIZE_EXTRA): no ray is ordinary, every site runs plain division --
+// the parent's arithmetic, for A/B runs.  Host builds and PINE_FAST_MATH never take the short forms.
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(PINE_FAST_MATH) && !defined(PINE_NO_SHORT_FORMS) && !defined(PINE_NO_SHORT_DIV)
+#define PINE_SHORT_DIV 1
+#endif
+constexpr float kDivLo = 0x1p-42f, kDivHi = 0x1p+42f;  // pdiv_short: |n| and |d| within
+constexpr float kRayLo = 0x1p-40f, kRayHi = 0x1p+40f;  // a ray's (and a box's local direction's) components within
+PINE_HD bool div_ordinary(float v) {  // (NaN compares false: not ordinary)
+  const float a = fabsf(v);
+  return a >= kDivLo && a <= kDivHi;
+}
+// prcp / psqrt without their range guards, for callers that have established 2^-120 <= |v| <= 2^120 (prcp) and
+// 2^-96 <= v <= 2^96 (psqrt) themselves
+PINE_HD float prcp_core(float v) {
+#if defined(PINE_SHORT_DIV)
+  const float r0 = __builtin_amdgcn_rcpf(v);
+  const float e0 = __builtin_fmaf(-v, r0, 1.0f);
+  return __builtin_fmaf(e0, r0, r0);
+#else
+  return prcp(v);
+#endif
+}
+PINE_HD float psqrt_core(float v) {
+#if defined(PINE_SHORT_DIV)
+  const float y = __builtin_amdgcn_rsqf(v);
+  const float s0 = v * y;
+  const float h = 0.5f * y;
+  const float r = __builtin_fmaf(-s0, s0, v);
+  return __builtin_fmaf(r, h, s0);
+#else
+  return psqrt(v);
+#endif
+}
+// n / d from r1 == prcp_core(d), for div_ordinary(n) && div_ordinary(d): the steps of the compiler's expansion
+// in its order and with its operand signs
+PINE_HD float pdiv_short(float n, float d, float r1) {
+#if defined(PINE_SHORT_DIV)
+  const float q = n * r1;
+  const float rem = __builtin_fmaf(-d, q, n);
+  const float q1 = __builtin_fmaf(rem, r1, q);
+  const float rem2 = __builtin_fmaf(-d, q1, n);
+  return __builtin_fmaf(rem2, r1, q1);
+#else
+  (void)r1;
+  return n / d;
+#endif
+}
+#if defined(PINE_DUP_DIV) && defined(__HIP_DEVICE_COMPILE__)  /* cost measurement only: a plain division once more on operands the compiler knows nothing about (same film; the extra time is its cost) */
+__device__ __forceinline__ void dup_div(float n, float d) {
+  asm volatile("" : "+v"(n), "+v"(d));
+  const float sink = n / d;
+  asm volatile("" : : "v"(sink));
+}
+#else
+PINE_HD void dup_div(float, float) {}
+#endif
 
 struct f2 {
   float x, y;
@@ -142,8 +223,19 @@ PINE_HD float length(f3 v) { return psqrt(length_squared(v)); }
 PINE_HD float distance(f3 a, f3 b) { return length(a - b); }
 // (Tried: v / len with one shared refined reciprocal applied to the three components behind a
 //  range guard.  Identical bits, 29 instead of 42 VALU instructions, and 3.5 % SLOWER in the path kernel:
-//  the guard's compares and the rare-path branch cost more than the divisions they save.  Plain division.)
+//  the guard's compares and the rare-path branch cost more than the divisions they save.  Plain division --
+//  here, for every caller without a bound on v.  The baked traversal's transformed boxes call normalize_short
+//  below, behind a range test that also stands in for the guards of psqrt and of three prcp: obb_local_lean,
+//  pine_device.h.)
 PINE_HD f3 div_by_length(f3 v, float d) { return v / d; }
+// normalize(v) for kRayLo <= |v.x|, |v.y|, |v.z| <= kRayHi: the squared length lies in [3 * 2^-80, 3 * 2^80], inside
+// psqrt's range; the length in [2^-40, 2^41), inside prcp's range and, like the components, inside pdiv_short's
+// window; and it is not zero, so normalize's `len == 0 ? v : q` selects q.
+PINE_HD f3 normalize_short(f3 v) {
+  const float len = psqrt_core(length_squared(v));
+  const float r1 = prcp_core(len);
+  return f3{pdiv_short(v.x, len, r1), pdiv_short(v.y, len, r1), pdiv_short(v.z, len, r1)};
+}
 PINE_HD f3 normalize(f3 v) {  // :736-741
   const float len = length(v);
   const f3 q = div_by_length(v, len);

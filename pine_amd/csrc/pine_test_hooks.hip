@@ -579,6 +579,97 @@ int pine_gpu_test_box_slabs(const float* boxes, const float* rays, int64_t n, ui
   return 0;
 }
 
+// pine_gpu_test_short_div: the baked traversal's short division (kind 0: the window test, pdiv_short over prcp_core, plain
+// division outside the window) and short normalisation (kind 1: local_direction_lean -- the direction and the reciprocals of
+// its components) beside the compiler's n / d and normalize() + prcp(), compared bit by bit on the device.
+__device__ __forceinline__ uint32_t short_div_word(uint64_t& x, uint32_t elo, uint32_t ehi) {  // splitmix64; a float's bits with a biased exponent in [elo, ehi]
+  x += 0x9e3779b97f4a7c15ull;
+  uint64_t z = x;
+  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+  z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+  z ^= z >> 31;
+  const uint32_t w = uint32_t(z), e = elo + uint32_t((uint64_t(uint32_t(z >> 32)) * (ehi - elo + 1)) >> 32);
+  return (w & 0x807fffffu) | (e << 23);
+}
+__device__ __forceinline__ bool bits_within(uint32_t u, float lo, float hi) {  // |value| in [lo, hi], asked of the bits
+  u &= 0x7fffffffu;
+  return u >= __float_as_uint(lo) && u <= __float_as_uint(hi);
+}
+__global__ void __launch_bounds__(256) test_short_div_kernel(const uint32_t* in, int kind, int gen, uint32_t p0, uint32_t p1, uint32_t p2, long long n,
+                                                             unsigned long long* stats, uint32_t* ex, int cap) {
+  unsigned long long taken = 0, outside = 0;
+  for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n; i += gridDim.x * 256ll) {
+    uint32_t u[3] = {0, 0, 0};
+    const int arity = kind == 0 ? 2 : 3;
+    if (gen == 0) {
+      for (int k = 0; k < arity; k++) u[k] = in[i * arity + k];
+    } else if (gen == 1) {  // numerator p1 over the denominators p0 + i
+      u[0] = p1, u[1] = p0 + uint32_t(i);
+    } else {
+      uint64_t x = (uint64_t(p0) << 32) ^ (uint64_t(i) * 3u);
+      for (int k = 0; k < arity; k++) u[k] = short_div_word(x, p1, p2);
+    }
+    uint32_t want[6], got[6];
+    int words;
+    bool took, inside;
+    if (kind == 0) {
+      const float num = __uint_as_float(u[0]), den = __uint_as_float(u[1]);
+      took = div_ordinary(num) && div_ordinary(den);
+      float q = pdiv_short(num, den, prcp_core(den));
+      if (!took) q = num / den;
+      want[0] = __float_as_uint(num / den), got[0] = __float_as_uint(q), words = 1;
+      inside = bits_within(u[0], kDivLo, kDivHi) && bits_within(u[1], kDivLo, kDivHi);
+    } else {
+      const f3 v = f3{__uint_as_float(u[0]), __uint_as_float(u[1]), __uint_as_float(u[2])};
+      f3 d, inv;
+      took = local_direction_lean(v, d, inv);
+      const f3 wd = normalize(v), winv = f3{prcp(wd.x), prcp(wd.y), prcp(wd.z)};
+      const float w6[6] = {wd.x, wd.y, wd.z, winv.x, winv.y, winv.z}, g6[6] = {d.x, d.y, d.z, inv.x, inv.y, inv.z};
+      for (int k = 0; k < 6; k++) want[k] = __float_as_uint(w6[k]), got[k] = __float_as_uint(g6[k]);
+      words = 6;
+      inside = bits_within(u[0], kRayLo, kRayHi) && bits_within(u[1], kRayLo, kRayHi) && bits_within(u[2], kRayLo, kRayHi);
+    }
+    taken += took ? 1 : 0;
+    outside += took && !inside ? 1 : 0;
+    int bad = -1;
+    for (int k = words - 1; k >= 0; k--)
+      if (want[k] != got[k]) bad = k;
+    if (bad >= 0) {
+      const unsigned long long slot = atomicAdd(&stats[1], 1ull);
+      if (slot < (unsigned long long)cap) {
+        uint32_t* e = ex + slot * 8;
+        e[0] = u[0], e[1] = u[1], e[2] = u[2], e[3] = uint32_t(bad), e[4] = want[bad], e[5] = got[bad], e[6] = took ? 1u : 0u, e[7] = 0u;
+      }
+    }
+  }
+  if (taken) atomicAdd(&stats[2], taken);
+  if (outside) atomicAdd(&stats[3], outside);
+}
+int pine_gpu_test_short_div(int device, int kind, int gen, const uint32_t* in, uint32_t p0, uint32_t p1, uint32_t p2, int64_t n, int64_t* stats,
+                            uint32_t* examples, int cap) {
+  if (kind < 0 || kind > 1 || gen < 0 || gen > 2 || (gen == 0) != (in != nullptr) || n < 0 || !stats || cap < 0 || (cap > 0 && !examples) ||
+      (gen == 1 && (kind != 0 || uint64_t(p0) + uint64_t(n) > 0x100000000ull)) || (gen == 2 && (p1 > p2 || p2 > 255u))) {
+    set_error("pine_gpu_test_short_div: bad argument");
+    return -1;
+  }
+  if (need_device(device)) return -1;
+  const size_t arity = kind == 0 ? 2 : 3;
+  DeviceBuffer<uint32_t> din, dex;
+  DeviceBuffer<unsigned long long> dstats;
+  if ((in && din.upload(in, size_t(n) * arity, __func__)) || dex.alloc(std::max<size_t>(size_t(cap) * 8, 1), __func__) || dstats.alloc(4, __func__)) return -1;
+  if (const hipError_t e = hipMemset(dstats, 0, 4 * sizeof(unsigned long long))) return hip_error(__func__, e);
+  if (const hipError_t e = hipMemset(dex, 0, std::max<size_t>(size_t(cap) * 8, 1) * 4)) return hip_error(__func__, e);
+  if (n > 0) {
+    const unsigned blocks = unsigned(std::min<int64_t>((n + 255) / 256, 4096));
+    hipLaunchKernelGGL(test_short_div_kernel, dim3(blocks), dim3(256), 0, 0, in ? din.get() : nullptr, kind, gen, p0, p1, p2, (long long)n, dstats.get(), dex.get(), cap);
+  }
+  unsigned long long h[4] = {};
+  if (hip_launch_check(__func__) || dstats.download(h, 4, __func__) || (cap > 0 && dex.download(examples, size_t(cap) * 8, __func__))) return -1;
+  stats[0] = n;
+  for (int k = 1; k < 4; k++) stats[k] = int64_t(h[k]);
+  return 0;
+}
+
 // pine_gpu_test_frame_table: the table as plan creation builds it (device < 0: here, on the host) or as a plan's kernels read it
 // (device >= 0: copied back from the plan's scene blob).  `generic`: per entry what the per-hit code computes at a point of that
 // face; `faces`: the face shape_surface_info reports for caller-given rays.
