@@ -146,6 +146,19 @@ int SceneHost::find_material(const char* name) const {
     if (material_names[i] == name) return i;
   return -1;
 }
+bool SceneHost::packed_prim_words(std::vector<int>& out) const {
+  out = accel.prims;
+  for (size_t i = size_t(accel.top_prim_begin); i < out.size(); i++) {
+    const int g = out[i];
+    if (g > kPrimIndexMask) {
+      set_error("too many geometries for the packed primitive word");
+      return false;
+    }
+    const DShape& sh = geometries[size_t(g)].shape;
+    out[i] = g | (materials[size_t(sh.material)].kind == MAT_EMISSIVE ? kPrimEmissiveBit : 0) | (sh.kind << kPrimKindShift);
+  }
+  return true;
+}
 // ---- shading nodes (node.h:13-297) ----------------------------------------------------------------
 static float node_un(char op, float x) {  // NodeUnary::eval node.h:158-175
   switch (op) {
@@ -2000,45 +2013,41 @@ int pine_gpu_scene_accel_bvhs(pine_gpu_scene* s, int32_t* out, int64_t cap) {
   return int(a.bvhs.size());
 }
 
-int64_t pine_gpu_scene_specialized_source(pine_gpu_scene* s, char* out, int64_t cap) {
-  if (!check(s)) return -1;
+// The generated text of the scene under the variant class that allows it ("": the scene does not qualify): without a mesh the
+// whole scene, which the kernels without traversal stages run; with meshes its top level, which those with such stages run.
+static bool scene_baked_text(pine_gpu_scene* s, std::string& text) {
+  if (!check(s)) return false;
   if (!s->host.accel.built) s->host.build_accel();
   const FlatAccel& a = s->host.accel;
   std::vector<DShape> shapes;
   for (auto& g : s->host.geometries) shapes.push_back(g.shape);
-  std::vector<int> words = a.prims;
-  for (size_t i = size_t(a.top_prim_begin); i < words.size(); i++) {
-    const DShape& sh = shapes[size_t(words[i])];
-    words[i] |= (s->host.materials[size_t(sh.material)].kind == MAT_EMISSIVE ? kPrimEmissiveBit : 0) | (sh.kind << kPrimKindShift);
-  }
-  // (no mesh: the whole scene; exactly one mesh: its top level, for the traversal-stage variants)
-  const std::string text = a.top_prim_begin == 0 ? generate_baked_scene(a, shapes, words) : a.bvhs.size() == 2 ? generate_baked_scene(a, shapes, words, true) : std::string();
+  std::vector<int> words;
+  if (!s->host.packed_prim_words(words)) return false;
+  text = bake_scene(a, shapes, words, a.top_prim_begin != 0).text;
+  return true;
+}
+int64_t pine_gpu_scene_specialized_source(pine_gpu_scene* s, char* out, int64_t cap) {
+  std::string text;
+  if (!scene_baked_text(s, text)) return -1;
   if (out && cap > int64_t(text.size())) memcpy(out, text.c_str(), text.size() + 1);
   return int64_t(text.size());
 }
 
 int pine_gpu_test_specialize_compile(pine_gpu_scene* s, uint32_t features, int ctx, const char* arch, char* path_out, int64_t cap) {
-  if (!arch || (s && !check(s))) return -1;
+  if (!arch) return -1;
   std::string text;  // (no scene: level 1, the feature set alone with the generic traversal)
   if (s) {
-    const int64_t n = pine_gpu_scene_specialized_source(s, nullptr, 0);
-    if (n <= 0) {
-      if (n == 0) set_error("the scene does not qualify for specialisation");
-      return -1;
-    }
-    text.assign(size_t(n) + 1, '\0');
-    pine_gpu_scene_specialized_source(s, &text[0], n + 1);
-    text.resize(size_t(n));
-    features |= 1u << 17;  // F_BAKED (pine_device.h)
+    if (!scene_baked_text(s, text)) return -1;
+    if (text.empty()) return set_error("the scene does not qualify for specialisation"), -1;
+    features |= kBakedFeature;
   }
-  std::string path, err;
-  bool hit = false;
-  if (!compile_baked_kernel(text, features, ctx, arch, path, err, &hit)) {
-    set_error(err);
-    return -1;
-  }
-  if (path_out && cap > int64_t(path.size())) memcpy(path_out, path.c_str(), path.size() + 1);
-  return hit ? 1 : 0;
+  KernelRequest R;  // lookup + compile, as plan creation does it for a caller who waits
+  R.baked = text, R.features = features, R.ctx = ctx, R.arch = arch;
+  std::string err;
+  const int found = kernel_cache_lookup(R, err);
+  if (found < 0 || (found == 0 && !kernel_compile(R, err))) return set_error(err), -1;
+  if (path_out && cap > int64_t(R.path.size())) memcpy(path_out, R.path.c_str(), R.path.size() + 1);
+  return found;
 }
 
 // Film::finalize + tone mapping + to_uint8_array (film.cpp:21-27,66-68; color.cpp:6-23;

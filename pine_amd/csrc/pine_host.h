@@ -145,6 +145,9 @@ struct SceneHost {
   f3 node_fold(int id) const { return nodes[size_t(id)].folded; }  // value of a node subtree that does not read the surface
   // flatten the programs of every material into `ops`; fills DMaterial::prog / folded literals of `out`
   bool compile_node_programs(std::vector<DMaterial>& out, std::vector<DNodeOp>& ops) const;
+  // accel.prims with every top-level entry as its packed primitive word (geometry | emissive | kind, pine_types.h), as the
+  // traversal reports it; false with the error set when a geometry index does not fit the word
+  bool packed_prim_words(std::vector<int>& out) const;
   int find_material(const char* name) const;
   int add_material(const char* name, const DMaterial& m, const std::string& desc);
   int add_geometry(HostGeometry g);

@@ -23,7 +23,6 @@
 #include <climits>
 #include <cmath>
 #include <cstring>
-#include <deque>
 
 #include "pine_plan.h"
 #include "pine_bvh_build_device.h"
@@ -247,27 +246,6 @@ static int validate_device_scene(const FlatAccel& A, const std::vector<DShape>& 
 
 using namespace pine_gpu;
 
-// Scene-specialised kernels (pine_specialize.h): the stage-queued kernel compiled FOR THIS SCENE.
-//  (1) its exact feature set: the precompiled variants are a handful of supersets (pine_variants.h) -- a scene of spheres
-//      under a point light runs the everything-but-Subsurface kernel and pays for every shape kind, node programs and the
-//      Sobol sampler in registers (38 spilled VGPRs).  `need` is what plan_build found in the scene; the LDS layout flags
-//      (and F_SSS, which sizes the per-context records) stay those of the chosen variant, so every buffer size computed
-//      from it stays right.
-//  (2) if the scene has no meshes and its BVH is small enough to unroll: the BVH and primitive records baked in; one mesh
-//      under a small top level: the top level as code.
-// Nothing to gain (the variant IS the exact set, nothing to bake): the precompiled kernel runs.
-//
-// Modes.  DEFAULT (no flag): automatic and never in the caller's way -- a code object already in the cache is loaded at plan
-// creation (about a millisecond); otherwise the compiler runs in the BACKGROUND (a process-wide queue of at most
-// kSpecWorkers compiler children, keyed by content, shared by every plan that wants the same kernel and outliving the plan
-// that asked first) while the precompiled kernel renders; the first launch after the build has finished -- of this plan or of
-// any later plan of the same geometry -- runs the scene's own kernel.  Nothing can fail because of it: no compiler, no
-// headers, no cache directory, a full queue all leave the precompiled kernel in place (plan stats: specialized 0 or -1).
-// PINE_GPU_FLAG_SPECIALIZE (or $PINE_GPU_SPECIALIZE=1): the caller WANTS the scene's kernel -- plan creation waits for the
-// compiler and a kernel that cannot be built fails the plan; with _ASYNC the build runs in the background as above but a
-// failure is still reported (specialized == -1).  PINE_GPU_FLAG_NO_SPECIALIZE / $PINE_GPU_SPECIALIZE=0: precompiled only.
-enum : int { kSpecSourceNone = 0, kSpecSourceCache = 1, kSpecSourceCompiledHere = 2, kSpecSourceBackground = 3 };
-
 namespace pine_gpu {
 AbiFingerprint abi_fingerprint() {
   return AbiFingerprint{sizeof(DeviceScene), sizeof(WorkParams), sizeof(Counters), sizeof(DNode), sizeof(DShape), sizeof(DMaterial), sizeof(DLight),
@@ -275,51 +253,6 @@ AbiFingerprint abi_fingerprint() {
                         kTravRecordDwords, kQCtxGlobalDwordsPlain, kQCtxGlobalDwordsSss};
 }
 }  // namespace pine_gpu
-
-// A code object loaded into a device's context, shared by the plans that run it: hipModuleLoadData of a scene's kernel is a
-// millisecond or two, which a one-shot render (create, launch, destroy) of the same geometry would pay on every call.  The
-// process keeps the last kMaxLoaded of them per (device, content key); a module is unloaded when the table has dropped it and
-// the last plan that launches it is gone.
-struct LoadedKernel {
-  int device = 0;
-  std::string key, image;  // (the image is kept for the module's lifetime: the runtime may build the program lazily from it)
-  hipModule_t module = nullptr;
-  hipFunction_t fn = nullptr;
-  ~LoadedKernel() {
-    if (module) {
-      int keep = 0;
-      (void)hipGetDevice(&keep);
-      (void)hipSetDevice(device);
-      (void)hipModuleUnload(module);
-      (void)hipSetDevice(keep);
-    }
-  }
-};
-struct LoadedKernels {
-  static constexpr size_t kMaxLoaded = 16;
-  std::mutex mu;
-  std::deque<std::shared_ptr<LoadedKernel>> recent;
-  static LoadedKernels& get() {
-    static LoadedKernels* q = new LoadedKernels();  // (never destroyed: unloading modules while the runtime goes down is not safe)
-    return *q;
-  }
-  std::shared_ptr<LoadedKernel> find(int device, const std::string& key) {
-    std::lock_guard<std::mutex> lock(mu);
-    for (auto& k : recent)
-      if (k->device == device && k->key == key) return k;
-    return nullptr;
-  }
-  void remember(const std::shared_ptr<LoadedKernel>& k) {
-    std::lock_guard<std::mutex> lock(mu);
-    recent.push_front(k);
-    if (recent.size() > kMaxLoaded) recent.pop_back();
-  }
-  void forget(const std::string& key) {
-    std::lock_guard<std::mutex> lock(mu);
-    for (auto it = recent.begin(); it != recent.end();)
-      it = (*it)->key == key ? recent.erase(it) : it + 1;
-  }
-};
 
 // The plan-time measurement aids, read from the environment once per plan: the phases of plan_build read only
 // this.  The numbers are kUnset when their variable is not set.
@@ -363,144 +296,20 @@ static PlanKnobs read_knobs() {
                    num("PINE_GPU_OWNED_TILES"), num("PINE_GPU_TEST_TILE_SLOTS"), num("PINE_GPU_FRAME_TABLE")};
 }
 
-static int plan_adopt_kernel(pine_gpu_plan* p, bool compile_here);
-static int plan_specialize(pine_gpu_plan* p, const FlatAccel& A, const std::vector<DShape>& shapes, const std::vector<int>& packed_prims,
-                           const pine_gpu_render_params* prm, unsigned need, const PlanKnobs& K) {
+// Plan creation asks for the scene's own kernel (SceneKernel::request, pine_scene_kernel.h: the modes), unless the caller or the
+// environment rules it out or the plan runs a kernel it does not replace.
+static int plan_request_scene_kernel(pine_gpu_plan* p, const FlatAccel& A, const std::vector<DShape>& shapes, const std::vector<int>& packed_prims,
+                                     const pine_gpu_render_params* prm, unsigned need, const PlanKnobs& K) {
   if (K.pin_kind >= 0) return 0;  // (PINE_GPU_TEST_VARIANT: the pinned variant renders; no cache lookup)
-  // explicit: the caller asked for the scene's kernel (failures are errors); automatic: the default (failures are silent)
-  bool explicit_want = (prm->flags & PINE_GPU_FLAG_SPECIALIZE) != 0;
-  bool automatic = !explicit_want && !(prm->flags & PINE_GPU_FLAG_NO_SPECIALIZE);
-  if (K.specialize != kUnset) {
-    if (K.specialize != 0) explicit_want = true, automatic = false;
-    else explicit_want = automatic = false;
-  }
-  if ((!explicit_want && !automatic) || p->queue_variant < 0 || (prm->flags & (PINE_GPU_FLAG_FAST | PINE_GPU_FLAG_VERTEX_LOG))) return 0;
-  const PineKernelVariant& V = kQueueVariants[p->queue_variant];
-  const auto t0 = std::chrono::steady_clock::now();
-  const unsigned kLayout = F_LDS_SCENE | F_LDS_TOP | F_LDS_REST | F_XSTAGE | F_SSS;
-  unsigned exact = (V.features & kLayout) | need;
-  std::string baked;
+  // 1: the caller asked for the scene's kernel (failures are errors); 0: automatic, the default (failures are silent); -1: not at all
+  int want = (prm->flags & PINE_GPU_FLAG_SPECIALIZE) ? 1 : (prm->flags & PINE_GPU_FLAG_NO_SPECIALIZE) ? -1 : 0;
+  if (K.specialize != kUnset) want = K.specialize != 0 ? 1 : -1;
+  if (want < 0 || p->queue_variant < 0 || (prm->flags & (PINE_GPU_FLAG_FAST | PINE_GPU_FLAG_VERTEX_LOG))) return 0;
+  const SceneKernel::Mode mode = want == 0 ? SceneKernel::Mode::kAutomatic
+                                 : (prm->flags & PINE_GPU_FLAG_SPECIALIZE_ASYNC) ? SceneKernel::Mode::kExplicitAsync : SceneKernel::Mode::kExplicit;
   // (a baked scene IS pine's visiting order as code: the EmbreeAccel order mode keeps to the feature-set level)
-  if (!(prm->flags & (PINE_GPU_FLAG_SPECIALIZE_NO_BAKE | PINE_GPU_FLAG_ORDER_EMBREE))) {
-    if (!(V.features & F_XSTAGE) && A.top_prim_begin == 0) baked = generate_baked_scene(A, shapes, packed_prims);
-    // one mesh under a small top level, traversal stages (C5's class): the top level as code, the mesh left to the flat traversal
-    else if ((V.features & F_XSTAGE) && A.bvhs.size() == 2) baked = generate_baked_scene(A, shapes, packed_prims, true);
-  }
-  if (baked.empty() && exact == V.features && !K.specialize_force) return 0;  // (FORCE: experiments through $PINE_GPU_SPECIALIZE_EXTRA)
-  if (!baked.empty()) exact |= F_BAKED;
-  hipDeviceProp_t prop;
-  HIP_OK(hipGetDeviceProperties(&prop, prm->device));
-  std::string arch = prop.gcnArchName;  // "gfx950:sramecc+:xnack-" -> "gfx950"
-  if (arch.find(':') != std::string::npos) arch = arch.substr(0, arch.find(':'));
-  KernelRequest& R = p->spec_request;
-  R.baked = baked, R.features = exact, R.ctx = V.ctx, R.arch = arch;
-  p->spec_t0 = t0;
-  p->spec_explicit = explicit_want;
-  std::string err;
-  const int found = kernel_cache_lookup(R, err);
-  if (found < 0) {
-    if (!explicit_want) {  // (no headers / no cache directory: the precompiled kernel it is)
-      R = KernelRequest();
-      return 0;
-    }
-    set_error(err);
-    return -1;
-  }
-  if (found == 1) {
-    // in the cache already: load it now (a file the runtime refuses is recompiled -- here when the caller waits for the
-    // scene's kernel anyway, in the background otherwise)
-    p->spec_source = kSpecSourceCache;
-    if (plan_adopt_kernel(p, explicit_want && !(prm->flags & PINE_GPU_FLAG_SPECIALIZE_ASYNC)) == 0) return 0;
-    if (explicit_want && !(prm->flags & PINE_GPU_FLAG_SPECIALIZE_ASYNC)) return -1;
-    // a code object the runtime refuses (cut short by a full disk, another ROCm's output): out of the way, and built afresh in
-    // the background; a packaged one that cannot be removed is bypassed for the user's cache
-    const bool packaged = R.packaged;
-    (void)unlink(R.path.c_str());
-    const int again = kernel_cache_lookup(R, err, packaged);
-    if (again < 0 || (again == 1 && plan_adopt_kernel(p, false) != 0)) {
-      p->spec_state.store(kSpecFailed);
-      p->spec_async_error = again < 0 ? err : std::string(pine_gpu_last_error());
-      return 0;
-    }
-    if (again == 1) return 0;
-  } else if (explicit_want && !(prm->flags & PINE_GPU_FLAG_SPECIALIZE_ASYNC)) {
-    p->spec_source = kSpecSourceCompiledHere;
-    return plan_adopt_kernel(p, true);
-  }
-  // the compiler runs beside the first renders (host work only: files and a child process); a launch adopts the kernel once
-  // it is there.  Until then -- and for good if the build fails -- the precompiled kernel renders the same film.
-  p->spec_source = kSpecSourceBackground;
-  p->spec_job = SpecQueue::get().submit(R, explicit_want);
-  if (!p->spec_job) {
-    p->spec_state.store(explicit_want ? kSpecFailed : kSpecNone);
-    p->spec_async_error = "the background compile queue is full";
-    return 0;
-  }
-  p->spec_state.store(kSpecBuilding);
-  return 0;
-}
-
-// Load the plan's scene-specialised kernel (compiling it first when `compile_here`) and make it the one that launches.
-// (Two attempts when compiling here: a cached code object the runtime refuses -- a file cut short by a full disk, another
-// ROCm's output -- is removed and compiled afresh, once; a packaged one that cannot be removed is bypassed.)
-static int plan_adopt_kernel(pine_gpu_plan* p, bool compile_here) {
-  KernelRequest& R = p->spec_request;
-  bool skip_packaged = false;
-  for (int attempt = 0;; attempt++) {
-    std::string err;
-    const int found = kernel_cache_lookup(R, err, skip_packaged);
-    if (found < 0 || (found == 0 && (!compile_here || !kernel_compile(R, err)))) {
-      set_error(found == 0 && !compile_here ? "scene specialisation: the code object is not in the cache" : err);
-      return -1;
-    }
-    const bool from_cache = found == 1;
-    if (auto loaded = LoadedKernels::get().find(p->device, R.key)) {  // this geometry's kernel is in this device's context already
-      p->spec_loaded = loaded;
-      p->spec_module = loaded->module, p->spec_fn = loaded->fn;
-      break;
-    }
-    hipError_t e = hipErrorInvalidImage;
-    auto k = std::make_shared<LoadedKernel>();
-    k->device = p->device, k->key = R.key;
-    if (read_file(R.path, k->image) && code_object_is_whole(k->image)) {
-      e = hipModuleLoadData(&k->module, k->image.data());
-      if (e == hipSuccess) e = hipModuleGetFunction(&k->fn, k->module, kernel_symbol(R.features, R.ctx).c_str());
-    }
-    if (e == hipSuccess) {
-      LoadedKernels::get().remember(k);
-      p->spec_loaded = k;
-      p->spec_module = k->module, p->spec_fn = k->fn;
-      break;
-    }
-    (void)hipGetLastError();
-    k.reset();  // (unloads what was loaded)
-    p->spec_module = nullptr, p->spec_fn = nullptr;
-    if (attempt == 0 && compile_here && from_cache) {
-      if (unlink(R.path.c_str()) != 0) skip_packaged = true;  // (a read-only install: compile into the user's cache instead)
-      continue;
-    }
-    set_error("scene specialisation: the runtime does not load " + R.path + " (" + hipGetErrorString(e) + ")");
-    return -1;
-  }
-  p->spec_features = R.features;
-  p->spec_baked = !R.baked.empty();
-  p->specialize_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - p->spec_t0).count();
-  return 0;
-}
-
-// PINE_GPU_FLAG_SPECIALIZE_ASYNC / automatic mode: has the background build finished?  Called by every launch and by stats_get.
-static void plan_poll_background(pine_gpu_plan* p) {
-  if (p->spec_state.load() != kSpecBuilding || !p->spec_job) return;
-  const int js = p->spec_job->state.load();
-  if (js == kSpecBuilding) return;
-  if (js == kSpecBuilt && plan_adopt_kernel(p, false) == 0) {
-    p->spec_state.store(kSpecAdopted);
-  } else {
-    p->spec_async_error = js == kSpecFailed ? p->spec_job->error : std::string(pine_gpu_last_error());
-    p->spec_state.store(kSpecFailed);
-  }
-  p->spec_job->waiters.fetch_sub(1);
-  p->spec_job.reset();
+  const bool may_bake = !(prm->flags & (PINE_GPU_FLAG_SPECIALIZE_NO_BAKE | PINE_GPU_FLAG_ORDER_EMBREE));
+  return p->scene_kernel.request(mode, p->device, kQueueVariants[p->queue_variant], need, may_bake, K.specialize_force, A, shapes, packed_prims);
 }
 
 static int plan_check_counters(const Counters& c) {
@@ -599,10 +408,6 @@ int pine_gpu_set_table_path(const char* path) {
 
 void pine_gpu_plan_destroy(pine_gpu_plan* p) {
   if (!p) return;
-  if (p->spec_job) {  // (a background build goes on for the next plan of this geometry; a job nobody waits for is dropped from the queue)
-    p->spec_job->waiters.fetch_sub(1);
-    p->spec_job.reset();
-  }
   (void)hipSetDevice(p->device);
   // the plan's buffers go back to the pool (its members' destructors), which hands them to the next plan without the device-wide
   // synchronisation hipFree implies: the plan's last launch must have finished first
@@ -695,7 +500,7 @@ static bool build_tri_packets(const FlatAccel& A, std::vector<uint32_t>& out, in
 }
 
 // The plan's precompiled path kernel: the declared-tolerance variant, else the stage-queued one, else the megakernel's.  (The
-// scene's own kernel, spec_fn, replaces a stage-queued variant and keeps its contexts and LDS layout.)
+// scene's own kernel, pine_gpu_plan::scene_kernel, replaces a stage-queued variant and keeps its contexts and LDS layout.)
 struct PathKernel {
   const void* fn;
   unsigned features;
@@ -799,16 +604,7 @@ static int assemble_scene(pine_gpu_plan* p, SceneHost& H, const pine_gpu_render_
   S.off_node_ops = put(sp.node_ops.data(), sp.node_ops.size() * sizeof(DNodeOp));
   S.off_bvhs = put(A.bvhs.data(), A.bvhs.size() * sizeof(DBvh));
   std::vector<int>& packed_prims = sp.packed_prims;
-  packed_prims = A.prims;
-  for (size_t i = size_t(A.top_prim_begin); i < packed_prims.size(); i++) {
-    const int g = packed_prims[i];
-    if (g > kPrimIndexMask) {
-      set_error("too many geometries for the packed primitive word");
-      return -1;
-    }
-    const DShape& sh = shapes[size_t(g)];
-    packed_prims[i] = g | (H.materials[size_t(sh.material)].kind == MAT_EMISSIVE ? kPrimEmissiveBit : 0) | (sh.kind << kPrimKindShift);
-  }
+  if (!H.packed_prim_words(packed_prims)) return -1;
   S.off_prims = 0;  // (the primitive index list stays on the host: the leaf-ordered record copies below replace it)
   std::vector<DShape> leaf_shapes;  // SceneView::leaf
   for (size_t i = size_t(A.top_prim_begin); i < packed_prims.size(); i++) {
@@ -1368,7 +1164,7 @@ static void schedule_params(pine_gpu_plan* p, const FlatAccel& A, const pine_gpu
   W.trav_min_trips = 8;
   // (a kernel with the top level baked in, pine_specialize.h: most rays end in the code part and free their lanes at once;
   //  refilling after three trips instead of eight: C5 107.3 -> 100.2 ms)
-  if (!p->spec_request.baked.empty() && (p->spec_request.features & F_XSTAGE)) W.trav_min_trips = 3;
+  if (p->scene_kernel.baked_top_requested()) W.trav_min_trips = 3;
   if (K.trav_min_lanes != kUnset) W.trav_min_lanes = K.trav_min_lanes;
   if (K.trav_min_trips != kUnset) W.trav_min_trips = K.trav_min_trips > 0 ? K.trav_min_trips : 1;
   // Subsurface is the only in-path user of the RNG and only before a path's first non-delta bounce: such a path hands its
@@ -1522,7 +1318,7 @@ static int plan_build(pine_gpu_plan* p, pine_gpu_scene* scene, const pine_gpu_re
   if (assemble_scene(p, H, prm, sp, frames) || upload_sampler_tables(p, *tables_blob, prm, spp)) return -1;
   p->S.spp = spp;
   const unsigned need = scene_features(sp, prm);
-  if (choose_variants_with_frames(p, A, sp, prm, need, K) || plan_specialize(p, A, sp.shapes, sp.packed_prims, prm, need, K)) return -1;
+  if (choose_variants_with_frames(p, A, sp, prm, need, K) || plan_request_scene_kernel(p, A, sp.shapes, sp.packed_prims, prm, need, K)) return -1;
   bool uber_rng = false;
   if (choose_items(p, H, sp, prm, spp, K, uber_rng)) return -1;
   schedule_params(p, A, prm, uber_rng, K);
@@ -1566,8 +1362,8 @@ static int launch_path_kernel(pine_gpu_plan* p, WorkParams& W, float4* samples, 
   // (the kernels of the other translation units: same argument layout, launched untyped; the megakernel has no context records)
   void* queue_args[] = {&p->S, &W, &ckpt, &samples, &fold, &ctxg, &counters};
   void* mega_args[] = {&p->S, &W, &ckpt, &samples, &fold, &counters};
-  if (p->spec_fn)
-    HIP_OK(hipModuleLaunchKernel(p->spec_fn, unsigned(grid), 1, 1, kQBlock, 1, 1, unsigned(p->lds_bytes), stream, queue_args, nullptr));
+  if (const hipFunction_t own = p->scene_kernel.fn())
+    HIP_OK(hipModuleLaunchKernel(own, unsigned(grid), 1, 1, kQBlock, 1, 1, unsigned(p->lds_bytes), stream, queue_args, nullptr));
   else
     HIP_OK(hipLaunchKernel(kernel.fn, dim3(grid), dim3(kernel.block), kernel.queued() ? queue_args : mega_args, p->lds_bytes, stream));
   return 0;
@@ -1588,7 +1384,7 @@ static int plan_launch_pass(pine_gpu_plan* p, int j, void* film_dev, hipStream_t
   // a background build that has finished: this launch and every later one run the scene's own kernel -- between two passes
   // too: the same bits.  (A code object the runtime refuses leaves the precompiled kernel in place -- same film; plan stats say
   // which one runs.)
-  plan_poll_background(p);
+  p->scene_kernel.poll();
   if (j == 0) g_progress.store(0.0f);
   const int spp = p->S.spp;
   const PassPlan::Pass a = PP.pass(j, spp);
@@ -1663,8 +1459,7 @@ static int plan_launch(pine_gpu_plan* p, void* film_dev, void* stream, bool pack
 
 void pine_gpu_release_cached_memory(void) {
   DevicePool::get().release_all();
-  std::lock_guard<std::mutex> lock(LoadedKernels::get().mu);
-  LoadedKernels::get().recent.clear();  // (a module is unloaded when the last plan that launches it is gone)
+  LoadedKernels::get().clear();
 }
 
 int pine_gpu_plan_launch(pine_gpu_plan* p, void* film_dev, void* stream) { return plan_launch(p, film_dev, stream, false); }
@@ -1755,13 +1550,9 @@ int pine_gpu_plan_stats_get(pine_gpu_plan* p, pine_gpu_plan_stats* out) {
   out->spp_effective = p->S.spp;
   out->samples_per_item = p->W.samples_per_item;
   out->serial_tiles = p->W.serial_tiles;
-  plan_poll_background(p);
-  out->specialized = p->spec_fn ? (p->spec_baked ? 2 : 1) : p->spec_state.load() == kSpecFailed ? -1 : 0;
-  out->specialize_source = p->spec_fn || p->spec_state.load() == kSpecBuilding ? p->spec_source : 0;
-  out->specialize_pending = p->spec_state.load() == kSpecBuilding ? 1 : 0;
   const PathKernel kernel = plan_kernel(p);
-  out->kernel_features = p->spec_fn ? p->spec_features : kernel.features;
-  out->specialize_ms = p->specialize_ms;
+  p->scene_kernel.poll();
+  p->scene_kernel.fill_stats(out, kernel.features);
   out->grid_blocks = p->grid;
   out->block_threads = kernel.block;
   out->lds_bytes = int(p->lds_bytes);
@@ -1836,12 +1627,12 @@ int pine_gpu_plan_debug_sections(pine_gpu_plan* p, uint64_t out[16]) {
     for (RegFn f : regs)
       if (f(rl, rh)) return -1;
   }
-  if (p->spec_module) {
+  if (const hipModule_t own = p->scene_kernel.module()) {
     // the scene's own kernel (a module of its own) keeps its own copies of the REGION counters
     hipDeviceptr_t dl = nullptr, dh = nullptr;
     size_t bl = 0, bh = 0;
-    if (hipModuleGetGlobal(&dl, &bl, p->spec_module, "_ZN8pine_gpuL14g_region_lanesE") == hipSuccess &&
-        hipModuleGetGlobal(&dh, &bh, p->spec_module, "_ZN8pine_gpuL13g_region_hitsE") == hipSuccess && bl == sizeof rl && bh == sizeof rh) {
+    if (hipModuleGetGlobal(&dl, &bl, own, "_ZN8pine_gpuL14g_region_lanesE") == hipSuccess &&
+        hipModuleGetGlobal(&dh, &bh, own, "_ZN8pine_gpuL13g_region_hitsE") == hipSuccess && bl == sizeof rl && bh == sizeof rh) {
       unsigned long long ml[16], mh[16];
       if (hipMemcpy(ml, dl, sizeof ml, hipMemcpyDeviceToHost) == hipSuccess && hipMemcpy(mh, dh, sizeof mh, hipMemcpyDeviceToHost) == hipSuccess)
         for (int i = 0; i < 16; i++) rl[i] += ml[i], rh[i] += mh[i];

@@ -8,7 +8,6 @@
 
 #include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <cstdio>
 #include <map>
 #include <memory>
@@ -21,7 +20,6 @@
 
 #include "../../include/pine_gpu.h"
 #include "pine_host.h"
-#include "pine_specialize.h"
 #include "pine_variants.h"
 
 struct pine_gpu_scene;
@@ -202,6 +200,7 @@ struct DevicePool {
 };
 }  // namespace pine_gpu
 #include "pine_device_buffer.h"
+#include "pine_scene_kernel.h"
 namespace pine_gpu {
 
 // The frame table of a scene's shapes (pine_device.h frame_entry): one entry per face of every Rect, AABB and OBB
@@ -290,21 +289,8 @@ struct pine_gpu_plan {
   PinnedOwner<unsigned long long> h_progress;  // host-mapped progress word (PINE_GPU_FLAG_PROGRESS)
   float accel_build_ms = 0.0f, upload_ms = 0.0f;  // host-side cost of plan creation (reported by stats_get)
   bool accel_on_device = false;
-  // PINE_GPU_FLAG_SPECIALIZE: the queue kernel compiled for this scene (pine_specialize.h); null: the precompiled variant
-  std::shared_ptr<struct LoadedKernel> spec_loaded;  // (shared with every plan of this geometry on this device: LoadedKernels)
-  hipModule_t spec_module = nullptr;
-  hipFunction_t spec_fn = nullptr;
-  unsigned spec_features = 0;  // ... its feature set (the scene's own), and whether the scene's BVH is baked in
-  bool spec_baked = false;
-  KernelRequest spec_request;  // what to compile (filled at plan creation)
-  std::chrono::steady_clock::time_point spec_t0;
-  bool spec_explicit = false;  // the caller asked for the scene's kernel (PINE_GPU_FLAG_SPECIALIZE): failures are errors
-  int spec_source = 0;         // kSpecSource*: where the scene's kernel came / comes from
-  // background build (the default mode, PINE_GPU_FLAG_SPECIALIZE_ASYNC): a job of the process-wide queue; a launch adopts its result
-  std::atomic<int> spec_state{0};  // kSpecNone / kSpecBuilding / kSpecAdopted / kSpecFailed
-  std::shared_ptr<SpecJob> spec_job;
-  std::string spec_async_error;
-  float specialize_ms = 0.0f;
+  // the stage-queued kernel compiled for this scene (pine_scene_kernel.h), when there is one: it launches instead of the variant
+  SceneKernel scene_kernel;
   // An AOIntegrator plan (pine_gpu_ao_plan_create, pine_ao_host.h): S.spp is the AO sample count, the kernel one of
   // pine_gpu_ao_variants() in the schedule `ao_serial` selects; per film pixel one counter of unoccluded rays.
   bool ao = false, ao_serial = false;

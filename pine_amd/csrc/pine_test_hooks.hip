@@ -366,13 +366,14 @@ int pine_gpu_plan_test_traverse_baked(pine_gpu_plan* p, const float* rays, int64
     set_error("null argument");
     return -1;
   }
-  if (!p->spec_module || !p->spec_baked) {
+  const hipModule_t baked = p->scene_kernel.baked_module();
+  if (!baked) {
     set_error("the plan has no baked scene (PINE_GPU_FLAG_SPECIALIZE, a scene that qualifies)");
     return -1;
   }
   HIP_OK(hipSetDevice(p->device));
   hipFunction_t fn;
-  HIP_OK(hipModuleGetFunction(&fn, p->spec_module, "pine_baked_traverse_test"));
+  HIP_OK(hipModuleGetFunction(&fn, baked, "pine_baked_traverse_test"));
   DeviceBuffer<float> dr;
   DeviceBuffer<unsigned> dout;
   if (dr.upload(rays, size_t(nrays) * 8, __func__) || dout.alloc(size_t(nrays) * 4, __func__)) return -1;

@@ -198,6 +198,34 @@ def test_generated_unit_checks_the_headers_it_is_compiled_from(monkeypatch, tmp_
     assert "not the ones libpine_gpu.so was built from" in _lib.last_error()
 
 
+@pytest.mark.parametrize("sanitizer", ["address,undefined", "thread"])
+def test_background_queue_and_waiter_handle_stand_alone(tmp_path, sanitizer):
+    """The background compile queue and the handle a waiting plan holds (SpecQueue, SpecWaiter) are plain C++:
+    tools/sanitize/spec_queue_main.cpp drives them with a fake compiler behind a gate -- a shared job, cancellation, a full
+    queue, failure and retry, the handle's count, shutdown -- as an ordinary program built with a sanitizer."""
+    import subprocess
+    from conftest import ROOT
+    if not shutil.which("g++"):
+        pytest.skip("no g++")
+    # (the runtimes linked into the program: an ordinary executable, whatever else the process environment loads)
+    static = ["-static-libtsan"] if sanitizer == "thread" else ["-static-libasan", "-static-libubsan"]
+    flags = ["g++", "-std=c++17", "-pthread", "-g", "-O1", "-fsanitize=" + sanitizer] + static
+    if sanitizer == "thread":  # (not every machine has the runtime, or an address-space layout it starts under)
+        probe = tmp_path / "probe.cpp"
+        probe.write_text("#include <thread>\nint main() { int x = 0; std::thread t([&] { x = 1; }); t.join(); return x - 1; }\n")
+        r = subprocess.run(flags + [str(probe), "-o", str(tmp_path / "probe")], capture_output=True, text=True)
+        if r.returncode != 0:
+            pytest.skip("g++ does not link -fsanitize=thread here: " + r.stderr[-300:])
+        r = subprocess.run([str(tmp_path / "probe")], capture_output=True, text=True, timeout=60)
+        if r.returncode != 0:
+            pytest.skip("ThreadSanitizer's runtime does not start here: " + r.stderr[-300:])
+    exe = tmp_path / "spec_queue_main"
+    r = subprocess.run(flags + [os.path.join(ROOT, "tools", "sanitize", "spec_queue_main.cpp"), "-o", str(exe), "-ldl"], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    r = subprocess.run([str(exe), os.path.join(ROOT, "pine_amd")], capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0 and "spec_queue_main: ok" in r.stdout, (r.returncode, r.stdout[-500:], r.stderr[-3000:])
+
+
 # ---- GPU ------------------------------------------------------------------------------------------------------------
 def _render(scene, spp, depth, **kw):
     import torch
