@@ -23,6 +23,9 @@ int main(int argc, char** argv) {
     // render in passes of about P samples per pixel (same film, device memory for one pass); the running film as a PNG after every pass
     else if (!strcmp(argv[i], "--passes") && i + 1 < argc) setenv("PINE_PRL_PASSES", argv[++i], 1);
     else if (!strcmp(argv[i], "--preview") && i + 1 < argc) setenv("PINE_PRL_PREVIEW", argv[++i], 1);
+    // the edge-avoiding filter on every PathIntegrator film before the script's save; the guide images of the filter as PNGs
+    else if (!strcmp(argv[i], "--denoise")) setenv("PINE_PRL_DENOISE", "1", 1);
+    else if (!strcmp(argv[i], "--guides") && i + 1 < argc) setenv("PINE_PRL_GUIDES", argv[++i], 1);
     else if (!strcmp(argv[i], "--tables") && i + 1 < argc) pine_gpu_set_table_path(argv[++i]);
     // which accel the two-argument PathIntegrator(sampler, n) stands for: embree (what real pine's default EmbreeAccel renders: the
     // default for scenes without meshes) or bvh (pine-BVH order, the bits of Accel(BVH())); only order-dependent shapes -- a
@@ -31,7 +34,7 @@ int main(int argc, char** argv) {
     else path = argv[i];
   }
   if (!path) {
-    fprintf(stderr, "Usage: pine-mi355x [--dry-run] [--device N | --devices 0,1,...] [--tables bluesobol_u8.bin] [--accel bvh|embree] [--passes P] [--preview FILE.png] [filename]\n");
+    fprintf(stderr, "Usage: pine-mi355x [--dry-run] [--device N | --devices 0,1,...] [--tables bluesobol_u8.bin] [--accel bvh|embree] [--passes P] [--preview FILE.png] [--denoise] [--guides PREFIX] [filename]\n");
     return 2;
   }
   std::ifstream f(path);

@@ -471,6 +471,54 @@ pine_gpu_plan* pine_gpu_ao_plan_create(pine_gpu_scene*, const pine_gpu_render_pa
 /* radius, then directions[8] (ao.cpp:6-9) as xyz: host only, no GPU */
 int pine_gpu_ao_constants(pine_gpu_scene*, float out[25]);
 
+/* ---- DenoiseIntegrator: guide images and the filter ------------------------------------------
+ * DenoiseIntegrator(Accel, Sampler, LightSampler) + render(Scene&): src/pine/impl/integrator/denoiser.cpp, which computes two guide
+ * images and hands them with the film the camera holds to denoise() (src/pine/core/denoise.h) -- Open Image Denoise in the reference,
+ * a library for x86 hosts; DESIGN.md 4.12 has what stands in its place here.
+ *
+ * The guide images (denoiser.cpp:13-23): per pixel the albedo and the normal of the closest hit through the pixel centre --
+ * camera.gen_ray((p + 0.5) / film_size, (0.5, 0.5)), material.albedo (an Emissive's colour, every other material's albedo node at
+ * the surface's p, n, uv) and the interaction's n, not turned towards the camera; zeros on a miss.  out: W*H*3 floats each, film row
+ * order, bit for bit the reference's with Accel = BVH().  prm: device and PINE_GPU_FLAG_DEVICE_BVH are read; spp, max_path_length
+ * and sampler are not (the pass draws nothing).  Refused with a message: PINE_GPU_FLAG_ORDER_EMBREE, _FAST, _SPECIALIZE and
+ * _VERTEX_LOG, a sharded film (shard_world != 1).  $PINE_GPU_GUIDES_VARIANT=<index> considers that kernel variant only (tests).
+ * _device: albedo_dev / normal_dev are DEVICE pointers to W*H*3 floats; the launch is on `stream`, which has been synchronised when
+ * the call returns (the scene's records on the device live for the length of the call). */
+int pine_gpu_guides_render(pine_gpu_scene*, const pine_gpu_render_params*, float* albedo_out_host, float* normal_out_host);
+int pine_gpu_guides_render_device(pine_gpu_scene*, const pine_gpu_render_params*, void* albedo_dev, void* normal_dev, void* stream);
+/* The precompiled guide kernels in the order of the host's first-fit search: up to `cap` feature words (F_* bits); returns their
+ * number.  Needs no GPU. */
+int pine_gpu_guides_variants(uint32_t* features, int cap);
+
+/* The filter: an a-trous edge-avoiding wavelet filter (Dammertz et al. 2010) on albedo-demodulated colour; the definition is in
+ * pine_amd/csrc/pine_denoise.h and DESIGN.md 4.12.  film / out: W*H float4 (rgb filtered, a kept); albedo / normal: W*H*3 floats,
+ * the guide images above.  A pixel whose normal is (0, 0, 0) -- a miss -- is copied through and contributes to no other pixel.
+ * iterations 0 ... 8 (0: the identity), step 2^i in iteration i; normal_power_log2 k: the normal weight is max(0, n.n')^(2^k).
+ * device >= 0: the gfx950 kernels on that device; device = -1 (pine_gpu_denoise only): the host-thread build of the same
+ * functions (at most min(16, $OMP_NUM_THREADS, hardware threads)) -- the same bytes either way. */
+typedef struct {
+  int32_t iterations;         /* 5 */
+  int32_t normal_power_log2;  /* 7: the power 128 */
+  float sigma_color;          /* of the demodulated colour in iteration 0; halved with every iteration */
+  float sigma_albedo;
+  float eps_albedo;           /* demodulation divides by max(albedo, eps_albedo) per component */
+  int32_t device;
+} pine_gpu_denoise_params;
+/* The defaults: of a sweep on four scenes the cell with the best mean error ratio among those where the filtered 16 spp film of
+ * EVERY scene is closer to its 4096 spp film than the unfiltered one (profiles/denoise_quality.txt).  That criterion is ruled by
+ * the few pixels that hold a sliver of a lamp, which only a small sigma_color leaves alone: the default is cautious, and
+ * sigma_color = 0.25 smooths the rest of a picture far more (same file). */
+#define PINE_GPU_DENOISE_SIGMA_COLOR 0.05f
+#define PINE_GPU_DENOISE_SIGMA_ALBEDO 0.3f
+#define PINE_GPU_DENOISE_EPS_ALBEDO 0.001f
+void pine_gpu_denoise_params_default(pine_gpu_denoise_params*);
+int pine_gpu_denoise(const pine_gpu_denoise_params*, int w, int h, const float* film_rgba_host, const float* albedo_host, const float* normal_host,
+                     float* out_rgba_host);
+/* ... on device memory, launched on `stream` (a hipStream_t, 0 = the default stream); out_dev may equal film_dev.  The stream has
+ * been synchronised when the call returns: the work buffers come from the memory pool and go back to it. */
+int pine_gpu_denoise_device(const pine_gpu_denoise_params*, int w, int h, const void* film_dev, const void* albedo_dev, const void* normal_dev,
+                            void* out_dev, void* stream);
+
 /* Host test hook: the reference's partition (src/psl/algorithm.h:394-402) as its sequential swap loop and as the data-parallel
  * formulation of the device BVH build; both permutations out, < 0 if they disagree. */
 int pine_gpu_test_lomuto(const unsigned char* pred, int n, int* perm_sequential, int* perm_parallel);

@@ -63,6 +63,17 @@ class PlanStats(C.Structure):
     ]
 
 
+class DenoiseParams(C.Structure):
+    _fields_ = [
+        ("iterations", C.c_int32),
+        ("normal_power_log2", C.c_int32),
+        ("sigma_color", C.c_float),
+        ("sigma_albedo", C.c_float),
+        ("eps_albedo", C.c_float),
+        ("device", C.c_int32),
+    ]
+
+
 FLAG_TIMING = 1
 FLAG_PROGRESS = 2
 FLAG_FAST = 4
@@ -182,7 +193,13 @@ SIGNATURES = {
     "pine_gpu_ao_render": (C.c_int, [C.c_void_p, C.POINTER(RenderParams), c_f_p]),
     "pine_gpu_ao_plan_create": (C.c_void_p, [C.c_void_p, C.POINTER(RenderParams)]),
     "pine_gpu_ao_constants": (C.c_int, [C.c_void_p, c_f_p]),
-    "pine_gpu_plan_debug_sections": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "pine_gpu_guides_render": (C.c_int, [C.c_void_p, C.POINTER(RenderParams), c_f_p, c_f_p]),
+    "pine_gpu_guides_render_device": (C.c_int, [C.c_void_p, C.POINTER(RenderParams), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pine_gpu_guides_variants": (C.c_int, [C.POINTER(C.c_uint32), C.c_int]),
+    "pine_gpu_denoise_params_default": (None, [C.POINTER(DenoiseParams)]),
+    "pine_gpu_denoise": (C.c_int, [C.POINTER(DenoiseParams), C.c_int, C.c_int, c_f_p, c_f_p, c_f_p, c_f_p]),
+    "pine_gpu_denoise_device": (C.c_int, [C.POINTER(DenoiseParams), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pine_gpu_plan_debug_sections":(C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "pine_gpu_plan_vertex_log": (C.c_int64, [C.c_void_p, c_f_p, C.c_int64]),
     "pine_gpu_test_lomuto": (C.c_int, [C.POINTER(C.c_uint8), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "pine_gpu_test_sampler": (C.c_int, [C.c_int, C.c_int, c_f_p, C.c_int64]),

@@ -713,6 +713,25 @@ class Plan:
         check(lib.pine_gpu_plan_read_samples(self._h, out.ctypes.data_as(_lib.c_f_p), out.size), "read_samples")
         return out
 
+    def denoise(self, film, **params):
+        """Denoise a film this plan rendered, on the device: `film` is a float32 CUDA tensor of shape (H, W, 4); the guide images
+        are rendered into device memory and the filter runs in place (pine_gpu_guides_render_device, pine_gpu_denoise_device).
+        Returns `film`."""
+        import torch
+        w, h = self.scene.camera.film().size
+        if tuple(film.shape) != (h, w, 4) or film.dtype != torch.float32 or not film.is_cuda or not film.is_contiguous():
+            raise PineError("Plan.denoise: a contiguous float32 CUDA tensor of shape (H, W, 4) is expected")
+        params.setdefault("device", self.params.device)
+        prm = denoise_params(**params)
+        stream = C.c_void_p(torch.cuda.current_stream(film.device).cuda_stream)
+        albedo = torch.empty((h, w, 3), dtype=torch.float32, device=film.device)
+        normal = torch.empty((h, w, 3), dtype=torch.float32, device=film.device)
+        rp = _lib.RenderParams(1, 1, int(prm.device), 0, 1, 0, 0, 0)
+        check(lib.pine_gpu_guides_render_device(self.scene._h, C.byref(rp), C.c_void_p(albedo.data_ptr()), C.c_void_p(normal.data_ptr()), stream), "guides")
+        check(lib.pine_gpu_denoise_device(C.byref(prm), w, h, C.c_void_p(film.data_ptr()), C.c_void_p(albedo.data_ptr()), C.c_void_p(normal.data_ptr()),
+                                          C.c_void_p(film.data_ptr()), stream), "denoise")
+        return film
+
     def close(self):
         if getattr(self, "_h", None):
             lib.pine_gpu_plan_destroy(self._h)
@@ -753,11 +772,20 @@ class PathIntegrator:
         self.sampler, self.max_path_length, self.device, self.flags = sampler, int(max_path_length), device, int(flags)
         self.devices = list(devices) if devices else None
 
-    def render(self, scene, pass_samples=None, on_pass=None):
-        """pass_samples: render in passes of about that many samples per pixel (one device); on_pass(j, n, film) is called
+    def render(self, scene, pass_samples=None, on_pass=None, denoise=False):
+        """denoise: filter the finished film with the scene's guide images (guides + denoise with default parameters, or with
+        the parameters of a dict), as DenoiseIntegrator(...).render(scene) afterwards would.
+        pass_samples: render in passes of about that many samples per pixel (one device); on_pass(j, n, film) is called
         with the running film (an (H, W, 4) array, valid during the call) after every pass and stops the render by
         returning something true -- the film returned is then the last one delivered.  The finished film is the same, bit
         for bit, with or without passes."""
+        if denoise:
+            film = self.render(scene, pass_samples, on_pass)
+            if getattr(self, "stopped", False) and (pass_samples is not None or on_pass is not None):
+                return film
+            params = dict(denoise) if isinstance(denoise, dict) else {}
+            params.setdefault("device", self.device)
+            return DenoiseIntegrator(**params).render(scene)
         if scene.camera is None:
             raise PineError("scene has no camera")
         film = scene.camera.film()
@@ -821,4 +849,74 @@ class AOIntegrator:
         out = np.zeros((film.size[1], film.size[0], 4), dtype=np.float32)
         check(lib.pine_gpu_ao_render(scene._h, C.byref(prm), out.ctypes.data_as(_lib.c_f_p)), "AOIntegrator.render")
         film.pixels = out
+        return film
+
+
+# ---- DenoiseIntegrator (src/pine/impl/integrator/denoiser.cpp, src/pine/core/denoise.h) -----------
+def guides(scene, device=0, flags=0, order="pine"):
+    """(albedo, normal) of DenoiseIntegrator's guide pass (denoiser.cpp:13-23): per pixel the albedo and the normal of the
+    closest hit through the pixel centre, zeros on a miss; two (H, W, 3) arrays, bit for bit the reference's with
+    Accel = BVH().  EmbreeAccel's order, sharded films and PINE_GPU_FLAG_FAST are refused."""
+    if scene.camera is None:
+        raise PineError("scene has no camera")
+    w, h = scene.camera.film().size
+    prm = _lib.RenderParams(1, 1, int(device), 0, 1, 0, int(flags) | _order_flags(order), 0)
+    albedo = np.zeros((h, w, 3), dtype=np.float32)
+    normal = np.zeros((h, w, 3), dtype=np.float32)
+    check(lib.pine_gpu_guides_render(scene._h, C.byref(prm), albedo.ctypes.data_as(_lib.c_f_p), normal.ctypes.data_as(_lib.c_f_p)), "guides")
+    return albedo, normal
+
+
+def guides_variants():
+    """Feature words (F_* bits) of the precompiled guide kernels, in the order of the first-fit search."""
+    out = (C.c_uint32 * 16)()
+    n = check(lib.pine_gpu_guides_variants(out, 16), "guides_variants")
+    return list(out[:n])
+
+
+def denoise_params(**params):
+    """pine_gpu_denoise_params: the defaults (pine_gpu_denoise_params_default) with `params` over them -- iterations (0 ... 8),
+    normal_power_log2, sigma_color, sigma_albedo, eps_albedo, device (-1: the host-thread build)."""
+    prm = _lib.DenoiseParams()
+    lib.pine_gpu_denoise_params_default(C.byref(prm))
+    names = [f[0] for f in _lib.DenoiseParams._fields_]
+    for k, v in params.items():
+        if k not in names:
+            raise PineError(f"denoise: unknown parameter {k!r} ({', '.join(names)})")
+        setattr(prm, k, v)
+    return prm
+
+
+def denoise(film, albedo, normal, **params):
+    """The edge-avoiding a-trous filter (pine_amd/csrc/pine_denoise.h) of an (H, W, 4) film guided by the
+    (H, W, 3) albedo and normal images; returns the filtered film (alpha kept, misses -- a zero normal -- copied through).
+    device=-1: the host-thread build of the same functions, the same bytes."""
+    pixels = film.pixels if isinstance(film, Film) else film
+    pixels = np.ascontiguousarray(pixels, dtype=np.float32)
+    albedo = np.ascontiguousarray(albedo, dtype=np.float32)
+    normal = np.ascontiguousarray(normal, dtype=np.float32)
+    if pixels.ndim != 3 or pixels.shape[2] != 4 or albedo.shape != pixels.shape[:2] + (3,) or normal.shape != albedo.shape:
+        raise PineError("denoise: film is (H, W, 4), albedo and normal are (H, W, 3)")
+    prm = denoise_params(**params)
+    out = np.empty_like(pixels)
+    fp = lambda a: a.ctypes.data_as(_lib.c_f_p)  # noqa: E731
+    check(lib.pine_gpu_denoise(C.byref(prm), pixels.shape[1], pixels.shape[0], fp(pixels), fp(albedo), fp(normal), fp(out)), "denoise")
+    return out
+
+
+class DenoiseIntegrator:
+    """DenoiseIntegrator(...).render(scene) (denoiser.cpp:9-27): computes the guide images and denoises, in place, the film the
+    scene's camera already holds.  The reference hands the three images to Open Image Denoise; here the filter is
+    pine_denoise.h's.  params: those of denoise(); device also selects where the guide pass runs."""
+
+    def __init__(self, **params):
+        self.params = dict(params)
+        denoise_params(**self.params)  # (an unknown name raises here)
+
+    def render(self, scene):
+        if scene.camera is None:
+            raise PineError("scene has no camera")
+        film = scene.camera.film()
+        albedo, normal = guides(scene, device=max(int(self.params.get("device", 0)), 0))
+        film.pixels = denoise(film.pixels, albedo, normal, **self.params)
         return film

@@ -1,0 +1,118 @@
+// pine_amd/csrc/pine_guides_host.h -- the host side of DenoiseIntegrator's guide images (kernels: pine_guides_kernel.h).  Included
+// by pine_kernels.hip after plan_build's phases, of which the guide pass shares check_params, assemble_scene and scene_features.
+// The pass has no plan of its own: the scene's records are uploaded into a pine_gpu_plan that lives for the length of the call.
+
+static int guides_render_device(pine_gpu_scene* scene, const pine_gpu_render_params* prm_in, float* albedo_dev, float* normal_dev, hipStream_t stream) {
+  SceneHost& H = scene_host(scene);
+  if (prm_in->flags & PINE_GPU_FLAG_ORDER_EMBREE) {
+    set_error("DenoiseIntegrator's guide images are rendered in pine-BVH order only, DenoiseIntegrator(BVH(), ...): EmbreeAccel's order would "
+              "need fixtures of the Embree build and its tie pixels (PINE_GPU_FLAG_ORDER_EMBREE refused)");
+    return -1;
+  }
+  if (prm_in->flags & (PINE_GPU_FLAG_FAST | PINE_GPU_FLAG_VERTEX_LOG | PINE_GPU_FLAG_SPECIALIZE)) {
+    set_error((prm_in->flags & PINE_GPU_FLAG_FAST)
+                  ? "guide images: PINE_GPU_FLAG_FAST is not available (the guide images are exact; there is no declared-tolerance kernel)"
+                  : "guide images: PINE_GPU_FLAG_SPECIALIZE / _VERTEX_LOG are not available (precompiled kernels only)");
+    return -1;
+  }
+  if (prm_in->shard_world != 1 || prm_in->shard_rank != 0) {
+    set_error("guide images: sharded films are not supported (shard_world must be 1)");
+    return -1;
+  }
+  pine_gpu_render_params prm = *prm_in;
+  prm.spp = 1, prm.sampler = PINE_GPU_SAMPLER_BLUE;  // (the pass draws nothing; check_params wants valid ones)
+  prm.max_path_length = 1;
+  prm.samples_per_item = 0;
+  if (check_params(H, &prm) < 0) return -1;
+  if (H.camera.W > 65535 || H.camera.H > 65535) {
+    set_error("film sides above 65535 are not supported");
+    return -1;
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+    set_error("no HIP device available: the guide images' hot path requires an AMD GPU (no CPU fallback)");
+    return -1;
+  }
+  HIP_OK(hipSetDevice(prm.device));
+  PlanOwner p(new pine_gpu_plan());
+  p->device = prm.device;
+  p->params = prm;
+  if (!H.accel.built) {
+    H.build_on_device = (prm.flags & PINE_GPU_FLAG_DEVICE_BVH) ? prm.device : -1;
+    H.build_accel();
+  }
+  SceneParts sp;
+  if (assemble_scene(p.get(), H, &prm, sp, false)) return -1;
+
+  // the kernel: the first variant that covers the scene's shape kinds and node programs; $PINE_GPU_GUIDES_VARIANT=<index>
+  // considers that variant only (tests)
+  const unsigned need = scene_features(sp, &prm) & (kFGuidesShapes | F_NODES);
+  const bool lds_ok = size_t(p->S.blob_bytes) <= 32 * 1024;
+  int count = 0, chosen = -1;
+  const PineGuidesVariant* table = pine_gpu_guides_variant_table(&count);
+  const char* pin = getenv("PINE_GPU_GUIDES_VARIANT");
+  for (int i = 0; i < count && chosen < 0; i++) {
+    if (pin && *pin && atoi(pin) != i) continue;
+    const unsigned F = table[i].features;
+    if ((need & ~F) == 0 && (!(F & F_LDS_SCENE) || lds_ok)) chosen = i;
+  }
+  if (chosen < 0) {
+    set_error(pin && *pin ? "$PINE_GPU_GUIDES_VARIANT names no guide kernel variant that covers this scene" : "no guide kernel variant covers this scene");
+    return -1;
+  }
+  const PineGuidesVariant& K = table[chosen];
+  const size_t lds_bytes = size_t(p->S.stack_total) * kBlock * sizeof(int) + ((K.features & F_LDS_SCENE) ? size_t(p->S.blob_bytes) : 0);
+  if (lds_bytes > 160 * 1024) {
+    set_error("guide images: the traversal stack of this scene does not fit LDS");
+    return -1;
+  }
+  HIP_OK(hipFuncSetAttribute(K.fn, hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_bytes)));
+  int tiles_x = (H.camera.W + kTile - 1) / kTile, num_tiles = tiles_x * ((H.camera.H + kTile - 1) / kTile);
+  void* args[] = {&p->S, &tiles_x, &num_tiles, &albedo_dev, &normal_dev};
+  const unsigned grid = unsigned((num_tiles + kBlock / 64 - 1) / (kBlock / 64));
+  HIP_OK(hipLaunchKernel(K.fn, dim3(grid), dim3(kBlock), args, lds_bytes, stream));
+  // the scene's records go back to the pool with `p`: the launch that reads them must have finished
+  HIP_OK(hipStreamSynchronize(stream));
+  return 0;
+}
+
+int pine_gpu_guides_render_device(pine_gpu_scene* scene, const pine_gpu_render_params* prm, void* albedo_dev, void* normal_dev, void* stream) {
+  if (!scene || !prm || !albedo_dev || !normal_dev) {
+    set_error("null argument");
+    return -1;
+  }
+  return guides_render_device(scene, prm, static_cast<float*>(albedo_dev), static_cast<float*>(normal_dev), static_cast<hipStream_t>(stream));
+}
+
+// DenoiseIntegrator's guide pass in one call: upload, launch, download.  Fails if there is no GPU.
+int pine_gpu_guides_render(pine_gpu_scene* scene, const pine_gpu_render_params* prm, float* albedo_out, float* normal_out) {
+  if (!scene || !prm || !albedo_out || !normal_out) {
+    set_error("null argument");
+    return -1;
+  }
+  SceneHost& H = scene_host(scene);
+  if (!H.has_camera) {
+    set_error("scene has no camera");
+    return -1;
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+    set_error("no HIP device available: the guide images' hot path requires an AMD GPU (no CPU fallback)");
+    return -1;
+  }
+  HIP_OK(hipSetDevice(prm->device));
+  const size_t n = size_t(H.camera.W) * size_t(H.camera.H) * 3;
+  const char* const what = "guide images: the output buffers";
+  DeviceBuffer<float> d_albedo(kFromPool), d_normal(kFromPool);
+  if (d_albedo.alloc(n, what) || d_normal.alloc(n, what)) return -1;
+  if (guides_render_device(scene, prm, d_albedo, d_normal, nullptr)) return -1;
+  return d_albedo.download(albedo_out, n, "guide images: download") || d_normal.download(normal_out, n, "guide images: download") ? -1 : 0;
+}
+
+int pine_gpu_guides_variants(uint32_t* features, int cap) {
+  int count = 0;
+  const PineGuidesVariant* table = pine_gpu_guides_variant_table(&count);
+  for (int i = 0; i < count && i < cap; i++)
+    if (features) features[i] = table[i].features;
+  return count;
+}

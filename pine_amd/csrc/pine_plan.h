@@ -28,6 +28,7 @@ SceneHost& scene_host(pine_gpu_scene* s);
 }  // namespace pine_gpu
 #include "pine_kernels_device.h"
 #include "pine_ao_kernel.h"
+#include "pine_guides_kernel.h"
 namespace pine_gpu {
 
 #define HIP_OK(expr)                                                                          \

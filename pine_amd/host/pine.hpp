@@ -373,6 +373,44 @@ class AOIntegrator {
   int device_;
 };
 
+// guides(scene, albedo, normal): the guide images of the reference's DenoiseIntegrator (src/pine/impl/integrator/denoiser.cpp:13-23)
+// -- per pixel the albedo and the normal of the closest hit through the pixel centre, zeros on a miss -- as W*H*3 floats each, film
+// row order; bit for bit the reference's with Accel = BVH().
+inline void guides(Scene& scene, std::vector<float>& albedo, std::vector<float>& normal, int device = 0) {
+  const vec2i size = scene.camera.film_.size();
+  albedo.assign(size_t(size.x) * size.y * 3, 0.0f);
+  normal.assign(size_t(size.x) * size.y * 3, 0.0f);
+  pine_gpu_render_params p{};
+  p.spp = 1;
+  p.max_path_length = 1;
+  p.device = device;
+  p.shard_world = 1;
+  check(pine_gpu_guides_render(scene.handle(), &p, albedo.data(), normal.data()), "guides");
+}
+
+// The filter's parameters (pine_gpu_denoise_params) with the library's defaults; device = -1: the host-thread build.
+struct DenoiseParams : pine_gpu_denoise_params {
+  DenoiseParams() { pine_gpu_denoise_params_default(this); }
+};
+
+// DenoiseIntegrator(params).render(scene) (denoiser.cpp:9-27): computes the guide images and denoises, in place, the film the
+// scene's camera already holds.  The reference hands the three images to Open Image Denoise; the filter here is the edge-avoiding
+// a-trous filter of pine_amd/csrc/pine_denoise.h.
+class DenoiseIntegrator {
+ public:
+  explicit DenoiseIntegrator(DenoiseParams params = DenoiseParams()) : params_(params) {}
+  void render(Scene& scene) {
+    std::vector<float> albedo, normal;
+    guides(scene, albedo, normal, params_.device < 0 ? 0 : params_.device);
+    Film& film = scene.camera.film_;
+    check(pine_gpu_denoise(&params_, film.size_.x, film.size_.y, film.pixels.data(), albedo.data(), normal.data(), film.pixels.data()),
+          "DenoiseIntegrator::render");
+  }
+
+ private:
+  DenoiseParams params_;
+};
+
 inline float get_progress() { return pine_gpu_progress(); }
 
 // load(scene, "file.glb" [, mat4]) (fileio.cpp:584-589): glTF import -- every mesh primitive with its material, and the

@@ -2041,6 +2041,39 @@ Interp::Interp() {
     } else {
       gpu_check(pine_gpu_path_render(s->h, &prm, f->pixels.data()), "PathIntegrator.render");
     }
+    // $PINE_PRL_DENOISE (pine-mi355x --denoise): the film is filtered here, so the script's save writes the denoised picture;
+    // $PINE_PRL_GUIDES = PREFIX (--guides): PREFIX_albedo.png and PREFIX_normal.png (0.5 n + 0.5), rows as save orders them.
+    // Both are the command line's, not the language's: PRL has no denoise(scene), because the reference's leaves every colour
+    // as it is and a script must keep rendering what the reference renders.
+    const char* denoise = getenv("PINE_PRL_DENOISE");
+    const char* guides = getenv("PINE_PRL_GUIDES");
+    if ((denoise && *denoise) || (guides && *guides)) {
+      const size_t n = size_t(f->w) * f->h;
+      std::vector<float> albedo(n * 3), normal(n * 3);
+      pine_gpu_render_params gp{};
+      gp.spp = 1, gp.max_path_length = 1, gp.device = in.device, gp.shard_world = 1;
+      gpu_check(pine_gpu_guides_render(s->h, &gp, albedo.data(), normal.data()), "--guides / --denoise");
+      if (guides && *guides) {
+        auto write = [&](const std::vector<float>& img, float scale, float offset, const std::string& path) {
+          std::vector<uint8_t> rgba(n * 4);
+          for (int y = 0; y < f->h; y++)
+            for (int x = 0; x < f->w; x++)
+              for (int c = 0; c < 4; c++) {
+                const float v = c == 3 ? 1.0f : img[(size_t(y) * f->w + x) * 3 + c] * scale + offset;
+                rgba[(size_t(f->h - 1 - y) * f->w + x) * 4 + c] = uint8_t(std::min(std::max(v, 0.0f), 1.0f) * 255.0f + 0.5f);
+              }
+          if (!png_writer::write_rgba8(path, f->w, f->h, rgba.data())) fail("--guides: cannot write `" + path + "`");
+        };
+        write(albedo, 1.0f, 0.0f, std::string(guides) + "_albedo.png");
+        write(normal, 0.5f, 0.5f, std::string(guides) + "_normal.png");
+      }
+      if (denoise && *denoise) {
+        pine_gpu_denoise_params dp;
+        pine_gpu_denoise_params_default(&dp);
+        dp.device = in.device;
+        gpu_check(pine_gpu_denoise(&dp, f->w, f->h, f->pixels.data(), albedo.data(), normal.data(), f->pixels.data()), "--denoise");
+      }
+    }
     in.last_film = f;
     return Value();
   });

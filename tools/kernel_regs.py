@@ -47,6 +47,14 @@ def short(name):
     m = re.search(r"ao_kernelILj(\d+)ELb(\d)", name)
     if m:
         return f"ao_kernel<{m.group(1)},{'regroup' if m.group(2) == '1' else 'serial'}>"
+    m = re.search(r"guides_kernelILj(\d+)E", name)
+    if m:
+        return f"guides_kernel<{m.group(1)}>"
+    m = re.search(r"denoise_iterate_kernelILb(\d)", name)
+    if m:
+        return f"denoise_iterate_kernel<{'last' if m.group(1) == '1' else 'inner'}>"
+    if "denoise_prepare_kernel" in name:
+        return "denoise_prepare_kernel"
     return None
 print(f"{'kernel':48s} vgpr vgpr_spill sgpr sgpr_spill scratch_bytes_per_lane")
 for r in sorted(rows):

@@ -12,6 +12,7 @@
 #include "../../include/pine_gpu.h"
 #include "../../pine_amd/csrc/pine_host.h"
 #include "../../pine_amd/csrc/pine_math_check.h"
+#include "../../pine_amd/csrc/pine_denoise_host.h"
 
 #include "../../pine_amd/csrc/pine_specialize.h"
 
@@ -49,6 +50,20 @@ pine_gpu_plan* pine_gpu_plan_create_passes(pine_gpu_scene*, const pine_gpu_rende
   fail();
   return nullptr;
 }
+int pine_gpu_guides_render(pine_gpu_scene*, const pine_gpu_render_params*, float*, float*) { return fail(); }
+int pine_gpu_guides_render_device(pine_gpu_scene*, const pine_gpu_render_params*, void*, void*, void*) { return fail(); }
+int pine_gpu_guides_variants(uint32_t*, int) { return fail(); }
+// (the filter's host-thread build, device = -1, is the real thing: pine_denoise_host.h)
+void pine_gpu_denoise_params_default(pine_gpu_denoise_params* prm) {
+  if (prm) *prm = pine_gpu_denoise_params{5, 7, PINE_GPU_DENOISE_SIGMA_COLOR, PINE_GPU_DENOISE_SIGMA_ALBEDO, PINE_GPU_DENOISE_EPS_ALBEDO, 0};
+}
+int pine_gpu_denoise(const pine_gpu_denoise_params* prm, int w, int h, const float* film, const float* albedo, const float* normal, float* out) {
+  pine_gpu::DenoiseConsts C;
+  if (pine_gpu::denoise_check(prm, w, h, C)) return -1;
+  if (!film || !albedo || !normal || !out || prm->device >= 0) return fail();
+  return pine_gpu::denoise_host(prm, C, film, albedo, normal, out);
+}
+int pine_gpu_denoise_device(const pine_gpu_denoise_params*, int, int, const void*, const void*, const void*, void*, void*) { return fail(); }
 int pine_gpu_plan_pass_count(pine_gpu_plan*) { return fail(); }
 int pine_gpu_plan_pass_info(pine_gpu_plan*, int, int32_t*) { return fail(); }
 int pine_gpu_plan_launch_pass(pine_gpu_plan*, int, void*, void*) { return fail(); }
