@@ -526,6 +526,20 @@ int pine_gpu_test_lomuto(const unsigned char* pred, int n, int* perm_sequential,
 /* Device-side unit-test hooks: run the device implementations on arrays (parity vs oracle). */
 int pine_gpu_test_sampler(int device, int spp, float* out_host, int64_t capacity);  /* layout of oracle_sampler_stream */
 int pine_gpu_test_rng(int device, uint64_t* out_host, int64_t capacity);            /* layout of oracle_rng_stream */
+/* The sampler front of the kernels, sampler_get1d / sampler_get2d, call by call: BlueSampler (kind 0), SobolSampler (1) or
+ * HaltonSampler (2) of `spp` samples on a w x h film, its tables built and uploaded by the code that builds a plan's.  n cases of 9
+ * int32 -- kind, spp, w, h (the call's own), px, py, sample index, pattern, calls -- one thread each: the sampler of that pixel
+ * and sample as the path kernels start it (dimension 0, HaltonSampler's 2), then `calls` calls of the pattern (0: get2d  1: get1d,
+ * get2d alternating  2: get1d).  out_host: every float, case after case (oracle_sampler_draws has the layout); returns their
+ * number.  mode 0: the tables read from memory; mode 1: the workgroup's LDS cache of a 256-thread kernel (stage_sobol_rows,
+ * load_lane_slice, lane_tables), as the megakernel and the AO kernel read them.  device = -1: the host build of the same functions
+ * (mode 0 only).  Refused without a launch: spp <= 0 or above 4096, a film side above 65535, a pixel outside the film, a sample
+ * index outside the pixel's, more than 65536 cases or calls, too small a capacity. */
+int64_t pine_gpu_test_sampler_draws(int device, int kind, int spp, int w, int h, int mode, const int32_t* cases_host, int64_t n,
+                                    float* out_host, int64_t capacity);
+/* Host test hook: CRC-32 and element counts of HaltonSampler's tables as the library derives them -- the primes, their prefix sums
+ * (int32 each), the digit permutations (uint16). */
+int pine_gpu_test_halton_tables(uint32_t crc32[3], int64_t counts[3]);
 int pine_gpu_test_sincos(int device, const float* x_host, int64_t n, float* sin_out, float* cos_out);
 int pine_gpu_test_powlog(int device, const float* x_host, const float* y_host, int64_t n, float* pow_out,
                          float* log_out);                                           /* powf(x, y), logf(x) */

@@ -99,6 +99,24 @@ def sampler_stream(spp):
     return out
 
 
+def draw_floats(cases):
+    """floats of each case[9] int32 of `pine_ref draws`: pattern 0 = get2d, 1 = get1d / get2d alternating, 2 = get1d"""
+    cases = np.asarray(cases).reshape(-1, 9)
+    pattern, calls = cases[:, 7].astype(np.int64), cases[:, 8].astype(np.int64)
+    return np.where(pattern == 0, 2 * calls, np.where(pattern == 1, calls + calls // 2, calls))
+
+
+def sampler_draws(cases: np.ndarray):
+    """cases[n,9] int32 (layout of `pine_ref draws`) -> every float drawn, case after case"""
+    cases = np.ascontiguousarray(cases, np.int32).reshape(-1, 9)
+    out = np.zeros(int(draw_floats(cases).sum()), np.float32)
+    lib().oracle_sampler_draws.restype = C.c_int64
+    n = lib().oracle_sampler_draws(_tp(), cases.ctypes.data_as(C.c_void_p), C.c_int64(len(cases)), out.ctypes.data_as(C.c_void_p),
+                                   C.c_int64(out.size))
+    assert n == out.size, n
+    return out
+
+
 def rng_stream():
     out = np.zeros(6 * 19, np.uint64)
     assert lib().oracle_rng_stream(out.ctypes.data_as(C.c_void_p), C.c_int64(out.size)) == 0

@@ -3718,6 +3718,33 @@ int oracle_sampler_stream(const uint8_t* tables, int spp_req, float* out, int64_
   return 0;
 }
 
+int64_t oracle_sampler_draws(const uint8_t* tables, const int32_t* cases, int64_t ncases, float* out, int64_t capacity) {
+  int64_t k = 0;
+  for (int64_t c = 0; c < ncases; c++) {
+    const int32_t* q = cases + c * 9;  // kind, spp, film w, film h, px, py, sample index, pattern, calls
+    if (q[0] < 0 || q[0] > 2 || q[1] <= 0 || q[6] < 0 || q[7] < 0 || q[7] > 2 || q[8] < 0) return -1;
+    const int64_t floats = q[7] == 0 ? 2 * int64_t(q[8]) : q[7] == 1 ? q[8] + q[8] / 2 : q[8];
+    if (k + floats > capacity) return -1;
+    Sampler s;  // as render_impl sets one up
+    s.kind = q[0];
+    s.spp = q[0] == SAMPLER_BLUE ? bluesobol_effective_spp(q[1]) : q[1];
+    s.t = select_tables(tables, q[0] == SAMPLER_BLUE ? s.spp : 1);
+    s.init(q[2], q[3]);
+    s.start_pixel(q[4], q[5], 0);
+    for (int i = 0; i < q[6]; i++) s.start_next_sample();
+    for (int i = 0; i < q[8]; i++) {
+      if (q[7] == 2 || (q[7] == 1 && i % 2 == 0)) {
+        out[k++] = s.get1d();
+      } else {
+        const vec2 v = s.get2d();
+        out[k++] = v.x;
+        out[k++] = v.y;
+      }
+    }
+  }
+  return k;
+}
+
 int oracle_rng_stream(uint64_t* out, int64_t capacity) {
   if (capacity < 6 * 19) return -1;
   int64_t k = 0;

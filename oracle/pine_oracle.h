@@ -56,6 +56,9 @@ int oracle_render_samples(const char* pscene, const uint8_t* tables, int spp, in
 
 /* BlueSobolSampler stream in the exact layout of `pine_ref sampler` (oracle/ref_driver.cpp). */
 int oracle_sampler_stream(const uint8_t* tables, int spp, float* out, int64_t capacity);
+/* get1d / get2d of the oracle's sampler object per case, cases (9 x int32 each) and floats in the layout of `pine_ref draws`.
+ * Returns the number of floats written, -1 for a bad case or too small a capacity. */
+int64_t oracle_sampler_draws(const uint8_t* tables, const int32_t* cases, int64_t ncases, float* out, int64_t capacity);
 /* hash/RNG known answers in the layout of `pine_ref rng`: 6 pixels x 19 u64 words. */
 int oracle_rng_stream(uint64_t* out, int64_t capacity);
 /* Host math known answers in the layout of `pine_ref host`. */

@@ -32,6 +32,9 @@
 //                                        through Mnode::eval(NodeEvalCtx{p, n, uv}) for every query (8 floats: p, n, uv)
 //   pine_ref lobes   <scene.pscene> <cases.bin> <out.bin>   Material::sample_bxdf(BxdfSampleCtx, sampler) per case: which lobe came
 //                                        back, its members, and what it drew from the sampler and from the pixel's RNG
+//   pine_ref draws   <cases.bin> <out.bin> [halton_tables.bin]   get1d / get2d of the reference's BlueSobolSampler / SobolSampler /
+//                                        HaltonSampler per case (spp, film size, pixel, sample index, call pattern), started as
+//                                        PathIntegrator::render starts one; optionally HaltonSampler's prime and permutation tables
 //   pine_ref prl     <literal>...        psl::stof / stoi / to_string of each literal, and the constant
 //                                        expressions of a cbox-class script evaluated with psl::stof values
 //                                        (pins the PRL front-end's literal and vector arithmetic)
@@ -357,6 +360,8 @@ template struct Rob<TagIndices, &BVH::indices>;
 template struct Rob<TagNodes, &BVHImpl::nodes>;
 struct TagSobolDimension { friend constexpr auto rob(TagSobolDimension); };
 template struct Rob<TagSobolDimension, &SobolSampler::dimension>;
+struct TagHaltonPerms { friend constexpr auto rob(TagHaltonPerms); };
+template struct Rob<TagHaltonPerms, &HaltonSampler::radicalInversePermutations>;
 
 // Canonical pre-order stream of one BVHImpl (independent of how nodes are numbered): an inner node is its two child boxes
 // (12 floats: lower, upper of child 0, then of child 1) followed by the two children; a child is either the word
@@ -1099,6 +1104,49 @@ int main(int argc, char** argv) {
     auto flipped = invert_y(film.pixels);
     auto u8 = to_uint8_array(flipped.size(), 4, &flipped.data()[0][0], false, true);
     write_file(argv[6], u8.data(), u8.size());
+    return 0;
+  }
+  if (cmd == "draws" && (argc == 4 || argc == 5)) {
+    // draws <cases.bin> <out.bin> [halton_tables.bin]: per case (9 x int32: kind 0 Blue / 1 Sobol / 2 Halton, spp, film w, film h,
+    // px, py, sample index, pattern, calls) the reference's own sampler object, started as PathIntegrator::render starts one --
+    // init(film size), start_pixel(p, 0), start_next_sample() up to the sample index -- then `calls` calls of the pattern
+    // (0: get2d  1: get1d, get2d alternating  2: get1d), every float written in order.  The optional third file gets
+    // HaltonSampler's tables as the reference holds them: Primes, PrimeSums (int32 x PrimeTablesize), then the private
+    // radicalInversePermutations (uint16).
+    std::ifstream cf(argv[2], std::ios::binary);
+    std::vector<int32_t> cases;
+    for (int32_t v; cf.read(reinterpret_cast<char*>(&v), 4);) cases.push_back(v);
+    if (cases.empty() || cases.size() % 9 != 0) {
+      fprintf(stderr, "draws: %s holds no whole cases\n", argv[2]);
+      return 2;
+    }
+    std::vector<float> out;
+    for (size_t c = 0; c < cases.size(); c += 9) {
+      const int32_t* q = &cases[c];
+      Sampler sampler = q[0] == 1 ? Sampler(SobolSampler(q[1])) : q[0] == 2 ? Sampler(HaltonSampler(q[1])) : Sampler(BlueSobolSampler(q[1]));
+      sampler.init(vec2i(q[2], q[3]));
+      sampler.start_pixel(vec2i(q[4], q[5]), 0);
+      for (int i = 0; i < q[6]; i++) sampler.start_next_sample();
+      for (int i = 0; i < q[8]; i++) {
+        if (q[7] == 2 || (q[7] == 1 && i % 2 == 0)) {
+          out.push_back(sampler.get1d());
+        } else {
+          const vec2 v = sampler.get2d();
+          out.push_back(v.x);
+          out.push_back(v.y);
+        }
+      }
+    }
+    write_file(argv[3], out.data(), out.size() * 4);
+    if (argc == 5) {
+      HaltonSampler make_tables(1);  // (the first HaltonSampler fills the static table)
+      const psl::vector<uint16_t>& perms = *rob(TagHaltonPerms{});
+      std::vector<uint8_t> bytes(size_t(8) * PrimeTablesize + perms.size() * 2);
+      memcpy(bytes.data(), Primes, size_t(4) * PrimeTablesize);
+      memcpy(bytes.data() + size_t(4) * PrimeTablesize, PrimeSums, size_t(4) * PrimeTablesize);
+      memcpy(bytes.data() + size_t(8) * PrimeTablesize, &perms[0], perms.size() * 2);
+      write_file(argv[4], bytes.data(), bytes.size());
+    }
     return 0;
   }
   fprintf(stderr, "usage: see header of oracle/ref_driver.cpp\n");

@@ -453,6 +453,26 @@ static const HaltonHostTables& halton_host_tables() {
   }();
   return tables;
 }
+int pine_gpu_test_halton_tables(uint32_t* crc32, int64_t* counts) {
+  if (!crc32 || !counts) {
+    set_error("pine_gpu_test_halton_tables: bad argument");
+    return -1;
+  }
+  const auto crc = [](const void* data, size_t bytes) {  // CRC-32 as zlib computes it (reflected 0xedb88320)
+    uint32_t c = 0xffffffffu;
+    for (size_t i = 0; i < bytes; i++) {
+      c ^= static_cast<const uint8_t*>(data)[i];
+      for (int b = 0; b < 8; b++) c = (c >> 1) ^ (0xedb88320u & (0u - (c & 1u)));
+    }
+    return ~c;
+  };
+  const HaltonHostTables& ht = halton_host_tables();
+  counts[0] = kHaltonDims, counts[1] = kHaltonDims, counts[2] = int64_t(ht.perms.size());
+  crc32[0] = crc(ht.primes_and_sums.data(), size_t(kHaltonDims) * sizeof(int));
+  crc32[1] = crc(ht.primes_and_sums.data() + kHaltonDims, size_t(kHaltonDims) * sizeof(int));
+  crc32[2] = crc(ht.perms.data(), ht.perms.size() * sizeof(uint16_t));
+  return 0;
+}
 
 // The mesh triangles as LDS-sized packets (DeviceScene::tri_packets): per leaf-ordered triangle an 8-byte entry -- three
 // 16-bit numbers into the table of the scene's DISTINCT vertices (by bit pattern) and the 16-bit triangle index -- then the
@@ -727,22 +747,33 @@ static int assemble_scene(pine_gpu_plan* p, SceneHost& H, const pine_gpu_render_
   return validate_device_scene(A, shapes, sp.materials.size(), sp.lights, S.stack_top, S.stack_total);
 }
 
-// BlueSampler's tables (sobol + the selected spp variant), HaltonSampler's, SobolSampler's digit counts.
-static int upload_sampler_tables(pine_gpu_plan* p, const std::vector<uint8_t>& tables, const pine_gpu_render_params* prm, int spp) {
-  const bool halton = prm->sampler == PINE_GPU_SAMPLER_HALTON;
-  const bool sobol = prm->sampler == PINE_GPU_SAMPLER_SOBOL || halton;
+// BlueSampler's tables (sobol + the selected spp variant), HaltonSampler's, SobolSampler's digit counts: T views what the two
+// blocks own on the current device (pine_plan.h).  host_tables: no device is touched, BlueSampler's bytes go there and
+// HaltonSampler's are viewed where halton_host_tables() keeps them.
+extern "C++" int pine_gpu::fill_sampler_tables(const std::vector<uint8_t>& tables, int kind, int spp, int W, int H, DTables& T, DeviceBuffer<uint8_t>& d_tables,
+                                  DeviceBuffer<uint8_t>& d_halton, std::vector<uint8_t>* host_tables) {
+  const bool halton = kind == 2;
+  const bool sobol = kind == 1 || halton;
   int k = 0;
   while ((1 << k) < spp) k++;
   if (sobol) k = 0;  // (SobolSampler reads no table; any variant keeps the BlueSampler window loads in bounds)
   // device layout: sobolT 64 KiB | scramble 128 KiB | rank 128 KiB | 64 bytes = rank[0..63] again, so
   // a pixel's 40 consecutive ranking bytes never need the reference's modulo wrap
   const char* const what = "plan creation: the sampler's tables";
-  if (p->d_tables.alloc(65536 + 262144 + 64, what) || p->d_tables.write(transposed_sobol(tables).data(), 65536, what)) return -1;
-  HIP_OK(hipMemcpy(p->d_tables + 65536, tables.data() + 65536 + size_t(k) * 262144, 262144, hipMemcpyHostToDevice));
-  HIP_OK(hipMemcpy(p->d_tables + 65536 + 262144, tables.data() + 65536 + size_t(k) * 262144 + 131072, 64,
-                   hipMemcpyHostToDevice));
-  DTables& T = p->S.tables;
-  T.sobol = p->d_tables, T.scramble = p->d_tables + 65536, T.rank = p->d_tables + 65536 + 131072;
+  const uint8_t* const variant = tables.data() + 65536 + size_t(k) * 262144;
+  const uint8_t* base = nullptr;
+  if (host_tables) {
+    *host_tables = transposed_sobol(tables);
+    host_tables->insert(host_tables->end(), variant, variant + 262144);
+    host_tables->insert(host_tables->end(), variant + 131072, variant + 131072 + 64);
+    base = host_tables->data();
+  } else {
+    if (d_tables.alloc(65536 + 262144 + 64, what) || d_tables.write(transposed_sobol(tables).data(), 65536, what)) return -1;
+    HIP_OK(hipMemcpy(d_tables + 65536, variant, 262144, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(d_tables + 65536 + 262144, variant + 131072, 64, hipMemcpyHostToDevice));
+    base = d_tables;
+  }
+  T.sobol = base, T.scramble = base + 65536, T.rank = base + 65536 + 131072;
   T.lds_sobol = nullptr, T.lds_tile = nullptr, T.lds_scr = nullptr;
   T.tile_stride = 0, T.win_lo = 0, T.win_len = 0;
   T.kind = halton ? 2 : sobol ? 1 : 0;
@@ -750,13 +781,21 @@ static int upload_sampler_tables(pine_gpu_plan* p, const std::vector<uint8_t>& t
   if (halton) {
     const HaltonHostTables& ht = halton_host_tables();
     const size_t head = size_t(2 * kHaltonDims) * sizeof(int), bytes = head + ht.perms.size() * sizeof(uint16_t);
-    if (p->d_halton.alloc(bytes, what)) return -1;
-    HIP_OK(hipMemcpy(p->d_halton, ht.primes_and_sums.data(), head, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(p->d_halton + head, ht.perms.data(), ht.perms.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-    T.halton_primes = reinterpret_cast<const int*>(p->d_halton.get()), T.halton_perms = reinterpret_cast<const uint16_t*>(p->d_halton + head);
+    if (host_tables) {
+      T.halton_primes = ht.primes_and_sums.data(), T.halton_perms = ht.perms.data();
+    } else {
+      if (d_halton.alloc(bytes, what)) return -1;
+      HIP_OK(hipMemcpy(d_halton, ht.primes_and_sums.data(), head, hipMemcpyHostToDevice));
+      HIP_OK(hipMemcpy(d_halton + head, ht.perms.data(), ht.perms.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+      T.halton_primes = reinterpret_cast<const int*>(d_halton.get()), T.halton_perms = reinterpret_cast<const uint16_t*>(d_halton + head);
+    }
   }
-  sobol_sampler_params(T, spp, p->S.cam.W, p->S.cam.H);
+  sobol_sampler_params(T, spp, W, H);
   return 0;
+}
+static int upload_sampler_tables(pine_gpu_plan* p, const std::vector<uint8_t>& tables, const pine_gpu_render_params* prm, int spp) {
+  const int kind = prm->sampler == PINE_GPU_SAMPLER_HALTON ? 2 : prm->sampler == PINE_GPU_SAMPLER_SOBOL ? 1 : 0;
+  return fill_sampler_tables(tables, kind, spp, p->S.cam.W, p->S.cam.H, p->S.tables, p->d_tables, p->d_halton, nullptr);
 }
 
 // The F_* features the scene needs: kernel specialisation takes the smallest compiled feature set that covers them.

@@ -220,6 +220,13 @@ inline void build_frame_table(const std::vector<DShape>& shapes, std::vector<flo
   }
 }
 
+// A sampler's tables as the kernels read them, from the packed table file, the sampler (DTables::kind; spp: BlueSampler's effective
+// count, the others' as given) and the film size (pine_kernels.hip): what a plan's kernels get, and pine_gpu_test_sampler_draws.
+// T views the two blocks, which own the memory on the current device -- or, with host_tables, host memory: that vector and the
+// library's own copy of HaltonSampler's tables (no device is touched: the host pass of the test hook).
+int fill_sampler_tables(const std::vector<uint8_t>& tables, int kind, int spp, int W, int H, DTables& T, DeviceBuffer<uint8_t>& d_tables,
+                        DeviceBuffer<uint8_t>& d_halton, std::vector<uint8_t>* host_tables = nullptr);
+
 static int need_device(int device) {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {

@@ -97,6 +97,44 @@ __global__ void test_sampler_kernel(DTables T, int spp, float* out) {
     s.index++;
   }
 }
+// pine_gpu_test_sampler_draws: one case (9 ints: kind, spp, film w, film h, px, py, sample index, pattern, calls) through the
+// sampler front the kernels call, started as they start it; host pass and device pass.
+constexpr int kDrawCaseInts = 9, kDrawMaxCases = 65536, kDrawMaxCalls = 65536;
+PINE_HD bool draw_is_get1d(int pattern, int call) { return pattern == 2 || (pattern == 1 && (call & 1) == 0); }
+template <int MODE>
+PINE_HD void test_draws_case(const DTables& T, const int32_t* q, float* o) {
+  DSampler s;
+  s.px = q[4];
+  s.py = q[5];
+  s.index = q[6];
+  s.dimension = T.kind == 2 ? 2 : 0;  // (HaltonSampler::start_pixel / start_next_sample: dimension = 2)
+  for (int i = 0; i < q[8]; i++) {
+    if (draw_is_get1d(q[7], i)) {
+      *o++ = sampler_get1d<MODE>(T, s);
+    } else {
+      const f2 v = sampler_get2d<MODE>(T, s);
+      *o++ = v.x;
+      *o++ = v.y;
+    }
+  }
+}
+// one thread per case; MODE & kSmLds: the launch has kLdsLaneStride threads a workgroup and every lane keeps its own pixel's slice,
+// as a lane of the megakernel or of the AO kernel does for the work item it holds
+template <int MODE>
+__global__ void test_draws_kernel(DTables tables, const int32_t* cases, const long long* offsets, int n, float* out) {
+  const int i = int(blockIdx.x * blockDim.x + threadIdx.x);
+  if constexpr ((MODE & kSmLds) != 0) {
+    __shared__ int lds_sobol[kLdsSamplerDims * 256 / 4];
+    __shared__ uint32_t lds_tile[kLdsTileDwords * kLdsLaneStride];
+    stage_sobol_rows(lds_sobol, tables, threadIdx.x, kLdsLaneStride);
+    const DTables T = lane_tables(tables, lds_sobol, lds_tile, threadIdx.x);
+    if (i < n) load_lane_slice(tables, cases[i * kDrawCaseInts + 4], cases[i * kDrawCaseInts + 5], lds_tile, threadIdx.x);
+    __syncthreads();
+    if (i < n) test_draws_case<MODE>(T, cases + i * kDrawCaseInts, out + offsets[i]);
+  } else {
+    if (i < n) test_draws_case<MODE>(tables, cases + i * kDrawCaseInts, out + offsets[i]);
+  }
+}
 __global__ void test_rng_kernel(unsigned long long* out) {
   const int pix = threadIdx.x;
   if (pix >= 6) return;
@@ -491,6 +529,60 @@ int pine_gpu_test_sampler(int device, int spp_req, float* out, int64_t capacity)
   DTables T{dt, dt + 65536, dt + 65536 + 131072, nullptr, nullptr, 0};
   hipLaunchKernelGGL(test_sampler_kernel, dim3(6), dim3(64), 0, 0, T, spp, dout.get());
   return hip_launch_check(__func__) || dout.download(out, size_t(need), __func__) ? -1 : 0;
+}
+int64_t pine_gpu_test_sampler_draws(int device, int kind, int spp, int w, int h, int mode, const int32_t* cases, int64_t n, float* out,
+                                    int64_t capacity) {
+  const auto refuse = [](const char* why) {
+    set_error(std::string("pine_gpu_test_sampler_draws: ") + why);
+    return int64_t(-1);
+  };
+  if (!cases || !out || n < 0 || n > kDrawMaxCases || kind < 0 || kind > 2 || (mode != 0 && mode != 1)) return refuse("bad argument");
+  if (spp <= 0) return refuse("samples per pixel must be positive");
+  if (spp > kMaxDeviceSpp) return refuse("at most 4096 samples per pixel");
+  if (w <= 0 || h <= 0 || w > 65535 || h > 65535) return refuse("a film side is 1 .. 65535 pixels");
+  if (device < 0 && mode != 0) return refuse("the LDS form runs on the device only");
+  const int sampler_spp = kind == 0 ? effective_spp(spp) : spp;  // (as check_params hands it to a plan)
+  std::vector<long long> offsets(size_t(n) + 1, 0);
+  for (int64_t i = 0; i < n; i++) {
+    const int32_t* q = cases + i * kDrawCaseInts;
+    if (q[0] != kind || q[1] != spp || q[2] != w || q[3] != h) return refuse("a case names another sampler or film than the call");
+    if (q[4] < 0 || q[4] >= w || q[5] < 0 || q[5] >= h) return refuse("a case's pixel lies outside the film");
+    if (q[6] < 0 || q[6] >= sampler_spp) return refuse("a case's sample index lies outside the pixel's samples");
+    if (q[7] < 0 || q[7] > 2 || q[8] < 0 || q[8] > kDrawMaxCalls) return refuse("a case's pattern is 0, 1 or 2, its calls at most 65536");
+    int floats = 0;
+    for (int c = 0; c < q[8]; c++) floats += draw_is_get1d(q[7], c) ? 1 : 2;
+    offsets[size_t(i) + 1] = offsets[size_t(i)] + floats;
+  }
+  const long long total = offsets[size_t(n)];
+  if (capacity < total) return refuse("capacity too small");
+  TableBlob tables_blob;
+  if (load_tables(tables_blob)) return -1;
+  DTables T{};
+  DeviceBuffer<uint8_t> d_tables, d_halton;
+  if (device < 0) {
+    std::vector<uint8_t> host_tables;
+    if (fill_sampler_tables(*tables_blob, kind, sampler_spp, w, h, T, d_tables, d_halton, &host_tables)) return -1;
+    for (int64_t i = 0; i < n; i++) {
+      if (kind == 0) test_draws_case<0>(T, cases + i * kDrawCaseInts, out + offsets[size_t(i)]);
+      else test_draws_case<kSmSobol>(T, cases + i * kDrawCaseInts, out + offsets[size_t(i)]);
+    }
+    return total;
+  }
+  if (need_device(device)) return -1;
+  if (n == 0) return 0;
+  DeviceBuffer<int32_t> dc;
+  DeviceBuffer<long long> doff;
+  DeviceBuffer<float> dout;
+  if (fill_sampler_tables(*tables_blob, kind, sampler_spp, w, h, T, d_tables, d_halton) || dc.upload(cases, size_t(n) * kDrawCaseInts, __func__) ||
+      doff.upload(offsets.data(), size_t(n), __func__) || dout.alloc(size_t(std::max(total, 1ll)), __func__))
+    return -1;
+  const dim3 block(mode ? kLdsLaneStride : 64), grid(unsigned((n + block.x - 1) / block.x));
+  const int m = (mode ? kSmLds : 0) | (kind ? kSmSobol : 0);
+  if (m == 0) hipLaunchKernelGGL(test_draws_kernel<0>, grid, block, 0, 0, T, dc.get(), doff.get(), int(n), dout.get());
+  else if (m == kSmLds) hipLaunchKernelGGL(test_draws_kernel<kSmLds>, grid, block, 0, 0, T, dc.get(), doff.get(), int(n), dout.get());
+  else if (m == kSmSobol) hipLaunchKernelGGL(test_draws_kernel<kSmSobol>, grid, block, 0, 0, T, dc.get(), doff.get(), int(n), dout.get());
+  else hipLaunchKernelGGL(test_draws_kernel<(kSmLds | kSmSobol)>, grid, block, 0, 0, T, dc.get(), doff.get(), int(n), dout.get());
+  return hip_launch_check(__func__) || dout.download(out, size_t(total), __func__) ? -1 : total;
 }
 int pine_gpu_test_rng(int device, uint64_t* out, int64_t capacity) {
   if (need_device(device)) return -1;

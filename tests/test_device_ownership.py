@@ -166,6 +166,9 @@ def test_hooks_give_back_what_they_took():
         assert stats[0] == 64 and stats[1] == 0
         stream = np.zeros(6 * 530, F32)
         ok(lib.pine_gpu_test_sampler(0, 1, fp(stream), stream.size), "sampler")
+        for kind, mode in ((2, 0), (1, 0), (0, 1)):  # HaltonSampler's table block; BlueSampler through the LDS form
+            draw = np.int32([[kind, 16, 300, 200, 129, 130, 15, 1, 8]])
+            ok(lib.pine_gpu_test_sampler_draws(0, kind, 16, 300, 200, mode, draw.ctypes.data_as(C.POINTER(C.c_int32)), 1, fp(big), big.size), "sampler_draws")
         words = np.zeros(6 * 19, np.uint64)
         ok(lib.pine_gpu_test_rng(0, words.ctypes.data_as(C.POINTER(C.c_uint64)), words.size), "rng")
         for flat in (0, 1):
@@ -205,6 +208,11 @@ def test_hooks_that_reject_their_arguments_give_back_what_they_took():
     with nothing_left_behind():
         rejected(lib.pine_gpu_test_math_eval(0, 13, None, None, None, 4, x.view(np.uint32).ctypes.data_as(P_U32)), "bad argument")
         rejected(lib.pine_gpu_test_sampler(0, 1, fp(big), 10), "capacity too small")
+        draw = np.int32([[2, 16, 300, 200, 129, 130, 15, 1, 8]])
+        rejected(lib.pine_gpu_test_sampler_draws(0, 2, 16, 300, 200, 0, draw.ctypes.data_as(C.POINTER(C.c_int32)), 1, fp(big), 11), "capacity too small")
+        draw[0, 4] = 300
+        rejected(lib.pine_gpu_test_sampler_draws(0, 2, 16, 300, 200, 0, draw.ctypes.data_as(C.POINTER(C.c_int32)), 1, fp(big), big.size),
+                 "pine_gpu_test_sampler_draws: a case's pixel lies outside the film")
         rejected(lib.pine_gpu_test_rng(0, np.zeros(4, np.uint64).ctypes.data_as(C.POINTER(C.c_uint64)), 4), "capacity too small")
         rejected(lib.pine_gpu_test_traverse(cbox._h, 0, fp(RAYS), len(RAYS), 0, 1, big.view(np.uint32).ctypes.data_as(P_U32)), "bad argument")
         rejected(lib.pine_gpu_test_shapes(cbox._h, 0, fp(RAYS), len(RAYS), fp(big), 1), "capacity too small")

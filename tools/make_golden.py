@@ -8,7 +8,8 @@ and the reference's outputs, no reference source) are committed and travel to th
     python tools/make_golden.py --bvh --vertices   # the reference's BVH + traversal orders, per-vertex path terms
     python tools/make_golden.py --sampling # BSDF lobes and shape / light sampling per call (tests/test_sampling_fixtures.py)
     python tools/make_golden.py --nodes    # shading-node programs and the material-to-lobe step per call (tests/test_node_fixtures.py)
-    python tools/make_golden.py --live     # the reference's films of the oracle tests' cbox and seeded random scenes
+    python tools/make_golden.py --draws    # Sobol / Halton / Blue sampler draws per call at real film sizes, the strip films (tests/test_sampler_draws.py)
+    python tools/make_golden.py --live    # the reference's films of the oracle tests' cbox and seeded random scenes
 """
 import hashlib
 import json
@@ -391,8 +392,80 @@ def live_fixture(tmp):
     np.savez_compressed(os.path.join(OUT, "oracle_scenes.npz"), **out)
 
 
+def draw_cases():
+    """The case tables of tests/golden/sampler_draws_*.npz, rows of `pine_ref draws`: kind (0 Blue, 1 Sobol, 2 Halton), spp,
+    film w, film h, px, py, sample index, pattern (0 get2d, 1 get1d / get2d alternating, 2 get1d), calls."""
+    sobol, halton, blue = [], [], []
+    # SobolSampler: a count that is no power of two (the index runs into the next pixel's range), 1 spp, real film sizes with an odd
+    # and an even log2(spp), the widest film at the most samples the device takes (indices up to 2^44), odd log2 on the tallest
+    for w, h, spp in ((45, 37, 12), (64, 64, 1), (1920, 1080, 2), (1920, 1080, 1024), (65535, 1, 4096), (1, 65535, 8)):
+        pixels = list(dict.fromkeys([(0, 0), (w - 1, 0), (0, h - 1), (w - 1, h - 1), (w * 2 // 3, h // 3)]))
+        for px, py in pixels:
+            for index in dict.fromkeys([0, spp // 2, spp - 1]):
+                for pattern in (0, 1):
+                    sobol.append((1, spp, w, h, px, py, index, pattern, 120))
+    # HaltonSampler(4096): pixels on both sides of the 128 wrap, the highest index the device takes (4095 * 31104 + offset < 2^27).
+    # The dimension starts at 2: get2d alone wraps once in 550 calls (1100 floats); get1d / get2d alternating meets the end of the
+    # table first as a get2d at 999 (dimension 999 is skipped), then as a get1d at 1000: 1340 calls pass both; get1d alone wraps
+    # once in 1100 calls, after reading dimension 999.
+    for px, py in ((0, 0), (127, 127), (128, 5), (129, 242), (1919, 1079), (65534, 0)):
+        for index in (0, 1, 4095):
+            halton.append((2, 4096, 65535, 1080, px, py, index, 0, 550))
+            halton.append((2, 4096, 65535, 1080, px, py, index, 1, 1340))
+        halton.append((2, 4096, 65535, 1080, px, py, 4095, 2, 1100))
+    # BlueSampler, for the LDS form of the kernels: pixels on both sides of the 128-pixel tile; both patterns leave the 40 cached
+    # dimensions, pass the wrap at 256 (get2d alone from 256, alternating calls as a get2d from 256 after a get1d of 255) and
+    # come back into the cache at dimension 2
+    for spp in (1, 16, 256):
+        for px, py in ((0, 0), (127, 127), (128, 5), (129, 242), (1919, 1079)):
+            blue.append((0, spp, 1920, 1080, px, py, spp - 1, 0, 135))
+            blue.append((0, spp, 1920, 1080, px, py, spp // 2, 1, 200))
+    return np.int32(sobol + blue), np.int32(halton)
+
+
+def draws_fixtures(tmp):
+    """tests/golden/sampler_draws_sobol.npz (SobolSampler and BlueSampler cases), sampler_draws_halton.npz (HaltonSampler cases and
+    the CRC-32 of the reference's Primes, PrimeSums and radicalInversePermutations), and the strip films: tests/test_sampler_draws.py."""
+    import zlib
+    from oracle.oracle import draw_floats
+    sobol, halton = draw_cases()
+    cp, op, tp = (os.path.join(tmp, x) for x in ("cases.bin", "draws.bin", "halton_tables.bin"))
+    total = 0
+    for name, cases in (("sobol", sobol), ("halton", halton)):
+        cases.tofile(cp)
+        run_ref("draws", cp, op, *([tp] if name == "halton" else []))
+        draws = np.fromfile(op, dtype=np.float32)
+        assert draws.size == int(draw_floats(cases).sum()), (draws.size, int(draw_floats(cases).sum()))
+        extra = {}
+        if name == "halton":
+            tables = open(tp, "rb").read()
+            n_perms = (len(tables) - 8000) // 2
+            assert n_perms == 3682913, n_perms  # = the sum of the first 1000 primes
+            extra = {"table_counts": np.int64([1000, 1000, n_perms]),
+                     "table_crc32": np.uint32([zlib.crc32(tables[:4000]), zlib.crc32(tables[4000:8000]), zlib.crc32(tables[8000:])])}
+        path = os.path.join(OUT, f"sampler_draws_{name}.npz")
+        np.savez_compressed(path, cases=cases, draws=draws, **extra)
+        total += os.path.getsize(path)
+        print(name, len(cases), "cases,", draws.size, "floats,", os.path.getsize(path), "bytes")
+    # the strip films (tests/strip_scenes.py): pixel coordinates past 128 and past a 512 Morton range through the whole kernel
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from strip_scenes import STRIP_FILM_NAMES, strip_scene
+    for name in STRIP_FILM_NAMES:
+        scene, sampler, spp, depth = strip_scene(name)
+        ps, film, info = ref_film(scene, spp, depth, tmp, sampler)
+        path = os.path.join(OUT, f"film_{name}.npz")
+        np.savez_compressed(path, film=film, pscene=np.array(ps), spp=spp, depth=depth)
+        total += os.path.getsize(path)
+        print(name, film.shape, hashlib.md5(film.tobytes()).hexdigest(), os.path.getsize(path), "bytes")
+    print("total", total, "bytes")
+
+
 def main():
     full = "--full" in sys.argv
+    if "--draws" in sys.argv:
+        with tempfile.TemporaryDirectory() as tmp:
+            draws_fixtures(tmp)
+        return
     if "--live" in sys.argv:
         with tempfile.TemporaryDirectory() as tmp:
             live_fixture(tmp)

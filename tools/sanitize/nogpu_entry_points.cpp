@@ -81,6 +81,8 @@ int64_t pine_gpu_plan_vertex_log(pine_gpu_plan*, float*, int64_t) { return fail(
 int pine_gpu_film_unpack(int, int, int, int, const void*, void*, void*) { return fail(); }
 int pine_gpu_test_sampler(int, int, float*, int64_t) { return fail(); }
 int pine_gpu_test_rng(int, uint64_t*, int64_t) { return fail(); }
+int64_t pine_gpu_test_sampler_draws(int, int, int, int, int, int, const int32_t*, int64_t, float*, int64_t) { return fail(); }
+int pine_gpu_test_halton_tables(uint32_t*, int64_t*) { return fail(); }
 int pine_gpu_test_sincos(int, const float*, int64_t, float*, float*) { return fail(); }
 int pine_gpu_test_powlog(int, const float*, const float*, int64_t, float*, float*) { return fail(); }
 int pine_gpu_test_atan(int, const float*, const float*, int64_t, float*, float*) { return fail(); }
