@@ -101,10 +101,11 @@ int pine_gpu_scene_set_env_atmosphere(pine_gpu_scene*, const float sun_direction
 /* Shading nodes (Nodef / Node3f: src/pine/core/node.h:13-297, registered node.cpp:29-116).  A node
  * lives in the scene's node table; each call returns its id (or < 0).  Supported: constants, the
  * surface inputs Position / Normal / UV, NodeBinary (+ - * / ^), NodeUnary (- abs sqr sqrt fract),
- * NodeComponent, NodeToVec3, NodeCheckerboard; `lerp` etc. are compositions of these exactly as
- * node.cpp:88-102 composes them.  Not supported: noise, image and function nodes.  Subtrees that do
- * not read the surface are folded to literals on the host with the same float operations; the rest
- * run as small postfix programs in the shading stage of the kernels. */
+ * NodeComponent, NodeToVec3, NodeCheckerboard, NodeImage / NodeImagef (`Texture`); `lerp` etc. are
+ * compositions of these exactly as node.cpp:88-102 composes them.  Not supported: noise and function
+ * nodes.  Subtrees that do not read the surface are folded to literals on the host with the same float
+ * operations (a `Texture` of a constant coordinate included); the rest run as small postfix programs in
+ * the shading stage of the kernels. */
 int pine_gpu_scene_node_constf(pine_gpu_scene*, float value);                 /* Nodef(float)   node.h:262 */
 int pine_gpu_scene_node_const3(pine_gpu_scene*, const float value[3]);        /* Node3f(vec3)   node.h:281 */
 int pine_gpu_scene_node_input(pine_gpu_scene*, int which);                    /* 0 Position, 1 Normal, 2 UV  node.h:113-127 */
@@ -115,6 +116,19 @@ int pine_gpu_scene_node_to_vec3(pine_gpu_scene*, int x, int y, int z);        /*
 int pine_gpu_scene_node_checkerboard(pine_gpu_scene*, int p, float ratio);    /* NodeCheckerboard node.h:232-239, node.cpp:15-18 */
 int pine_gpu_scene_node_splat(pine_gpu_scene*, int a);                        /* a Nodef where a Node3f is expected  node.h:78,291-293 */
 int pine_gpu_scene_node_is_vec3(pine_gpu_scene*, int id);                     /* 1 Node3f, 0 Nodef */
+/* Images for NodeImage / NodeImagef (image.h:11-25), rows as loaded (nothing is flipped); each call returns the image's id.
+ * Float texels (Array2d<vec3>: 3 per texel, finite) are kept as they are.  8-bit texels (Array2d<vec3u8> / <vec4u8>:
+ * `channels` 3 or 4) are kept as one word each and linearised on lookup, pow(value / 255, 2.2) (image.cpp:10-13); the alpha
+ * of a 4-channel image never reaches a result, as in vec3(vec4).  Refused: w or h below 1, more than 2^26 texels, a float
+ * texel that is not finite, `channels` other than 3 or 4. */
+int pine_gpu_scene_add_image(pine_gpu_scene*, const float* rgb, int w, int h);
+int pine_gpu_scene_add_image_u8(pine_gpu_scene*, const uint8_t* texels, int channels, int w, int h);
+/* NodeImage(p, image) -> Node3f, NodeImagef(p, image) -> Nodef (its .x)  node.h:236-251, node.cpp:20-27: the texel at
+ * min(vec2i(size * fract(vec2(p))), size - 1) -- nearest, repeating, unfiltered.  Where a coordinate is not finite the
+ * reference's float-to-int conversion is undefined; here that axis reads texel 0.  Refused: an image id that does not exist,
+ * a `p` that is not a Node3f. */
+int pine_gpu_scene_node_image(pine_gpu_scene*, int p, int image);
+int pine_gpu_scene_node_imagef(pine_gpu_scene*, int p, int image);
 /* Materials whose parameters are nodes (albedo: Node3f; the others: Nodef). */
 int pine_gpu_scene_add_material_diffuse_n(pine_gpu_scene*, const char* name, int albedo);
 int pine_gpu_scene_add_material_uber_n(pine_gpu_scene*, const char* name, int albedo, int roughness, int metallic,
@@ -648,6 +662,9 @@ int64_t pine_gpu_test_env_table(pine_gpu_scene*, float* out, int64_t capacity);
  * parameter is a literal of the record), then per op 4 words: opcode, x, y, z (float bits).  Returns the number of words (they
  * are written when out is not NULL and capacity_words suffices), or < 0: a node tree needs more than the evaluator's stack. */
 int64_t pine_gpu_test_node_programs(pine_gpu_scene*, int32_t* out, int64_t capacity_words);
+/* ... and the size in 4-byte words of the image buffer a plan of the scene would upload for them: 0 where no program reads
+ * an image, else the 256-word 8-bit table and every image a program names, once (tests/test_texture.py). */
+int64_t pine_gpu_test_tex_words(pine_gpu_scene*);
 /* The material-to-parameters step, for tests/test_node_fixtures.py: compiles the node programs, then material_params of every
  * material (scene order) at n queries of 8 floats (p, n, uv).  out_host: per (material, query) 10 floats -- 0-2 albedo
  * 3-5 albedo / Pi  6 roughness  7 metallic  8 transmission  9 ior.  device = -1: the host build of the same functions. */

@@ -135,6 +135,10 @@ SIGNATURES = {
     "pine_gpu_scene_node_to_vec3": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "pine_gpu_scene_node_checkerboard": (C.c_int, [C.c_void_p, C.c_int, C.c_float]),
     "pine_gpu_scene_node_splat": (C.c_int, [C.c_void_p, C.c_int]),
+    "pine_gpu_scene_add_image": (C.c_int, [C.c_void_p, c_f_p, C.c_int, C.c_int]),
+    "pine_gpu_scene_add_image_u8": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_int]),
+    "pine_gpu_scene_node_image": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "pine_gpu_scene_node_imagef": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "pine_gpu_scene_node_is_vec3": (C.c_int, [C.c_void_p, C.c_int]),
     "pine_gpu_scene_add_material_diffuse_n": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     "pine_gpu_scene_add_material_uber_n": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float]),
@@ -227,6 +231,7 @@ SIGNATURES = {
     "pine_gpu_test_env_light_sample": (C.c_int, [C.c_void_p, C.c_int, c_f_p, C.c_int64, c_f_p]),
     "pine_gpu_test_env_table": (C.c_int64, [C.c_void_p, c_f_p, C.c_int64]),
     "pine_gpu_test_node_programs": (C.c_int64, [C.c_void_p, C.POINTER(C.c_int32), C.c_int64]),
+    "pine_gpu_test_tex_words": (C.c_int64, [C.c_void_p]),
     "pine_gpu_test_material_params": (C.c_int, [C.c_void_p, C.c_int, c_f_p, C.c_int64, c_f_p]),
     "pine_gpu_test_choose_lobe": (C.c_int, [C.c_void_p, C.c_int, c_f_p, C.c_int64, c_f_p]),
     "pine_gpu_test_frame_table": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int, c_f_p, c_f_p, C.c_int64, C.POINTER(C.c_int32), C.c_int64,

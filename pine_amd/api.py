@@ -14,6 +14,8 @@ Everything here is plumbing over the C ABI (include/pine_gpu.h); all arithmetic 
 render (shape constructors, matrices, camera, BVH) happens in libpine_gpu.so.
 """
 import ctypes as C
+import os
+
 import numpy as np
 
 from . import _lib
@@ -162,10 +164,68 @@ class Node:
             r = lib.pine_gpu_scene_node_checkerboard(h, sub(a[0]), float(a[1]))
         elif k == "splat":
             r = lib.pine_gpu_scene_node_splat(h, sub(a[0]))
+        elif k in ("image", "imagef"):
+            p = sub(a[0])
+            fn = lib.pine_gpu_scene_node_image if k == "image" else lib.pine_gpu_scene_node_imagef
+            r = fn(h, p, a[1]._instantiate(scene))
         else:
             raise PineError("unknown node kind " + k)
         memo[id(self)] = (self, check(r, "node"))  # (keeps the node alive: ids of dead temporaries get reused)
         return memo[id(self)][1]
+
+
+class Image:
+    """An image for Texture / Texturef (image.h:11-25), rows as loaded: an (h, w, 3) float32 array (kept as it is), an
+    (h, w, 3) or (h, w, 4) uint8 array (a texel reads as pow(value / 255, 2.2); alpha never reaches a result), or the path of
+    a Radiance .hdr or a .png file (pine_amd/png.py: expanded to 3 channels, as the reference's image_from loads it).  One
+    Image object is one image of a scene however many nodes look it up."""
+    def __init__(self, array_or_path):
+        a = array_or_path
+        if isinstance(a, (str, bytes)) or hasattr(a, "__fspath__"):
+            path = os.fsdecode(a)
+            with open(path, "rb") as f:
+                head = f.read(8)
+            if head == b"\x89PNG\r\n\x1a\n":
+                from .png import read_png
+                a = read_png(path, 3)
+            elif head[:2] == b"#?":
+                from .hdr import read_hdr
+                a = read_hdr(path)
+            elif head[:3] == b"\xff\xd8\xff":
+                raise PineError(f"{path}: JPEG images are not supported (a lossy format; use PNG or Radiance .hdr)")
+            else:
+                raise PineError(f"{path}: neither a PNG nor a Radiance .hdr file")
+        a = np.asarray(a)
+        if a.dtype != np.uint8:
+            a = a.astype(np.float32, copy=False)
+        if a.ndim != 3 or a.shape[2] not in ((3, 4) if a.dtype == np.uint8 else (3,)):
+            raise PineError("Image: expected (h, w, 3) float32 or (h, w, 3 | 4) uint8 texels")
+        self.texels = np.ascontiguousarray(a)
+
+    @staticmethod
+    def of(x):
+        return x if isinstance(x, Image) else Image(x)
+
+    def _instantiate(self, scene):
+        if id(self) not in scene._images:  # (the scene keeps the object alive: ids of dead temporaries get reused)
+            t = self.texels
+            h, w, ch = t.shape
+            if t.dtype == np.uint8:
+                r = lib.pine_gpu_scene_add_image_u8(scene._h, t.ctypes.data_as(C.POINTER(C.c_uint8)), ch, w, h)
+            else:
+                r = lib.pine_gpu_scene_add_image(scene._h, t.ctypes.data_as(_lib.c_f_p), w, h)
+            scene._images[id(self)] = (self, check(r, "Image"))
+        return scene._images[id(self)][1]
+
+
+def Texture(p, image):
+    """NodeImage (node.h:236-243, node.cpp:20-23): the rgb of the texel at min(vec2i(size * fract(vec2(p))), size - 1)."""
+    return Node("image", Node.of(p, True), Image.of(image), is_vec3=True)
+
+
+def Texturef(p, image):
+    """NodeImagef (node.h:244-251, node.cpp:24-27): the same texel's first component."""
+    return Node("imagef", Node.of(p, True), Image.of(image))
 
 
 def Position(): return Node("position", is_vec3=True)
@@ -469,6 +529,7 @@ class Scene:
         self._h = C.c_void_p(check(lib.pine_gpu_scene_create(), "Scene()"))
         self.camera = None
         self._anon = 0
+        self._images = {}  # id(Image) -> (Image, its id in this scene): one Image object is stored once
 
     def __del__(self):
         try:

@@ -8,6 +8,7 @@
 #pragma once
 #include "pine_math.h"
 #include "pine_atmosphere.h"
+#include "pine_image_node.h"
 #include "pine_types.h"
 
 namespace pine_gpu {
@@ -1369,7 +1370,7 @@ PINE_HD bool bxdf_is_delta(const DBxdf& b) {
 // A float node travels as a splat; every operation is componentwise, so the float result is each
 // component of the vec3 result.
 // ------------------------------------------------------------------------------------------------
-PINE_HD f3 node_program_eval(const DNodeOp* ops, int start, f3 p, f3 n, f2 uv) {
+PINE_HD f3 node_program_eval(const DNodeOp* ops, const float* tex, int start, f3 p, f3 n, f2 uv) {
   f3 st[kNodeStack];
   int sp = 0;
   for (int pc = start;; pc++) {
@@ -1414,6 +1415,11 @@ PINE_HD f3 node_program_eval(const DNodeOp* ops, int start, f3 p, f3 n, f2 uv) {
         const f3 x{(a.x - floorf(a.x)) - o.x, (a.y - floorf(a.y)) - o.x, (a.z - floorf(a.z)) - o.x};
         const float v = float(x.x * x.y * x.z > 0);
         st[sp - 1] = f3{v, v, v};
+        break;
+      }
+      case N_IMAGE: {
+        const int hz = as_int(o.z);
+        st[sp - 1] = image_lookup(tex, tex + as_int(o.x), as_int(o.y), hz & ~kTexU8Bit, (hz & kTexU8Bit) != 0, st[sp - 1]);
         break;
       }
       default: break;
@@ -1600,17 +1606,17 @@ struct MatParams {
   float roughness, metallic, transmission, ior;
 };
 template <unsigned F = F_ALL>
-PINE_HD MatParams material_params(const DMaterial* m, const DNodeOp* ops, f3 p, f3 n, f2 uv) {
+PINE_HD MatParams material_params(const DMaterial* m, const DNodeOp* ops, const float* tex, f3 p, f3 n, f2 uv) {
   MatParams r{ld3(m->color), ld3(m->color_over_pi), m->roughness, m->metallic, m->transmission, m->ior};
   if constexpr (F & F_NODES) {
     if (m->prog[0] >= 0) {
-      r.albedo = node_program_eval(ops, m->prog[0], p, n, uv);
+      r.albedo = node_program_eval(ops, tex, m->prog[0], p, n, uv);
       r.albedo_over_pi = r.albedo / kPi;  // the Lambertian f (bxdf.cpp:21,27)
     }
-    if (m->prog[1] >= 0) r.roughness = node_program_eval(ops, m->prog[1], p, n, uv).x;
-    if (m->prog[2] >= 0) r.metallic = node_program_eval(ops, m->prog[2], p, n, uv).x;
+    if (m->prog[1] >= 0) r.roughness = node_program_eval(ops, tex, m->prog[1], p, n, uv).x;
+    if (m->prog[2] >= 0) r.metallic = node_program_eval(ops, tex, m->prog[2], p, n, uv).x;
     if (m->prog[3] >= 0) {
-      const float v = node_program_eval(ops, m->prog[3], p, n, uv).x;
+      const float v = node_program_eval(ops, tex, m->prog[3], p, n, uv).x;
       if (m->kind == MAT_GLOSSY || m->kind == MAT_GLASS) r.ior = v;
       else r.transmission = v;
     }

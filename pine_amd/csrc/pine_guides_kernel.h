@@ -31,7 +31,7 @@ __global__ void __launch_bounds__(kBlock) guides_kernel(DeviceScene S, int tiles
     const DShape* shape = &V.shapes[geom & kPrimIndexMask];
     DSurface it;
     hit_surface<F>(V, shape, prim, r.o, r.d, r.tmax, it);
-    a = material_params<F>(&V.materials[shape->material], V.node_ops, it.p, it.n, it.uv).albedo;
+    a = material_params<F>(&V.materials[shape->material], V.node_ops, V.tex, it.p, it.n, it.uv).albedo;
     n = it.n;
   }
   const size_t at = (size_t(py) * size_t(S.cam.W) + size_t(px)) * 3;

@@ -6,6 +6,7 @@
 #include "pine_embree_order.h"
 #include "pine_math_check.h"
 #include "pine_atmosphere.h"
+#include "pine_image_node.h"
 
 #include <algorithm>
 #include <cmath>
@@ -207,8 +208,31 @@ static f3 fold_node(const SceneHost& S, const HostNode& k) {
       return f3{v, v, v};
     }
     case HostNode::Splat: return S.node_fold(k.a);
+    case HostNode::Image:
+    case HostNode::ImageF: {  // the device's own lookup (pine_device.h image_lookup), on the scene's copy of the image
+      const HostImage& im = S.images[size_t(k.n)];
+      const f3 v = image_lookup(u8_linear_table(), im.words.data(), im.w, im.h, im.u8, S.node_fold(k.a));
+      return k.kind == HostNode::Image ? v : f3{v.x, v.x, v.x};
+    }
     default: return f3{0, 0, 0};
   }
+}
+bool tex_ops_valid(const std::vector<DNodeOp>& ops, size_t tex_words) {
+  for (const DNodeOp& o : ops) {
+    if (o.op != N_IMAGE) continue;
+    const long long at = as_int(o.x), w = as_int(o.y), h = as_int(o.z) & ~kTexU8Bit;
+    const long long per = (as_int(o.z) & kTexU8Bit) ? 1 : 3;
+    if (at < kTexTableWords || w < 1 || h < 1 || w * h > kTexMaxTexels || at + w * h * per > (long long)tex_words) return false;
+  }
+  return true;
+}
+const float* u8_linear_table() {
+  static const std::vector<float> table = [] {
+    std::vector<float> t(256);
+    for (int v = 0; v < 256; v++) t[size_t(v)] = std::pow(float(v) / 255.0f, 2.2f);
+    return t;
+  }();
+  return table.data();
 }
 int SceneHost::add_node(const HostNode& n) {
   auto ok = [&](int id, bool want_vec3) {
@@ -235,6 +259,14 @@ int SceneHost::add_node(const HostNode& n) {
       break;
     case HostNode::Un3:
     case HostNode::Checker:
+      if (!ok(n.a, true)) return -1;
+      break;
+    case HostNode::Image:
+    case HostNode::ImageF:
+      if (n.n < 0 || n.n >= int(images.size())) {
+        set_error("`Texture`: image id out of range");
+        return -1;
+      }
       if (!ok(n.a, true)) return -1;
       break;
     case HostNode::Comp:
@@ -269,7 +301,8 @@ int SceneHost::add_node(const HostNode& n) {
 }
 // postfix flattening of one node tree; returns the maximum stack depth, or -1 -- at once where the tree needs more than
 // kNodeStack slots: every node pushes a value, and a tree of shared operands has exponentially many to walk
-static int emit_program(const SceneHost& S, int id, std::vector<DNodeOp>& ops, int depth) {
+// `tex`, `tex_at`: the plan's image buffer and each image's first word in it (-1: not yet there)
+static int emit_program(const SceneHost& S, int id, std::vector<DNodeOp>& ops, int depth, std::vector<float>& tex, std::vector<long long>& tex_at) {
   if (depth >= kNodeStack) return -1;
   const HostNode& k = S.nodes[size_t(id)];
   auto push = [&](int op, float x = 0, float y = 0, float z = 0) { ops.push_back(DNodeOp{op, x, y, z}); };
@@ -287,9 +320,9 @@ static int emit_program(const SceneHost& S, int id, std::vector<DNodeOp>& ops, i
     case HostNode::UV: push(N_UV); break;
     case HostNode::BinF:
     case HostNode::Bin3: {
-      const int m1 = emit_program(S, k.a, ops, depth);
+      const int m1 = emit_program(S, k.a, ops, depth, tex, tex_at);
       if (m1 < 0) return -1;
-      const int m2 = emit_program(S, k.b, ops, depth + 1);
+      const int m2 = emit_program(S, k.b, ops, depth + 1, tex, tex_at);
       if (m2 < 0) return -1;
       push(binop(k.op));
       m = std::max(m1, m2);
@@ -297,42 +330,59 @@ static int emit_program(const SceneHost& S, int id, std::vector<DNodeOp>& ops, i
     }
     case HostNode::UnF:
     case HostNode::Un3:
-      m = emit_program(S, k.a, ops, depth);
+      m = emit_program(S, k.a, ops, depth, tex, tex_at);
       if (m < 0) return -1;
       push(unop(k.op));
       break;
     case HostNode::Comp:
-      m = emit_program(S, k.a, ops, depth);
+      m = emit_program(S, k.a, ops, depth, tex, tex_at);
       if (m < 0) return -1;
       push(N_COMP, float(k.n));
       break;
     case HostNode::ToVec3:
       if (k.b < 0) {
-        m = emit_program(S, k.a, ops, depth);  // splat already
+        m = emit_program(S, k.a, ops, depth, tex, tex_at);  // splat already
       } else {
-        const int m1 = emit_program(S, k.a, ops, depth);
+        const int m1 = emit_program(S, k.a, ops, depth, tex, tex_at);
         if (m1 < 0) return -1;
-        const int m2 = emit_program(S, k.b, ops, depth + 1);
+        const int m2 = emit_program(S, k.b, ops, depth + 1, tex, tex_at);
         if (m2 < 0) return -1;
-        const int m3 = emit_program(S, k.c, ops, depth + 2);
+        const int m3 = emit_program(S, k.c, ops, depth + 2, tex, tex_at);
         if (m3 < 0) return -1;
         push(N_TOVEC3);
         m = std::max(m1, std::max(m2, m3));
       }
       break;
     case HostNode::Checker:
-      m = emit_program(S, k.a, ops, depth);
+      m = emit_program(S, k.a, ops, depth, tex, tex_at);
       if (m < 0) return -1;
       push(N_CHECKER, k.f);
       break;
-    case HostNode::Splat: m = emit_program(S, k.a, ops, depth); break;
+    case HostNode::Splat: m = emit_program(S, k.a, ops, depth, tex, tex_at); break;
+    case HostNode::Image:
+    case HostNode::ImageF: {
+      m = emit_program(S, k.a, ops, depth, tex, tex_at);
+      if (m < 0) return -1;
+      const HostImage& im = S.images[size_t(k.n)];
+      long long& at = tex_at[size_t(k.n)];
+      if (at < 0) {  // an image that several nodes name is stored once
+        if (tex.empty()) tex.assign(u8_linear_table(), u8_linear_table() + kTexTableWords);
+        at = (long long)tex.size();
+        tex.insert(tex.end(), im.words.begin(), im.words.end());
+      }
+      push(N_IMAGE, as_float(int(at)), as_float(im.w), as_float(im.h | (im.u8 ? kTexU8Bit : 0)));
+      if (k.kind == HostNode::ImageF) push(N_COMP, 0.0f);
+      break;
+    }
     default: return -1;
   }
   return m;
 }
-bool SceneHost::compile_node_programs(std::vector<DMaterial>& out, std::vector<DNodeOp>& ops) const {
+bool SceneHost::compile_node_programs(std::vector<DMaterial>& out, std::vector<DNodeOp>& ops, std::vector<float>& tex) const {
   out = materials;
   ops.clear();
+  tex.clear();
+  std::vector<long long> tex_at(images.size(), -1);
   for (size_t i = 0; i < out.size(); i++) {
     DMaterial& m = out[i];
     for (int k = 0; k < 4; k++) {
@@ -351,8 +401,12 @@ bool SceneHost::compile_node_programs(std::vector<DMaterial>& out, std::vector<D
         continue;
       }
       m.prog[k] = int(ops.size());
-      const int depth = emit_program(*this, id, ops, 0);
+      const int depth = emit_program(*this, id, ops, 0, tex, tex_at);
       ops.push_back(DNodeOp{N_END, 0, 0, 0});
+      if ((long long)tex.size() > kTexMaxWords) {
+        set_error("the images of the scene's `Texture` nodes need more than 2^30 words of device memory");
+        return false;
+      }
       if (depth < 0 || depth > kNodeStack) {
         set_error("shading-node tree too deep for the device evaluator");
         return false;
@@ -687,6 +741,7 @@ void SceneHost::build_accel() {  // BVH::build bvh.cpp:453-495
 std::string SceneHost::describe() const {
   std::string s = "# pine scene description v1 (hexfloat); written by libpine_gpu\n";
   // materials and geometry interleaved in creation order is not needed: materials first
+  for (size_t i = 0; i < images.size(); i++) s += fmt("image %d ", int(i)) + images[i].describe + "\n";
   for (size_t i = 0; i < nodes.size(); i++) {
     const HostNode& k = nodes[i];
     std::string l = fmt("node %d ", int(i));
@@ -704,6 +759,8 @@ std::string SceneHost::describe() const {
       case HostNode::ToVec3: l += k.b < 0 ? fmt("tovec3 %d", k.a) : fmt("tovec3 %d %d %d", k.a, k.b, k.c); break;
       case HostNode::Checker: l += fmt("checker %d %a", k.a, k.f); break;
       case HostNode::Splat: l += fmt("splat %d", k.a); break;
+      case HostNode::Image: l += fmt("image %d %d", k.a, k.n); break;
+      case HostNode::ImageF: l += fmt("imagef %d %d", k.a, k.n); break;
     }
     s += l + "\n";
   }
@@ -1310,6 +1367,49 @@ int pine_gpu_scene_node_splat(pine_gpu_scene* s, int a) {
   n.a = a;
   return add_node(s, n);
 }
+// ---- images of NodeImage / NodeImagef ----
+static bool image_size_ok(int w, int h) {
+  if (w < 1 || h < 1) return set_error("`Image` needs at least 1 x 1 texels"), false;
+  if ((long long)w * h > kTexMaxTexels) return set_error("`Image` has more than 2^26 texels"), false;
+  return true;
+}
+int pine_gpu_scene_add_image(pine_gpu_scene* s, const float* rgb, int w, int h) {
+  if (!check(s, rgb) || !image_size_ok(w, h)) return -1;
+  HostImage im;
+  im.w = w, im.h = h;
+  im.words.assign(rgb, rgb + size_t(w) * size_t(h) * 3);
+  for (float v : im.words)
+    if (!std::isfinite(v)) return set_error("`Image` has a texel that is not finite"), -1;
+  im.describe = fmt("%d %d f32 ", w, h) + md5_hex(rgb, im.words.size() * 4);
+  s->host.images.push_back(std::move(im));
+  return int(s->host.images.size()) - 1;
+}
+int pine_gpu_scene_add_image_u8(pine_gpu_scene* s, const uint8_t* texels, int channels, int w, int h) {
+  if (!check(s, texels)) return -1;
+  if (channels != 3 && channels != 4) return set_error("`Image`: 8-bit texels have 3 or 4 channels"), -1;
+  if (!image_size_ok(w, h)) return -1;
+  HostImage im;
+  im.w = w, im.h = h, im.u8 = true;
+  const size_t n = size_t(w) * size_t(h);
+  im.words.resize(n);
+  for (size_t i = 0; i < n; i++) {
+    const uint8_t* t = texels + i * size_t(channels);
+    const uint32_t word = uint32_t(t[0]) | uint32_t(t[1]) << 8 | uint32_t(t[2]) << 16 | (channels == 4 ? uint32_t(t[3]) << 24 : 0u);
+    memcpy(&im.words[i], &word, 4);
+  }
+  im.describe = fmt("%d %d u8x%d ", w, h, channels) + md5_hex(texels, n * size_t(channels));
+  s->host.images.push_back(std::move(im));
+  return int(s->host.images.size()) - 1;
+}
+static int add_image_node(pine_gpu_scene* s, HostNode::Kind kind, int p, int image) {
+  HostNode n;
+  n.kind = kind;
+  n.a = p;
+  n.n = image;
+  return add_node(s, n);
+}
+int pine_gpu_scene_node_image(pine_gpu_scene* s, int p, int image) { return add_image_node(s, HostNode::Image, p, image); }
+int pine_gpu_scene_node_imagef(pine_gpu_scene* s, int p, int image) { return add_image_node(s, HostNode::ImageF, p, image); }
 static int add_node_material(pine_gpu_scene* s, const char* name, int kind, const int ids[4], const bool used[4],
                              float ior, const std::string& desc_kind, const std::string& desc_tail) {
   if (!check(s)) return -1;

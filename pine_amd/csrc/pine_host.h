@@ -97,9 +97,9 @@ struct FlatAccel {
 
 // One shading node of the scene's node table (node.h:13-297); ids are indices into SceneHost::nodes.
 struct HostNode {
-  enum Kind { ConstF, Const3, Position, Normal, UV, BinF, Bin3, UnF, Un3, Comp, ToVec3, Checker, Splat } kind = ConstF;
+  enum Kind { ConstF, Const3, Position, Normal, UV, BinF, Bin3, UnF, Un3, Comp, ToVec3, Checker, Splat, Image, ImageF } kind = ConstF;
   char op = 0;
-  int a = -1, b = -1, c = -1, n = 0;
+  int a = -1, b = -1, c = -1, n = 0;  // (Image, ImageF: a = the coordinate node, n = the image's index in SceneHost::images)
   float f = 0;
   f3 v{0, 0, 0};
   // Filled in by SceneHost::add_node, once per node (operands always precede the node, and a script may share one operand
@@ -107,8 +107,15 @@ struct HostNode {
   bool reads_surface = false;
   f3 folded{0, 0, 0};
   bool is_vec3() const {
-    return kind == Const3 || kind == Position || kind == Normal || kind == UV || kind == Bin3 || kind == Un3 || kind == ToVec3 || kind == Splat;
+    return kind == Const3 || kind == Position || kind == Normal || kind == UV || kind == Bin3 || kind == Un3 || kind == ToVec3 || kind == Splat || kind == Image;
   }
+};
+// One image that NodeImage / NodeImagef nodes look up (image.h:11: the four alternatives of `Image` as two storage forms).
+struct HostImage {
+  int w = 0, h = 0;
+  bool u8 = false;           // one word per texel, r | g << 8 | b << 16 (| a << 24, never read); else 3 floats per texel
+  std::vector<float> words;  // as the device reads them (an 8-bit texel's word travels as a float's bits)
+  std::string describe;      // its .pscene line without the index
 };
 // node ids of a material's parameters (-1: the literal in DMaterial is used)
 struct MaterialNodes {
@@ -117,6 +124,7 @@ struct MaterialNodes {
 
 struct SceneHost {
   std::vector<HostNode> nodes;
+  std::vector<HostImage> images;
   std::vector<MaterialNodes> material_nodes;  // parallel to `materials`
   std::vector<DMaterial> materials;
   std::vector<std::string> material_names;
@@ -144,7 +152,9 @@ struct SceneHost {
   bool node_reads_surface(int id) const { return nodes[size_t(id)].reads_surface; }
   f3 node_fold(int id) const { return nodes[size_t(id)].folded; }  // value of a node subtree that does not read the surface
   // flatten the programs of every material into `ops`; fills DMaterial::prog / folded literals of `out`
-  bool compile_node_programs(std::vector<DMaterial>& out, std::vector<DNodeOp>& ops) const;
+  // and collects in `tex` what N_IMAGE ops read (pine_types.h): the 8-bit table, then each image a program names, once --
+  // empty where no program has such an op
+  bool compile_node_programs(std::vector<DMaterial>& out, std::vector<DNodeOp>& ops, std::vector<float>& tex) const;
   // accel.prims with every top-level entry as its packed primitive word (geometry | emissive | kind, pine_types.h), as the
   // traversal reports it; false with the error set when a geometry index does not fit the word
   bool packed_prim_words(std::vector<int>& out) const;
@@ -174,7 +184,12 @@ int atmosphere_table_device(int device, const float sun_dir[3], int w, int h, fl
 // Every index the device code forms from the `words` of an ImageSky or an Atmosphere stays inside it (checked before a plan
 // uploads it).
 bool env_image_valid(const DLight& L, const std::vector<float>& words);
+// Every N_IMAGE op of `ops` names an image that lies inside a `tex` buffer of `tex_words` words (checked before a plan or a
+// hook uploads it).
+bool tex_ops_valid(const std::vector<DNodeOp>& ops, size_t tex_words);
 std::string md5_hex(const void* data, size_t bytes);
+// pow(v / 255.0f, 2.2f) for v = 0 .. 255: Image::operator[] of an 8-bit image (image.cpp:10-13), as every 8-bit path computes it
+const float* u8_linear_table();
 
 // The pass planner: how a render of `spp` samples per pixel is split into launches that keep at most about
 // `pass_samples` sample rows per tile -- one launch with every row (n = 1, P = spp, slice = whole_tiles) when pass_samples

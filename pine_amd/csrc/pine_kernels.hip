@@ -555,6 +555,7 @@ struct SceneParts {
   std::vector<DShape> shapes;
   std::vector<DMaterial> materials;  // literals folded, node programs attached
   std::vector<DNodeOp> node_ops;
+  std::vector<float> tex;            // DeviceScene::tex (empty: no program reads an image)
   std::vector<int> packed_prims;     // top-level entries: geometry | emissive | kind (pine_types.h)
   std::vector<DLight> lights;        // + the environment light last (lightsampler.cpp:6-10)
   size_t tri_packet_bytes = 0;        // (0: no triangle packets, build_tri_packets)
@@ -619,7 +620,7 @@ static int assemble_scene(pine_gpu_plan* p, SceneHost& H, const pine_gpu_render_
   DeviceScene& S = p->S;
   S.off_nodes = put(A.nodes.data(), A.nodes.size() * sizeof(DNode));
   S.off_shapes = put(shapes.data(), shapes.size() * sizeof(DShape));
-  if (!H.compile_node_programs(sp.materials, sp.node_ops)) return -1;
+  if (!H.compile_node_programs(sp.materials, sp.node_ops, sp.tex)) return -1;
   S.off_materials = put(sp.materials.data(), sp.materials.size() * sizeof(DMaterial));
   S.off_node_ops = put(sp.node_ops.data(), sp.node_ops.size() * sizeof(DNodeOp));
   S.off_bvhs = put(A.bvhs.data(), A.bvhs.size() * sizeof(DBvh));
@@ -719,6 +720,15 @@ static int assemble_scene(pine_gpu_plan* p, SceneHost& H, const pine_gpu_render_
     }
     if (p->d_env.upload(H.env_words, what)) return -1;
     S.env = p->d_env;
+  }
+  S.tex = nullptr;
+  if (!sp.tex.empty()) {
+    if (!tex_ops_valid(sp.node_ops, sp.tex.size())) {
+      set_error("internal: an image node reads outside the plan's image buffer");
+      return -1;
+    }
+    if (p->d_tex.upload(sp.tex, what)) return -1;
+    S.tex = p->d_tex;
   }
 
   S.blob = reinterpret_cast<const uint4*>(p->d_blob.get());

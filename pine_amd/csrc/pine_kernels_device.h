@@ -68,6 +68,7 @@ struct DeviceScene {
   const DMaterial* materials;
   const DNode* nodes;
   const float* env;  // ImageSky, Atmosphere: rotation, density tree, pdf table and texels / colours (pine_device.h EnvImage), or null; plan-owned
+  const float* tex;  // image nodes: the u8 table, then every image the node programs read (pine_types.h N_IMAGE), or null; plan-owned
   const DBvh* bvhs;
   const float* tri_verts;
   const DLight* lights;
@@ -121,6 +122,7 @@ struct SceneView {
   const DMaterial* materials;
   const DNode* nodes;
   const float* env;  // DeviceScene::env (global memory, never staged)
+  const float* tex;  // DeviceScene::tex (global memory, never staged)
   const DBvh* bvhs;
   const DLight* lights;
   const float* tri_verts;
@@ -653,7 +655,7 @@ path_trace_kernel(DeviceScene S, WorkParams W, const ulonglong2* __restrict__ ck
       const f3 wi = -ray_d;
       m3 l2w = surface_frame(V, frame, it.n);
       m3 w2l = transpose(l2w);
-      const MatParams mp = material_params<F>(mat, V.node_ops, it.p, it.n, it.uv);
+      const MatParams mp = material_params<F>(mat, V.node_ops, V.tex, it.p, it.n, it.uv);
       DBxdf bx;
       choose_lobe<F, kSM>(mat, mp, wi, it.n, st.diffuse_length() > 0, false, rng_load, rng_store, T, sampler, bx);
       bx.wi = mul(w2l, wi);  // material.h:119

@@ -254,6 +254,7 @@ struct pine_gpu_plan {
   DeviceBuffer<uint32_t> d_tri_packets{kFromPool};  // (DeviceScene::tri_packets views it as uint4)
   DeviceBuffer<uint8_t> d_halton{kFromPool};
   DeviceBuffer<float> d_tri_attrs{kFromPool};
+  DeviceBuffer<float> d_tex{kFromPool};  // image nodes: what compile_node_programs collected (null: no program reads an image)
   DeviceBuffer<float> d_env{kFromPool};  // ImageSky, Atmosphere: SceneHost::env_words (null: another environment light, or none)
   DeviceBuffer<uint8_t> d_tables{kFromPool};
   int variant = -1;

@@ -845,7 +845,7 @@ __device__ __forceinline__ void path_queue_body(const DeviceScene& S, const Work
         const f3 wi = -ray_d;
         m3 l2w = surface_frame(V, frame, it.n);
         m3 w2l = transpose(l2w);
-        const MatParams mp = material_params<F>(mat, V.node_ops, it.p, it.n, it.uv);
+        const MatParams mp = material_params<F>(mat, V.node_ops, V.tex, it.p, it.n, it.uv);
         auto rng_load = [&]() -> DRng {
           return DRng{uint64_t(cg[0]) | (uint64_t(cg[1]) << 32), uint64_t(cg[2]) | (uint64_t(cg[3]) << 32)};
         };

@@ -45,6 +45,7 @@ __device__ __forceinline__ SceneView scene_view_global(const DeviceScene& S) {
   V.materials = S.materials;
   V.nodes = S.nodes;
   V.env = S.env;
+  V.tex = S.tex;
   V.bvhs = S.bvhs;
   V.lights = S.lights;
   V.tri_verts = S.tri_verts;

@@ -352,22 +352,22 @@ __global__ void __launch_bounds__(64) test_env_light_kernel(DLight L, const floa
   test_env_light_case(&L, env, queries + t * 5, out + t * 13);
 }
 // pine_gpu_test_material_params: material_params<F_ALL> of one material at one query (p, n, uv) -> 10 floats
-PINE_HD void test_material_params_case(const DMaterial* m, const DNodeOp* ops, const float* q, float* o) {
-  const MatParams mp = material_params<F_ALL>(m, ops, ld3(q), ld3(q + 3), f2{q[6], q[7]});
+PINE_HD void test_material_params_case(const DMaterial* m, const DNodeOp* ops, const float* tex, const float* q, float* o) {
+  const MatParams mp = material_params<F_ALL>(m, ops, tex, ld3(q), ld3(q + 3), f2{q[6], q[7]});
   o[0] = mp.albedo.x, o[1] = mp.albedo.y, o[2] = mp.albedo.z;
   o[3] = mp.albedo_over_pi.x, o[4] = mp.albedo_over_pi.y, o[5] = mp.albedo_over_pi.z;
   o[6] = mp.roughness, o[7] = mp.metallic, o[8] = mp.transmission, o[9] = mp.ior;
 }
-__global__ void __launch_bounds__(64) test_material_params_kernel(const DMaterial* mats, int num_mats, const DNodeOp* ops, const float* queries,
+__global__ void __launch_bounds__(64) test_material_params_kernel(const DMaterial* mats, int num_mats, const DNodeOp* ops, const float* tex, const float* queries,
                                                                  long long n, float* out) {
   const long long t = blockIdx.x * 64ll + threadIdx.x;
   if (t >= n * num_mats) return;
-  test_material_params_case(&mats[t / n], ops, queries + (t % n) * 8, out + t * 10);
+  test_material_params_case(&mats[t / n], ops, tex, queries + (t % n) * 8, out + t * 10);
 }
 // pine_gpu_test_choose_lobe: material_params, then choose_lobe as the path kernels call it, one thread per (after_walk, case).
 // The pixel's RNG lives in a local; the sampler is SobolSampler(64) on a 1024 x 1024 image, as in test_bxdf_case.  A slot the
 // chosen lobe does not have (bxdf.h:38-138: no roughness in Diffuse / BSSRDF, no ior in Diffuse / Conductor) is written as 0.
-__global__ void __launch_bounds__(64) test_choose_lobe_kernel(const DMaterial* mats, const DNodeOp* ops, const float* cases, long long n, float* out) {
+__global__ void __launch_bounds__(64) test_choose_lobe_kernel(const DMaterial* mats, const DNodeOp* ops, const float* tex, const float* cases, long long n, float* out) {
   const long long t = blockIdx.x * 64ll + threadIdx.x;
   if (t >= 2 * n) return;
   const float* c = cases + (t % n) * 16;
@@ -383,7 +383,7 @@ __global__ void __launch_bounds__(64) test_choose_lobe_kernel(const DMaterial* m
   s.index = int(c[15]);
   s.dimension = 0;
   DRng g = rng_seed(hash_pixel(s.px, s.py, 0));  // Sampler::start_pixel(p, 0): path.cpp:32
-  const MatParams mp = material_params<F_ALL>(mat, ops, ld3(c + 1), nn, f2{c[7], c[8]});
+  const MatParams mp = material_params<F_ALL>(mat, ops, tex, ld3(c + 1), nn, f2{c[7], c[8]});
   DBxdf bx;
   choose_lobe<F_ALL, kSmSobol>(mat, mp, ld3(c + 9), nn, c[12] != 0.0f, t >= n, [&]() -> DRng { return g; }, [&](const DRng& x) { g = x; }, T, s, bx);
   o[0] = float(bx.kind);
@@ -1033,7 +1033,8 @@ int64_t pine_gpu_test_node_programs(pine_gpu_scene* scene, int32_t* out, int64_t
   }
   std::vector<DMaterial> mats;
   std::vector<DNodeOp> ops;
-  if (!scene_host(scene).compile_node_programs(mats, ops)) return -1;
+  std::vector<float> tex;
+  if (!scene_host(scene).compile_node_programs(mats, ops, tex) || !tex_ops_valid(ops, tex.size())) return -1;
   const int64_t words = 2 + 4 * int64_t(mats.size()) + 4 * int64_t(ops.size());
   if (out && capacity_words >= words) {
     int32_t* o = out;
@@ -1046,6 +1047,18 @@ int64_t pine_gpu_test_node_programs(pine_gpu_scene* scene, int32_t* out, int64_t
   return words;
 }
 
+int64_t pine_gpu_test_tex_words(pine_gpu_scene* scene) {
+  if (!scene) {
+    set_error("null argument");
+    return -1;
+  }
+  std::vector<DMaterial> mats;
+  std::vector<DNodeOp> ops;
+  std::vector<float> tex;
+  if (!scene_host(scene).compile_node_programs(mats, ops, tex) || !tex_ops_valid(ops, tex.size())) return -1;
+  return int64_t(tex.size());
+}
+
 int pine_gpu_test_material_params(pine_gpu_scene* scene, int device, const float* queries, int64_t n, float* out) {
   if (!scene || !queries || !out || n < 0 || n > (1 << 20)) {
     set_error("bad argument");
@@ -1053,22 +1066,23 @@ int pine_gpu_test_material_params(pine_gpu_scene* scene, int device, const float
   }
   std::vector<DMaterial> mats;
   std::vector<DNodeOp> ops;
-  if (!scene_host(scene).compile_node_programs(mats, ops)) return -1;
+  std::vector<float> tex;
+  if (!scene_host(scene).compile_node_programs(mats, ops, tex) || !tex_ops_valid(ops, tex.size())) return -1;
   const int nm = int(mats.size());
   if (device < 0) {
     for (int k = 0; k < nm; k++)
-      for (int64_t i = 0; i < n; i++) test_material_params_case(&mats[size_t(k)], ops.data(), queries + i * 8, out + (k * n + i) * 10);
+      for (int64_t i = 0; i < n; i++) test_material_params_case(&mats[size_t(k)], ops.data(), tex.data(), queries + i * 8, out + (k * n + i) * 10);
     return 0;
   }
   if (n == 0 || nm == 0) return 0;
   if (need_device(device)) return -1;
   DeviceBuffer<DMaterial> dm;
   DeviceBuffer<DNodeOp> dops;
-  DeviceBuffer<float> dq, dout;
+  DeviceBuffer<float> dq, dout, dtex;
   const size_t words = size_t(n) * size_t(nm) * 10;
-  if (dm.upload(mats, __func__) || dops.upload(ops, __func__) || dq.upload(queries, size_t(n) * 8, __func__) || dout.alloc(words, __func__)) return -1;
+  if (dm.upload(mats, __func__) || dops.upload(ops, __func__) || dtex.upload(tex, __func__) || dq.upload(queries, size_t(n) * 8, __func__) || dout.alloc(words, __func__)) return -1;
   const long long total = (long long)n * nm;
-  hipLaunchKernelGGL(test_material_params_kernel, dim3(unsigned((total + 63) / 64)), dim3(64), 0, 0, dm.get(), nm, dops.get(), dq.get(), (long long)n, dout.get());
+  hipLaunchKernelGGL(test_material_params_kernel, dim3(unsigned((total + 63) / 64)), dim3(64), 0, 0, dm.get(), nm, dops.get(), dtex.get(), dq.get(), (long long)n, dout.get());
   return hip_launch_check(__func__) || dout.download(out, words, __func__) ? -1 : 0;
 }
 
@@ -1083,7 +1097,8 @@ int pine_gpu_test_choose_lobe(pine_gpu_scene* scene, int device, const float* ca
   }
   std::vector<DMaterial> mats;
   std::vector<DNodeOp> ops;
-  if (!scene_host(scene).compile_node_programs(mats, ops)) return -1;
+  std::vector<float> tex;
+  if (!scene_host(scene).compile_node_programs(mats, ops, tex) || !tex_ops_valid(ops, tex.size())) return -1;
   for (int64_t i = 0; i < n; i++) {
     const float* c = cases + i * 16;
     const bool whole = c[0] >= 0 && c[0] < float(mats.size()) && c[0] == float(int(c[0]));
@@ -1100,9 +1115,9 @@ int pine_gpu_test_choose_lobe(pine_gpu_scene* scene, int device, const float* ca
   if (need_device(device)) return -1;
   DeviceBuffer<DMaterial> dm;
   DeviceBuffer<DNodeOp> dops;
-  DeviceBuffer<float> dc, dout;
-  if (dm.upload(mats, __func__) || dops.upload(ops, __func__) || dc.upload(cases, size_t(n) * 16, __func__) || dout.alloc(size_t(n) * 16, __func__)) return -1;
-  hipLaunchKernelGGL(test_choose_lobe_kernel, dim3(unsigned((2 * n + 63) / 64)), dim3(64), 0, 0, dm.get(), dops.get(), dc.get(), (long long)n, dout.get());
+  DeviceBuffer<float> dc, dout, dtex;
+  if (dm.upload(mats, __func__) || dops.upload(ops, __func__) || dtex.upload(tex, __func__) || dc.upload(cases, size_t(n) * 16, __func__) || dout.alloc(size_t(n) * 16, __func__)) return -1;
+  hipLaunchKernelGGL(test_choose_lobe_kernel, dim3(unsigned((2 * n + 63) / 64)), dim3(64), 0, 0, dm.get(), dops.get(), dtex.get(), dc.get(), (long long)n, dout.get());
   return hip_launch_check(__func__) || dout.download(out, size_t(n) * 16, __func__) ? -1 : 0;
 }
 

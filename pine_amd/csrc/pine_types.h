@@ -80,12 +80,21 @@ enum NodeOpCode : int {
   N_COMP,     // x = component index (as float): pop v, push splat(v[n])
   N_TOVEC3,   // pop z, y, x (splats), push (x, y, z)
   N_CHECKER,  // x = ratio: pop p, push splat(float(prod(fract(p) - ratio) > 0))  node.cpp:15-18
+  N_IMAGE,    // pop p, push the rgb of the texel at min(vec2i(size * fract(vec2(p))), size - 1)  node.cpp:20-23 (NodeImagef:
+              // followed by N_COMP 0)
 };
+// N_IMAGE carries three integers in the bits of its floats (read back with as_int, never used as numbers): x = the image's
+// first word in the plan's `tex` buffer, y = its width, z = its height, with kTexU8Bit set where a texel is one RGBA8 word
+// (r in the low byte) that the lookup linearises through the table in tex[0, kTexTableWords); else a texel is 3 floats.
 struct alignas(16) DNodeOp {
   int op;
   float x, y, z;
 };
 constexpr int kNodeStack = 8;  // evaluation stack depth the host guarantees
+constexpr int kTexTableWords = 256;  // tex[v] = pow(v / 255.0f, 2.2f): Image::operator[] of an 8-bit image (image.cpp:10-13)
+constexpr int kTexU8Bit = 1 << 30;
+constexpr long long kTexMaxTexels = 1ll << 26;  // per image
+constexpr long long kTexMaxWords = 1ll << 30;   // per plan: an offset stays a positive int whose bits are no NaN
 
 // 64-byte BVH node: the two child boxes live in the parent (as in pine's BVH) so one fetch decides
 // both children.  child[i] >= 0 with count[i] == 0: inner node index.  count[i] > 0: child i is a

@@ -5,9 +5,17 @@ Uber(baseColor, roughness, metallic, transmission, ior) from the pbrMetallicRoug
 extensions, or an Emissive(emissiveFactor * emissiveStrength) when that product is not zero; a node with a camera sets
 ThinLenCamera(Film([640 * aspect, 640]), position, position + R * (0, 0, -1), yfov / 2).
 
+Image textures (fileio.cpp:150-160, 278-293): each glTF image -- a PNG in a buffer view, in a data URI or in a file beside the
+document -- becomes one 8-bit image of 4 components, as tinygltf hands it over (pine_amd/png.py).  A baseColorTexture becomes
+Texture(UV(), image) and REPLACES the factor (it is not multiplied with it); a metallicRoughnessTexture becomes the roughness
+Comp(Texture(UV(), image), 1) and the metallic Comp(Texture(UV(), image), 2).  The reference walks the material's
+pbrMetallicRoughness parameters in name order, so a roughnessFactor written beside a metallicRoughnessTexture wins over the
+texture's roughness (a metallicFactor does not win over its metallic).  Samplers, texCoord indices and texture transforms are
+ignored, as in the reference: the lookup is always fract (repeat) and nearest.  An image in another format (JPEG: a lossy format
+whose decoder's arithmetic is not restated here) is refused by name.
+
 SURVEY.md 8(f) rank 4.  All matrix arithmetic goes through the library's host math (binary32, the reference's operand
-order).  Image textures (baseColorTexture, metallicRoughnessTexture -> NodeImage) are not supported: such a material is
-refused by name."""
+order)."""
 import base64
 import json
 import os
@@ -17,7 +25,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .api import Scene, Mesh, Uber, Emissive, Film, ThinLenCamera, PineError
+from .api import Scene, Mesh, Uber, Emissive, Film, ThinLenCamera, PineError, Image, Texture, UV, Node
 
 lib = _lib.lib
 _COMPONENT = {5120: np.int8, 5121: np.uint8, 5122: np.int16, 5123: np.uint16, 5125: np.uint32, 5126: np.float32, 5130: np.float64}
@@ -115,6 +123,41 @@ def load(path, scene=None, transform=None):
 
     scene = scene or Scene()
     counter = [0]
+    images = {}
+
+    def image_bytes(im, index):
+        if "bufferView" in im:
+            view = doc["bufferViews"][im["bufferView"]]
+            start = view.get("byteOffset", 0)
+            return buffers[view["buffer"]][start:start + view["byteLength"]]
+        uri = im.get("uri")
+        if uri is None:
+            raise PineError(f"glTF image {index} has neither a bufferView nor a uri")
+        if uri.startswith("data:"):
+            return base64.b64decode(uri.split(",", 1)[1])
+        with open(os.path.join(base, uri), "rb") as f:  # (the uri as written: not percent-decoded, in either importer)
+            return f.read()
+
+    def image_of(texture_info):
+        """The Image of a textureInfo's texture: decoded once, one image of the scene however many materials use it."""
+        textures, gl_images = doc.get("textures", []), doc.get("images", [])
+        ti = texture_info.get("index", -1)
+        if not isinstance(ti, int) or not 0 <= ti < len(textures):
+            raise PineError("glTF: a material names a texture that does not exist")
+        source = textures[ti].get("source", -1)
+        if not isinstance(source, int) or not 0 <= source < len(gl_images):  # (a texture that carries only an extension's image, too)
+            raise PineError("glTF: a texture names an image that does not exist")
+        if source not in images:
+            from .png import SIGNATURE, read_png_bytes
+            im = doc["images"][source]
+            name = im.get("name") or im.get("uri", "")[:40] or f"image {source}"
+            data = image_bytes(im, source)
+            if data[:3] == b"\xff\xd8\xff" or im.get("mimeType") == "image/jpeg":
+                raise PineError(f"glTF image `{name}` is a JPEG: not supported (a lossy format; re-encode it as PNG)")
+            if data[:8] != SIGNATURE:
+                raise PineError(f"glTF image `{name}` is not a PNG: not supported")
+            images[source] = Image(read_png_bytes(data, 4, name))
+        return images[source]
 
     def material_of(prim):
         basecolor, roughness, metallic, transmission = [1.0, 1.0, 1.0], 1.0, 0.0, 0.0
@@ -130,17 +173,24 @@ def load(path, scene=None, transform=None):
             if "KHR_materials_emissive_strength" in ext:
                 emission_strength = ext["KHR_materials_emissive_strength"].get("emissiveStrength", 1.0)
             pbr = mat.get("pbrMetallicRoughness", {})
-            if "baseColorTexture" in pbr or "metallicRoughnessTexture" in pbr:
-                raise PineError("glTF material `%s` uses image textures (NodeImage): not supported" % mat.get("name", mi))
             basecolor = list(pbr.get("baseColorFactor", [1.0, 1.0, 1.0, 1.0]))[:3]   # tinygltf defaults
             metallic = pbr.get("metallicFactor", 1.0)
             roughness = pbr.get("roughnessFactor", 1.0)
             emission_color = list(mat.get("emissiveFactor", [0.0, 0.0, 0.0]))
+            # fileio.cpp:278-293 walks mat.values, a map: the parameters the document wrote, in name order
+            if "baseColorTexture" in pbr:      # (after baseColorFactor)
+                basecolor = Texture(UV(), image_of(pbr["baseColorTexture"]))
+            if "metallicRoughnessTexture" in pbr:  # (after metallicFactor, before roughnessFactor)
+                image = image_of(pbr["metallicRoughnessTexture"])
+                if "roughnessFactor" not in pbr:
+                    roughness = Texture(UV(), image)[1]
+                metallic = Texture(UV(), image)[2]
         f32 = lambda v: float(np.float32(v))
+        num = lambda v: v if isinstance(v, Node) else f32(v)  # noqa: E731
         emission = [f32(np.float32(c) * np.float32(emission_strength)) for c in emission_color]
         counter[0] += 1
         if all(e == 0.0 for e in emission):
-            return Uber([f32(c) for c in basecolor], f32(roughness), f32(metallic), f32(transmission), f32(ior))
+            return Uber(basecolor if isinstance(basecolor, Node) else [f32(c) for c in basecolor], num(roughness), num(metallic), f32(transmission), f32(ior))
         return Emissive(emission)
 
     def process(node_index, xf):

@@ -8,7 +8,11 @@
 // material Uber(baseColor, roughness, metallic, transmission, ior) from the pbrMetallicRoughness factors and the KHR
 // transmission / ior extensions, or Emissive(emissiveFactor * emissiveStrength) when that product is not zero; a node with a
 // camera sets ThinLenCamera(Film([640 * aspect, 640]), pos, pos + R * (0, 0, -1), yfov / 2).  All matrix arithmetic is the
-// library's host math (binary32, the reference's operand order).  Image textures (NodeImage) are refused by name.
+// library's host math (binary32, the reference's operand order).  Image textures (fileio.cpp:150-160, 278-293): each glTF image
+// (a PNG in a buffer view, a data URI or a file beside the document; png_read.hpp) becomes one 8-bit image of 4 components;
+// baseColorTexture -> Texture(UV(), image) in place of the factor, metallicRoughnessTexture -> roughness Comp(.., 1) and
+// metallic Comp(.., 2), a roughnessFactor written beside it winning (the reference walks the parameters in name order);
+// samplers, texCoord and transforms are ignored.  A JPEG, or any other format, is refused by name.
 #pragma once
 #include <cstdint>
 #include <cstdio>
@@ -20,6 +24,7 @@
 #include <vector>
 
 #include "../../include/pine_gpu.h"
+#include "png_read.hpp"
 
 namespace pine_gltf {
 
@@ -339,9 +344,65 @@ inline ImportedCamera import_scene(pine_gpu_scene* scene, const std::string& pat
     return out;
   };
 
+  // Each glTF image becomes one image of the scene: 8-bit, 4 components, as tinygltf hands it over (fileio.cpp:150-160) --
+  // decoded at its first use, from a buffer view, a data URI or a file beside the document.
+  std::vector<int> image_ids;       // per glTF image: its id in the scene, or -1 while no node reads it
+  std::vector<pine::PngImage> image_texels;
+  auto image_of = [&](const Json& info) -> int {  // -> the glTF image's index, decoded
+    const Json* textures = doc.find("textures");
+    const Json* images = doc.find("images");
+    const int ti = info.find("index") ? info.at("index").integer(-1) : -1;
+    if (!textures || !images || ti < 0 || size_t(ti) >= textures->size()) throw Error("glTF: a material names a texture that does not exist");
+    const Json& tex = textures->at(size_t(ti));
+    const int source = tex.find("source") ? tex.at("source").integer(-1) : -1;
+    if (source < 0 || size_t(source) >= images->size()) throw Error("glTF: a texture names an image that does not exist");
+    image_ids.resize(images->size(), -1);
+    image_texels.resize(images->size());
+    if (image_texels[size_t(source)].w) return source;
+    const Json& im = images->at(size_t(source));
+    std::string name = im.find("name") ? im.at("name").str : std::string();
+    std::vector<uint8_t> data;
+    if (const Json* bv = im.find("bufferView")) {
+      const Json* views = doc.find("bufferViews");
+      const int vi = bv->integer(-1);
+      if (!views || vi < 0 || size_t(vi) >= views->size()) throw Error("glTF: an image names a bufferView that does not exist");
+      const Json& view = views->at(size_t(vi));
+      const int bi = view.find("buffer") ? view.at("buffer").integer(-1) : -1;
+      if (bi < 0 || size_t(bi) >= buffers.size()) throw Error("glTF: bufferView names a buffer that does not exist");
+      const double off = view.find("byteOffset") ? view.at("byteOffset").number(0) : 0.0, len = view.find("byteLength") ? view.at("byteLength").number(0) : 0.0;
+      const std::vector<uint8_t>& raw = buffers[size_t(bi)];
+      if (!(off >= 0.0 && len >= 0.0 && off <= double(raw.size()) && len <= double(raw.size()) - off)) throw Error("glTF: an image's bufferView runs past its buffer");
+      data.assign(raw.begin() + long(off), raw.begin() + long(off) + long(len));
+    } else if (const Json* uri = im.find("uri")) {
+      if (name.empty()) name = uri->str.substr(0, 40);
+      if (uri->str.compare(0, 5, "data:") == 0) data = base64(uri->str.substr(uri->str.find(',') + 1));
+      else data = read_file(base + "/" + uri->str);
+    } else {
+      throw Error("glTF image " + std::to_string(source) + " has neither a bufferView nor a uri");
+    }
+    if (name.empty()) name = "image " + std::to_string(source);
+    const bool jpeg_mime = im.find("mimeType") && im.at("mimeType").str == "image/jpeg";
+    if (jpeg_mime || (data.size() >= 3 && data[0] == 0xff && data[1] == 0xd8 && data[2] == 0xff))
+      throw Error("glTF image `" + name + "` is a JPEG: not supported (a lossy format; re-encode it as PNG)");
+    static const unsigned char sig[8] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1a, '\n'};
+    if (data.size() < 8 || memcmp(data.data(), sig, 8) != 0) throw Error("glTF image `" + name + "` is not a PNG: not supported");
+    try {
+      image_texels[size_t(source)] = pine::read_png_bytes(data, 4, name);
+    } catch (const std::exception& e) {
+      throw Error(e.what());
+    }
+    return source;
+  };
+  auto scene_image = [&](int source) {
+    const pine::PngImage& png = image_texels[size_t(source)];
+    if (image_ids[size_t(source)] < 0) image_ids[size_t(source)] = check(pine_gpu_scene_add_image_u8(scene, png.texels.data(), 4, png.w, png.h), "Image");
+    return image_ids[size_t(source)];
+  };
+
   auto material_of = [&](const Json& prim) {
     float basecolor[3] = {1, 1, 1}, roughness = 1.0f, metallic = 0.0f, transmission = 0.0f, ior = 1.45f;
     float emission_color[3] = {1, 1, 1}, emission_strength = 0.0f;
+    int base_image = -1, roughness_image = -1, metallic_image = -1;  // (glTF images, or -1: the factor)
     const Json* mi = prim.find("material");
     if (mi && mi->integer(-1) >= 0) {
       const Json& mat = doc.at("materials").at(size_t(mi->integer(0)));
@@ -351,8 +412,6 @@ inline ImportedCamera import_scene(pine_gpu_scene* scene, const std::string& pat
         if (const Json* e = ext->find("KHR_materials_emissive_strength")) emission_strength = float(e->find("emissiveStrength") ? e->at("emissiveStrength").number(1) : 1.0);
       }
       const Json* pbr = mat.find("pbrMetallicRoughness");
-      if (pbr && (pbr->find("baseColorTexture") || pbr->find("metallicRoughnessTexture")))
-        throw Error("glTF material `" + (mat.find("name") ? mat.at("name").str : std::string("?")) + "` uses image textures (NodeImage): not supported");
       for (int k = 0; k < 3; k++) basecolor[k] = 1.0f;
       metallic = 1.0f, roughness = 1.0f;  // tinygltf's defaults once a material is present
       if (pbr) {
@@ -360,6 +419,13 @@ inline ImportedCamera import_scene(pine_gpu_scene* scene, const std::string& pat
           for (int k = 0; k < 3; k++) basecolor[k] = float(c->at(size_t(k)).number(1));
         if (const Json* v = pbr->find("metallicFactor")) metallic = float(v->number(1));
         if (const Json* v = pbr->find("roughnessFactor")) roughness = float(v->number(1));
+        // fileio.cpp:278-293 walks mat.values, a map: the parameters the document wrote, in name order -- baseColorTexture after
+        // baseColorFactor, metallicRoughnessTexture after metallicFactor and BEFORE roughnessFactor, which then wins
+        if (const Json* t = pbr->find("baseColorTexture")) base_image = image_of(*t);
+        if (const Json* t = pbr->find("metallicRoughnessTexture")) {
+          metallic_image = image_of(*t);
+          if (!pbr->find("roughnessFactor")) roughness_image = metallic_image;
+        }
       }
       for (int k = 0; k < 3; k++) emission_color[k] = 0.0f;
       if (const Json* e = mat.find("emissiveFactor"))
@@ -367,8 +433,18 @@ inline ImportedCamera import_scene(pine_gpu_scene* scene, const std::string& pat
     }
     const float emission[3] = {emission_color[0] * emission_strength, emission_color[1] * emission_strength, emission_color[2] * emission_strength};
     const std::string name;  // (anonymous: the library numbers it, as for scene.add(shape, material))
-    if (emission[0] == 0.0f && emission[1] == 0.0f && emission[2] == 0.0f)
-      return check(pine_gpu_scene_add_material_uber(scene, name.c_str(), basecolor, roughness, metallic, transmission, ior), "Uber");
+    if (emission[0] == 0.0f && emission[1] == 0.0f && emission[2] == 0.0f) {
+      if (base_image < 0 && roughness_image < 0 && metallic_image < 0)
+        return check(pine_gpu_scene_add_material_uber(scene, name.c_str(), basecolor, roughness, metallic, transmission, ior), "Uber");
+      // NodeImage(NodeUV(), image), one per use (fileio.cpp:286-291); the nodes in the order pine_amd/gltf.py creates them
+      auto texture = [&](int image) { return check(pine_gpu_scene_node_image(scene, check(pine_gpu_scene_node_input(scene, 2), "UV"), scene_image(image)), "Texture"); };
+      auto component = [&](int image, int c) { return check(pine_gpu_scene_node_component(scene, texture(image), c), "Comp"); };
+      const int a = base_image >= 0 ? texture(base_image) : check(pine_gpu_scene_node_const3(scene, basecolor), "Node3f");
+      const int r = roughness_image >= 0 ? component(roughness_image, 1) : check(pine_gpu_scene_node_constf(scene, roughness), "Nodef");
+      const int m = metallic_image >= 0 ? component(metallic_image, 2) : check(pine_gpu_scene_node_constf(scene, metallic), "Nodef");
+      const int t = check(pine_gpu_scene_node_constf(scene, transmission), "Nodef");
+      return check(pine_gpu_scene_add_material_uber_n(scene, name.c_str(), a, r, m, t, ior), "Uber");
+    }
     return check(pine_gpu_scene_add_material_emissive(scene, name.c_str(), emission), "Emissive");
   };
 

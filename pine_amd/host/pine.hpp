@@ -18,6 +18,7 @@
 #include "../../include/pine_gpu.h"
 #include "gltf_import.hpp"
 #include "hdr_read.hpp"
+#include "png_read.hpp"
 
 namespace pine {
 
@@ -154,8 +155,9 @@ struct Sampler {  // the variant PathIntegrator takes (sampler.h:275-; UniformSa
   Sampler(HaltonSampler s) : requested(s.requested), kind(PINE_GPU_SAMPLER_HALTON) {}
 };
 
-// An image as ImageSky takes it (image.h:11-30): float texels (a Radiance HDR file, or an array), or 8-bit texels that the
-// library converts as the reference's vec3u8 images are read (pow(value / 255, 2.2)).  Rows top first, 3 values per texel.
+// An image as ImageSky takes it (image.h:11-30): float texels (a Radiance HDR file, or an array), or 8-bit texels (a PNG file
+// expanded to 3 channels as the reference's image_from loads it -- png_read.hpp -- or an array) that the library converts as
+// the reference's vec3u8 images are read (pow(value / 255, 2.2)).  Rows top first, 3 values per texel.
 struct Image {
   vec2i size;
   std::vector<float> rgb;
@@ -163,9 +165,20 @@ struct Image {
   Image(vec2i size, std::vector<float> texels) : size(size), rgb(std::move(texels)) { expect(rgb.size()); }
   Image(vec2i size, std::vector<uint8_t> texels) : size(size), u8(std::move(texels)) { expect(u8.size()); }
   explicit Image(vec3 color) : size{1, 1}, rgb{color.x, color.y, color.z} {}  // ImagePtr(vec3): the reference's 1 x 1 image
-  explicit Image(const std::string& hdr_file) {
+  explicit Image(const std::string& file) {  // a Radiance .hdr or a .png file, told apart by the file's first bytes
     try {
-      HdrImage f = read_hdr(hdr_file);
+      unsigned char head[4] = {0, 0, 0, 0};
+      if (FILE* f = fopen(file.c_str(), "rb")) {
+        if (fread(head, 1, 4, f) != 4) head[0] = 0;
+        fclose(f);
+      }
+      if (head[0] == 0x89 && head[1] == 'P' && head[2] == 'N' && head[3] == 'G') {
+        PngImage p = read_png(file, 3);
+        size = vec2i{p.w, p.h};
+        u8 = std::move(p.texels);
+        return;
+      }
+      HdrImage f = read_hdr(file);
       size = vec2i{f.w, f.h};
       rgb = std::move(f.rgb);
     } catch (const std::runtime_error& e) {

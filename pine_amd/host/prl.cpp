@@ -122,8 +122,10 @@ struct CameraObj : Object {
 // typed "Nodef" here and every vec3-valued one "Node3f": the reference gives each node struct its own
 // type name ("Addf", "Checkerboard", ...) that converts in one step to Nodef / Node3f and to nothing
 // else, so overload resolution picks the same function either way.
+struct ImageObj;
 struct NodeObj : Object {
-  std::string kind;  // constf const3 position normal uv bin un comp tovec3 checker splat
+  std::string kind;  // constf const3 position normal uv bin un comp tovec3 checker splat image imagef
+  std::shared_ptr<ImageObj> image;  // image, imagef: NodeImage / NodeImagef (a = the coordinate)
   char op = 0;
   int n = 0;
   float f = 0, v[3] = {0, 0, 0};
@@ -146,12 +148,14 @@ struct ShapeObj : Object {
 struct SceneObj : Object {
   pine_gpu_scene* h = nullptr;
   Cell camera;  // type "Camera"
+  std::map<std::shared_ptr<ImageObj>, int> images;  // the images Texture nodes of this scene read: each stored once
   SceneObj() : h(pine_gpu_scene_create()) {}
   ~SceneObj() override { pine_gpu_scene_destroy(h); }
 };
-struct ImageObj : Object {  // ImagePtr: float texels, 3 each, rows top first
+struct ImageObj : Object {  // ImagePtr: float texels (a .hdr file, a vec3), or 8-bit texels (a .png file); 3 each, rows top first
   int w = 0, h = 0;
   std::vector<float> rgb;
+  std::vector<uint8_t> u8;  // (not empty: the image is 8-bit, image_from's Array2d<vec3u8>)
 };
 struct LightObj : Object {
   std::string kind;  // PointLight | SpotLight | DirectionalLight | Sky | ImageSky | Atmosphere (b = sun direction, c = sun colour)
@@ -1037,6 +1041,17 @@ static int instantiate_node(SceneObj& s, const NodeP3& n, std::map<const NodeObj
     id = pine_gpu_scene_node_to_vec3(s.h, x, y, z);
   } else if (n->kind == "checker") id = pine_gpu_scene_node_checkerboard(s.h, instantiate_node(s, n->a, memo), n->f);
   else if (n->kind == "splat") id = pine_gpu_scene_node_splat(s.h, instantiate_node(s, n->a, memo));
+  else if (n->kind == "image" || n->kind == "imagef") {
+    const int p = instantiate_node(s, n->a, memo);
+    auto it2 = s.images.find(n->image);
+    if (it2 == s.images.end()) {
+      const ImageObj& im = *n->image;
+      const int image = im.u8.empty() ? pine_gpu_scene_add_image(s.h, im.rgb.data(), im.w, im.h) : pine_gpu_scene_add_image_u8(s.h, im.u8.data(), 3, im.w, im.h);
+      gpu_check(image, "Image");
+      it2 = s.images.emplace(n->image, image).first;
+    }
+    id = n->kind == "image" ? pine_gpu_scene_node_image(s.h, p, it2->second) : pine_gpu_scene_node_imagef(s.h, p, it2->second);
+  }
   gpu_check(id, "shading node");
   memo[n.get()] = id;
   return id;
@@ -1533,6 +1548,34 @@ Interp::Interp() {
   };
   r.def("Checkerboard", {"Node3f"}, "Nodef", [=](Interp&, std::vector<Cell>& a) { return checker(nobj(a[0]), 0.5f); });
   r.def("Checkerboard", {"Node3f", "f32"}, "Nodef", [=](Interp&, std::vector<Cell>& a) { return checker(nobj(a[0]), a[1]->f[0]); });
+  // Texture(Node3f, ImagePtr) (node.cpp:66-67).  The reference registers NodeImagef and then NodeImage under the ONE type name
+  // "Texture" (context.h:571-576: the second type() finds the name taken and shares its trait; both C++ types now answer to
+  // "Texture").  Their constructors have the same unique name, `Texture(Node3f, ImagePtr): Texture`, so the second add_f
+  // overrides the first (context.cpp:120-133): a script's Texture(p, img) constructs a NodeImage, typed "Texture".  That value
+  // converts in one step both ways: `@convert.Texture.Node3f` (Node3f's ctor_variant lists NodeImage) and
+  // `@convert.Texture.Nodef` (Nodef's lists NodeImagef; the converter reads the NodeImage object as a NodeImagef -- the two
+  // structs have the same members -- so it evaluates to the texel's .x).  Hence Diffuse(Texture(UV(), img)) takes the rgb,
+  // and a Texture in a Nodef slot (Uber's roughness, ...) takes the first component; where both conversions fit equally
+  // well (Texture(...) * 0.5) find_f reports an ambiguous call, and Node3f(...) / Nodef(...) say which is meant.
+  r.types["Texture"] = true;
+  auto image_node = [](const char* kind, NodeP3 p, std::shared_ptr<ImageObj> im) {
+    auto n = std::make_shared<NodeObj>();
+    n->kind = kind;
+    n->is3 = std::string(kind) == "image";
+    n->a = p;
+    n->image = im;
+    return n;
+  };
+  r.def("Texture", {"Node3f", "ImagePtr"}, "Texture", [=](Interp&, std::vector<Cell>& a) {
+    return mk_obj("Texture", image_node("image", nobj(a[0]), obj<ImageObj>(a[1])));
+  });
+  auto texture3 = [=](const Value& v) { return mk_node(std::static_pointer_cast<NodeObj>(v.o)); };  // (the node itself: shared by every use)
+  auto texturef = [=](const Value& v) {
+    auto n = std::static_pointer_cast<NodeObj>(v.o);
+    return mk_node(image_node("imagef", n->a, n->image));
+  };
+  r.convert("Texture", "Node3f", texture3);
+  r.convert("Texture", "Nodef", texturef);
   // lerp: node.cpp:88-102 (the scalar one is psl::lerp, math.cpp:21)
   r.def("lerp", {"f32", "f32", "f32"}, "f32", [](Interp&, std::vector<Cell>& a) { return mk_f32((1 - a[0]->f[0]) * a[1]->f[0] + a[0]->f[0] * a[2]->f[0]); });
   r.def("lerp", {"Nodef", "Nodef", "Nodef"}, "Nodef", [=](Interp&, std::vector<Cell>& a) {
@@ -1851,13 +1894,24 @@ Interp::Interp() {
     return mk_obj("Atmosphere", l);
   });
   r.convert("Atmosphere", "EnvironmentLight", [](const Value& v) { return retype(v, "EnvironmentLight"); });
-  // ImagePtr(str) / load_image(str): a Radiance .hdr file; ImagePtr(vec3): the reference's 1 x 1 image (image.cpp:49-61)
+  // ImagePtr(str) / load_image(str): a Radiance .hdr file, or a .png file expanded to 3 channels as image_from asks stb to
+  // (told apart by the file's first bytes); ImagePtr(vec3): the reference's 1 x 1 image (image.cpp:49-61)
   auto image_file = [](Interp&, std::vector<Cell>& a) {
     auto im = std::make_shared<ImageObj>();
     try {
-      pine::HdrImage f = pine::read_hdr(a[0]->s);
-      im->w = f.w, im->h = f.h, im->rgb = std::move(f.rgb);
-    } catch (const std::runtime_error& e) {
+      unsigned char head[4] = {0, 0, 0, 0};
+      if (FILE* fp = fopen(a[0]->s.c_str(), "rb")) {
+        if (fread(head, 1, 4, fp) != 4) head[0] = 0;
+        fclose(fp);
+      }
+      if (head[0] == 0x89 && head[1] == 'P' && head[2] == 'N' && head[3] == 'G') {
+        pine::PngImage f = pine::read_png(a[0]->s, 3);
+        im->w = f.w, im->h = f.h, im->u8 = std::move(f.texels);
+      } else {
+        pine::HdrImage f = pine::read_hdr(a[0]->s);
+        im->w = f.w, im->h = f.h, im->rgb = std::move(f.rgb);
+      }
+    } catch (const std::exception& e) {
       fail(std::string("Unable to load `") + a[0]->s + "`: " + e.what());
     }
     return mk_obj("ImagePtr", im);
@@ -1901,7 +1955,8 @@ Interp::Interp() {
       gpu_check(pine_gpu_scene_set_env_atmosphere(obj<SceneObj>(a[0])->h, l->b, l->c, 1024, 1024, (in.flags & PINE_PRL_DRY_RUN) ? -1 : in.device),
                 "scene.set(environment light)");
     else if (l->kind == "ImageSky")
-      gpu_check(pine_gpu_scene_set_env_image(obj<SceneObj>(a[0])->h, l->image->rgb.data(), l->image->w, l->image->h, l->c, l->falloff, l->extra),
+      gpu_check(!l->image->u8.empty() ? pine_gpu_scene_set_env_image_u8(obj<SceneObj>(a[0])->h, l->image->u8.data(), l->image->w, l->image->h, l->c, l->falloff, l->extra)
+                                      : pine_gpu_scene_set_env_image(obj<SceneObj>(a[0])->h, l->image->rgb.data(), l->image->w, l->image->h, l->c, l->falloff, l->extra),
                 "scene.set(environment light)");
     else
       gpu_check(pine_gpu_scene_set_env_sky(obj<SceneObj>(a[0])->h, l->c), "scene.set(environment light)");

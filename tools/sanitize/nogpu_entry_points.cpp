@@ -105,6 +105,7 @@ int pine_gpu_test_atmosphere_color(int, const float*, int64_t, float*) { return 
 int64_t pine_gpu_test_env_table(pine_gpu_scene*, float*, int64_t) { return fail(); }
 int pine_gpu_test_env_light_sample(pine_gpu_scene*, int, const float*, int64_t, float*) { return fail(); }
 int64_t pine_gpu_test_node_programs(pine_gpu_scene*, int32_t*, int64_t) { return fail(); }
+int64_t pine_gpu_test_tex_words(pine_gpu_scene*) { return fail(); }
 int pine_gpu_test_material_params(pine_gpu_scene*, int, const float*, int64_t, float*) { return fail(); }
 int pine_gpu_test_choose_lobe(pine_gpu_scene*, int, const float*, int64_t, float*) { return fail(); }
 int pine_gpu_plan_test_traverse_baked(pine_gpu_plan*, const float*, int64_t, uint32_t*) { return fail(); }
