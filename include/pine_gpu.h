@@ -102,7 +102,7 @@ int pine_gpu_scene_set_env_atmosphere(pine_gpu_scene*, const float sun_direction
  * lives in the scene's node table; each call returns its id (or < 0).  Supported: constants, the
  * surface inputs Position / Normal / UV, NodeBinary (+ - * / ^), NodeUnary (- abs sqr sqrt fract),
  * NodeComponent, NodeToVec3, NodeCheckerboard, NodeImage / NodeImagef (`Texture`); `lerp` etc. are
- * compositions of these exactly as node.cpp:88-102 composes them.  Not supported: noise and function
+ * compositions of these exactly as node.cpp:88-102 composes them; NodeNoisef / NodeNoise3f.  Not supported: function
  * nodes.  Subtrees that do not read the surface are folded to literals on the host with the same float
  * operations (a `Texture` of a constant coordinate included); the rest run as small postfix programs in
  * the shading stage of the kernels. */
@@ -129,6 +129,15 @@ int pine_gpu_scene_add_image_u8(pine_gpu_scene*, const uint8_t* texels, int chan
  * a `p` that is not a Node3f. */
 int pine_gpu_scene_node_image(pine_gpu_scene*, int p, int image);
 int pine_gpu_scene_node_imagef(pine_gpu_scene*, int p, int image);
+/* NodeNoisef(p, octaves) -> Nodef, NodeNoise3f(p, octaves) -> Node3f  node.h:209-225, node.cpp:7-13: fbm(p, int(octaves)) and
+ * fbm3d(p, int(octaves)) of noise.cpp:29-41, 63-75 -- Perlin gradient noise, summed over `octaves` rounds of doubled frequency
+ * and halved weight; Noisef equals the first component of Noise3f.  The octaves value truncates to int and may differ per
+ * surface point; fewer than one round gives the reference's 0 / 0, a NaN.  The rounds are bounded by 32: a value above it
+ * (+inf included) runs 32, a NaN none.  Pinned to the reference for |p| * 2^(octaves - 1) < 2^30.  Refused, each by the node's
+ * name: a `p` that is not a Node3f, an `octaves` that is not a Nodef, an id out of range, a constant octaves above 32 or not
+ * finite. */
+int pine_gpu_scene_node_noisef(pine_gpu_scene*, int p, int octaves);
+int pine_gpu_scene_node_noise3f(pine_gpu_scene*, int p, int octaves);
 /* Materials whose parameters are nodes (albedo: Node3f; the others: Nodef). */
 int pine_gpu_scene_add_material_diffuse_n(pine_gpu_scene*, const char* name, int albedo);
 int pine_gpu_scene_add_material_uber_n(pine_gpu_scene*, const char* name, int albedo, int roughness, int metallic,

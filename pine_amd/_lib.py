@@ -139,6 +139,8 @@ SIGNATURES = {
     "pine_gpu_scene_add_image_u8": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_int]),
     "pine_gpu_scene_node_image": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "pine_gpu_scene_node_imagef": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "pine_gpu_scene_node_noisef": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "pine_gpu_scene_node_noise3f": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "pine_gpu_scene_node_is_vec3": (C.c_int, [C.c_void_p, C.c_int]),
     "pine_gpu_scene_add_material_diffuse_n": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     "pine_gpu_scene_add_material_uber_n": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float]),

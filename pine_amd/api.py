@@ -168,6 +168,10 @@ class Node:
             p = sub(a[0])
             fn = lib.pine_gpu_scene_node_image if k == "image" else lib.pine_gpu_scene_node_imagef
             r = fn(h, p, a[1]._instantiate(scene))
+        elif k in ("noisef", "noise3f"):
+            p = sub(a[0])
+            fn = lib.pine_gpu_scene_node_noisef if k == "noisef" else lib.pine_gpu_scene_node_noise3f
+            r = fn(h, p, sub(a[1]))
         else:
             raise PineError("unknown node kind " + k)
         memo[id(self)] = (self, check(r, "node"))  # (keeps the node alive: ids of dead temporaries get reused)
@@ -226,6 +230,16 @@ def Texture(p, image):
 def Texturef(p, image):
     """NodeImagef (node.h:244-251, node.cpp:24-27): the same texel's first component."""
     return Node("imagef", Node.of(p, True), Image.of(image))
+
+
+def Noisef(p, octaves):
+    """NodeNoisef (node.h:209-216, node.cpp:7-9): fbm(p, int(octaves)), the reference's Perlin fbm; the first component of Noise3f."""
+    return Node("noisef", Node.of(p, True), Node.of(octaves, False))
+
+
+def Noise3f(p, octaves):
+    """NodeNoise3f (node.h:218-225, node.cpp:11-13): fbm3d(p, int(octaves)), three channels of the same noise."""
+    return Node("noise3f", Node.of(p, True), Node.of(octaves, False), is_vec3=True)
 
 
 def Position(): return Node("position", is_vec3=True)

@@ -9,6 +9,8 @@
 #include "pine_math.h"
 #include "pine_atmosphere.h"
 #include "pine_image_node.h"
+#include "pine_noise.h"
+#include "pine_rng.h"
 #include "pine_types.h"
 
 namespace pine_gpu {
@@ -45,61 +47,6 @@ enum : unsigned {
                           // a few variants only (pine_variants.h), never chosen without the flag
   F_ALL = 0xffu | F_NODES | F_LIGHTS | F_XSHAPES | F_SOBOL,
 };
-
-// ------------------------------------------------------------------------------------------------
-// hash + RNG (src/pine/core/rng.h:9-144) -- integer exact
-// ------------------------------------------------------------------------------------------------
-PINE_HD uint64_t hash_pixel(int px, int py, int sample_index) {
-  // murmur_hash64A over the 12 bytes {px, py, sample_index}, seed 0 (rng.h:9-49, :60-65)
-  const uint64_t m = 0xc6a4a7935bd1e995ull;
-  const int r = 47;
-  uint64_t h = 0 ^ (12ull * m);
-  uint64_t k = uint64_t(uint32_t(px)) | (uint64_t(uint32_t(py)) << 32);
-  k *= m;
-  k ^= k >> r;
-  k *= m;
-  h ^= k;
-  h *= m;
-  uint32_t t = uint32_t(sample_index);  // tail of 4 bytes: cases 4..1
-  h ^= uint64_t((t >> 24) & 0xff) << 24;
-  h ^= uint64_t((t >> 16) & 0xff) << 16;
-  h ^= uint64_t((t >> 8) & 0xff) << 8;
-  h ^= uint64_t(t & 0xff);
-  h *= m;
-  h ^= h >> r;
-  h *= m;
-  h ^= h >> r;
-  return h;
-}
-struct DRng {
-  uint64_t s0, s1;
-};
-PINE_HD uint64_t split_mix_64(uint64_t& s) {  // rng.h:72-77
-  uint64_t r = s += 0x9E3779B97f4A7C15ULL;
-  r = (r ^ (r >> 30)) * 0xBF58476D1CE4E5B9ULL;
-  r = (r ^ (r >> 27)) * 0x94D049BB133111EBULL;
-  return r ^ (r >> 31);
-}
-PINE_HD DRng rng_seed(uint64_t seed) {  // RNG::RNG rng.h:98-101
-  DRng g;
-  g.s0 = split_mix_64(seed);
-  g.s1 = split_mix_64(seed);
-  return g;
-}
-PINE_HD uint64_t rotl64(uint64_t x, int k) { return (x << k) | (x >> (64 - k)); }
-PINE_HD uint64_t rng_next64(DRng& g) {  // rng.h:116-126
-  const uint64_t s0 = g.s0;
-  uint64_t s1 = g.s1;
-  const uint64_t result = s0 + s1;
-  s1 ^= s0;
-  g.s0 = rotl64(s0, 24) ^ s1 ^ (s1 << 16);
-  g.s1 = rotl64(s1, 37);
-  return result;
-}
-PINE_HD float rng_nextf(DRng& g) {  // rng.h:132-135
-  uint64_t u = rng_next64(g);
-  return pmin(float(uint32_t(u ^ (u >> 32))) * 0x1p-32f, kOneMinusEps);
-}
 
 // ------------------------------------------------------------------------------------------------
 // BlueSobolSampler (src/pine/core/sampler.h:166-201, src/contrib/bluesobol/bluenoise_*spp.cpp:14-34)
@@ -1370,6 +1317,14 @@ PINE_HD bool bxdf_is_delta(const DBxdf& b) {
 // A float node travels as a splat; every operation is componentwise, so the float result is each
 // component of the vec3 result.
 // ------------------------------------------------------------------------------------------------
+// N_NOISE's body (pine_noise.h).  In the kernels it is a function of its own, called from the evaluator's switch: inlined there,
+// kernels whose scenes hold no noise node paid for it (profiles/noise_speed.txt has both versions' figures; -DPINE_NOISE_INLINE
+// builds the inlined one).  Every callee of the body is inlined into it; nothing recurses.
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(PINE_NOISE_INLINE)
+__device__ inline __attribute__((noinline)) f3 noise_node(f3 p, float octaves, bool three) { return noise_fbm(p, noise_octaves(octaves), three); }
+#else
+PINE_HD f3 noise_node(f3 p, float octaves, bool three) { return noise_fbm(p, noise_octaves(octaves), three); }
+#endif
 PINE_HD f3 node_program_eval(const DNodeOp* ops, const float* tex, int start, f3 p, f3 n, f2 uv) {
   f3 st[kNodeStack];
   int sp = 0;
@@ -1422,6 +1377,7 @@ PINE_HD f3 node_program_eval(const DNodeOp* ops, const float* tex, int start, f3
         st[sp - 1] = image_lookup(tex, tex + as_int(o.x), as_int(o.y), hz & ~kTexU8Bit, (hz & kTexU8Bit) != 0, st[sp - 1]);
         break;
       }
+      case N_NOISE: sp--; st[sp - 1] = noise_node(st[sp - 1], st[sp].x, o.x != 0.0f); break;
       default: break;
     }
   }

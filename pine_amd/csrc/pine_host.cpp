@@ -7,6 +7,7 @@
 #include "pine_math_check.h"
 #include "pine_atmosphere.h"
 #include "pine_image_node.h"
+#include "pine_noise.h"
 
 #include <algorithm>
 #include <cmath>
@@ -214,6 +215,9 @@ static f3 fold_node(const SceneHost& S, const HostNode& k) {
       const f3 v = image_lookup(u8_linear_table(), im.words.data(), im.w, im.h, im.u8, S.node_fold(k.a));
       return k.kind == HostNode::Image ? v : f3{v.x, v.x, v.x};
     }
+    case HostNode::Noise:
+    case HostNode::Noise3:  // the device's own function (pine_noise.h), on the operands' values
+      return noise_fbm(S.node_fold(k.a), noise_octaves(S.node_fold(k.b).x), k.kind == HostNode::Noise3);
     default: return f3{0, 0, 0};
   }
 }
@@ -269,6 +273,20 @@ int SceneHost::add_node(const HostNode& n) {
       }
       if (!ok(n.a, true)) return -1;
       break;
+    case HostNode::Noise:
+    case HostNode::Noise3: {  // NodeNoisef / NodeNoise3f(Node3f p, Nodef octaves)  node.h:209-225
+      const std::string who = n.kind == HostNode::Noise ? "`Noisef`" : "`Noise3f`";
+      for (int id : {n.a, n.b})
+        if (id < 0 || id >= int(nodes.size())) return set_error(who + ": operand id out of range"), -1;
+      if (!nodes[size_t(n.a)].is_vec3()) return set_error(who + ": p must be a Node3f"), -1;
+      if (nodes[size_t(n.b)].is_vec3()) return set_error(who + ": octaves must be a Nodef"), -1;
+      if (!node_reads_surface(n.b)) {  // (a value that reads the surface is bounded where it is evaluated: noise_octaves)
+        const float o = node_fold(n.b).x;
+        if (!std::isfinite(o)) return set_error(who + ": constant octaves is not finite"), -1;
+        if (o > float(kNoiseMaxOctaves)) return set_error(who + fmt(": constant octaves is above %d", kNoiseMaxOctaves)), -1;
+      }
+      break;
+    }
     case HostNode::Comp:
       if (!ok(n.a, true)) return -1;
       if (n.n < 0 || n.n > 2) {  // node.h:181-182
@@ -372,6 +390,16 @@ static int emit_program(const SceneHost& S, int id, std::vector<DNodeOp>& ops, i
       }
       push(N_IMAGE, as_float(int(at)), as_float(im.w), as_float(im.h | (im.u8 ? kTexU8Bit : 0)));
       if (k.kind == HostNode::ImageF) push(N_COMP, 0.0f);
+      break;
+    }
+    case HostNode::Noise:
+    case HostNode::Noise3: {
+      const int m1 = emit_program(S, k.a, ops, depth, tex, tex_at);
+      if (m1 < 0) return -1;
+      const int m2 = emit_program(S, k.b, ops, depth + 1, tex, tex_at);
+      if (m2 < 0) return -1;
+      push(N_NOISE, k.kind == HostNode::Noise3 ? 1.0f : 0.0f);
+      m = std::max(m1, m2);
       break;
     }
     default: return -1;
@@ -761,6 +789,8 @@ std::string SceneHost::describe() const {
       case HostNode::Splat: l += fmt("splat %d", k.a); break;
       case HostNode::Image: l += fmt("image %d %d", k.a, k.n); break;
       case HostNode::ImageF: l += fmt("imagef %d %d", k.a, k.n); break;
+      case HostNode::Noise: l += fmt("noisef %d %d", k.a, k.b); break;
+      case HostNode::Noise3: l += fmt("noise3f %d %d", k.a, k.b); break;
     }
     s += l + "\n";
   }
@@ -1367,6 +1397,15 @@ int pine_gpu_scene_node_splat(pine_gpu_scene* s, int a) {
   n.a = a;
   return add_node(s, n);
 }
+static int add_noise_node(pine_gpu_scene* s, HostNode::Kind kind, int p, int octaves) {
+  HostNode n;
+  n.kind = kind;
+  n.a = p;
+  n.b = octaves;
+  return add_node(s, n);
+}
+int pine_gpu_scene_node_noisef(pine_gpu_scene* s, int p, int octaves) { return add_noise_node(s, HostNode::Noise, p, octaves); }
+int pine_gpu_scene_node_noise3f(pine_gpu_scene* s, int p, int octaves) { return add_noise_node(s, HostNode::Noise3, p, octaves); }
 // ---- images of NodeImage / NodeImagef ----
 static bool image_size_ok(int w, int h) {
   if (w < 1 || h < 1) return set_error("`Image` needs at least 1 x 1 texels"), false;

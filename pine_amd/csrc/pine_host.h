@@ -97,9 +97,10 @@ struct FlatAccel {
 
 // One shading node of the scene's node table (node.h:13-297); ids are indices into SceneHost::nodes.
 struct HostNode {
-  enum Kind { ConstF, Const3, Position, Normal, UV, BinF, Bin3, UnF, Un3, Comp, ToVec3, Checker, Splat, Image, ImageF } kind = ConstF;
+  enum Kind { ConstF, Const3, Position, Normal, UV, BinF, Bin3, UnF, Un3, Comp, ToVec3, Checker, Splat, Image, ImageF, Noise, Noise3 } kind = ConstF;
   char op = 0;
-  int a = -1, b = -1, c = -1, n = 0;  // (Image, ImageF: a = the coordinate node, n = the image's index in SceneHost::images)
+  int a = -1, b = -1, c = -1, n = 0;  // (Image, ImageF: a = the coordinate node, n = the image's index in SceneHost::images;
+                                      // Noise, Noise3: a = p, b = octaves)
   float f = 0;
   f3 v{0, 0, 0};
   // Filled in by SceneHost::add_node, once per node (operands always precede the node, and a script may share one operand
@@ -107,7 +108,7 @@ struct HostNode {
   bool reads_surface = false;
   f3 folded{0, 0, 0};
   bool is_vec3() const {
-    return kind == Const3 || kind == Position || kind == Normal || kind == UV || kind == Bin3 || kind == Un3 || kind == ToVec3 || kind == Splat || kind == Image;
+    return kind == Const3 || kind == Position || kind == Normal || kind == UV || kind == Bin3 || kind == Un3 || kind == ToVec3 || kind == Splat || kind == Image || kind == Noise3;
   }
 };
 // One image that NodeImage / NodeImagef nodes look up (image.h:11: the four alternatives of `Image` as two storage forms).

@@ -82,6 +82,8 @@ enum NodeOpCode : int {
   N_CHECKER,  // x = ratio: pop p, push splat(float(prod(fract(p) - ratio) > 0))  node.cpp:15-18
   N_IMAGE,    // pop p, push the rgb of the texel at min(vec2i(size * fract(vec2(p))), size - 1)  node.cpp:20-23 (NodeImagef:
               // followed by N_COMP 0)
+  N_NOISE,    // x = 0: NodeNoisef, else NodeNoise3f: pop octaves, pop p, push fbm(p, int(octaves)) as a splat or
+              // fbm3d(p, int(octaves))  node.cpp:7-13 (pine_noise.h; the rounds are bounded by kNoiseMaxOctaves)
 };
 // N_IMAGE carries three integers in the bits of its floats (read back with as_int, never used as numbers): x = the image's
 // first word in the plan's `tex` buffer, y = its width, z = its height, with kTexU8Bit set where a texel is one RGBA8 word

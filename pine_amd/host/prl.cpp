@@ -35,6 +35,7 @@
 
 #include "../../include/pine_gpu.h"
 #include "../../include/pine_prl.h"
+#include "../csrc/pine_noise.h"  // fbm / fbm3d / pnoise / pnoise3d: the host build of the kernels' own function
 #include "gltf_import.hpp"
 #include "hdr_read.hpp"
 #include "png_writer.hpp"
@@ -124,7 +125,7 @@ struct CameraObj : Object {
 // else, so overload resolution picks the same function either way.
 struct ImageObj;
 struct NodeObj : Object {
-  std::string kind;  // constf const3 position normal uv bin un comp tovec3 checker splat image imagef
+  std::string kind;  // constf const3 position normal uv bin un comp tovec3 checker splat image imagef noisef noise3f
   std::shared_ptr<ImageObj> image;  // image, imagef: NodeImage / NodeImagef (a = the coordinate)
   char op = 0;
   int n = 0;
@@ -1041,7 +1042,10 @@ static int instantiate_node(SceneObj& s, const NodeP3& n, std::map<const NodeObj
     id = pine_gpu_scene_node_to_vec3(s.h, x, y, z);
   } else if (n->kind == "checker") id = pine_gpu_scene_node_checkerboard(s.h, instantiate_node(s, n->a, memo), n->f);
   else if (n->kind == "splat") id = pine_gpu_scene_node_splat(s.h, instantiate_node(s, n->a, memo));
-  else if (n->kind == "image" || n->kind == "imagef") {
+  else if (n->kind == "noisef" || n->kind == "noise3f") {
+    const int p = instantiate_node(s, n->a, memo), octaves = instantiate_node(s, n->b, memo);
+    id = n->kind == "noisef" ? pine_gpu_scene_node_noisef(s.h, p, octaves) : pine_gpu_scene_node_noise3f(s.h, p, octaves);
+  } else if (n->kind == "image" || n->kind == "imagef") {
     const int p = instantiate_node(s, n->a, memo);
     auto it2 = s.images.find(n->image);
     if (it2 == s.images.end()) {
@@ -1548,6 +1552,40 @@ Interp::Interp() {
   };
   r.def("Checkerboard", {"Node3f"}, "Nodef", [=](Interp&, std::vector<Cell>& a) { return checker(nobj(a[0]), 0.5f); });
   r.def("Checkerboard", {"Node3f", "f32"}, "Nodef", [=](Interp&, std::vector<Cell>& a) { return checker(nobj(a[0]), a[1]->f[0]); });
+  // Noisef / Noise3f(Node3f, Nodef) (node.cpp:63-64): Nodef's and Node3f's ctor_variant list them, so they stand where a node does
+  for (const char* name : {"Noisef", "Noise3f"})
+    r.def(name, {"Node3f", "Nodef"}, name[5] == '3' ? "Node3f" : "Nodef", [=](Interp&, std::vector<Cell>& a) {
+      auto n = std::make_shared<NodeObj>();
+      n->kind = name[5] == '3' ? "noise3f" : "noisef";
+      n->is3 = name[5] == '3';
+      n->a = nobj(a[0]);
+      n->b = nobj(a[1]);
+      return mk_node(n);
+    });
+  // the script-level noise functions (node.cpp:115-132), vec3 overloads only: pnoise(p, seed) = perlin_noise, fbm(p, octaves)
+  // -- pine_noise.h, the function the kernels run, in its host build; the second argument is an int as in the reference, and
+  // fbm's rounds are bounded by kNoiseMaxOctaves as everywhere
+  auto p3 = [](const Cell& c) { return pine_gpu::f3{c->f[0], c->f[1], c->f[2]}; };
+  r.def("pnoise", {"vec3", "i32"}, "f32", [=](Interp&, std::vector<Cell>& a) { return mk_f32(pine_gpu::perlin_noise3(p3(a[0]), a[1]->i[0])); });
+  r.def("pnoise3d", {"vec3", "i32"}, "vec3", [=](Interp&, std::vector<Cell>& a) {
+    const int seed = a[1]->i[0];
+    const float v[3] = {pine_gpu::perlin_noise3(p3(a[0]), seed), pine_gpu::perlin_noise3(p3(a[0]), seed + 1), pine_gpu::perlin_noise3(p3(a[0]), seed + 2)};
+    return mk_vecf(3, v);
+  });
+  r.def("fbm", {"vec3", "i32"}, "f32", [=](Interp&, std::vector<Cell>& a) { return mk_f32(pine_gpu::noise_fbm(p3(a[0]), a[1]->i[0], false).x); });
+  r.def("fbm3d", {"vec3", "i32"}, "vec3", [=](Interp&, std::vector<Cell>& a) {
+    const pine_gpu::f3 v = pine_gpu::noise_fbm(p3(a[0]), a[1]->i[0], true);
+    const float f[3] = {v.x, v.y, v.z};
+    return mk_vecf(3, f);
+  });
+  // (the float and vec2 overloads are other functions in the reference -- 1-d and 2-d noise -- and are not built: refused by name,
+  // before a number's conversion to vec3 could answer for them)
+  for (const char* name : {"pnoise", "pnoise3d", "fbm", "fbm3d"})
+    for (const char* first : {"f32", "vec2"})
+      r.def(name, {first, "i32"}, name[std::strlen(name) - 1] == 'd' ? "vec3" : "f32", [=](Interp&, std::vector<Cell>&) -> Value {
+        fail(std::string("`") + name + "(" + first + ", i32)` is not supported: of the noise functions only the vec3 overloads are");
+        return mk_f32(0);
+      });
   // Texture(Node3f, ImagePtr) (node.cpp:66-67).  The reference registers NodeImagef and then NodeImage under the ONE type name
   // "Texture" (context.h:571-576: the second type() finds the name taken and shares its trait; both C++ types now answer to
   // "Texture").  Their constructors have the same unique name, `Texture(Node3f, ImagePtr): Texture`, so the second add_f
