@@ -1,7 +1,10 @@
 // pine_amd/csrc/pine_ao_host.h -- the host side of AOIntegrator plans (kernels: pine_ao_kernel.h).  Included by
-// pine_kernels.hip after plan_build's phases, which an AO plan shares: check_params, assemble_scene, upload_sampler_tables,
-// scene_features, the work decomposition's fields, the RNG checkpoint prepass.  An AO plan is a pine_gpu_plan with `ao`
-// set: pine_gpu_plan_launch / _stats_get / _check / _destroy take it as they take any plan.
+// pine_kernels.hip after plan_build's phases.  Of those an AO plan runs the ones that decide nothing about path kernels --
+// check_params, assemble_scene, upload_sampler_tables, scene_features -- and between them the steps of pine_plan_steps.h, in its
+// own order: plan_open_device, pick_variant, shard_tiles, items_of_k_samples, plan_progress_word, plan_timing_events to build
+// (create_plan around them); launch_begin, launch_mark, checkpoint_prepass, launch_end to launch.  Its refusals, its kernel's LDS size, the chunks
+// of k samples and its buffers are its own.  An AO plan is a pine_gpu_plan with `ao` set: pine_gpu_plan_launch / _stats_get /
+// _check / _destroy take it as they take any plan.
 
 // The AO sample count (ao.cpp:13) of a sampler whose own count is `sampler_spp`.
 static int ao_effective_spp(int sampler_spp) { return std::max(sampler_spp / 8, 1); }
@@ -23,24 +26,10 @@ static int ao_plan_build(pine_gpu_plan* p, pine_gpu_scene* scene, const pine_gpu
   const int spp = ao_effective_spp(sampler_spp);
   TableBlob tables_blob;
   if (load_tables(tables_blob)) return -1;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    set_error("no HIP device available: the AOIntegrator hot path requires an AMD GPU (no CPU fallback)");
-    return -1;
-  }
-  HIP_OK(hipSetDevice(prm.device));
+  std::chrono::steady_clock::time_point t_build1;
+  if (plan_open_device(p, H, &prm, "the AOIntegrator hot path", t_build1)) return -1;
   p->ao = true;
-  p->device = prm.device;
-  p->params = prm;
   const size_t tally0 = g_alloc_tally;
-  const auto t_build0 = std::chrono::steady_clock::now();
-  if (!H.accel.built) {
-    H.build_on_device = (prm.flags & PINE_GPU_FLAG_DEVICE_BVH) ? prm.device : -1;
-    H.build_accel();
-  }
-  const auto t_build1 = std::chrono::steady_clock::now();
-  p->accel_build_ms = std::chrono::duration<float, std::milli>(t_build1 - t_build0).count();
-  p->accel_on_device = H.built_on_device;
 
   SceneParts sp;
   // (the sampler keeps its ORIGINAL count -- BlueSampler's table, SobolSampler's index stride -- only fewer indices are drawn)
@@ -56,16 +45,9 @@ static int ao_plan_build(pine_gpu_plan* p, pine_gpu_scene* scene, const pine_gpu
   const bool lds_ok = size_t(p->S.blob_bytes) <= 32 * 1024;
   int count = 0;
   const PineAoVariant* table = pine_gpu_ao_variants(&count);
-  const char* pin = getenv("PINE_GPU_AO_VARIANT");
-  for (int i = 0; i < count && p->ao_variant < 0; i++) {
-    if (pin && *pin && atoi(pin) != i) continue;
-    const unsigned F = table[i].features;
-    if ((need & ~F) == 0 && (!(F & F_LDS_SCENE) || lds_ok)) p->ao_variant = i;
-  }
-  if (p->ao_variant < 0) {
-    set_error(pin && *pin ? "$PINE_GPU_AO_VARIANT names no AO kernel variant that covers this scene" : "no AO kernel variant covers this scene");
-    return -1;
-  }
+  p->ao_variant = pick_variant(table, count, need, lds_ok, "PINE_GPU_AO_VARIANT", "no AO kernel variant covers this scene",
+                               "$PINE_GPU_AO_VARIANT names no AO kernel variant that covers this scene");
+  if (p->ao_variant < 0) return -1;
   p->ao_serial = true;  // (the faster of the two on two of the three measured scenes: DESIGN.md 4.11, profiles/ao_speed.txt)
   if (const char* e = getenv("PINE_GPU_AO_KERNEL")) {
     if (!strcmp(e, "regroup")) p->ao_serial = false;
@@ -87,20 +69,10 @@ static int ao_plan_build(pine_gpu_plan* p, pine_gpu_scene* scene, const pine_gpu
   // still leaves 2^20 items (a lane walks its k samples in sequence; the chunks start from RNG checkpoints)
   WorkParams& W = p->W;
   p->film_w = H.camera.W, p->film_h = H.camera.H;
-  if (p->film_w > 65535 || p->film_h > 65535) {
-    set_error("film sides above 65535 are not supported");
-    return -1;
-  }
-  W.tiles_x = (p->film_w + kTile - 1) / kTile, W.tiles_y = (p->film_h + kTile - 1) / kTile;
-  W.shard_rank = prm.shard_rank, W.shard_world = prm.shard_world;
-  W.num_local_tiles = (W.tiles_x * W.tiles_y - prm.shard_rank + prm.shard_world - 1) / prm.shard_world;
+  if (shard_tiles(W, p->film_w, p->film_h, &prm)) return -1;
   int k = 1;
   while (spp % (2 * k) == 0 && (unsigned long long)W.num_local_tiles * 64ull * unsigned(spp / (2 * k)) >= (1ull << 20)) k *= 2;
-  W.samples_per_item = k;
-  W.items_per_pixel = spp / k;
-  W.log2_items_per_pixel = 0;
-  while ((1 << W.log2_items_per_pixel) < W.items_per_pixel) W.log2_items_per_pixel++;
-  W.tiles_x_magic = unsigned(((1ull << 32) + unsigned(W.tiles_x) - 1) / unsigned(W.tiles_x));
+  items_of_k_samples(W, spp, k);
   W.total_items = (unsigned long long)W.num_local_tiles * unsigned(W.items_per_pixel) * 64ull;
   if (W.total_items >= (1ull << 32)) {  // (decode_item's tile-and-chunk number is 32 bits less the pixel's six)
     set_error("film pixels x AO samples per pixel of one shard must stay below 2^32 (render in several shards)");
@@ -108,22 +80,13 @@ static int ao_plan_build(pine_gpu_plan* p, pine_gpu_scene* scene, const pine_gpu
   }
   W.tile_order = nullptr;
   W.serial_tiles = 0;
-  W.pass_first_chunk = 0;
-  W.pass_chunks = W.items_per_pixel;
-  W.pass_chunks_magic = W.pass_chunks > 1 ? unsigned(((1ull << 32) + unsigned(W.pass_chunks) - 1) / unsigned(W.pass_chunks)) : 0u;
-  W.pass_row_stride = spp;
   W.free_tile_base = 0;
-  W.pass_first_serial_tile = 0;
   W.debug_force_bail = (prm.flags & PINE_GPU_FLAG_DEBUG_FORCE_BAIL) ? 1 : 0;
   W.progress = nullptr;
   W.vertex_log = nullptr;
   p->pass_plan = PassPlan();
   p->pass_plan.free_tiles = W.num_local_tiles;
-  if (prm.flags & PINE_GPU_FLAG_PROGRESS) {
-    if (alloc_pinned(p->h_progress, 1, hipHostMallocMapped, "plan creation: the progress word")) return -1;
-    p->h_progress[0] = 0;
-    HIP_OK(hipHostGetDevicePointer((void**)&W.progress, p->h_progress.get(), 0));
-  }
+  if (plan_progress_word(p, &prm)) return -1;
   const char* const what = "plan creation: the launch buffers";
   hipDeviceProp_t prop;
   HIP_OK(hipGetDeviceProperties(&prop, prm.device));
@@ -137,45 +100,20 @@ static int ao_plan_build(pine_gpu_plan* p, pine_gpu_scene* scene, const pine_gpu
     if (p->d_ckpt.alloc(W.total_items, what)) return -1;
   }
   if (p->d_ao_counts.alloc(size_t(p->film_w) * p->film_h, what) || p->d_counters.alloc(1, what)) return -1;
-  p->timed = (prm.flags & PINE_GPU_FLAG_TIMING) != 0;
-  if (p->timed)
-    for (auto& slot : p->ev)
-      for (auto& e : slot)
-        if (create_event(e, hipEventDefault, "plan creation: the timing events")) return -1;
+  if (plan_timing_events(p, &prm)) return -1;
   p->bytes_total = g_alloc_tally - tally0;
   HIP_OK(hipDeviceSynchronize());
   p->upload_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_build1).count();
   return 0;
 }
 
-// One AO render into film_dev: counters cleared, checkpoint prepass (first launch), the AO kernel, the film from the counts.
+// One AO render into film_dev: counters and counts cleared, checkpoint prepass (first launch), the AO kernel, the film from the counts.
 static int ao_launch(pine_gpu_plan* p, void* film_dev, hipStream_t stream) {
-  HIP_OK(hipSetDevice(p->device));
-  (void)hipGetLastError();
-  g_progress.store(0.0f);
   WorkParams& W = p->W;
-  const size_t pixels = size_t(p->film_w) * p->film_h;
-  if (W.shard_world > 1) HIP_OK(hipMemsetAsync(film_dev, 0, pixels * sizeof(float4), stream));
-  HIP_OK(hipMemsetAsync(p->d_counters, 0, sizeof(Counters), stream));
-  HIP_OK(hipMemsetAsync(p->d_ao_counts, 0, pixels * sizeof(unsigned), stream));
-  const EventOwner* ev = p->ev[p->launch_count % pine_gpu_plan::kEvRing];
-  if (p->timed) HIP_OK(hipEventRecord(ev[0].get(), stream));
-  const bool has_work = W.total_items > 0;
-  if (has_work && W.items_per_pixel > 1) {
-    if (!p->ckpt_valid) {
-      const unsigned long long n = (unsigned long long)W.num_local_tiles * 64ull;
-      hipLaunchKernelGGL(rng_checkpoint_kernel, dim3(unsigned((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, W, p->film_w, p->film_h, p->S.spp,
-                         p->d_ckpt, W.num_local_tiles, (ulonglong2*)nullptr);
-      if (!p->ckpt_done && create_event(p->ckpt_done, hipEventDisableTiming, "launch: the checkpoint event")) return -1;
-      HIP_OK(hipEventRecord(p->ckpt_done.get(), stream));
-      p->ckpt_stream = stream;
-      p->ckpt_valid = true;
-    } else if (stream != p->ckpt_stream) {
-      HIP_OK(hipStreamWaitEvent(stream, p->ckpt_done.get(), 0));
-    }
-  }
-  if (p->timed) HIP_OK(hipEventRecord(ev[1].get(), stream));
-  if (has_work) {
+  if (launch_begin(p, 0, film_dev, stream, false)) return -1;
+  HIP_OK(hipMemsetAsync(p->d_ao_counts, 0, size_t(p->film_w) * p->film_h * sizeof(unsigned), stream));
+  if (launch_mark(p, 0, stream) || checkpoint_prepass(p, W, stream) || launch_mark(p, 1, stream)) return -1;
+  if (W.total_items > 0) {
     const PathKernel kernel = plan_kernel(p);
     const ulonglong2* ckpt = p->d_ckpt;
     unsigned* counts = p->d_ao_counts;
@@ -183,33 +121,17 @@ static int ao_launch(pine_gpu_plan* p, void* film_dev, hipStream_t stream) {
     void* args[] = {&p->S, &W, &p->ao_params, &ckpt, &counts, &counters};
     HIP_OK(hipLaunchKernel(kernel.fn, dim3(p->grid), dim3(kBlock), args, p->lds_bytes, stream));
   }
-  if (p->timed) HIP_OK(hipEventRecord(ev[2].get(), stream));
+  if (launch_mark(p, 2, stream)) return -1;
   if (W.num_local_tiles > 0) {
     const unsigned long long n = (unsigned long long)W.num_local_tiles * 64ull;
     hipLaunchKernelGGL(ao_film_kernel, dim3(unsigned((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, W, p->film_w, p->film_h, p->S.spp,
                        p->d_ao_counts.get(), (float4*)film_dev);
   }
-  if (p->timed) HIP_OK(hipEventRecord(ev[3].get(), stream));
-  HIP_OK(hipGetLastError());
-  p->launched = true;
-  p->launch_count++;
-  p->last_stream = stream;
-  return 0;
+  return launch_end(p, stream);
 }
 
 pine_gpu_plan* pine_gpu_ao_plan_create(pine_gpu_scene* scene, const pine_gpu_render_params* prm) {
-  if (!scene || !prm) {
-    set_error("null argument");
-    return nullptr;
-  }
-  pine_gpu_plan* p = new pine_gpu_plan();
-  if (ao_plan_build(p, scene, prm)) {
-    std::string keep = pine_gpu_last_error();
-    pine_gpu_plan_destroy(p);
-    set_error(keep);
-    return nullptr;
-  }
-  return p;
+  return create_plan(scene, prm, [&](pine_gpu_plan* p) { return ao_plan_build(p, scene, prm); });
 }
 
 // AOIntegrator(BVH(), sampler).render(scene) in one call: upload, launch, download.  Fails if there is no GPU.

@@ -1,6 +1,8 @@
 // pine_amd/csrc/pine_guides_host.h -- the host side of DenoiseIntegrator's guide images (kernels: pine_guides_kernel.h).  Included
-// by pine_kernels.hip after plan_build's phases, of which the guide pass shares check_params, assemble_scene and scene_features.
-// The pass has no plan of its own: the scene's records are uploaded into a pine_gpu_plan that lives for the length of the call.
+// by pine_kernels.hip after plan_build's phases, of which the guide pass runs check_params, assemble_scene and scene_features;
+// of the steps of pine_plan_steps.h it takes shard_tiles, plan_open_device (open_device alone for the output buffers) and
+// pick_variant.  The pass has no plan of its own and no launch frame: the scene's records are uploaded into a pine_gpu_plan that
+// lives for the length of the call, one kernel is launched and waited for.
 
 static int guides_render_device(pine_gpu_scene* scene, const pine_gpu_render_params* prm_in, float* albedo_dev, float* normal_dev, hipStream_t stream) {
   SceneHost& H = scene_host(scene);
@@ -24,23 +26,9 @@ static int guides_render_device(pine_gpu_scene* scene, const pine_gpu_render_par
   prm.max_path_length = 1;
   prm.samples_per_item = 0;
   if (check_params(H, &prm) < 0) return -1;
-  if (H.camera.W > 65535 || H.camera.H > 65535) {
-    set_error("film sides above 65535 are not supported");
-    return -1;
-  }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    set_error("no HIP device available: the guide images' hot path requires an AMD GPU (no CPU fallback)");
-    return -1;
-  }
-  HIP_OK(hipSetDevice(prm.device));
   PlanOwner p(new pine_gpu_plan());
-  p->device = prm.device;
-  p->params = prm;
-  if (!H.accel.built) {
-    H.build_on_device = (prm.flags & PINE_GPU_FLAG_DEVICE_BVH) ? prm.device : -1;
-    H.build_accel();
-  }
+  std::chrono::steady_clock::time_point built;
+  if (shard_tiles(p->W, H.camera.W, H.camera.H, &prm) || plan_open_device(p.get(), H, &prm, "the guide images' hot path", built)) return -1;
   SceneParts sp;
   if (assemble_scene(p.get(), H, &prm, sp, false)) return -1;
 
@@ -48,18 +36,11 @@ static int guides_render_device(pine_gpu_scene* scene, const pine_gpu_render_par
   // considers that variant only (tests)
   const unsigned need = scene_features(sp, &prm) & (kFGuidesShapes | F_NODES);
   const bool lds_ok = size_t(p->S.blob_bytes) <= 32 * 1024;
-  int count = 0, chosen = -1;
+  int count = 0;
   const PineGuidesVariant* table = pine_gpu_guides_variant_table(&count);
-  const char* pin = getenv("PINE_GPU_GUIDES_VARIANT");
-  for (int i = 0; i < count && chosen < 0; i++) {
-    if (pin && *pin && atoi(pin) != i) continue;
-    const unsigned F = table[i].features;
-    if ((need & ~F) == 0 && (!(F & F_LDS_SCENE) || lds_ok)) chosen = i;
-  }
-  if (chosen < 0) {
-    set_error(pin && *pin ? "$PINE_GPU_GUIDES_VARIANT names no guide kernel variant that covers this scene" : "no guide kernel variant covers this scene");
-    return -1;
-  }
+  const int chosen = pick_variant(table, count, need, lds_ok, "PINE_GPU_GUIDES_VARIANT", "no guide kernel variant covers this scene",
+                                  "$PINE_GPU_GUIDES_VARIANT names no guide kernel variant that covers this scene");
+  if (chosen < 0) return -1;
   const PineGuidesVariant& K = table[chosen];
   const size_t lds_bytes = size_t(p->S.stack_total) * kBlock * sizeof(int) + ((K.features & F_LDS_SCENE) ? size_t(p->S.blob_bytes) : 0);
   if (lds_bytes > 160 * 1024) {
@@ -67,7 +48,7 @@ static int guides_render_device(pine_gpu_scene* scene, const pine_gpu_render_par
     return -1;
   }
   HIP_OK(hipFuncSetAttribute(K.fn, hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_bytes)));
-  int tiles_x = (H.camera.W + kTile - 1) / kTile, num_tiles = tiles_x * ((H.camera.H + kTile - 1) / kTile);
+  int tiles_x = p->W.tiles_x, num_tiles = p->W.num_local_tiles;  // (shard_world is 1: every tile of the film)
   void* args[] = {&p->S, &tiles_x, &num_tiles, &albedo_dev, &normal_dev};
   const unsigned grid = unsigned((num_tiles + kBlock / 64 - 1) / (kBlock / 64));
   HIP_OK(hipLaunchKernel(K.fn, dim3(grid), dim3(kBlock), args, lds_bytes, stream));
@@ -95,12 +76,7 @@ int pine_gpu_guides_render(pine_gpu_scene* scene, const pine_gpu_render_params* 
     set_error("scene has no camera");
     return -1;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    set_error("no HIP device available: the guide images' hot path requires an AMD GPU (no CPU fallback)");
-    return -1;
-  }
-  HIP_OK(hipSetDevice(prm->device));
+  if (open_device(prm, "the guide images' hot path")) return -1;  // (for the output buffers)
   const size_t n = size_t(H.camera.W) * size_t(H.camera.H) * 3;
   const char* const what = "guide images: the output buffers";
   DeviceBuffer<float> d_albedo(kFromPool), d_normal(kFromPool);

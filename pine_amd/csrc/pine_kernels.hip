@@ -323,6 +323,8 @@ static int plan_check_counters(const Counters& c) {
   return -1;
 }
 
+#include "pine_plan_steps.h"  // what path plans, AO plans and the guide pass build and launch alike, one function per step
+
 // The launch side of a one-shot render (create, launch, download, destroy), which the path and the AO render share: a film from
 // the pool, `run(film, bytes)` -- launches, downloads, checks; 0, PINE_GPU_RENDER_STOPPED or -1 -- while get_progress() follows
 // the plan's progress word over `total_items`, the error kept across the cleanup.  After a failure a launch may still be
@@ -1112,17 +1114,8 @@ static int choose_items(pine_gpu_plan* p, const SceneHost& H, const SceneParts& 
   WorkParams& W = p->W;
   p->film_w = H.camera.W;
   p->film_h = H.camera.H;
-  W.tiles_x = (p->film_w + kTile - 1) / kTile;
-  W.tiles_y = (p->film_h + kTile - 1) / kTile;
-  const int total_tiles = W.tiles_x * W.tiles_y;
-  W.shard_rank = prm->shard_rank;
-  W.shard_world = prm->shard_world;
-  W.num_local_tiles = (total_tiles - prm->shard_rank + prm->shard_world - 1) / prm->shard_world;
-  W.samples_per_item = kspi;
-  W.items_per_pixel = spp / kspi;
-  W.log2_items_per_pixel = 0;
-  while ((1 << W.log2_items_per_pixel) < W.items_per_pixel) W.log2_items_per_pixel++;
-  W.tiles_x_magic = unsigned(((1ull << 32) + unsigned(W.tiles_x) - 1) / unsigned(W.tiles_x));  // tiles_x >= 1
+  if (shard_tiles(W, p->film_w, p->film_h, prm)) return -1;
+  items_of_k_samples(W, spp, kspi);
   W.total_items = (unsigned long long)W.num_local_tiles * W.items_per_pixel * 64ull;
   W.tile_order = nullptr;
   W.serial_tiles = 0;
@@ -1137,25 +1130,10 @@ static int choose_items(pine_gpu_plan* p, const SceneHost& H, const SceneParts& 
     p->tile_order.insert(p->tile_order.end(), free_tiles.begin(), free_tiles.end());
     W.serial_tiles = int(serial.size());
     // the independent class: one sample per item, RNG checkpoints (the Subsurface variants are F_LDS_TOP ones)
-    W.samples_per_item = 1;
-    W.items_per_pixel = spp;
-    W.log2_items_per_pixel = 0;
-    while ((1 << W.log2_items_per_pixel) < W.items_per_pixel) W.log2_items_per_pixel++;
+    items_of_k_samples(W, spp, 1);
     W.total_items = (unsigned long long)W.serial_tiles * 64ull + (unsigned long long)(W.num_local_tiles - W.serial_tiles) * W.items_per_pixel * 64ull;
   }
-  // packing limits of the kernels: pixel coordinates travel as 16 + 16 bits, the sample-buffer index of a
-  // context as 32 bits
-  if (p->film_w > 65535 || p->film_h > 65535) {
-    set_error("film sides above 65535 are not supported");
-    return -1;
-  }
-  // the pass window of the plan's W: the whole render (pass_work narrows it to a pass)
-  W.pass_first_chunk = 0;
-  W.pass_chunks = W.items_per_pixel;
-  W.pass_chunks_magic = W.pass_chunks > 1 ? unsigned(((1ull << 32) + unsigned(W.pass_chunks) - 1) / unsigned(W.pass_chunks)) : 0u;
-  W.pass_row_stride = spp;
   W.free_tile_base = W.serial_tiles;
-  W.pass_first_serial_tile = 0;
   if (!plan_passes(W.num_local_tiles, spp, W.samples_per_item, W.serial_tiles, p->pass_samples_req, p->pass_plan)) return -1;
   // the 32-bit sample-buffer index covers one pass: its rows, and the rows before its first sample that decode_item adds to a
   // whole-pixel item's base (one pass: all tiles x 64 x spp)
@@ -1240,11 +1218,7 @@ static void schedule_params(pine_gpu_plan* p, const FlatAccel& A, const pine_gpu
 static int size_and_allocate(pine_gpu_plan* p, const pine_gpu_render_params* prm, int spp, const PlanKnobs& K) {
   const char* const what = "plan creation: the launch buffers";
   WorkParams& W = p->W;
-  if (prm->flags & PINE_GPU_FLAG_PROGRESS) {
-    if (alloc_pinned(p->h_progress, 1, hipHostMallocMapped, "plan creation: the progress word")) return -1;
-    p->h_progress[0] = 0;
-    HIP_OK(hipHostGetDevicePointer((void**)&W.progress, p->h_progress.get(), 0));
-  }
+  if (plan_progress_word(p, prm)) return -1;
   hipDeviceProp_t prop;
   HIP_OK(hipGetDeviceProperties(&prop, prm->device));
   int blocks_per_cu = 0;
@@ -1327,12 +1301,7 @@ static int size_and_allocate(pine_gpu_plan* p, const pine_gpu_render_params* prm
   // (the owned tiles' done marks sit behind the counters: one clear for both)
   if (p->d_counters.alloc_bytes(sizeof(Counters) + (W.owned_tiles > 0 ? size_t(W.num_local_tiles) * sizeof(unsigned) : 0), what)) return -1;
   W.tile_done = W.owned_tiles > 0 ? reinterpret_cast<unsigned*>(p->d_counters + 1) : nullptr;
-  p->timed = (prm->flags & PINE_GPU_FLAG_TIMING) != 0;
-  if (p->timed)
-    for (auto& slot : p->ev)
-      for (auto& e : slot)
-        if (create_event(e, hipEventDefault, "plan creation: the timing events")) return -1;
-  return 0;
+  return plan_timing_events(p, prm);
 }
 
 static int plan_build(pine_gpu_plan* p, pine_gpu_scene* scene, const pine_gpu_render_params* prm) {
@@ -1342,23 +1311,9 @@ static int plan_build(pine_gpu_plan* p, pine_gpu_scene* scene, const pine_gpu_re
   if (spp < 0) return -1;
   TableBlob tables_blob;
   if (load_tables(tables_blob)) return -1;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    set_error("no HIP device available: the PathIntegrator hot path requires an AMD GPU (no CPU fallback)");
-    return -1;
-  }
-  HIP_OK(hipSetDevice(prm->device));
-  p->device = prm->device;
-  p->params = *prm;
-  const size_t tally0 = g_alloc_tally;
-  const auto t_build0 = std::chrono::steady_clock::now();
-  if (!H.accel.built) {
-    H.build_on_device = (prm->flags & PINE_GPU_FLAG_DEVICE_BVH) ? prm->device : -1;
-    H.build_accel();
-  }
-  const auto t_build1 = std::chrono::steady_clock::now();
-  p->accel_build_ms = std::chrono::duration<float, std::milli>(t_build1 - t_build0).count();
-  p->accel_on_device = H.built_on_device;
+  std::chrono::steady_clock::time_point t_build1;
+  if (plan_open_device(p, H, prm, "the PathIntegrator hot path", t_build1)) return -1;
+  const size_t tally0 = g_alloc_tally;  // (the BVH build takes nothing from the pool)
   const FlatAccel& A = H.accel;
 
   SceneParts sp;
@@ -1379,19 +1334,10 @@ static int plan_build(pine_gpu_plan* p, pine_gpu_scene* scene, const pine_gpu_re
 }
 
 static pine_gpu_plan* plan_create(pine_gpu_scene* scene, const pine_gpu_render_params* prm, int pass_samples) {
-  if (!scene || !prm) {
-    set_error("null argument");
-    return nullptr;
-  }
-  pine_gpu_plan* p = new pine_gpu_plan();
-  p->pass_samples_req = pass_samples;
-  if (plan_build(p, scene, prm)) {
-    std::string keep = pine_gpu_last_error();
-    pine_gpu_plan_destroy(p);
-    set_error(keep);
-    return nullptr;
-  }
-  return p;
+  return create_plan(scene, prm, [&](pine_gpu_plan* p) {
+    p->pass_samples_req = pass_samples;
+    return plan_build(p, scene, prm);
+  });
 }
 pine_gpu_plan* pine_gpu_plan_create(pine_gpu_scene* scene, const pine_gpu_render_params* prm) { return plan_create(scene, prm, 0); }
 pine_gpu_plan* pine_gpu_plan_create_passes(pine_gpu_scene* scene, const pine_gpu_render_params* prm, int32_t pass_samples) {
@@ -1419,56 +1365,19 @@ static int launch_path_kernel(pine_gpu_plan* p, WorkParams& W, float4* samples, 
   return 0;
 }
 
-// Pass j of the plan -- the only place that enqueues a render: checkpoint prepass, the path kernel over the pass window, the
-// resolve that continues the running sum and writes the film.  A plan of one pass renders the whole film here.
-static int plan_launch_pass(pine_gpu_plan* p, int j, void* film_dev, hipStream_t stream, bool packed) {
+// Pass j of a path plan: checkpoint prepass, the path kernel over the pass window, the resolve that continues the running sum
+// and writes the film.  A plan of one pass renders the whole film here.
+static int path_launch_pass(pine_gpu_plan* p, int j, void* film_dev, hipStream_t stream, bool packed) {
   const PassPlan& PP = p->pass_plan;
-  if (j < 0 || j >= PP.n || (j != 0 && j != p->next_pass)) {
-    set_error("passes run in order: pass " + std::to_string(j) + " asked for, pass " + std::to_string(p->next_pass >= PP.n ? 0 : p->next_pass) +
-              (p->next_pass > 0 && p->next_pass < PP.n ? " (or 0, which starts the film afresh)" : "") + " is next; nothing was launched");
-    return -1;
-  }
-  if (p->ao) return packed ? (set_error("an AOIntegrator plan has no packed launch"), -1) : ao_launch(p, film_dev, stream);
-  HIP_OK(hipSetDevice(p->device));
-  (void)hipGetLastError();  // (HIP's last error is sticky: what the check at the end reports must come from THIS launch's calls)
-  // a background build that has finished: this launch and every later one run the scene's own kernel -- between two passes
-  // too: the same bits.  (A code object the runtime refuses leaves the precompiled kernel in place -- same film; plan stats say
-  // which one runs.)
-  p->scene_kernel.poll();
-  if (j == 0) g_progress.store(0.0f);
+  if (launch_begin(p, j, film_dev, stream, packed)) return -1;
   const int spp = p->S.spp;
   const PassPlan::Pass a = PP.pass(j, spp);
   WorkParams W = pass_work(p, j);
-  const size_t film_bytes = size_t(p->film_w) * p->film_h * sizeof(float4);
-  if (p->W.shard_world > 1 && !packed) HIP_OK(hipMemsetAsync(film_dev, 0, film_bytes, stream));
-  // the counters of the sequence start with pass 0; every pass hands out its own items from zero
-  const size_t done_bytes = p->W.tile_done ? size_t(p->W.num_local_tiles) * sizeof(unsigned) : 0;  // (owned tiles: plans of one pass)
-  HIP_OK(hipMemsetAsync(p->d_counters, 0, j == 0 ? sizeof(Counters) + done_bytes : sizeof(unsigned long long), stream));
   W.film = (float4*)film_dev;
   W.film_packed = packed ? 1 : 0;
-  static_assert(offsetof(Counters, next_item) == 0, "the per-pass reset clears next_item");
-  const EventOwner* ev = p->ev[p->launch_count % pine_gpu_plan::kEvRing];
-  if (p->timed) HIP_OK(hipEventRecord(ev[0].get(), stream));
+  if (launch_mark(p, 0, stream) || checkpoint_prepass(p, W, stream) || launch_mark(p, 1, stream)) return -1;
   // (a shard can own no tile at all -- more ranks than 8x8 tiles: nothing to launch, the film / slab stays zero)
-  const bool has_work = W.total_items > 0;
-  if (has_work && p->W.items_per_pixel > 1 && PP.free_tiles > 0) {
-    // a plan of one pass computes its checkpoints once and keeps them; a pass of a longer sequence walks on from the carried states
-    if (PP.n > 1 || !p->ckpt_valid || p->ckpt_every_launch) {
-      const unsigned long long n = (unsigned long long)PP.free_tiles * 64ull;
-      hipLaunchKernelGGL(rng_checkpoint_kernel, dim3(unsigned((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, W, p->film_w, p->film_h,
-                         spp, p->d_ckpt, PP.free_tiles, p->d_rng_carry);
-      if (PP.n == 1) {
-        if (!p->ckpt_done && create_event(p->ckpt_done, hipEventDisableTiming, "launch: the checkpoint event")) return -1;
-        HIP_OK(hipEventRecord(p->ckpt_done.get(), stream));
-        p->ckpt_stream = stream;
-        p->ckpt_valid = true;
-      }
-    } else if (stream != p->ckpt_stream) {
-      HIP_OK(hipStreamWaitEvent(stream, p->ckpt_done.get(), 0));
-    }
-  }
-  if (p->timed) HIP_OK(hipEventRecord(ev[1].get(), stream));
-  if (has_work) {
+  if (W.total_items > 0) {
     // (the largest pass fills p->grid: the only pass of a plan of one)
     const int ctx = plan_kernel(p).ctx;
     const int grid = int(std::min<unsigned long long>((unsigned long long)p->grid, (W.total_items + ctx - 1) / ctx));
@@ -1476,7 +1385,7 @@ static int plan_launch_pass(pine_gpu_plan* p, int j, void* film_dev, hipStream_t
     float4* const samples = p->d_samples - size_t(W.pass_first_chunk) * size_t(W.samples_per_item) * 64u;
     if (launch_path_kernel(p, W, samples, grid, stream)) return -1;
   }
-  if (p->timed) HIP_OK(hipEventRecord(ev[2].get(), stream));
+  if (launch_mark(p, 2, stream)) return -1;
   if (p->W.num_local_tiles > 0) {
     ResolvePass R;
     R.film_w = p->film_w, R.film_h = p->film_h, R.spp = spp;
@@ -1487,13 +1396,24 @@ static int plan_launch_pass(pine_gpu_plan* p, int j, void* film_dev, hipStream_t
     hipLaunchKernelGGL(resolve_kernel, dim3(unsigned((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, p->W, R, p->d_samples, p->d_sum,
                        (float4*)film_dev, p->d_counters);
   }
-  if (p->timed) HIP_OK(hipEventRecord(ev[3].get(), stream));
-  HIP_OK(hipGetLastError());
-  p->launched = true;
-  p->launch_count++;
-  p->last_stream = stream;
+  if (launch_end(p, stream)) return -1;
   p->next_pass = j + 1;
   return 0;
+}
+
+// Pass j of the plan -- the only place that enqueues a render.  A launch that fails may have left the RNG checkpoints unwritten:
+// the next one computes them again.
+static int plan_launch_pass(pine_gpu_plan* p, int j, void* film_dev, hipStream_t stream, bool packed) {
+  const PassPlan& PP = p->pass_plan;
+  if (j < 0 || j >= PP.n || (j != 0 && j != p->next_pass)) {
+    set_error("passes run in order: pass " + std::to_string(j) + " asked for, pass " + std::to_string(p->next_pass >= PP.n ? 0 : p->next_pass) +
+              (p->next_pass > 0 && p->next_pass < PP.n ? " (or 0, which starts the film afresh)" : "") + " is next; nothing was launched");
+    return -1;
+  }
+  if (p->ao && packed) return set_error("an AOIntegrator plan has no packed launch"), -1;
+  const int rc = p->ao ? ao_launch(p, film_dev, stream) : path_launch_pass(p, j, film_dev, stream, packed);
+  if (rc) p->ckpt_valid = false;
+  return rc;
 }
 
 // All passes of the plan, in order.

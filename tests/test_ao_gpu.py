@@ -95,6 +95,30 @@ def test_two_launches_one_film():
     assert st.trace_ms > 0 and st.grid_blocks > 0 and st.block_threads == 256 and st.lds_bytes > 0
 
 
+def test_second_launch_on_another_stream_waits_for_the_checkpoints():
+    """AO count 2: a pixel is two items, the second starts from an RNG checkpoint.  The first launch computes the table on
+    stream A; the second, on stream B, reuses it behind the plan's checkpoint event.  No host synchronisation in between.  (B is
+    ordered behind A on the device: the plan's launch buffers serve one launch at a time.)"""
+    import torch
+    import pine_amd as pa
+    name = "cbox_ragged_45x37_s16"
+    want, spp = fixture(name)
+    assert spp >= 2
+    plan = pa.Plan(ao_scene(name), ao_sampler(name), 1, integrator="ao")
+    assert plan.device_bytes()[1] > 0
+    a, b = torch.cuda.Stream(), torch.cuda.Stream()
+    films = [torch.full(want.shape, -1.0, dtype=torch.float32, device="cuda") for _ in range(2)]
+    torch.cuda.synchronize()  # (the fills ran on the current stream)
+    plan.launch(films[0].data_ptr(), a.cuda_stream)
+    b.wait_stream(a)
+    plan.launch(films[1].data_ptr(), b.cuda_stream)
+    a.synchronize()
+    b.synchronize()
+    plan.check()
+    for i, film in enumerate(films):
+        assert_bit_equal(film.cpu().numpy(), want, f"{name}: film {i + 1} of two streams")
+
+
 def test_refusals():
     import torch
     import pine_amd as pa

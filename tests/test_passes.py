@@ -401,6 +401,33 @@ def test_pass_protocol(monkeypatch):
 
 
 @pytest.mark.gpu
+def test_one_pass_plan_reuses_its_checkpoints_on_another_stream(monkeypatch):
+    """A plan of one pass computes its RNG checkpoints in the first launch (stream A) and keeps them; the second launch, on
+    stream B with no host synchronisation in between, reuses the table behind the plan's checkpoint event.  (B is ordered behind
+    A on the device: the plan's launch buffers serve one launch at a time.)"""
+    import torch
+    import pine_amd as pa
+    monkeypatch.delenv("PINE_GPU_KERNEL", raising=False)
+    name = "cbox_committed_ragged_45x37_s8_d3"
+    ref, ps, spp, depth = load_film(name)
+    plan = pa.Plan(film_scene(name), spp, depth, specialize=False)
+    assert plan.pass_count == 1
+    assert plan.device_bytes()[1] > 0, "the plan uses no checkpoints: this test would check nothing"
+    a, b = torch.cuda.Stream(), torch.cuda.Stream()
+    films = [torch.full(ref.shape, -1.0, dtype=torch.float32, device="cuda") for _ in range(2)]
+    torch.cuda.synchronize()  # (the fills ran on the current stream)
+    plan.launch(films[0].data_ptr(), a.cuda_stream)
+    b.wait_stream(a)
+    plan.launch(films[1].data_ptr(), b.cuda_stream)
+    a.synchronize()
+    b.synchronize()
+    plan.check()
+    plan.close()
+    for i, film in enumerate(films):
+        assert_bit_equal(film.cpu().numpy(), ref, f"{name}: film {i + 1} of two streams")
+
+
+@pytest.mark.gpu
 def test_a_bailed_out_pass_fails_check_and_stats(monkeypatch):
     """PINE_GPU_FLAG_DEBUG_FORCE_BAIL (the existing test hook) in pass 0 of a plan with passes: check() and stats() fail."""
     import torch
