@@ -513,6 +513,55 @@ int pine_gpu_guides_render_device(pine_gpu_scene*, const pine_gpu_render_params*
  * number.  Needs no GPU. */
 int pine_gpu_guides_variants(uint32_t* features, int cap);
 
+/* ---- Accel: batched ray queries ----------------------------------------------------------------
+ * Accel::build(scene), intersect(ray, it), hit(ray): src/pine/core/accel.h:10-25, as RTIntegrator::intersect / hit hand them on
+ * (src/pine/core/integrator.h:31-38) and CustomRayIntegrator exposes them to a user's radiance() (integrator.h:61-74,
+ * src/pine/core/interpreter.cpp:46-53).  Here a query is a batch: n rays in, n answers out, in device memory on the caller's stream
+ * or in host memory.  The traversal and the surface point are the path kernels' own: the answers are the reference's bit for bit,
+ * with Accel = BVH() (src/pine/impl/accel/bvh.cpp:497-548) or -- PINE_GPU_FLAG_ORDER_EMBREE -- EmbreeAccel()
+ * (src/pine/impl/accel/embree.cpp:144-165, :195-256).
+ *
+ * One ray is 8 floats: o[3], d[3], tmin, tmax (Ray, src/pine/core/ray.h:8-23).  The direction is used as given: it is not
+ * normalised and t is in units of d; tmin is honoured.  One hit record is 12 words (48 bytes):
+ *   0      f32  ray.tmax after the query        (miss: the tmax that came in, as the reference leaves it)
+ *   1      i32  geometry index, in add order    (miss: -1)
+ *   2      i32  triangle index within its mesh, -1 for every other shape (miss: -1)
+ *   3      i32  material index                  (miss: -1)
+ *   4-6    f32  it.p                            (miss: 0)
+ *   7-9    f32  it.n as the interaction carries it: not turned towards the ray, interpolated where the mesh has normals (miss: 0)
+ *   10-11  f32  it.uv                           (miss: 0)
+ * A ray with a non-finite word or a zero direction is answered without a fault; what the answer is, is unspecified.
+ *
+ * pine_gpu_accel_create (Accel::build, bvh.cpp:453-495): builds the scene's BVH if nobody has yet, uploads the scene's records to
+ * `device` and keeps them: a snapshot -- a geometry added to the scene later is not in an existing accel.  flags: 0 (pine's BVH
+ * order) or PINE_GPU_FLAG_ORDER_EMBREE (a hierarchy deeper than the per-ray stack of 192 entries fails here, as for plans);
+ * PINE_GPU_FLAG_FAST, _SPECIALIZE and _VERTEX_LOG are refused with a message, as is any other bit.  A scene no precompiled kernel
+ * variant covers is refused by name.  The scene needs no camera (only pine_gpu_accel_camera_rays_device does).  Fails if there is
+ * no GPU.  $PINE_GPU_ACCEL_VARIANT=<index> considers that kernel variant only (tests).
+ * An accel holds no mutable device state: queries on different streams, and from different threads, may run at once.
+ * pine_gpu_accel_destroy waits for the device when a query was ever launched, then gives the records back. */
+typedef struct pine_gpu_accel pine_gpu_accel;
+pine_gpu_accel* pine_gpu_accel_create(pine_gpu_scene*, int device, uint32_t flags);
+void pine_gpu_accel_destroy(pine_gpu_accel*);
+/* Accel::intersect (accel.h:22-24; bvh.cpp:513-548) for n rays: rays_dev -> n * 8 floats, hits_dev -> n * 12 words, DEVICE pointers,
+ * both 16-byte aligned (else the call fails; a row slice of either buffer keeps the alignment).  The two buffers must not overlap
+ * (not checked).  The launch is enqueued on `stream` (a hipStream_t, 0 = the default stream) and the call returns without
+ * synchronising.  n == 0: returns 0, nothing is launched; n < 0 or n > 2^31 - 1 fails.  Words behind the n-th record are not written. */
+int pine_gpu_accel_intersect_device(pine_gpu_accel*, const void* rays_dev, int64_t n, void* hits_dev, void* stream);
+/* Accel::hit (accel.h:16-18; bvh.cpp:497-511, embree.cpp:144-165) for n rays: occluded_dev -> n bytes, 1 where anything lies within
+ * [tmin, tmax), else 0.  rays_dev must be 16-byte aligned; the bytes need no alignment.  Otherwise as above. */
+int pine_gpu_accel_hit_device(pine_gpu_accel*, const void* rays_dev, int64_t n, void* occluded_dev, void* stream);
+/* ... on HOST arrays: upload, launch, wait, download. */
+int pine_gpu_accel_intersect(pine_gpu_accel*, const float* rays_host, int64_t n, void* hits_host);
+int pine_gpu_accel_hit(pine_gpu_accel*, const float* rays_host, int64_t n, uint8_t* occluded_host);
+/* The rays of DenoiseIntegrator's guide images (src/pine/impl/integrator/denoiser.cpp:13-23): camera.gen_ray((p + 0.5) / film_size,
+ * (0.5, 0.5)) (src/pine/core/camera.cpp:17-33) for every pixel of the film the scene's camera had at creation, row-major, tmin = 0,
+ * tmax = FLT_MAX: W * H * 8 floats to the 16-byte aligned DEVICE pointer rays_dev, enqueued on `stream`. */
+int pine_gpu_accel_camera_rays_device(pine_gpu_accel*, void* rays_dev, void* stream);
+/* out: the chosen kernel variant's feature word (F_* bits), its dynamic LDS bytes per workgroup, the film's W and H (0 0: the scene
+ * had no camera).  Needs no GPU call. */
+int pine_gpu_accel_info(pine_gpu_accel*, int32_t out[4]);
+
 /* The filter: an a-trous edge-avoiding wavelet filter (Dammertz et al. 2010) on albedo-demodulated colour; the definition is in
  * pine_amd/csrc/pine_denoise.h and DESIGN.md 4.12.  film / out: W*H float4 (rgb filtered, a kept); albedo / normal: W*H*3 floats,
  * the guide images above.  A pixel whose normal is (0, 0, 0) -- a miss -- is copied through and contributes to no other pixel.

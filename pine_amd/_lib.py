@@ -202,6 +202,14 @@ SIGNATURES = {
     "pine_gpu_guides_render": (C.c_int, [C.c_void_p, C.POINTER(RenderParams), c_f_p, c_f_p]),
     "pine_gpu_guides_render_device": (C.c_int, [C.c_void_p, C.POINTER(RenderParams), C.c_void_p, C.c_void_p, C.c_void_p]),
     "pine_gpu_guides_variants": (C.c_int, [C.POINTER(C.c_uint32), C.c_int]),
+    "pine_gpu_accel_create": (C.c_void_p, [C.c_void_p, C.c_int, C.c_uint32]),
+    "pine_gpu_accel_destroy": (None, [C.c_void_p]),
+    "pine_gpu_accel_intersect_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "pine_gpu_accel_hit_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "pine_gpu_accel_intersect": (C.c_int, [C.c_void_p, c_f_p, C.c_int64, C.c_void_p]),
+    "pine_gpu_accel_hit": (C.c_int, [C.c_void_p, c_f_p, C.c_int64, C.POINTER(C.c_uint8)]),
+    "pine_gpu_accel_camera_rays_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pine_gpu_accel_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "pine_gpu_denoise_params_default": (None, [C.POINTER(DenoiseParams)]),
     "pine_gpu_denoise": (C.c_int, [C.POINTER(DenoiseParams), C.c_int, C.c_int, c_f_p, c_f_p, c_f_p, c_f_p]),
     "pine_gpu_denoise_device": (C.c_int, [C.POINTER(DenoiseParams), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

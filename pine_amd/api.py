@@ -995,3 +995,140 @@ class DenoiseIntegrator:
         albedo, normal = guides(scene, device=max(int(self.params.get("device", 0)), 0))
         film.pixels = denoise(film.pixels, albedo, normal, **self.params)
         return film
+
+
+# ---- Accel: batched ray queries (src/pine/core/accel.h:10-25, core/integrator.h:31-38, :61-74) ----
+HIT_DTYPE = np.dtype([("t", "<f4"), ("geometry", "<i4"), ("triangle", "<i4"), ("material", "<i4"), ("p", "<f4", 3), ("n", "<f4", 3),
+                      ("uv", "<f4", 2)])
+assert HIT_DTYPE.itemsize == 48
+
+
+class AccelHits:
+    """What Accel.intersect returns for a torch tensor of rays: `records`, an (N, 12) float32 tensor on the rays' device
+    (include/pine_gpu.h has the layout), and views of its columns -- t, geometry, triangle, material (int32, -1 on a miss), p, n, uv."""
+
+    def __init__(self, records):
+        import torch
+        self.records = records
+        self.t = records[:, 0]
+        self.geometry = records[:, 1].view(torch.int32)
+        self.triangle = records[:, 2].view(torch.int32)
+        self.material = records[:, 3].view(torch.int32)
+        self.p = records[:, 4:7]
+        self.n = records[:, 7:10]
+        self.uv = records[:, 10:12]
+
+    def __len__(self):
+        return int(self.records.shape[0])
+
+
+def _is_torch_tensor(x):
+    return type(x).__module__.split(".")[0] == "torch" and hasattr(x, "data_ptr")
+
+
+def _check_rays(rays, device=None):
+    """The (N, 8) float32 rays of an Accel query: a C-contiguous numpy array, or a contiguous CUDA torch tensor on the accel's
+    device.  Anything else raises ValueError before anything is launched.  -> True for a torch tensor."""
+    if _is_torch_tensor(rays):
+        import torch
+        if rays.dtype != torch.float32:
+            raise ValueError(f"Accel: rays must be float32, not {rays.dtype}")
+        if rays.dim() != 2 or rays.shape[1] != 8:
+            raise ValueError(f"Accel: rays must have shape (N, 8), not {tuple(rays.shape)}")
+        if not rays.is_cuda:
+            raise ValueError("Accel: a torch tensor of rays must live on the GPU (pass a numpy array for host rays)")
+        if device is not None and rays.device.index != int(device):
+            raise ValueError(f"Accel: the rays are on {rays.device}, the accel on device {int(device)}")
+        if not rays.is_contiguous():
+            raise ValueError("Accel: rays must be contiguous")
+        return True
+    if not isinstance(rays, np.ndarray):
+        raise ValueError("Accel: rays must be a numpy array or a torch tensor")
+    if rays.dtype != np.float32:
+        raise ValueError(f"Accel: rays must be float32, not {rays.dtype}")
+    if rays.ndim != 2 or rays.shape[1] != 8:
+        raise ValueError(f"Accel: rays must have shape (N, 8), not {rays.shape}")
+    if not rays.flags["C_CONTIGUOUS"]:
+        raise ValueError("Accel: rays must be C-contiguous")
+    return False
+
+
+class Accel:
+    """Accel(scene): the scene's BVH on the device, answering batches of rays -- what a CustomRayIntegrator's radiance() gets as
+    intersect(ray, it) and hit(ray) (core/integrator.h:61-74).  One ray is a row of 8 float32: o, d, tmin, tmax; d is used as
+    given (t is in units of d).  order: "pine" -- Accel(BVH()); "embree" -- Accel(EmbreeAccel()).  The answers are the
+    reference's, bit for bit.  The accel is a snapshot of the scene at creation.  A context manager; close() frees the device
+    memory."""
+
+    def __init__(self, scene, order="pine", device=0):
+        self._h = None
+        self.device = int(device)
+        h = lib.pine_gpu_accel_create(scene._h, self.device, _order_flags(order))
+        if not h:
+            raise PineError("Accel: " + _lib.last_error())
+        self._h = C.c_void_p(h)
+        info = (C.c_int32 * 4)()
+        check(lib.pine_gpu_accel_info(self._h, info), "Accel")
+        self.kernel_features, self.lds_bytes, self.film_size = int(info[0]) & 0xFFFFFFFF, int(info[1]), (int(info[2]), int(info[3]))
+
+    def _handle(self):
+        if not self._h:
+            raise PineError("Accel: closed")
+        return self._h
+
+    def intersect(self, rays):
+        """Closest hits.  A numpy array in: a structured array of HIT_DTYPE out.  A CUDA tensor in: an AccelHits over a new
+        (N, 12) tensor on its device, enqueued on its current stream, nothing copied and nothing waited for."""
+        if _check_rays(rays, self.device):
+            import torch
+            out = torch.empty((rays.shape[0], 12), dtype=torch.float32, device=rays.device)
+            stream = C.c_void_p(torch.cuda.current_stream(rays.device).cuda_stream)
+            check(lib.pine_gpu_accel_intersect_device(self._handle(), C.c_void_p(rays.data_ptr()), rays.shape[0], C.c_void_p(out.data_ptr()), stream),
+                  "Accel.intersect")
+            return AccelHits(out)
+        out = np.zeros(rays.shape[0], dtype=HIT_DTYPE)
+        check(lib.pine_gpu_accel_intersect(self._handle(), rays.ctypes.data_as(_lib.c_f_p), rays.shape[0], out.ctypes.data_as(C.c_void_p)), "Accel.intersect")
+        return out
+
+    def hit(self, rays):
+        """Any hit within [tmin, tmax): an (N,) bool array for a numpy array, an (N,) uint8 tensor (0 or 1) for a CUDA tensor."""
+        if _check_rays(rays, self.device):
+            import torch
+            out = torch.empty((rays.shape[0],), dtype=torch.uint8, device=rays.device)
+            stream = C.c_void_p(torch.cuda.current_stream(rays.device).cuda_stream)
+            check(lib.pine_gpu_accel_hit_device(self._handle(), C.c_void_p(rays.data_ptr()), rays.shape[0], C.c_void_p(out.data_ptr()), stream), "Accel.hit")
+            return out
+        out = np.zeros(rays.shape[0], dtype=np.uint8)
+        check(lib.pine_gpu_accel_hit(self._handle(), rays.ctypes.data_as(_lib.c_f_p), rays.shape[0], out.ctypes.data_as(C.POINTER(C.c_uint8))), "Accel.hit")
+        return out.view(np.bool_)
+
+    def camera_rays(self, tensor=False):
+        """The (H * W, 8) pixel-centre rays of the scene's camera, row-major: camera.gen_ray((p + 0.5) / film_size, (0.5, 0.5)),
+        DenoiseIntegrator's guide rays (denoiser.cpp:13-23).  tensor=True: a CUDA tensor on the accel's device (written on the
+        current stream); else a numpy array."""
+        import torch
+        w, h = self.film_size
+        if w * h == 0:
+            raise PineError("Accel.camera_rays: scene has no camera")
+        dev = torch.device("cuda", self.device)
+        rays = torch.empty((w * h, 8), dtype=torch.float32, device=dev)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        check(lib.pine_gpu_accel_camera_rays_device(self._handle(), C.c_void_p(rays.data_ptr()), stream), "Accel.camera_rays")
+        return rays if tensor else rays.cpu().numpy()
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib.pine_gpu_accel_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

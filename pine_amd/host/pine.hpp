@@ -424,6 +424,52 @@ class DenoiseIntegrator {
   DenoiseParams params_;
 };
 
+// Accel accel(scene, BVH{} | Embree{}): the scene's accel answering batches of rays (src/pine/core/accel.h:10-25) -- what
+// RTIntegrator::intersect / hit hand to a CustomRayIntegrator's radiance() (core/integrator.h:31-38, :61-74).  A snapshot of
+// the scene at construction.  BVH{}: Accel(BVH()); Embree{}: Accel(EmbreeAccel()), the reference's default.
+struct BVH {};
+struct Embree {};
+struct Ray {  // ray.h:8-23; d is used as given: t is in units of d
+  vec3 o, d;
+  float tmin = 0.0f, tmax = 3.402823466e+38f;
+};
+struct Interaction {  // one hit record (include/pine_gpu.h): on a miss t is the ray's tmax as it came, the indices are -1, the rest 0
+  float t;
+  int32_t geometry, triangle, material;
+  float p[3], n[3], uv[2];
+  bool hit() const { return geometry >= 0; }
+};
+static_assert(sizeof(Ray) == 32 && sizeof(Interaction) == 48, "the layouts of pine_gpu_accel_intersect");
+class Accel {
+ public:
+  Accel(Scene& scene, BVH = BVH{}, int device = 0) : h_(pine_gpu_accel_create(scene.handle(), device, 0)) { created(); }
+  Accel(Scene& scene, Embree, int device = 0) : h_(pine_gpu_accel_create(scene.handle(), device, PINE_GPU_FLAG_ORDER_EMBREE)) { created(); }
+  ~Accel() { pine_gpu_accel_destroy(h_); }
+  Accel(const Accel&) = delete;
+  Accel& operator=(const Accel&) = delete;
+  // host arrays: upload, query, wait, download
+  void intersect(const Ray* rays, int64_t n, Interaction* out) const {
+    check(pine_gpu_accel_intersect(h_, reinterpret_cast<const float*>(rays), n, out), "Accel::intersect");
+  }
+  void hit(const Ray* rays, int64_t n, uint8_t* occluded) const { check(pine_gpu_accel_hit(h_, reinterpret_cast<const float*>(rays), n, occluded), "Accel::hit"); }
+  // 16-byte aligned device pointers, enqueued on `stream` (a hipStream_t), nothing waited for
+  void intersect_device(const void* rays_dev, int64_t n, void* hits_dev, void* stream = nullptr) const {
+    check(pine_gpu_accel_intersect_device(h_, rays_dev, n, hits_dev, stream), "Accel::intersect_device");
+  }
+  void hit_device(const void* rays_dev, int64_t n, void* occluded_dev, void* stream = nullptr) const {
+    check(pine_gpu_accel_hit_device(h_, rays_dev, n, occluded_dev, stream), "Accel::hit_device");
+  }
+  // W * H pixel-centre rays of the scene's camera, row-major (denoiser.cpp:13-23), to device memory
+  void camera_rays_device(void* rays_dev, void* stream = nullptr) const { check(pine_gpu_accel_camera_rays_device(h_, rays_dev, stream), "Accel::camera_rays_device"); }
+  pine_gpu_accel* handle() const { return h_; }
+
+ private:
+  void created() const {
+    if (!h_) throw Error(std::string("Accel: ") + pine_gpu_last_error());
+  }
+  pine_gpu_accel* h_;
+};
+
 inline float get_progress() { return pine_gpu_progress(); }
 
 // load(scene, "file.glb" [, mat4]) (fileio.cpp:584-589): glTF import -- every mesh primitive with its material, and the

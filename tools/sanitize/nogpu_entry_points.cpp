@@ -53,6 +53,17 @@ pine_gpu_plan* pine_gpu_plan_create_passes(pine_gpu_scene*, const pine_gpu_rende
 int pine_gpu_guides_render(pine_gpu_scene*, const pine_gpu_render_params*, float*, float*) { return fail(); }
 int pine_gpu_guides_render_device(pine_gpu_scene*, const pine_gpu_render_params*, void*, void*, void*) { return fail(); }
 int pine_gpu_guides_variants(uint32_t*, int) { return fail(); }
+pine_gpu_accel* pine_gpu_accel_create(pine_gpu_scene*, int, uint32_t) {
+  fail();
+  return nullptr;
+}
+void pine_gpu_accel_destroy(pine_gpu_accel*) {}
+int pine_gpu_accel_intersect_device(pine_gpu_accel*, const void*, int64_t, void*, void*) { return fail(); }
+int pine_gpu_accel_hit_device(pine_gpu_accel*, const void*, int64_t, void*, void*) { return fail(); }
+int pine_gpu_accel_intersect(pine_gpu_accel*, const float*, int64_t, void*) { return fail(); }
+int pine_gpu_accel_hit(pine_gpu_accel*, const float*, int64_t, uint8_t*) { return fail(); }
+int pine_gpu_accel_camera_rays_device(pine_gpu_accel*, void*, void*) { return fail(); }
+int pine_gpu_accel_info(pine_gpu_accel*, int32_t*) { return fail(); }
 // (the filter's host-thread build, device = -1, is the real thing: pine_denoise_host.h)
 void pine_gpu_denoise_params_default(pine_gpu_denoise_params* prm) {
   if (prm) *prm = pine_gpu_denoise_params{5, 7, PINE_GPU_DENOISE_SIGMA_COLOR, PINE_GPU_DENOISE_SIGMA_ALBEDO, PINE_GPU_DENOISE_EPS_ALBEDO, 0};
