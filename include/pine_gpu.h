@@ -770,6 +770,17 @@ int pine_gpu_test_kernel_variants(int kind, uint32_t* features, int32_t* ctx, in
  * has been destroyed or was never created holds none.  out[1]: the blocks the device memory pool keeps for the next plan
  * (pine_gpu_release_cached_memory frees them).  Reads two counters and launches nothing; returns 0. */
 int pine_gpu_test_live_device_blocks(int64_t out[2]);
+/* The poison mode of device memory, a test mode: with $PINE_GPU_TEST_POISON=<32-bit hex word> set -- read at every allocation --
+ * every device block the library allocates (fresh or recycled by the pool, the pool's slack behind the requested bytes included)
+ * and every pinned host block is filled with that word before anything else touches it, and the fill is complete on the device
+ * before the allocation returns.  A value that is no 32-bit hex word (hex digits, an optional 0x) fails every allocation.  Unset,
+ * nothing changes.  out[0]: the blocks poisoned by this process so far, out[1]: their
+ * bytes.  Reads two counters and launches nothing; returns 0. */
+int pine_gpu_test_poison_stats(int64_t out[2]);
+/* One block of `bytes` bytes (> 0) on `device`, taken from the plans' memory pool (from_pool != 0) or from plain hipMalloc the way
+ * every block of the library is, with nothing written to it: its first `bytes` bytes are copied to out_words ((bytes + 3) / 4
+ * words).  Under $PINE_GPU_TEST_POISON they hold the word.  Launches nothing; 0, or -1 with the last error set. */
+int pine_gpu_test_poison_probe(int device, int from_pool, int64_t bytes, uint32_t* out_words);
 
 /* ---- Film (host side, after the hot path) ----------------------------------------------------
  * Film::finalize + tone mapping + to_uint8_array: src/pine/core/film.cpp:12-27,66-68,

@@ -251,6 +251,8 @@ SIGNATURES = {
                                           C.POINTER(C.c_int64), C.POINTER(C.c_uint32), C.c_int]),
     "pine_gpu_test_kernel_variants": (C.c_int, [C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int]),
     "pine_gpu_test_live_device_blocks": (C.c_int, [C.POINTER(C.c_int64)]),
+    "pine_gpu_test_poison_stats": (C.c_int, [C.POINTER(C.c_int64)]),
+    "pine_gpu_test_poison_probe": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_uint32)]),
     "pine_gpu_film_finalize_u8": (C.c_int, [c_f_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8)]),
 }
 for _name, (_res, _args) in SIGNATURES.items():

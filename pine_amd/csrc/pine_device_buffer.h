@@ -24,6 +24,36 @@ inline int hip_launch_check(const char* what) {
 
 enum BlockSource : bool { kFromMalloc = false, kFromPool = true };
 
+// Test mode: $PINE_GPU_TEST_POISON=<32-bit hex word> fills every block handed out with that word before the caller sees it
+// (tests/test_poisoned_memory.py; DESIGN.md 4.3.1 lists every block and who writes it first).  Read at every allocation, so
+// that a test can switch it inside one process; unset, nothing here makes a HIP call.
+inline std::atomic<long long> g_poisoned_blocks{0}, g_poisoned_bytes{0};  // (pine_gpu_test_poison_stats)
+// 0: unset (or empty); 1: `word` is the variable's value; -1: the value is no 32-bit hex word (hex digits only, an optional 0x in
+// front) -- the allocation then fails: a value that parsed as 0 would "poison" with the zeros the mode exists to avoid.
+inline int poison_word(uint32_t& word) {
+  const char* e = getenv("PINE_GPU_TEST_POISON");
+  if (!e || !*e) return 0;
+  char* end = nullptr;
+  const unsigned long long v = isxdigit((unsigned char)*e) ? strtoull(e, &end, 16) : 0;
+  if (!end || end == e || *end || v > 0xffffffffull) return -1;
+  word = uint32_t(v);
+  return 1;
+}
+inline int bad_poison_word(const char* what) {
+  if (what) set_error(std::string(what) + ": PINE_GPU_TEST_POISON is not a 32-bit hex word");
+  return -1;
+}
+// `bytes` of device memory at q filled with `word`: whole words, then the last 1 - 3 bytes with its low byte.  Complete on
+// the device when it returns: plans launch on the caller's streams, which a fill on the null stream does not order against.
+inline hipError_t poison_device_block(void* q, size_t bytes, uint32_t word) {
+  const size_t words = bytes / 4, tail = bytes % 4;
+  hipError_t e = words ? hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(q), int(word), words) : hipSuccess;
+  if (e == hipSuccess && tail) e = hipMemset(static_cast<char*>(q) + words * 4, int(word & 0xff), tail);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) g_poisoned_blocks++, g_poisoned_bytes += (long long)bytes;
+  return e;
+}
+
 // One device block of T, move-only.  It remembers the device it was allocated on and where it came from (DevicePool, or plain
 // hipMalloc) and returns it the same way with that device current; the caller's current device is left as it was.
 template <class T>
@@ -62,6 +92,9 @@ class DeviceBuffer {
   int alloc(size_t n, const char* what) { return alloc_bytes(n * sizeof(T), what); }
   int alloc_bytes(size_t bytes, const char* what) {
     reset();
+    uint32_t word = 0;
+    const int poison = poison_word(word);
+    if (poison < 0) return bad_poison_word(what);
     void* q = nullptr;
     const hipError_t e = source_ == kFromPool ? DevicePool::get().alloc(&q, bytes) : hipMalloc(&q, bytes);
     if (e != hipSuccess) return hip_error(what, e);
@@ -69,6 +102,13 @@ class DeviceBuffer {
     p_ = static_cast<T*>(q);
     (void)hipGetDevice(&device_);
     g_live_handles++;
+    if (poison) {  // a pooled block over its rounded size: the slack behind `bytes` is memory a kernel could read
+      const size_t block = source_ == kFromPool ? DevicePool::get().block_bytes(q, bytes) : bytes;
+      if (const hipError_t pe = poison_device_block(q, block, word)) {
+        reset();
+        return hip_error(what, pe);
+      }
+    }
     return 0;
   }
   // the first n elements from / to the host
@@ -110,9 +150,18 @@ inline int create_stream(StreamOwner& out, unsigned flags, const char* what) {
 }
 template <class T>
 int alloc_pinned(PinnedOwner<T>& out, size_t n, unsigned flags, const char* what) {
+  uint32_t word = 0;
+  const int poison = poison_word(word);
+  if (poison < 0) return bad_poison_word(what);
   void* q = nullptr;
   if (const hipError_t err = hipHostMalloc(&q, n * sizeof(T), flags)) return hip_error(what, err);
   out.reset(static_cast<T*>(q)), g_live_handles++;
+  if (poison) {
+    unsigned char* b = static_cast<unsigned char*>(q);  // (whole words, then the word's low byte, as on the device)
+    const size_t bytes = n * sizeof(T), whole = bytes & ~size_t(3);
+    for (size_t i = 0; i < bytes; i++) b[i] = (unsigned char)(i < whole ? word >> (8 * (i % 4)) : word);
+    g_poisoned_blocks++, g_poisoned_bytes += (long long)bytes;
+  }
   return 0;
 }
 

@@ -8,7 +8,9 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cctype>
 #include <cstdio>
+#include <cstdlib>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -110,7 +112,9 @@ static int effective_spp(int spp) {  // BlueSobolSampler ctor sampler.cpp:115-12
 // what a ONE-SHOT render (pine_gpu_path_render: create, launch, destroy -- what PathIntegrator::render does) spends outside
 // its kernels.  A destroyed plan's blocks of 256 KB and more go to a per-device free list instead and the next plan takes
 // the smallest one that fits within 25 %; at most $PINE_GPU_POOL_MB (default 16 384; 0: no pool) are kept,
-// pine_gpu_release_cached_memory() frees them.  No kernel reads a buffer before writing it (hipMalloc does not clear either).
+// pine_gpu_release_cached_memory() frees them.  No kernel reads a buffer before writing it (hipMalloc does not clear either):
+// DESIGN.md 4.3.1 lists every block with its first writer and first reader, and tests/test_poisoned_memory.py runs every kernel
+// family on blocks that PINE_GPU_TEST_POISON (pine_device_buffer.h) has filled with a word no kernel wrote.
 inline thread_local size_t g_alloc_tally = 0;  // bytes asked of DevicePool::alloc by this thread (plan_build: pine_gpu_plan_device_bytes)
 struct DevicePool {
   struct Block {
@@ -165,6 +169,12 @@ struct DevicePool {
       live[*out] = Block{*out, want, device};
     }
     return e;
+  }
+  // the size of the block alloc handed out for `bytes`: the rounded size of a pooled one (PINE_GPU_TEST_POISON fills all of it)
+  size_t block_bytes(void* p, size_t bytes) {
+    std::lock_guard<std::mutex> lock(mu);
+    auto it = live.find(p);
+    return it != live.end() ? it->second.bytes : bytes;
   }
   void free(void* p) {
     if (!p) return;

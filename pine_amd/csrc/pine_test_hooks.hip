@@ -1134,4 +1134,28 @@ int pine_gpu_test_live_device_blocks(int64_t out[2]) {
   return 0;
 }
 
+// PINE_GPU_TEST_POISON (pine_device_buffer.h): the blocks and bytes this process has poisoned so far, device and pinned ones
+// together.  Reads two counters; launches nothing.
+int pine_gpu_test_poison_stats(int64_t out[2]) {
+  if (!out) {
+    set_error("null argument");
+    return -1;
+  }
+  out[0] = g_poisoned_blocks.load(), out[1] = g_poisoned_bytes.load();
+  return 0;
+}
+
+// One block of `bytes` bytes on `device`, from the pool (from_pool != 0) or from hipMalloc, as DeviceBuffer hands it out: nothing
+// is written to it, its first `bytes` bytes are downloaded to out_words ((bytes + 3) / 4 words; the bytes behind `bytes` in the
+// last word are left as they were).  Launches nothing.
+int pine_gpu_test_poison_probe(int device, int from_pool, int64_t bytes, uint32_t* out_words) {
+  if (!out_words || bytes <= 0) {
+    set_error("pine_gpu_test_poison_probe: null argument or no bytes");
+    return -1;
+  }
+  if (const hipError_t e = hipSetDevice(device)) return hip_error(__func__, e);
+  DeviceBuffer<uint8_t> d(from_pool ? kFromPool : kFromMalloc);
+  return d.alloc_bytes(size_t(bytes), __func__) || d.download(reinterpret_cast<uint8_t*>(out_words), size_t(bytes), __func__) ? -1 : 0;
+}
+
 }  // extern "C"

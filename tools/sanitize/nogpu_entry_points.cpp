@@ -124,6 +124,8 @@ int pine_gpu_test_kernel_variants(int, uint32_t*, int32_t*, int32_t*, int) { ret
 int pine_gpu_test_box_slabs(const float*, const float*, int64_t, uint32_t*) { return fail(); }
 int pine_gpu_test_short_div(int, int, int, const uint32_t*, uint32_t, uint32_t, uint32_t, int64_t, int64_t*, uint32_t*, int) { return fail(); }
 int pine_gpu_test_live_device_blocks(int64_t*) { return fail(); }
+int pine_gpu_test_poison_stats(int64_t*) { return fail(); }
+int pine_gpu_test_poison_probe(int, int, int64_t, uint32_t*) { return fail(); }
 int64_t pine_gpu_test_frame_table(pine_gpu_scene*, pine_gpu_plan*, int, float*, float*, int64_t, int32_t*, int64_t, const float*, int64_t, int32_t*) {
   return fail();
 }
