@@ -531,6 +531,20 @@ int pine_gpu_guides_variants(uint32_t* features, int cap);
  *   7-9    f32  it.n as the interaction carries it: not turned towards the ray, interpolated where the mesh has normals (miss: 0)
  *   10-11  f32  it.uv                           (miss: 0)
  * A ray with a non-finite word or a zero direction is answered without a fault; what the answer is, is unspecified.
+ * Everything else is the reference's answer, odd or not (the _edge.npz files of tests/golden hold it for tmin > 0, scaled and axis-parallel
+ * directions with signed zeros, origins on a surface and spans that end exactly at a hit).  In particular:
+ *   - the ends of [tmin, tmax] belong to the span or not shape by shape, and differently in intersect and hit: Plane and Sphere
+ *     accept t == tmin and t == tmax in intersect and refuse both in hit; a Disk's intersect accepts both, its hit t == tmin only;
+ *     a Triangle's (and a mesh's under pine's BVH) intersect refuses both and its hit accepts both; Rect refuses both in both;
+ *     Cylinder, Cone, Line, Box and the transformed Box decide alike in both;
+ *   - the reported t can lie outside the span: a transformed Box reports the box's far t where the near one is not above tmin, in
+ *     units of the NORMALISED direction while tmin / tmax stay in units of d; a Cylinder's second root is not compared with tmin;
+ *     a Sphere's t ignores the length of d.  A scaled direction therefore hits such shapes where the reference does, not where
+ *     geometry would;
+ *   - a ray that lies in a Plane, or runs along a Cylinder's axis, divides 0 by 0: it "hits" with t = NaN, and no box of the
+ *     hierarchy is entered after that.
+ * Unspecified under PINE_GPU_FLAG_ORDER_EMBREE: a negative tmin.  Embree requires tnear >= 0, clamps it to 0 for its node boxes
+ * and not in its triangle test, so a hit behind the origin depends on which leaves its own hierarchy reaches.
  *
  * pine_gpu_accel_create (Accel::build, bvh.cpp:453-495): builds the scene's BVH if nobody has yet, uploads the scene's records to
  * `device` and keeps them: a snapshot -- a geometry added to the scene later is not in an existing accel.  flags: 0 (pine's BVH
@@ -548,8 +562,8 @@ void pine_gpu_accel_destroy(pine_gpu_accel*);
  * (not checked).  The launch is enqueued on `stream` (a hipStream_t, 0 = the default stream) and the call returns without
  * synchronising.  n == 0: returns 0, nothing is launched; n < 0 or n > 2^31 - 1 fails.  Words behind the n-th record are not written. */
 int pine_gpu_accel_intersect_device(pine_gpu_accel*, const void* rays_dev, int64_t n, void* hits_dev, void* stream);
-/* Accel::hit (accel.h:16-18; bvh.cpp:497-511, embree.cpp:144-165) for n rays: occluded_dev -> n bytes, 1 where anything lies within
- * [tmin, tmax), else 0.  rays_dev must be 16-byte aligned; the bytes need no alignment.  Otherwise as above. */
+/* Accel::hit (accel.h:16-18; bvh.cpp:497-511, embree.cpp:144-165) for n rays: occluded_dev -> n bytes, 1 where a shape's hit() finds
+ * something in the span, else 0 -- the ends count as each shape's hit() decides, which is not always as its intersect() does (above).  rays_dev must be 16-byte aligned; the bytes need no alignment.  Otherwise as above. */
 int pine_gpu_accel_hit_device(pine_gpu_accel*, const void* rays_dev, int64_t n, void* occluded_dev, void* stream);
 /* ... on HOST arrays: upload, launch, wait, download. */
 int pine_gpu_accel_intersect(pine_gpu_accel*, const float* rays_host, int64_t n, void* hits_host);
