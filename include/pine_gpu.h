@@ -576,6 +576,68 @@ int pine_gpu_accel_camera_rays_device(pine_gpu_accel*, void* rays_dev, void* str
  * had no camera).  Needs no GPU call. */
 int pine_gpu_accel_info(pine_gpu_accel*, int32_t out[4]);
 
+/* ---- Shader: batched path-vertex shading queries on device buffers ----
+ * One vertex of PathIntegrator::radiance() (src/pine/impl/integrator/path.cpp:42-123, without the medium lines) for n paths that
+ * live in the CALLER's device buffers -- what a CustomRayIntegrator's radiance() gets besides the ray queries: the scene's
+ * materials, the light sampler and the sampler (core/integrator.h:27-74).  With an accel,
+ *   begin -> intersect -> vertex -> hit(shadow rays) -> intersect(next rays) -> vertex -> ... -> fold -> resolve
+ * is a complete path tracer whose every ray, hit and vertex record the caller sees; run over all paths at every level it gives
+ * PathIntegrator's film bit for bit (an accel of either order: the shader shades whatever hits it is given).
+ *
+ * A ray is Accel's: 8 floats, o[3] d[3] tmin tmax.  The null ray -- where a vertex has no shadow or next ray -- is o = 0,
+ * d = (0, 0, 1), tmin = 0, tmax = -1: finite, answered at once, its answer never read.
+ * A path state is 8 words (32 bytes):
+ *   0-3  the pixel's RNG (two u64)          4  sample index (bits 0-11) | Vertex::length (21-26) | diffuse_length > 0 (27) | is_delta (28)
+ *   5    px | py << 16                      6  the sampler's dimension counter (i32)         7  0: live, 1: done
+ * A vertex record is 16 words (64 bytes):
+ *   0     i32  kind: -1 none (the path was done before), 0 the ray left the scene, 1 it met an emissive surface, 2 the path-length
+ *              limit, 3 a shaded vertex
+ *   1     i32  Vertex::length                2  u32  flags: 1 has_shadow_ray, 2 has_next_ray, 4 the light pdf is there
+ *   3     f32  kinds 0, 1: the pdf of having picked the vertex by light sampling, -1: none
+ *   4-6   f32  kinds 0, 1: the returned Lo   7  f32  cosine
+ *   8-10  f32  kind 3: the direct term, UNSHADOWED             11  f32  bs.pdf
+ *   12-14 f32  bs.f                          15 f32  bs.is_delta (0 or 1)
+ * The log of pine_gpu_shader_fold_device is 16 floats per vertex, the words of pine_gpu_plan_vertex_log:
+ *   kind | length | direct term after visibility (3) | bs.f (3) | cosine | bs.pdf | is_delta | mis | light pdf (-1: none) | Lo (3)
+ *
+ * pine_gpu_shader_create reads spp, sampler, max_path_length and device of the parameters; the effective spp follows the plan's
+ * rules (BlueSampler: rounded up to a power of two, at most 256; SobolSampler / HaltonSampler: as given, at most 4096).  It
+ * uploads the scene's records -- a snapshot -- and keeps them.  Refused with a message, nothing approximated: a scene with a
+ * Subsurface material (by name: its BSSRDF walk traverses inside the vertex), any flag bit (PINE_GPU_FLAG_ORDER_EMBREE too: the
+ * order is the Accel's business), shard_world != 1, a scene no kernel variant covers, a machine without a GPU.  The scene needs
+ * no camera (only pine_gpu_shader_begin_device does).  $PINE_GPU_SHADER_VARIANT=<index> considers that kernel variant only (tests).
+ * A shader holds no mutable device state: calls on different streams may run at once.  pine_gpu_shader_destroy waits for the
+ * device when anything was ever launched.
+ *
+ * Every _device call enqueues on `stream` (a hipStream_t, 0 = the default stream) and returns without synchronising.  Every
+ * buffer is a 16-byte aligned DEVICE pointer (the occlusion bytes need no alignment).  n == 0 returns 0 and launches nothing;
+ * n < 0 or n > 2^31 - 1 fails.  Every word of every output of the n paths is written; nothing behind them is. */
+typedef struct pine_gpu_shader pine_gpu_shader;
+pine_gpu_shader* pine_gpu_shader_create(pine_gpu_scene*, const pine_gpu_render_params*);
+void pine_gpu_shader_destroy(pine_gpu_shader*);
+/* out: bytes of a path state, bytes of a vertex record, floats of a ray, floats of a log entry.  Needs no GPU. */
+int pine_gpu_shader_layout(int32_t out[4]);
+/* out: the film's W and H (0 0: no camera), the effective spp, max_path_length, the chosen kernel variant's index, its feature
+ * word (F_* bits), its dynamic LDS bytes per workgroup, the sampler kind.  Needs no GPU call. */
+int pine_gpu_shader_info(pine_gpu_shader*, int32_t out[8]);
+/* Sample `sample` (in [0, spp)) of every pixel of the film starts: W * H paths in row order.  Sample 0 seeds the pixel's RNG as
+ * Sampler::start_pixel does; a later sample goes on from the RNG the state holds, as left by sample - 1 -- the RNG is serial over a
+ * pixel's samples, so a caller renders them in order.  Writes every state (live, Vertex::first_vertex()) and the camera rays. */
+int pine_gpu_shader_begin_device(pine_gpu_shader*, int sample, void* states_dev, void* rays_dev, void* stream);
+/* One radiance() invocation per path: rays_dev[i] is the ray that led to the vertex, hits_dev[i] Accel's 12-word answer for it.
+ * Writes the record, the shadow ray and the next ray of every path and advances its state.  A path whose state says done gets a
+ * "none" record and null rays and keeps its state byte for byte: all n paths may be launched at every level. */
+int pine_gpu_shader_vertex_device(pine_gpu_shader*, const void* rays_dev, const void* hits_dev, int64_t n, void* states_dev, void* records_dev,
+                                  void* shadow_rays_dev, void* next_rays_dev, void* stream);
+/* The backward fold of one sample (path.cpp:114-121): records_dev is levels x n records, occluded_dev levels x n bytes (what
+ * Accel's hit answered for the shadow rays; read only where a record has one), level-major, 1 <= levels <= max_path_length.
+ * sum_dev: n float4 -- path i adds its radiance to xyz (the running sum in sample order; sample 0 overwrites), w is the sample
+ * count.  log_dev_or_null: levels x n x 16 floats, zeros past a path's end. */
+int pine_gpu_shader_fold_device(pine_gpu_shader*, const void* records_dev, const void* occluded_dev, int levels, int64_t n, int sample, void* sum_dev,
+                                void* log_dev_or_null, void* stream);
+/* film_dev[i] = (sum_dev[i].xyz / spp, 1), the division of PathIntegrator's film. */
+int pine_gpu_shader_resolve_device(pine_gpu_shader*, const void* sum_dev, int64_t n, void* film_dev, void* stream);
+
 /* The filter: an a-trous edge-avoiding wavelet filter (Dammertz et al. 2010) on albedo-demodulated colour; the definition is in
  * pine_amd/csrc/pine_denoise.h and DESIGN.md 4.12.  film / out: W*H float4 (rgb filtered, a kept); albedo / normal: W*H*3 floats,
  * the guide images above.  A pixel whose normal is (0, 0, 0) -- a miss -- is copied through and contributes to no other pixel.

@@ -210,7 +210,15 @@ SIGNATURES = {
     "pine_gpu_accel_hit": (C.c_int, [C.c_void_p, c_f_p, C.c_int64, C.POINTER(C.c_uint8)]),
     "pine_gpu_accel_camera_rays_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "pine_gpu_accel_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
-    "pine_gpu_denoise_params_default": (None, [C.POINTER(DenoiseParams)]),
+    "pine_gpu_shader_create": (C.c_void_p, [C.c_void_p, C.POINTER(RenderParams)]),
+    "pine_gpu_shader_destroy": (None, [C.c_void_p]),
+    "pine_gpu_shader_layout": (C.c_int, [C.POINTER(C.c_int32)]),
+    "pine_gpu_shader_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "pine_gpu_shader_begin_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pine_gpu_shader_vertex_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pine_gpu_shader_fold_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pine_gpu_shader_resolve_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "pine_gpu_denoise_params_default":(None, [C.POINTER(DenoiseParams)]),
     "pine_gpu_denoise": (C.c_int, [C.POINTER(DenoiseParams), C.c_int, C.c_int, c_f_p, c_f_p, c_f_p, c_f_p]),
     "pine_gpu_denoise_device": (C.c_int, [C.POINTER(DenoiseParams), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pine_gpu_plan_debug_sections":(C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),

@@ -1053,6 +1053,24 @@ def _check_rays(rays, device=None):
     return False
 
 
+def _check_tensor(t, what, dtype, shape, device=None):
+    """A contiguous CUDA torch tensor of `dtype` and `shape` (None in a place: any size) on `device`, or ValueError -- before
+    anything is launched."""
+    if not _is_torch_tensor(t):
+        raise ValueError(f"{what} must be a torch tensor, not {type(t).__name__}")
+    if t.dtype != dtype:
+        raise ValueError(f"{what} must be {dtype}, not {t.dtype}")
+    if t.dim() != len(shape) or any(want is not None and int(have) != int(want) for have, want in zip(t.shape, shape)):
+        raise ValueError(f"{what} must have shape {tuple('N' if d is None else int(d) for d in shape)}, not {tuple(t.shape)}")
+    if not t.is_cuda:
+        raise ValueError(f"{what} must live on the GPU")
+    if device is not None and t.device.index != int(device):
+        raise ValueError(f"{what} are on {t.device}, not on device {int(device)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{what} must be contiguous")
+    return t
+
+
 class Accel:
     """Accel(scene): the scene's BVH on the device, answering batches of rays -- what a CustomRayIntegrator's radiance() gets as
     intersect(ray, it) and hit(ray) (core/integrator.h:61-74).  One ray is a row of 8 float32: o, d, tmin, tmax; d is used as
@@ -1076,12 +1094,16 @@ class Accel:
             raise PineError("Accel: closed")
         return self._h
 
-    def intersect(self, rays):
+    def intersect(self, rays, out=None):
         """Closest hits.  A numpy array in: a structured array of HIT_DTYPE out.  A CUDA tensor in: an AccelHits over a new
-        (N, 12) tensor on its device, enqueued on its current stream, nothing copied and nothing waited for."""
+        (N, 12) tensor on its device (or over `out`, such a tensor of the caller's), enqueued on its current stream, nothing
+        copied and nothing waited for."""
         if _check_rays(rays, self.device):
             import torch
-            out = torch.empty((rays.shape[0], 12), dtype=torch.float32, device=rays.device)
+            if out is None:
+                out = torch.empty((rays.shape[0], 12), dtype=torch.float32, device=rays.device)
+            else:
+                _check_tensor(out, "Accel: the hit records", torch.float32, (rays.shape[0], 12), self.device)
             stream = C.c_void_p(torch.cuda.current_stream(rays.device).cuda_stream)
             check(lib.pine_gpu_accel_intersect_device(self._handle(), C.c_void_p(rays.data_ptr()), rays.shape[0], C.c_void_p(out.data_ptr()), stream),
                   "Accel.intersect")
@@ -1090,11 +1112,15 @@ class Accel:
         check(lib.pine_gpu_accel_intersect(self._handle(), rays.ctypes.data_as(_lib.c_f_p), rays.shape[0], out.ctypes.data_as(C.c_void_p)), "Accel.intersect")
         return out
 
-    def hit(self, rays):
-        """Any hit within [tmin, tmax): an (N,) bool array for a numpy array, an (N,) uint8 tensor (0 or 1) for a CUDA tensor."""
+    def hit(self, rays, out=None):
+        """Any hit within [tmin, tmax): an (N,) bool array for a numpy array, an (N,) uint8 tensor (0 or 1) for a CUDA tensor
+        (a new one, or `out`, such a tensor of the caller's)."""
         if _check_rays(rays, self.device):
             import torch
-            out = torch.empty((rays.shape[0],), dtype=torch.uint8, device=rays.device)
+            if out is None:
+                out = torch.empty((rays.shape[0],), dtype=torch.uint8, device=rays.device)
+            else:
+                _check_tensor(out, "Accel: the occlusion bytes", torch.uint8, (rays.shape[0],), self.device)
             stream = C.c_void_p(torch.cuda.current_stream(rays.device).cuda_stream)
             check(lib.pine_gpu_accel_hit_device(self._handle(), C.c_void_p(rays.data_ptr()), rays.shape[0], C.c_void_p(out.data_ptr()), stream), "Accel.hit")
             return out
@@ -1132,3 +1158,214 @@ class Accel:
             self.close()
         except Exception:
             pass
+
+
+# ---- Shader: batched path-vertex shading queries (core/integrator.h:27-74, impl/integrator/path.cpp:42-123) ----
+# (pine_gpu_shader_layout reports the same: tests/test_shader.py)
+SHADER_STATE_WORDS, SHADER_RECORD_WORDS, SHADER_RAY_FLOATS, SHADER_LOG_FLOATS = 8, 16, 8, 16
+KIND_NONE, KIND_MISS, KIND_EMISSIVE, KIND_LIMIT, KIND_SHADED = -1, 0, 1, 2, 3
+RECORD_DTYPE = np.dtype([("kind", "<i4"), ("length", "<i4"), ("flags", "<u4"), ("light_pdf", "<f4"), ("lo", "<f4", 3), ("cosine", "<f4"),
+                         ("direct", "<f4", 3), ("pdf", "<f4"), ("f", "<f4", 3), ("is_delta", "<f4")])
+assert RECORD_DTYPE.itemsize == 4 * SHADER_RECORD_WORDS
+
+
+class ShaderRecords:
+    """What Shader.vertex writes: `records`, an (N, 16) float32 tensor (include/pine_gpu.h has the layout), and views of its
+    columns -- kind (int32: KIND_NONE / _MISS / _EMISSIVE / _LIMIT / _SHADED), length, flags (int32: 1 has_shadow_ray, 2
+    has_next_ray, 4 the light pdf is there), light_pdf, lo, cosine, direct (unshadowed), pdf, f, is_delta."""
+
+    def __init__(self, records):
+        import torch
+        self.records = records
+        self.kind = records[:, 0].view(torch.int32)
+        self.length = records[:, 1].view(torch.int32)
+        self.flags = records[:, 2].view(torch.int32)
+        self.light_pdf = records[:, 3]
+        self.lo = records[:, 4:7]
+        self.cosine = records[:, 7]
+        self.direct = records[:, 8:11]
+        self.pdf = records[:, 11]
+        self.f = records[:, 12:15]
+        self.is_delta = records[:, 15]
+
+    @property
+    def has_shadow_ray(self):
+        return (self.flags & 1) != 0
+
+    @property
+    def has_next_ray(self):
+        return (self.flags & 2) != 0
+
+    def __len__(self):
+        return int(self.records.shape[0])
+
+
+class Shader:
+    """Shader(scene, sampler, max_path_length): one vertex of PathIntegrator's radiance() for N paths at a time, on contiguous
+    CUDA torch tensors of the caller's -- on their device and the current stream, nothing copied and nothing waited for.  With an
+    Accel: begin -> intersect -> vertex -> hit -> intersect -> vertex ... -> fold -> resolve (WavefrontPathIntegrator is that
+    loop).  A pixel's samples are rendered in order: its RNG travels in the states.  A tensor of the wrong dtype, shape, device
+    or layout raises ValueError before anything is launched.  A snapshot of the scene at creation; a context manager."""
+
+    def __init__(self, scene, sampler, max_path_length, device=0, flags=0):
+        self._h = None
+        self.device = int(device)
+        prm = _lib.RenderParams(int(sampler.requested), int(max_path_length), self.device, 0, 1, 0, int(flags), getattr(sampler, "kind", 0))
+        h = lib.pine_gpu_shader_create(scene._h, C.byref(prm))
+        if not h:
+            raise PineError("Shader: " + _lib.last_error())
+        self._h = C.c_void_p(h)
+        info = (C.c_int32 * 8)()
+        check(lib.pine_gpu_shader_info(self._h, info), "Shader")
+        self.film_size, self.spp, self.max_path_length = (int(info[0]), int(info[1])), int(info[2]), int(info[3])
+        self.variant, self.kernel_features, self.lds_bytes = int(info[4]), int(info[5]) & 0xFFFFFFFF, int(info[6])
+
+    def _handle(self):
+        if not self._h:
+            raise PineError("Shader: closed")
+        return self._h
+
+    def _stream(self, t):
+        import torch
+        return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+
+    def _new(self, shape, like=None, dtype=None):
+        import torch
+        return torch.empty(shape, dtype=dtype or torch.float32, device=like.device if like is not None else torch.device("cuda", self.device))
+
+    def begin(self, sample, states=None, rays=None):
+        """Sample `sample` of every pixel starts: -> (states (W*H, 8) int32, rays (W*H, 8) float32), new tensors or the ones
+        given.  A sample after the first needs the states sample - 1 left."""
+        import torch
+        n = self.film_size[0] * self.film_size[1]
+        if n == 0:
+            raise PineError("Shader.begin: scene has no camera")
+        if states is None:
+            if int(sample) != 0:
+                raise ValueError("Shader.begin: a sample after the first goes on from the states of the sample before")
+            states = self._new((n, SHADER_STATE_WORDS), dtype=torch.int32)
+        _check_tensor(states, "Shader: the states", torch.int32, (n, SHADER_STATE_WORDS), self.device)
+        if rays is None:
+            rays = self._new((n, 8), states)
+        _check_tensor(rays, "Shader: the rays", torch.float32, (n, 8), self.device)
+        check(lib.pine_gpu_shader_begin_device(self._handle(), int(sample), C.c_void_p(states.data_ptr()), C.c_void_p(rays.data_ptr()), self._stream(states)),
+              "Shader.begin")
+        return states, rays
+
+    def vertex(self, rays, hits, states, records=None, shadow_rays=None, next_rays=None):
+        """One radiance() invocation per path: rays (N, 8), hits (an AccelHits or its (N, 12) records) and states (N, 8) in;
+        -> (ShaderRecords, shadow_rays (N, 8), next_rays (N, 8)), new tensors or the ones given.  The states advance in place."""
+        import torch
+        hits = getattr(hits, "records", hits)
+        _check_tensor(rays, "Shader: the rays", torch.float32, (None, 8), self.device)
+        n = int(rays.shape[0])
+        _check_tensor(hits, "Shader: the hit records", torch.float32, (n, 12), self.device)
+        _check_tensor(states, "Shader: the states", torch.int32, (n, SHADER_STATE_WORDS), self.device)
+        records = getattr(records, "records", records)
+        if records is None:
+            records = self._new((n, SHADER_RECORD_WORDS), rays)
+        if shadow_rays is None:
+            shadow_rays = self._new((n, 8), rays)
+        if next_rays is None:
+            next_rays = self._new((n, 8), rays)
+        _check_tensor(records, "Shader: the vertex records", torch.float32, (n, SHADER_RECORD_WORDS), self.device)
+        _check_tensor(shadow_rays, "Shader: the shadow rays", torch.float32, (n, 8), self.device)
+        _check_tensor(next_rays, "Shader: the next rays", torch.float32, (n, 8), self.device)
+        if next_rays.data_ptr() == rays.data_ptr() and n:
+            raise ValueError("Shader: the next rays must not be written over the rays")
+        check(lib.pine_gpu_shader_vertex_device(self._handle(), C.c_void_p(rays.data_ptr()), C.c_void_p(hits.data_ptr()), n, C.c_void_p(states.data_ptr()),
+                                                C.c_void_p(records.data_ptr()), C.c_void_p(shadow_rays.data_ptr()), C.c_void_p(next_rays.data_ptr()),
+                                                self._stream(rays)), "Shader.vertex")
+        return ShaderRecords(records), shadow_rays, next_rays
+
+    def fold(self, records, occluded, sample, sum, log=None):
+        """The backward fold of one sample: records (levels, N, 16) float32 and occluded (levels, N) uint8 (Accel.hit's answers
+        for the shadow rays), level-major; path i adds its radiance to sum[i] ((N, 4) float32: xyz the running sum, w the sample
+        count; sample 0 overwrites).  log: None, or a (levels, N, 16) float32 tensor for the per-vertex terms.  -> sum."""
+        import torch
+        _check_tensor(records, "Shader: the vertex records", torch.float32, (None, None, SHADER_RECORD_WORDS), self.device)
+        levels, n = int(records.shape[0]), int(records.shape[1])
+        _check_tensor(occluded, "Shader: the occlusion bytes", torch.uint8, (levels, n), self.device)
+        _check_tensor(sum, "Shader: the sums", torch.float32, (n, 4), self.device)
+        if log is not None:
+            _check_tensor(log, "Shader: the log", torch.float32, (levels, n, SHADER_LOG_FLOATS), self.device)
+        check(lib.pine_gpu_shader_fold_device(self._handle(), C.c_void_p(records.data_ptr()), C.c_void_p(occluded.data_ptr()), levels, n, int(sample),
+                                              C.c_void_p(sum.data_ptr()), C.c_void_p(log.data_ptr() if log is not None else 0), self._stream(records)),
+              "Shader.fold")
+        return sum
+
+    def resolve(self, sum, film=None):
+        """film[i] = (sum[i].xyz / spp, 1): -> film, an (N, 4) float32 tensor (a new one, or the one given)."""
+        import torch
+        _check_tensor(sum, "Shader: the sums", torch.float32, (None, 4), self.device)
+        n = int(sum.shape[0])
+        if film is None:
+            film = self._new((n, 4), sum)
+        _check_tensor(film, "Shader: the film", torch.float32, (n, 4), self.device)
+        check(lib.pine_gpu_shader_resolve_device(self._handle(), C.c_void_p(sum.data_ptr()), n, C.c_void_p(film.data_ptr()), self._stream(sum)),
+              "Shader.resolve")
+        return film
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib.pine_gpu_shader_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class WavefrontPathIntegrator:
+    """PathIntegrator's film, bit for bit, from a loop written in Python over Accel's and Shader's batched calls: every level
+    of every sample is an intersect, a vertex and a hit over all W * H paths (no compaction: a finished path costs a null ray).
+    on_vertex(level, rays, hits, records) sees every level's tensors (valid during the call, on the current stream) -- AOVs,
+    light baking, path filters.  Several times slower than PathIntegrator (profiles/shade_speed.txt): every vertex goes
+    through device memory."""
+
+    def __init__(self, sampler, max_path_length, order="pine", device=0):
+        if max_path_length <= 0:  # path.cpp:12-13
+            raise PineError(f"`PathIntegrator` expect `max_path_length` to be positive, get {max_path_length}")
+        self.sampler, self.max_path_length, self.order, self.device = sampler, int(max_path_length), order, int(device)
+        self.vertex_log = None
+
+    def render(self, scene, on_vertex=None, vertex_log=False):
+        """-> the scene's Film, its `pixels` the (H, W, 4) float32 film.  vertex_log: keep the fold's log of every sample in
+        self.vertex_log, an (H, W, spp, max_path_length, 16) array -- the layout of pine_gpu_plan_vertex_log."""
+        import torch
+        if scene.camera is None:
+            raise PineError("scene has no camera")
+        film = scene.camera.film()
+        with Accel(scene, order=self.order, device=self.device) as accel, Shader(scene, self.sampler, self.max_path_length, self.device) as shader:
+            (w, h), depth, dev = shader.film_size, shader.max_path_length, torch.device("cuda", self.device)
+            n = w * h
+            records = torch.empty((depth, n, SHADER_RECORD_WORDS), dtype=torch.float32, device=dev)
+            occluded = torch.empty((depth, n), dtype=torch.uint8, device=dev)
+            hits = torch.empty((n, 12), dtype=torch.float32, device=dev)
+            rays, shadow_rays, next_rays = (torch.empty((n, 8), dtype=torch.float32, device=dev) for _ in range(3))
+            states = torch.empty((n, SHADER_STATE_WORDS), dtype=torch.int32, device=dev)
+            sums = torch.empty((n, 4), dtype=torch.float32, device=dev)
+            logs = torch.empty((shader.spp, depth, n, SHADER_LOG_FLOATS), dtype=torch.float32, device=dev) if vertex_log else None
+            for s in range(shader.spp):
+                shader.begin(s, states, rays)
+                for level in range(depth):
+                    found = accel.intersect(rays, out=hits)
+                    rec, _, _ = shader.vertex(rays, found, states, records[level], shadow_rays, next_rays)
+                    accel.hit(shadow_rays, out=occluded[level])
+                    if on_vertex is not None:
+                        on_vertex(level, rays, found, rec)
+                    rays, next_rays = next_rays, rays
+                shader.fold(records, occluded, s, sums, logs[s] if vertex_log else None)
+            pixels = shader.resolve(sums).cpu().numpy()  # (waits for the stream)
+            if vertex_log:
+                self.vertex_log = np.ascontiguousarray(logs.cpu().numpy().reshape(shader.spp, depth, h, w, SHADER_LOG_FLOATS).transpose(2, 3, 0, 1, 4))
+        film.pixels = pixels.reshape(h, w, 4)
+        return film

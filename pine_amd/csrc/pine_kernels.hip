@@ -1347,6 +1347,7 @@ pine_gpu_plan* pine_gpu_plan_create_passes(pine_gpu_scene* scene, const pine_gpu
 #include "pine_ao_host.h"  // AOIntegrator plans: ao_plan_build, ao_launch and the three pine_gpu_ao_* entry points
 #include "pine_guides_host.h"  // DenoiseIntegrator's guide images: the pine_gpu_guides_* entry points
 #include "pine_accel_host.h"  // Accel's batched ray queries: the pine_gpu_accel_* entry points
+#include "pine_shade_host.h"  // Shader's batched path-vertex queries: the pine_gpu_shader_* entry points
 
 // The path kernel of the plan -- the scene's own, or the precompiled one -- over the work decomposition W, its samples going
 // to `samples` (+ sample index * 64, decode_item).

@@ -32,6 +32,7 @@ SceneHost& scene_host(pine_gpu_scene* s);
 #include "pine_ao_kernel.h"
 #include "pine_guides_kernel.h"
 #include "pine_accel_kernel.h"
+#include "pine_shade_kernel.h"
 namespace pine_gpu {
 
 #define HIP_OK(expr)                                                                          \

@@ -470,6 +470,62 @@ class Accel {
   pine_gpu_accel* h_;
 };
 
+// Shader(scene, sampler, max_path_length): one vertex of PathIntegrator::radiance() for n paths at a time in the caller's device
+// buffers (include/pine_gpu.h has the layouts of the state, the vertex record and the log).  With an Accel:
+// begin -> intersect -> vertex -> hit -> intersect -> vertex -> ... -> fold -> resolve.  Every call takes 16-byte aligned device
+// pointers, is enqueued on `stream` (a hipStream_t) and waits for nothing.
+struct VertexRecord {
+  int32_t kind, length;  // kind: -1 none, 0 miss, 1 emissive, 2 the path-length limit, 3 shaded
+  uint32_t flags;        // 1 has_shadow_ray, 2 has_next_ray, 4 the light pdf is there
+  float light_pdf, lo[3], cosine, direct[3], pdf, f[3], is_delta;
+  bool has_shadow_ray() const { return (flags & 1u) != 0; }
+  bool has_next_ray() const { return (flags & 2u) != 0; }
+};
+static_assert(sizeof(VertexRecord) == 64, "the layout of pine_gpu_shader_vertex_device");
+class Shader {
+ public:
+  Shader(Scene& scene, Sampler sampler, int max_path_length, int device = 0) {
+    pine_gpu_render_params p{};
+    p.spp = sampler.requested;
+    p.max_path_length = max_path_length;
+    p.device = device;
+    p.shard_rank = 0;
+    p.shard_world = 1;
+    p.sampler = sampler.kind;
+    h_ = pine_gpu_shader_create(scene.handle(), &p);
+    if (!h_) throw Error(std::string("Shader: ") + pine_gpu_last_error());
+    check(pine_gpu_shader_info(h_, info_), "Shader");
+  }
+  ~Shader() { pine_gpu_shader_destroy(h_); }
+  Shader(const Shader&) = delete;
+  Shader& operator=(const Shader&) = delete;
+  int film_width() const { return info_[0]; }
+  int film_height() const { return info_[1]; }
+  int spp() const { return info_[2]; }  // effective
+  int max_path_length() const { return info_[3]; }
+  static constexpr int state_bytes = 32, record_bytes = 64, ray_floats = 8, log_floats = 16;
+  // sample `sample` of every pixel starts: W * H states and camera rays, row-major
+  void begin_device(int sample, void* states_dev, void* rays_dev, void* stream = nullptr) const {
+    check(pine_gpu_shader_begin_device(h_, sample, states_dev, rays_dev, stream), "Shader::begin_device");
+  }
+  void vertex_device(const void* rays_dev, const void* hits_dev, int64_t n, void* states_dev, void* records_dev, void* shadow_rays_dev,
+                     void* next_rays_dev, void* stream = nullptr) const {
+    check(pine_gpu_shader_vertex_device(h_, rays_dev, hits_dev, n, states_dev, records_dev, shadow_rays_dev, next_rays_dev, stream), "Shader::vertex_device");
+  }
+  void fold_device(const void* records_dev, const void* occluded_dev, int levels, int64_t n, int sample, void* sum_dev, void* log_dev = nullptr,
+                   void* stream = nullptr) const {
+    check(pine_gpu_shader_fold_device(h_, records_dev, occluded_dev, levels, n, sample, sum_dev, log_dev, stream), "Shader::fold_device");
+  }
+  void resolve_device(const void* sum_dev, int64_t n, void* film_dev, void* stream = nullptr) const {
+    check(pine_gpu_shader_resolve_device(h_, sum_dev, n, film_dev, stream), "Shader::resolve_device");
+  }
+  pine_gpu_shader* handle() const { return h_; }
+
+ private:
+  pine_gpu_shader* h_ = nullptr;
+  int32_t info_[8] = {};
+};
+
 inline float get_progress() { return pine_gpu_progress(); }
 
 // load(scene, "file.glb" [, mat4]) (fileio.cpp:584-589): glTF import -- every mesh primitive with its material, and the

@@ -64,6 +64,17 @@ int pine_gpu_accel_intersect(pine_gpu_accel*, const float*, int64_t, void*) { re
 int pine_gpu_accel_hit(pine_gpu_accel*, const float*, int64_t, uint8_t*) { return fail(); }
 int pine_gpu_accel_camera_rays_device(pine_gpu_accel*, void*, void*) { return fail(); }
 int pine_gpu_accel_info(pine_gpu_accel*, int32_t*) { return fail(); }
+pine_gpu_shader* pine_gpu_shader_create(pine_gpu_scene*, const pine_gpu_render_params*) {
+  fail();
+  return nullptr;
+}
+void pine_gpu_shader_destroy(pine_gpu_shader*) {}
+int pine_gpu_shader_layout(int32_t*) { return fail(); }
+int pine_gpu_shader_info(pine_gpu_shader*, int32_t*) { return fail(); }
+int pine_gpu_shader_begin_device(pine_gpu_shader*, int, void*, void*, void*) { return fail(); }
+int pine_gpu_shader_vertex_device(pine_gpu_shader*, const void*, const void*, int64_t, void*, void*, void*, void*, void*) { return fail(); }
+int pine_gpu_shader_fold_device(pine_gpu_shader*, const void*, const void*, int, int64_t, int, void*, void*, void*) { return fail(); }
+int pine_gpu_shader_resolve_device(pine_gpu_shader*, const void*, int64_t, void*, void*) { return fail(); }
 // (the filter's host-thread build, device = -1, is the real thing: pine_denoise_host.h)
 void pine_gpu_denoise_params_default(pine_gpu_denoise_params* prm) {
   if (prm) *prm = pine_gpu_denoise_params{5, 7, PINE_GPU_DENOISE_SIGMA_COLOR, PINE_GPU_DENOISE_SIGMA_ALBEDO, PINE_GPU_DENOISE_EPS_ALBEDO, 0};
