@@ -1071,12 +1071,41 @@ def _check_tensor(t, what, dtype, shape, device=None):
     return t
 
 
-class Accel:
+class _SceneQuery:
+    """What Accel and Shader share: the library's handle of the scene's records on the device (self._h), freed by close();
+    a context manager.  A subclass names itself (_NAME) and the function that destroys its handle (_DESTROY)."""
+    _NAME, _DESTROY = "", None
+
+    def _handle(self):
+        if not self._h:
+            raise PineError(f"{self._NAME}: closed")
+        return self._h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._DESTROY(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Accel(_SceneQuery):
     """Accel(scene): the scene's BVH on the device, answering batches of rays -- what a CustomRayIntegrator's radiance() gets as
     intersect(ray, it) and hit(ray) (core/integrator.h:61-74).  One ray is a row of 8 float32: o, d, tmin, tmax; d is used as
     given (t is in units of d).  order: "pine" -- Accel(BVH()); "embree" -- Accel(EmbreeAccel()).  The answers are the
     reference's, bit for bit.  The accel is a snapshot of the scene at creation.  A context manager; close() frees the device
     memory."""
+    _NAME, _DESTROY = "Accel", lib.pine_gpu_accel_destroy
 
     def __init__(self, scene, order="pine", device=0):
         self._h = None
@@ -1088,11 +1117,6 @@ class Accel:
         info = (C.c_int32 * 4)()
         check(lib.pine_gpu_accel_info(self._h, info), "Accel")
         self.kernel_features, self.lds_bytes, self.film_size = int(info[0]) & 0xFFFFFFFF, int(info[1]), (int(info[2]), int(info[3]))
-
-    def _handle(self):
-        if not self._h:
-            raise PineError("Accel: closed")
-        return self._h
 
     def intersect(self, rays, out=None):
         """Closest hits.  A numpy array in: a structured array of HIT_DTYPE out.  A CUDA tensor in: an AccelHits over a new
@@ -1142,23 +1166,6 @@ class Accel:
         check(lib.pine_gpu_accel_camera_rays_device(self._handle(), C.c_void_p(rays.data_ptr()), stream), "Accel.camera_rays")
         return rays if tensor else rays.cpu().numpy()
 
-    def close(self):
-        if getattr(self, "_h", None):
-            lib.pine_gpu_accel_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 # ---- Shader: batched path-vertex shading queries (core/integrator.h:27-74, impl/integrator/path.cpp:42-123) ----
 # (pine_gpu_shader_layout reports the same: tests/test_shader.py)
@@ -1200,12 +1207,13 @@ class ShaderRecords:
         return int(self.records.shape[0])
 
 
-class Shader:
+class Shader(_SceneQuery):
     """Shader(scene, sampler, max_path_length): one vertex of PathIntegrator's radiance() for N paths at a time, on contiguous
     CUDA torch tensors of the caller's -- on their device and the current stream, nothing copied and nothing waited for.  With an
     Accel: begin -> intersect -> vertex -> hit -> intersect -> vertex ... -> fold -> resolve (WavefrontPathIntegrator is that
     loop).  A pixel's samples are rendered in order: its RNG travels in the states.  A tensor of the wrong dtype, shape, device
     or layout raises ValueError before anything is launched.  A snapshot of the scene at creation; a context manager."""
+    _NAME, _DESTROY = "Shader", lib.pine_gpu_shader_destroy
 
     def __init__(self, scene, sampler, max_path_length, device=0, flags=0):
         self._h = None
@@ -1219,11 +1227,6 @@ class Shader:
         check(lib.pine_gpu_shader_info(self._h, info), "Shader")
         self.film_size, self.spp, self.max_path_length = (int(info[0]), int(info[1])), int(info[2]), int(info[3])
         self.variant, self.kernel_features, self.lds_bytes = int(info[4]), int(info[5]) & 0xFFFFFFFF, int(info[6])
-
-    def _handle(self):
-        if not self._h:
-            raise PineError("Shader: closed")
-        return self._h
 
     def _stream(self, t):
         import torch
@@ -1305,23 +1308,6 @@ class Shader:
         check(lib.pine_gpu_shader_resolve_device(self._handle(), C.c_void_p(sum.data_ptr()), n, C.c_void_p(film.data_ptr()), self._stream(sum)),
               "Shader.resolve")
         return film
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib.pine_gpu_shader_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class WavefrontPathIntegrator:

@@ -1,17 +1,12 @@
 // pine_amd/csrc/pine_accel_host.h -- the host side of Accel's batched ray queries (kernels: pine_accel_kernel.h).  Included by
-// pine_kernels.hip after plan_build's phases, of which an accel runs assemble_scene and scene_features; of the steps of
-// pine_plan_steps.h it takes plan_open_device and pick_variant.  An accel has no film, no sampler and no work items: it is the
-// scene's records on the device -- held in a pine_gpu_plan that is never launched, so that the buffers have the owners and the
-// pool every plan's have -- and the kernel pair chosen for them.  The records are a snapshot: a geometry added to the scene
-// later is not in them.  Nothing on the device is written after creation, so queries may run on several streams at once.
+// pine_kernels.hip after plan_build's phases; of the shared steps (pine_plan_steps.h, pine_scene_steps.h) it takes
+// upload_scene_records, pick_variant, lane_stack_lds_bytes, raise_lds_limit and create_object.  An accel has no film, no sampler
+// and no work items: it is a SceneQuery -- the scene's records on the device, its launch and its destroy -- and the kernel pair
+// chosen for the records.  The records are a snapshot: a geometry added to the scene later is not in them.  Nothing on the device
+// is written after creation, so queries may run on several streams at once.
 
-struct pine_gpu_accel {
-  PlanOwner plan;  // S: the scene view; the d_* blocks behind it
-  int device = 0;
+struct pine_gpu_accel : SceneQuery {
   const PineAccelVariant* kernel = nullptr;
-  size_t lds_bytes = 0;
-  bool has_camera = false;
-  std::atomic<bool> queried{false};  // a launch may still be reading the records: destroy waits for the device first
 };
 
 // What every query checks before it looks at the accel: the ray count, then -- unless there is no ray -- the two buffers
@@ -33,19 +28,6 @@ static int accel_check_query(int64_t n, const void* rays, const void* out, bool 
   return 0;
 }
 
-// The largest dynamic LDS size each kernel of the table has been asked for so far: the attribute belongs to the function, not
-// to the accel, and a later, smaller accel must not lower it under an earlier one's launches.
-static int accel_raise_lds_limit(const void* fn, size_t lds_bytes) {
-  static std::mutex mu;
-  static std::map<const void*, size_t> limit;
-  std::lock_guard<std::mutex> lock(mu);
-  size_t& have = limit[fn];
-  if (lds_bytes <= have) return 0;
-  HIP_OK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_bytes)));
-  have = lds_bytes;
-  return 0;
-}
-
 static int accel_build(pine_gpu_accel* a, pine_gpu_scene* scene, int device, uint32_t flags) {
   if (flags & (PINE_GPU_FLAG_FAST | PINE_GPU_FLAG_SPECIALIZE | PINE_GPU_FLAG_VERTEX_LOG)) {
     set_error((flags & PINE_GPU_FLAG_FAST)
@@ -64,70 +46,39 @@ static int accel_build(pine_gpu_accel* a, pine_gpu_scene* scene, int device, uin
   a->plan.reset(new pine_gpu_plan());
   pine_gpu_plan* p = a->plan.get();
   std::chrono::steady_clock::time_point built;
-  if (plan_open_device(p, H, &prm, "Accel's ray queries", built)) return -1;
+  SceneRecords R;
+  // (PINE_GPU_FLAG_ORDER_EMBREE: EmbreeAccel's hierarchy is built and checked against the per-ray stack in there)
+  if (upload_scene_records(p, H, &prm, "Accel's ray queries", built, R)) return -1;
   a->device = device;
   a->has_camera = H.has_camera;
-  SceneParts sp;
-  // (PINE_GPU_FLAG_ORDER_EMBREE: EmbreeAccel's hierarchy is built and checked against the per-ray stack in there)
-  if (assemble_scene(p, H, &prm, sp, false)) return -1;
 
   // the kernels: the first variant that covers the scene's shape kinds in the order asked for; $PINE_GPU_ACCEL_VARIANT=<index>
   // considers that variant only (tests)
-  const unsigned need = scene_features(sp, &prm) & (kFAccelShapes | F_EMBREE);
-  const bool lds_ok = size_t(p->S.blob_bytes) <= 32 * 1024;
+  const unsigned need = R.need & (kFAccelShapes | F_EMBREE);
   int count = 0;
   const PineAccelVariant* table = pine_gpu_accel_variant_table(&count);
-  const int chosen = pick_variant(table, count, need, lds_ok, "PINE_GPU_ACCEL_VARIANT", "no Accel kernel variant covers this scene",
-                                  "$PINE_GPU_ACCEL_VARIANT names no Accel kernel variant that covers this scene");
+  const int chosen = pick_variant(table, count, need, R.lds_ok, "PINE_GPU_ACCEL_VARIANT", "Accel");
   if (chosen < 0) return -1;
   if (((table[chosen].features ^ need) & F_EMBREE) != 0) {  // (a pinned variant of the other order)
     set_error("$PINE_GPU_ACCEL_VARIANT names a variant of the other traversal order");
     return -1;
   }
   a->kernel = &table[chosen];
-  a->lds_bytes = size_t(p->S.stack_total) * kBlock * sizeof(int) + ((a->kernel->features & F_LDS_SCENE) ? size_t(p->S.blob_bytes) : 0);
-  if (a->lds_bytes > 160 * 1024) {
-    set_error("Accel: the traversal stack of this scene does not fit LDS");
-    return -1;
-  }
-  return accel_raise_lds_limit(a->kernel->intersect, a->lds_bytes) || accel_raise_lds_limit(a->kernel->hit, a->lds_bytes) ? -1 : 0;
+  if (lane_stack_lds_bytes(p->S, a->kernel->features, 0, "Accel", a->lds_bytes)) return -1;
+  return raise_lds_limit(device, a->kernel->intersect, a->lds_bytes) || raise_lds_limit(device, a->kernel->hit, a->lds_bytes) ? -1 : 0;
 }
 
 pine_gpu_accel* pine_gpu_accel_create(pine_gpu_scene* scene, int device, uint32_t flags) {
-  if (!scene) {
-    set_error("null argument");
-    return nullptr;
-  }
-  pine_gpu_accel* a = new pine_gpu_accel();
-  if (accel_build(a, scene, device, flags)) {
-    std::string keep = pine_gpu_last_error();
-    pine_gpu_accel_destroy(a);
-    set_error(keep);
-    return nullptr;
-  }
-  return a;
+  return create_object(scene != nullptr, pine_gpu_accel_destroy, [&](pine_gpu_accel* a) { return accel_build(a, scene, device, flags); });
 }
 
-void pine_gpu_accel_destroy(pine_gpu_accel* a) {
-  if (!a) return;
-  if (a->queried.load()) {
-    // the records go back to the pool with the plan: every query that reads them, on whatever stream, must have finished
-    (void)hipSetDevice(a->device);
-    (void)hipDeviceSynchronize();
-  }
-  delete a;
-}
+void pine_gpu_accel_destroy(pine_gpu_accel* a) { destroy_query(a); }
 
 // One launch of `fn` over n rays on `stream`; nothing is waited for.
-static int accel_launch(pine_gpu_accel* a, const void* fn, const void* rays_dev, int64_t n, void* out_dev, hipStream_t stream) {
-  HIP_OK(hipSetDevice(a->device));
-  (void)hipGetLastError();
+static int accel_launch(pine_gpu_accel* a, const void* fn, const void* rays_dev, int64_t n, void* out_dev, void* stream) {
   long long count = n;
   void* args[] = {&a->plan->S, (void*)&rays_dev, &count, &out_dev};
-  const unsigned grid = unsigned((n + kBlock - 1) / kBlock);
-  a->queried.store(true);
-  HIP_OK(hipLaunchKernel(fn, dim3(grid), dim3(kBlock), args, a->lds_bytes, stream));
-  return 0;
+  return a->launch(fn, args, n, a->lds_bytes, stream);
 }
 
 int pine_gpu_accel_intersect_device(pine_gpu_accel* a, const void* rays_dev, int64_t n, void* hits_dev, void* stream) {
@@ -137,7 +88,7 @@ int pine_gpu_accel_intersect_device(pine_gpu_accel* a, const void* rays_dev, int
     return -1;
   }
   if (n == 0) return 0;
-  return accel_launch(a, a->kernel->intersect, rays_dev, n, hits_dev, static_cast<hipStream_t>(stream));
+  return accel_launch(a, a->kernel->intersect, rays_dev, n, hits_dev, stream);
 }
 
 int pine_gpu_accel_hit_device(pine_gpu_accel* a, const void* rays_dev, int64_t n, void* occluded_dev, void* stream) {
@@ -152,7 +103,7 @@ int pine_gpu_accel_hit_device(pine_gpu_accel* a, const void* rays_dev, int64_t n
     return -1;
   }
   if (n == 0) return 0;
-  return accel_launch(a, a->kernel->hit, rays_dev, n, occluded_dev, static_cast<hipStream_t>(stream));
+  return accel_launch(a, a->kernel->hit, rays_dev, n, occluded_dev, stream);
 }
 
 // The host forms: upload, launch on the null stream, wait, download.
@@ -204,14 +155,9 @@ int pine_gpu_accel_camera_rays_device(pine_gpu_accel* a, void* rays_dev, void* s
     set_error("scene has no camera");
     return -1;
   }
-  HIP_OK(hipSetDevice(a->device));
-  (void)hipGetLastError();
-  const DCamera& cam = a->plan->S.cam;
-  const long long n = (long long)cam.W * cam.H;
-  void* args[] = {const_cast<DCamera*>(&cam), &rays_dev};
-  a->queried.store(true);
-  HIP_OK(hipLaunchKernel(pine_gpu_accel_camera_rays_fn(), dim3(unsigned((n + kBlock - 1) / kBlock)), dim3(kBlock), args, 0, static_cast<hipStream_t>(stream)));
-  return 0;
+  DCamera& cam = a->plan->S.cam;
+  void* args[] = {&cam, &rays_dev};
+  return a->launch(pine_gpu_accel_camera_rays_fn(), args, int64_t(cam.W) * cam.H, 0, stream);
 }
 
 int pine_gpu_accel_info(pine_gpu_accel* a, int32_t out[4]) {

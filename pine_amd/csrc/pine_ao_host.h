@@ -1,9 +1,9 @@
 // pine_amd/csrc/pine_ao_host.h -- the host side of AOIntegrator plans (kernels: pine_ao_kernel.h).  Included by
-// pine_kernels.hip after plan_build's phases.  Of those an AO plan runs the ones that decide nothing about path kernels --
-// check_params, assemble_scene, upload_sampler_tables, scene_features -- and between them the steps of pine_plan_steps.h, in its
-// own order: plan_open_device, pick_variant, shard_tiles, items_of_k_samples, plan_progress_word, plan_timing_events to build
-// (create_plan around them); launch_begin, launch_mark, checkpoint_prepass, launch_end to launch.  Its refusals, its kernel's LDS size, the chunks
-// of k samples and its buffers are its own.  An AO plan is a pine_gpu_plan with `ao` set: pine_gpu_plan_launch / _stats_get /
+// pine_kernels.hip after plan_build's phases.  Of those an AO plan runs check_params and upload_sampler_tables itself, and
+// between them the shared steps (pine_plan_steps.h, pine_scene_steps.h), in its own order: upload_scene_records, pick_variant,
+// lane_stack_lds_bytes, raise_lds_limit, shard_tiles, items_of_k_samples, plan_progress_word, plan_timing_events to build
+// (create_object around them); launch_begin, launch_mark, checkpoint_prepass, launch_end to launch.  Its refusals, the chunks of
+// k samples and its buffers are its own.  An AO plan is a pine_gpu_plan with `ao` set: pine_gpu_plan_launch / _stats_get /
 // _check / _destroy take it as they take any plan.
 
 // The AO sample count (ao.cpp:13) of a sampler whose own count is `sampler_spp`.
@@ -27,13 +27,12 @@ static int ao_plan_build(pine_gpu_plan* p, pine_gpu_scene* scene, const pine_gpu
   TableBlob tables_blob;
   if (load_tables(tables_blob)) return -1;
   std::chrono::steady_clock::time_point t_build1;
-  if (plan_open_device(p, H, &prm, "the AOIntegrator hot path", t_build1)) return -1;
+  const size_t tally0 = g_alloc_tally;  // (the BVH build takes nothing from the pool)
+  SceneRecords R;
+  if (upload_scene_records(p, H, &prm, "the AOIntegrator hot path", t_build1, R)) return -1;
   p->ao = true;
-  const size_t tally0 = g_alloc_tally;
-
-  SceneParts sp;
   // (the sampler keeps its ORIGINAL count -- BlueSampler's table, SobolSampler's index stride -- only fewer indices are drawn)
-  if (assemble_scene(p, H, &prm, sp, false) || upload_sampler_tables(p, *tables_blob, &prm, sampler_spp)) return -1;
+  if (upload_sampler_tables(p, *tables_blob, &prm, sampler_spp)) return -1;
   p->S.spp = spp;
   if (pine_gpu_ao_constants(scene, &p->ao_params.radius)) return -1;
   static_assert(offsetof(AoParams, dir) == sizeof(float) && sizeof(AoParams) == 26 * sizeof(float), "radius, then directions[8]");
@@ -41,12 +40,9 @@ static int ao_plan_build(pine_gpu_plan* p, pine_gpu_scene* scene, const pine_gpu
 
   // the kernel: the first variant that covers the scene's shape kinds and sampler, in the schedule $PINE_GPU_AO_KERNEL names
   // (serial, the default: lane = sample; regroup: the wave's occlusion rays regrouped); $PINE_GPU_AO_VARIANT=<index> considers that variant only (tests)
-  const unsigned need = scene_features(sp, &prm) & (kFAoShapes | F_SOBOL);
-  const bool lds_ok = size_t(p->S.blob_bytes) <= 32 * 1024;
   int count = 0;
   const PineAoVariant* table = pine_gpu_ao_variants(&count);
-  p->ao_variant = pick_variant(table, count, need, lds_ok, "PINE_GPU_AO_VARIANT", "no AO kernel variant covers this scene",
-                               "$PINE_GPU_AO_VARIANT names no AO kernel variant that covers this scene");
+  p->ao_variant = pick_variant(table, count, R.need & (kFAoShapes | F_SOBOL), R.lds_ok, "PINE_GPU_AO_VARIANT", "AO");
   if (p->ao_variant < 0) return -1;
   p->ao_serial = true;  // (the faster of the two on two of the three measured scenes: DESIGN.md 4.11, profiles/ao_speed.txt)
   if (const char* e = getenv("PINE_GPU_AO_KERNEL")) {
@@ -57,13 +53,9 @@ static int ao_plan_build(pine_gpu_plan* p, pine_gpu_scene* scene, const pine_gpu
     }
   }
   const PathKernel kernel = plan_kernel(p);
-  p->lds_bytes = size_t(ao_off_stack(!p->ao_serial)) * 4 + size_t(p->S.stack_total) * kBlock * sizeof(int) +
-                 ((kernel.features & F_LDS_SCENE) ? size_t(p->S.blob_bytes) : 0);
-  if (p->lds_bytes > 160 * 1024) {
-    set_error("AOIntegrator: the traversal stack of this scene does not fit LDS");
+  if (lane_stack_lds_bytes(p->S, kernel.features, size_t(ao_off_stack(!p->ao_serial)) * 4, "AOIntegrator", p->lds_bytes) ||
+      raise_lds_limit(prm.device, kernel.fn, p->lds_bytes))
     return -1;
-  }
-  HIP_OK(hipFuncSetAttribute(kernel.fn, hipFuncAttributeMaxDynamicSharedMemorySize, int(p->lds_bytes)));
 
   // work items: [local tile][chunk of k samples][pixel in tile]; k the largest power of two dividing the AO count that
   // still leaves 2^20 items (a lane walks its k samples in sequence; the chunks start from RNG checkpoints)
@@ -131,7 +123,7 @@ static int ao_launch(pine_gpu_plan* p, void* film_dev, hipStream_t stream) {
 }
 
 pine_gpu_plan* pine_gpu_ao_plan_create(pine_gpu_scene* scene, const pine_gpu_render_params* prm) {
-  return create_plan(scene, prm, [&](pine_gpu_plan* p) { return ao_plan_build(p, scene, prm); });
+  return create_object(scene && prm, pine_gpu_plan_destroy, [&](pine_gpu_plan* p) { return ao_plan_build(p, scene, prm); });
 }
 
 // AOIntegrator(BVH(), sampler).render(scene) in one call: upload, launch, download.  Fails if there is no GPU.

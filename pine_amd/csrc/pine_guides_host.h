@@ -1,8 +1,8 @@
 // pine_amd/csrc/pine_guides_host.h -- the host side of DenoiseIntegrator's guide images (kernels: pine_guides_kernel.h).  Included
-// by pine_kernels.hip after plan_build's phases, of which the guide pass runs check_params, assemble_scene and scene_features;
-// of the steps of pine_plan_steps.h it takes shard_tiles, plan_open_device (open_device alone for the output buffers) and
-// pick_variant.  The pass has no plan of its own and no launch frame: the scene's records are uploaded into a pine_gpu_plan that
-// lives for the length of the call, one kernel is launched and waited for.
+// by pine_kernels.hip after plan_build's phases, of which the guide pass runs check_params itself; of the shared steps
+// (pine_plan_steps.h, pine_scene_steps.h) it takes shard_tiles, upload_scene_records (open_device alone for the output buffers),
+// pick_variant, lane_stack_lds_bytes and raise_lds_limit.  The pass has no plan of its own and no launch frame: the scene's
+// records are uploaded into a pine_gpu_plan that lives for the length of the call, one kernel is launched and waited for.
 
 static int guides_render_device(pine_gpu_scene* scene, const pine_gpu_render_params* prm_in, float* albedo_dev, float* normal_dev, hipStream_t stream) {
   SceneHost& H = scene_host(scene);
@@ -28,26 +28,19 @@ static int guides_render_device(pine_gpu_scene* scene, const pine_gpu_render_par
   if (check_params(H, &prm) < 0) return -1;
   PlanOwner p(new pine_gpu_plan());
   std::chrono::steady_clock::time_point built;
-  if (shard_tiles(p->W, H.camera.W, H.camera.H, &prm) || plan_open_device(p.get(), H, &prm, "the guide images' hot path", built)) return -1;
-  SceneParts sp;
-  if (assemble_scene(p.get(), H, &prm, sp, false)) return -1;
+  SceneRecords R;
+  // (the film-size refusal comes before the device check)
+  if (shard_tiles(p->W, H.camera.W, H.camera.H, &prm) || upload_scene_records(p.get(), H, &prm, "the guide images' hot path", built, R)) return -1;
 
   // the kernel: the first variant that covers the scene's shape kinds and node programs; $PINE_GPU_GUIDES_VARIANT=<index>
   // considers that variant only (tests)
-  const unsigned need = scene_features(sp, &prm) & (kFGuidesShapes | F_NODES);
-  const bool lds_ok = size_t(p->S.blob_bytes) <= 32 * 1024;
   int count = 0;
   const PineGuidesVariant* table = pine_gpu_guides_variant_table(&count);
-  const int chosen = pick_variant(table, count, need, lds_ok, "PINE_GPU_GUIDES_VARIANT", "no guide kernel variant covers this scene",
-                                  "$PINE_GPU_GUIDES_VARIANT names no guide kernel variant that covers this scene");
+  const int chosen = pick_variant(table, count, R.need & (kFGuidesShapes | F_NODES), R.lds_ok, "PINE_GPU_GUIDES_VARIANT", "guide");
   if (chosen < 0) return -1;
   const PineGuidesVariant& K = table[chosen];
-  const size_t lds_bytes = size_t(p->S.stack_total) * kBlock * sizeof(int) + ((K.features & F_LDS_SCENE) ? size_t(p->S.blob_bytes) : 0);
-  if (lds_bytes > 160 * 1024) {
-    set_error("guide images: the traversal stack of this scene does not fit LDS");
-    return -1;
-  }
-  HIP_OK(hipFuncSetAttribute(K.fn, hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_bytes)));
+  size_t lds_bytes = 0;
+  if (lane_stack_lds_bytes(p->S, K.features, 0, "guide images", lds_bytes) || raise_lds_limit(prm.device, K.fn, lds_bytes)) return -1;
   int tiles_x = p->W.tiles_x, num_tiles = p->W.num_local_tiles;  // (shard_world is 1: every tile of the film)
   void* args[] = {&p->S, &tiles_x, &num_tiles, &albedo_dev, &normal_dev};
   const unsigned grid = unsigned((num_tiles + kBlock / 64 - 1) / (kBlock / 64));

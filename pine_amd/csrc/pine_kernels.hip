@@ -323,7 +323,7 @@ static int plan_check_counters(const Counters& c) {
   return -1;
 }
 
-#include "pine_plan_steps.h"  // what path plans, AO plans and the guide pass build and launch alike, one function per step
+#include "pine_plan_steps.h"  // what path plans, AO plans, the guide pass, accels and shaders build and launch alike, one function per step
 
 // The launch side of a one-shot render (create, launch, download, destroy), which the path and the AO render share: a film from
 // the pool, `run(film, bytes)` -- launches, downloads, checks; 0, PINE_GPU_RENDER_STOPPED or -1 -- while get_progress() follows
@@ -1225,7 +1225,7 @@ static int size_and_allocate(pine_gpu_plan* p, const pine_gpu_render_params* prm
   const PathKernel kernel = plan_kernel(p);
   if (kernel.queued()) {
     blocks_per_cu = 1;  // one 1024-thread workgroup per CU owns the CU's LDS
-    HIP_OK(hipFuncSetAttribute(kernel.fn, hipFuncAttributeMaxDynamicSharedMemorySize, int(p->lds_bytes)));
+    if (raise_lds_limit(prm->device, kernel.fn, p->lds_bytes)) return -1;
   } else {
     HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, kernel.fn, kBlock, p->lds_bytes));
   }
@@ -1334,7 +1334,7 @@ static int plan_build(pine_gpu_plan* p, pine_gpu_scene* scene, const pine_gpu_re
 }
 
 static pine_gpu_plan* plan_create(pine_gpu_scene* scene, const pine_gpu_render_params* prm, int pass_samples) {
-  return create_plan(scene, prm, [&](pine_gpu_plan* p) {
+  return create_object(scene && prm, pine_gpu_plan_destroy, [&](pine_gpu_plan* p) {
     p->pass_samples_req = pass_samples;
     return plan_build(p, scene, prm);
   });
@@ -1344,6 +1344,7 @@ pine_gpu_plan* pine_gpu_plan_create_passes(pine_gpu_scene* scene, const pine_gpu
   return plan_create(scene, prm, pass_samples);
 }
 
+#include "pine_scene_steps.h"  // the shared step that runs assemble_scene and scene_features: upload_scene_records
 #include "pine_ao_host.h"  // AOIntegrator plans: ao_plan_build, ao_launch and the three pine_gpu_ao_* entry points
 #include "pine_guides_host.h"  // DenoiseIntegrator's guide images: the pine_gpu_guides_* entry points
 #include "pine_accel_host.h"  // Accel's batched ray queries: the pine_gpu_accel_* entry points

@@ -1,7 +1,9 @@
 // pine_amd/csrc/pine_plan_steps.h -- the host steps that building and launching a plan of any kind share: path plans (plan_build,
 // path_launch_pass in pine_kernels.hip), AOIntegrator plans (pine_ao_host.h) and the guide pass (pine_guides_host.h).  Each is
 // one free function that does one thing; an integrator calls the ones it needs in its own order, between its own decisions
-// (refusals, kernel choice, LDS sizing, work items, buffers).  Included by pine_kernels.hip behind g_progress.
+// (refusals, kernel choice, work items, buffers).  Accel's and Shader's query objects (pine_accel_host.h, pine_shade_host.h)
+// take the build steps too, and are one SceneQuery underneath: one launch, one destroy.  Included by pine_kernels.hip behind
+// g_progress; the step that needs plan_build's phases (upload_scene_records) is in pine_scene_steps.h, included after them.
 
 // The device check every hot path starts with (`who` names it in the error), then the caller's device made current.
 static int open_device(const pine_gpu_render_params* prm, const char* who) {
@@ -33,18 +35,45 @@ static int plan_open_device(pine_gpu_plan* p, SceneHost& H, const pine_gpu_rende
 }
 
 // The first variant of `table` whose features cover `need` -- scene-in-LDS variants only if the blob fits (`lds_ok`); the
-// environment variable `pin_env`=<index> considers that variant only (tests).  The index, or -1.
+// environment variable `pin_env`=<index> considers that variant only (tests).  The index, or -1: `family` names the kernels in
+// the error ("AO", "guide", "Accel", "Shader").
 template <class Variant>
-static int pick_variant(const Variant* table, int count, unsigned need, bool lds_ok, const char* pin_env, const char* no_cover_msg,
-                        const char* pin_msg) {
+static int pick_variant(const Variant* table, int count, unsigned need, bool lds_ok, const char* pin_env, const char* family) {
   const char* pin = getenv(pin_env);
   for (int i = 0; i < count; i++) {
     if (pin && *pin && atoi(pin) != i) continue;
     const unsigned F = table[i].features;
     if ((need & ~F) == 0 && (!(F & F_LDS_SCENE) || lds_ok)) return i;
   }
-  set_error(pin && *pin ? pin_msg : no_cover_msg);
+  set_error(pin && *pin ? std::string("$") + pin_env + " names no " + family + " kernel variant that covers this scene"
+                        : std::string("no ") + family + " kernel variant covers this scene");
   return -1;
+}
+
+// The dynamic LDS of a kernel whose lanes keep their traversal stacks there: `extra` bytes of the kernel's own, a stack per lane
+// of a block, and the scene's blob if the variant stages it (F_LDS_SCENE).  More than a CU's 160 KiB is refused in `who`'s name.
+static int lane_stack_lds_bytes(const DeviceScene& S, unsigned features, size_t extra, const char* who, size_t& lds_bytes) {
+  lds_bytes = extra + size_t(S.stack_total) * kBlock * sizeof(int) + ((features & F_LDS_SCENE) ? size_t(S.blob_bytes) : 0);
+  if (lds_bytes > 160 * 1024) {
+    set_error(std::string(who) + ": the traversal stack of this scene does not fit LDS");
+    return -1;
+  }
+  return 0;
+}
+
+// hipFuncAttributeMaxDynamicSharedMemorySize of kernel `fn` on `device` (the current one), raised to `lds_bytes` and never
+// lowered: the attribute belongs to the function on that device, not to the plan or query object that asks, and a later,
+// smaller object must not lower it under an earlier one's launches.  So the limit is the largest size any object, live or
+// gone, has asked for: never below what a launch needs.
+static int raise_lds_limit(int device, const void* fn, size_t lds_bytes) {
+  static std::mutex mu;
+  static std::map<std::pair<int, const void*>, size_t> limit;
+  std::lock_guard<std::mutex> lock(mu);
+  size_t& have = limit[{device, fn}];
+  if (lds_bytes <= have) return 0;
+  HIP_OK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_bytes)));
+  have = lds_bytes;
+  return 0;
 }
 
 // The film's 8x8 tiles and this shard's share of them (local tile t is film tile t * shard_world + shard_rank).  Pixel
@@ -94,21 +123,52 @@ static int plan_timing_events(pine_gpu_plan* p, const pine_gpu_render_params* pr
   return 0;
 }
 
-// A new plan that `build(plan)` fills, or null with build's error: what the failed build left is destroyed with the plan.
-template <class Build>
-static pine_gpu_plan* create_plan(pine_gpu_scene* scene, const pine_gpu_render_params* prm, Build build) {
-  if (!scene || !prm) {
+// A new object -- a plan, an accel, a shader -- that `build(object)` fills, or null with build's error: what the failed build
+// left is destroyed with the object.  `have_args`: none of the caller's pointers is null.
+template <class Object, class Build>
+static Object* create_object(bool have_args, void (*destroy)(Object*), Build build) {
+  if (!have_args) {
     set_error("null argument");
     return nullptr;
   }
-  pine_gpu_plan* p = new pine_gpu_plan();
-  if (build(p)) {
+  Object* o = new Object();
+  if (build(o)) {
     std::string keep = pine_gpu_last_error();
-    pine_gpu_plan_destroy(p);
+    destroy(o);
     set_error(keep);
     return nullptr;
   }
-  return p;
+  return o;
+}
+
+// What an accel and a shader are: the scene's records on a device -- held in a pine_gpu_plan that is never launched, so that
+// the buffers have the owners and the pool every plan's have -- read by kernels that write the caller's buffers only.
+struct SceneQuery {
+  PlanOwner plan;  // S: the scene view; the d_* blocks behind it
+  int device = 0;
+  size_t lds_bytes = 0;  // of the kernels that read the scene
+  bool has_camera = false;
+  std::atomic<bool> launched{false};  // a launch may still be reading the records: destroy waits for the device first
+
+  // One launch of `fn` over n lanes on `stream`; nothing is waited for.
+  int launch(const void* fn, void** args, int64_t n, size_t lds, void* stream) {
+    HIP_OK(hipSetDevice(device));
+    (void)hipGetLastError();
+    launched.store(true);
+    HIP_OK(hipLaunchKernel(fn, dim3(unsigned((n + kBlock - 1) / kBlock)), dim3(kBlock), args, lds, static_cast<hipStream_t>(stream)));
+    return 0;
+  }
+};
+
+// The records go back to the pool with the plan: every launch that reads them, on whatever stream, must have finished.
+template <class Query>
+static void destroy_query(Query* q) {
+  if (!q) return;
+  if (q->launched.load()) {
+    (void)hipSetDevice(q->device);
+    (void)hipDeviceSynchronize();
+  }
+  delete q;
 }
 
 // A launch is: launch_begin, [the integrator's own clears], mark 0, checkpoint_prepass, mark 1, [its kernel], mark 2, [its film

@@ -5,15 +5,10 @@
 // tables -- and the vertex kernel chosen for them.  The records are a snapshot.  Nothing on the device is written after creation:
 // paths live in the caller's buffers, so calls on several streams may run at once.
 
-struct pine_gpu_shader {
-  PlanOwner plan;  // S: the scene view and the sampler's tables; the d_* blocks behind them
-  int device = 0;
+struct pine_gpu_shader : SceneQuery {  // (plan->S: the sampler's tables too)
   int variant = 0;
   const PineShadeVariant* kernel = nullptr;
-  size_t lds_bytes = 0;
-  bool has_camera = false;
   int spp = 0;  // effective
-  std::atomic<bool> launched{false};  // a launch may still be reading the records: destroy waits for the device first
 };
 
 static int shader_build(pine_gpu_shader* s, pine_gpu_scene* scene, const pine_gpu_render_params* prm) {
@@ -72,21 +67,19 @@ static int shader_build(pine_gpu_shader* s, pine_gpu_scene* scene, const pine_gp
   s->plan.reset(new pine_gpu_plan());
   pine_gpu_plan* p = s->plan.get();
   std::chrono::steady_clock::time_point built;
-  if (plan_open_device(p, H, prm, "Shader's vertex queries", built)) return -1;
+  SceneRecords R;
+  // (without a frame table: the hit record carries no entry)
+  if (upload_scene_records(p, H, prm, "Shader's vertex queries", built, R)) return -1;
   s->device = prm->device;
   s->has_camera = H.has_camera;
   s->spp = spp;
-  SceneParts sp;
-  if (assemble_scene(p, H, prm, sp, false) || upload_sampler_tables(p, *tables_blob, prm, spp)) return -1;
+  if (upload_sampler_tables(p, *tables_blob, prm, spp)) return -1;
   p->S.spp = spp;
 
   // the vertex kernel: the first variant that covers the scene; $PINE_GPU_SHADER_VARIANT=<index> considers that variant only (tests)
-  const unsigned need = scene_features(sp, prm);
-  const bool lds_ok = size_t(p->S.blob_bytes) <= 32 * 1024;
   int count = 0;
   const PineShadeVariant* table = pine_gpu_shade_variant_table(&count);
-  const int chosen = pick_variant(table, count, need, lds_ok, "PINE_GPU_SHADER_VARIANT", "no Shader kernel variant covers this scene",
-                                  "$PINE_GPU_SHADER_VARIANT names no Shader kernel variant that covers this scene");
+  const int chosen = pick_variant(table, count, R.need, R.lds_ok, "PINE_GPU_SHADER_VARIANT", "Shader");
   if (chosen < 0) return -1;
   s->variant = chosen;
   s->kernel = &table[chosen];
@@ -96,29 +89,10 @@ static int shader_build(pine_gpu_shader* s, pine_gpu_scene* scene, const pine_gp
 }
 
 pine_gpu_shader* pine_gpu_shader_create(pine_gpu_scene* scene, const pine_gpu_render_params* prm) {
-  if (!scene || !prm) {
-    set_error("null argument");
-    return nullptr;
-  }
-  pine_gpu_shader* s = new pine_gpu_shader();
-  if (shader_build(s, scene, prm)) {
-    std::string keep = pine_gpu_last_error();
-    pine_gpu_shader_destroy(s);
-    set_error(keep);
-    return nullptr;
-  }
-  return s;
+  return create_object(scene && prm, pine_gpu_shader_destroy, [&](pine_gpu_shader* s) { return shader_build(s, scene, prm); });
 }
 
-void pine_gpu_shader_destroy(pine_gpu_shader* s) {
-  if (!s) return;
-  if (s->launched.load()) {
-    // the records go back to the pool with the plan: every launch that reads them, on whatever stream, must have finished
-    (void)hipSetDevice(s->device);
-    (void)hipDeviceSynchronize();
-  }
-  delete s;
-}
+void pine_gpu_shader_destroy(pine_gpu_shader* s) { destroy_query(s); }
 
 int pine_gpu_shader_layout(int32_t out[4]) {
   if (!out) {
@@ -172,15 +146,6 @@ static int shader_check_sample(const pine_gpu_shader* s, int sample) {
   return 0;
 }
 
-// One launch of `fn` over n lanes on `stream`; nothing is waited for.
-static int shader_launch(pine_gpu_shader* s, const void* fn, void** args, int64_t n, size_t lds_bytes, void* stream) {
-  HIP_OK(hipSetDevice(s->device));
-  (void)hipGetLastError();
-  s->launched.store(true);
-  HIP_OK(hipLaunchKernel(fn, dim3(unsigned((n + kBlock - 1) / kBlock)), dim3(kBlock), args, lds_bytes, static_cast<hipStream_t>(stream)));
-  return 0;
-}
-
 int pine_gpu_shader_begin_device(pine_gpu_shader* s, int sample, void* states_dev, void* rays_dev, void* stream) {
   if (shader_check(s, 1, {states_dev, rays_dev})) return -1;
   if (!s->has_camera) {
@@ -191,7 +156,7 @@ int pine_gpu_shader_begin_device(pine_gpu_shader* s, int sample, void* states_de
   DCamera cam = s->plan->S.cam;
   int kind = s->plan->S.tables.kind;
   void* args[] = {&cam, &kind, &sample, &states_dev, &rays_dev};
-  return shader_launch(s, pine_gpu_shade_begin_fn(), args, int64_t(cam.W) * cam.H, 0, stream);
+  return s->launch(pine_gpu_shade_begin_fn(), args, int64_t(cam.W) * cam.H, 0, stream);
 }
 
 int pine_gpu_shader_vertex_device(pine_gpu_shader* s, const void* rays_dev, const void* hits_dev, int64_t n, void* states_dev, void* records_dev,
@@ -200,7 +165,7 @@ int pine_gpu_shader_vertex_device(pine_gpu_shader* s, const void* rays_dev, cons
   if (n == 0) return 0;
   long long count = n;
   void* args[] = {&s->plan->S, (void*)&rays_dev, (void*)&hits_dev, &count, &states_dev, &records_dev, &shadow_rays_dev, &next_rays_dev};
-  return shader_launch(s, s->kernel->vertex, args, n, s->lds_bytes, stream);
+  return s->launch(s->kernel->vertex, args, n, s->lds_bytes, stream);
 }
 
 int pine_gpu_shader_fold_device(pine_gpu_shader* s, const void* records_dev, const void* occluded_dev, int levels, int64_t n, int sample, void* sum_dev,
@@ -223,7 +188,7 @@ int pine_gpu_shader_fold_device(pine_gpu_shader* s, const void* records_dev, con
   }
   long long count = n;
   void* args[] = {(void*)&records_dev, (void*)&occluded_dev, &levels, &count, &sample, &sum_dev, &log_dev_or_null};
-  return shader_launch(s, pine_gpu_shade_fold_fn(), args, n, 0, stream);
+  return s->launch(pine_gpu_shade_fold_fn(), args, n, 0, stream);
 }
 
 int pine_gpu_shader_resolve_device(pine_gpu_shader* s, const void* sum_dev, int64_t n, void* film_dev, void* stream) {
@@ -232,5 +197,5 @@ int pine_gpu_shader_resolve_device(pine_gpu_shader* s, const void* sum_dev, int6
   long long count = n;
   int spp = s->spp;
   void* args[] = {(void*)&sum_dev, &count, &spp, &film_dev};
-  return shader_launch(s, pine_gpu_shade_resolve_fn(), args, n, 0, stream);
+  return s->launch(pine_gpu_shade_resolve_fn(), args, n, 0, stream);
 }

@@ -1,5 +1,5 @@
-"""What the shared build steps of path plans, AOIntegrator plans and the guide pass (pine_plan_steps.h) promise a caller on a
-machine without a device: each hot path's own "no HIP device available" text, and an integrator's refusals before it."""
+"""What the shared build steps of path plans, AOIntegrator plans, the guide pass, Accel and Shader (pine_plan_steps.h) promise a
+caller on a machine without a device: each hot path's own "no HIP device available" text, and an integrator's refusals before it."""
 import ctypes as C
 
 import numpy as np
@@ -41,6 +41,10 @@ def test_each_hot_path_names_itself_when_there_is_no_device(no_device):
     for device_pointers in (False, True):
         assert _guides(scene, _params(), device_pointers) < 0
         assert _lib.last_error() == text % "the guide images' hot path"
+    assert not lib.pine_gpu_accel_create(scene._h, 0, 0)
+    assert _lib.last_error() == text % "Accel's ray queries"
+    assert not lib.pine_gpu_shader_create(scene._h, C.byref(_params()))
+    assert _lib.last_error() == text % "Shader's vertex queries"
 
 
 def test_refusals_come_before_the_device_check(no_device):
