@@ -84,6 +84,40 @@ constexpr int kQCtxGlobalDwordsPlain = 4, kQCtxGlobalDwordsSss = 20;
 constexpr int q_ctx_trav_offset(unsigned F) { return (F & F_SSS) ? kQCtxGlobalDwordsSss : kQCtxGlobalDwordsPlain; }
 constexpr int q_ctx_global_dwords(unsigned F) { return q_ctx_trav_offset(F) + ((F & F_LDS_TOP) ? kTravRecordDwords : 0); }
 
+// Case ledger of the baked top level (-DPINE_TOP_CASES, a diagnostic build of a one-mesh scene's own kernel; DESIGN.md 4.9
+// item 3): every ray is counted once into the slot of the branch of the protocol it took, in Counters::section_cycles
+// (pine_gpu_plan_debug_sections reads them).  tests/test_baked_top_gpu.py mirrors the names; the counts say whether a test
+// scene reached the branch it was built for, never what the film should be.  Without the define TOP_CASE is nothing.
+enum TopCase : int {
+  // closest-hit rays (their sum = the launch's radiance() invocations, PlanStats::vertices)
+  TC_SETTLED = 0,          // settled where the ray was created: the mesh's place was not reached
+  TC_REACHED_MISS = 1,     // through the mesh's BVH, no triangle accepted, the first pass's result is a miss
+  TC_REACHED_PRIM = 2,     // ... is a top-level primitive
+  TC_TRI_NONE_AFTER = 3,   // the triangle stands: no primitive stored after the mesh had been accepted (r_pb == 0)
+  TC_TRI_IN_FRONT = 4,     // the triangle stands: r_pb, but the first pass's final tmax is not below the triangle's (r_pa >= t_M)
+  TC_TRI_TIE = 5,          // ... of those (counted in both): r_pa == t_M exactly
+  TC_REPLAY_CAMERA = 6,    // the top level replayed from the float maximum (camera rays; the exit ray of a BSSRDF walk)
+  TC_REPLAY_SPAWNED = 7,   // ... from spawn_ray's tmax
+  TC_REACHED_WITH_HIT = 8, // (counted besides one of 1..7) reached the mesh's place with a hit already recorded (id_a >= 0)
+  // shadow rays (their sum = PlanStats::shadow_rays)
+  TC_SHADOW_TOP_OCCLUDED = 9,  // occluded by a top-level primitive in stage S
+  TC_SHADOW_TOP_CLEAR = 10,    // clear, the mesh's place not reached
+  TC_SHADOW_XS_OCCLUDED = 11,  // sent to stage XS, occluded by the mesh
+  TC_SHADOW_XS_CLEAR = 12,     // sent to stage XS, clear
+  // vertices with a parked shadow ray (their sum = slots 11 + 12)
+  TC_PARKED_NEXT_RESOLVED = 13,  // the next ray was settled where it was created (kTravClosestResolved)
+  TC_PARKED_NEXT_XC = 14,        // the next ray goes on to stage XC
+  TC_PARKED_NO_NEXT = 15,        // the path ends at this vertex
+};
+#ifdef PINE_TOP_CASES
+#if defined(PINE_PROFILE_SECTIONS) || defined(PINE_TOP_SHADOW_IN_XS) || defined(PINE_TOP_CLOSEST_IN_XC)
+#error "PINE_TOP_CASES counts into Counters::section_cycles and follows the default protocol: not with PINE_PROFILE_SECTIONS, PINE_TOP_SHADOW_IN_XS or PINE_TOP_CLOSEST_IN_XC"
+#endif
+#define TOP_CASE(slot) atomicAdd(&counters->section_cycles[slot], 1ull)
+#else
+#define TOP_CASE(slot)
+#endif
+
 // Subsurface (F_SSS): the BSSRDF random walk (bxdf.cpp:329-353) is a stage of its own, W -- ONE free-flight
 // step per pass (closest hit inside the shape, exponential free flight, exit or uniform-sphere scatter), the
 // context re-queued between steps, so that a wave's 64 lanes are 64 walks in the same phase whatever their
@@ -314,6 +348,7 @@ __device__ __forceinline__ void path_queue_body(const DeviceScene& S, const Work
       cstf[CF_TMAX * kQCtx + id] = r.tmax;
       cstu[CF_GEOM * kQCtx + id] = unsigned(hit ? baked_top_word(g) : -1);
       cstu[CF_PRIM * kQCtx + id] = 0u;
+      TOP_CASE(TC_SETTLED);
       return true;
     }
     const bool camera = tmax == kFloatMax;
@@ -542,6 +577,7 @@ __device__ __forceinline__ void path_queue_body(const DeviceScene& S, const Work
             ts.r_pb = id_r != id_a ? 1 : 0;
             ts.r_pbn = int((packed >> 8) & 1u);
             bm.reached = true;
+            if (id_a >= 0) TOP_CASE(TC_REACHED_WITH_HIT);
 #endif
           }
           if (bm.reached) {
@@ -575,6 +611,10 @@ __device__ __forceinline__ void path_queue_body(const DeviceScene& S, const Work
         const PackedState st{cstu[CF_ST * kQCtx + id]};
         if (ANY) {
           const bool occluded = ts.hit_geom >= 0;
+#ifdef PINE_BAKED_TOP
+          if (occluded) TOP_CASE(TC_SHADOW_XS_OCCLUDED);
+          else TOP_CASE(TC_SHADOW_XS_CLEAR);
+#endif
           if (flags & kTravTerminalAfterShadow) {
             if (occluded) {  // Lo = min(beta * 0, 8) = 0
               cstf[CF_DX * kQCtx + id] = 0.0f;
@@ -609,10 +649,15 @@ __device__ __forceinline__ void path_queue_body(const DeviceScene& S, const Work
             if (ts.hit_geom != kBakedMeshWord) {
               // no triangle accepted: every bound of the first pass was the reference's -- its result stands
               ray.tmax = __int_as_float(ts.r_pa), ts.hit_geom = ts.r_pan;
-            } else if (ts.r_pb && __int_as_float(ts.r_pa) < ray.tmax) {
+              if (ts.hit_geom >= 0) TOP_CASE(TC_REACHED_PRIM);
+              else TOP_CASE(TC_REACHED_MISS);
+            } else if (!kBakedTopPlainRects || (ts.r_pb && __int_as_float(ts.r_pa) < ray.tmax)) {
               // a triangle at ray.tmax, and a primitive stored AFTER the mesh had been accepted against the larger bound with
               // a SMALLER t (were the first pass's final tmax not below the triangle's, no such primitive could pass the
-              // reference's test `t < tmax` either: whatever the reference accepts, the first pass accepted or bettered):
+              // reference's test `t < tmax` either: whatever the reference accepts, the first pass accepted or bettered --
+              // an argument about primitives whose t does not depend on the bound: axis-aligned Rects.  With any other
+              // primitive in the top level every triangle is settled here: a ray that starts INSIDE a scaled Box(AABB, mat4)
+              // gets a smaller t from it under the triangle's bound than under the first pass's):
               // replay the top level with the mesh's result in its place (the reference's own sequence)
               DRay rr{ray.o, ray.d, 0.0f, ts.r_pbn ? kFloatMax : kFloatMax * (1.0f - 1e-3f)};  // (camera_gen_ray's / spawn_ray's tmax)
               BakedMesh bm{true, ray.tmax, -1};
@@ -620,6 +665,13 @@ __device__ __forceinline__ void path_queue_body(const DeviceScene& S, const Work
               const bool hit = scene_traverse_baked_top<false, F, 1>(rr, g, bm);
               ray.tmax = rr.tmax;
               ts.hit_geom = hit ? baked_top_word(g) : -1;
+              if (ts.r_pbn) TOP_CASE(TC_REPLAY_CAMERA);
+              else TOP_CASE(TC_REPLAY_SPAWNED);
+            } else if (ts.r_pb) {
+              TOP_CASE(TC_TRI_IN_FRONT);
+              if (__int_as_float(ts.r_pa) == ray.tmax) TOP_CASE(TC_TRI_TIE);
+            } else {
+              TOP_CASE(TC_TRI_NONE_AFTER);
             }
           }
 #endif
@@ -955,8 +1007,10 @@ __device__ __forceinline__ void path_queue_body(const DeviceScene& S, const Work
           if (scene_traverse_baked_top<true, F, 0>(sr, g, bm)) {
             nee = mk3(0.0f);  // occluded
             have_shadow = false;
+            TOP_CASE(TC_SHADOW_TOP_OCCLUDED);
           } else if (!bm.reached) {
             have_shadow = false;  // visible
+            TOP_CASE(TC_SHADOW_TOP_CLEAR);
           }
         }
 #endif
@@ -1054,6 +1108,11 @@ __device__ __forceinline__ void path_queue_body(const DeviceScene& S, const Work
             r4[1] = make_float4(shadow_ray.d.y, shadow_ray.d.z, shadow_ray.tmax,
                                 __uint_as_float((continues ? 0u : kTravTerminalAfterShadow) | (closest_resolved ? kTravClosestResolved : 0u)));
             to_xs = true;
+#ifdef PINE_BAKED_TOP
+            if (!continues) TOP_CASE(TC_PARKED_NO_NEXT);
+            else if (closest_resolved) TOP_CASE(TC_PARKED_NEXT_RESOLVED);
+            else TOP_CASE(TC_PARKED_NEXT_XC);
+#endif
           }
         }
       }

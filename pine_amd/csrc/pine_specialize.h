@@ -62,8 +62,9 @@ constexpr unsigned kBakedFeature = 1u << 17;  // F_BAKED for host code that cann
 // (scene_traverse_baked_top), run once per ray at full lane occupancy, and the flat traversal of the traversal stages is left
 // the mesh's BVH alone.  Pine's order survives by construction: the first pass (MODE 0) walks the top level with the mesh
 // skipped and notes the state at the mesh's place (reached? tmax and hit so far); the mesh is traversed with that tmax; if
-// it is hit and a primitive stored AFTER the mesh had been accepted, the top level is REPLAYED (MODE 1) with the mesh's
-// result put in at its place -- the reference's own sequence of tests, same bounds at every box and primitive.
+// it is hit and a primitive stored AFTER the mesh had been accepted (or any primitive of the top level is not an axis-aligned
+// Rect: kBakedTopPlainRects), the top level is REPLAYED (MODE 1) with the mesh's result put in at its place -- the reference's
+// own sequence of tests, same bounds at every box and primitive.
 inline std::string generate_baked_scene(const FlatAccel& A, const std::vector<DShape>& shapes, const std::vector<int>& words, bool top_with_mesh = false) {
   if (A.bvhs.size() != (top_with_mesh ? 2u : 1u)) return "";  // (a mesh brings a second BVH)
   const DBvh top = A.bvhs[0];
@@ -84,7 +85,7 @@ inline std::string generate_baked_scene(const FlatAccel& A, const std::vector<DS
   int instances = 0, node_copies = 0;
   int mesh_word = -1, mesh_id = -1;
   std::vector<int> top_words;
-  bool ok = true;
+  bool ok = true, plain_rects = true;
   auto leaf = [&](int start, int count, const std::string& ind, std::string& o) {
     for (int i = start; i < start + count && ok; i++) {
       const int g = A.prims[size_t(i)];
@@ -189,6 +190,7 @@ inline std::string generate_baked_scene(const FlatAccel& A, const std::vector<DS
           continue;
         }
       }
+      plain_rects = false;  // (a primitive that goes through a generic test: see kBakedTopPlainRects below)
       if (!have[size_t(g)]) {
         have[size_t(g)] = 1;
         recs += "__device__ static constexpr float kBakedRec" + std::to_string(g) + "[30] = {";
@@ -264,6 +266,11 @@ inline std::string generate_baked_scene(const FlatAccel& A, const std::vector<DS
     out = "#define PINE_BAKED_TOP 1\n" + out;
     out += "struct BakedMesh { bool reached; float t; int geom; };  // at the mesh's place: MODE 0 out (tmax and hit so far), MODE 1 in (t = the mesh's hit)\n";
     out += "constexpr int kBakedMeshWord = " + std::to_string(mesh_word) + ", kBakedMeshId = " + std::to_string(mesh_id) + ";\n";
+    // Every primitive beside the mesh is an inline axis-aligned Rect (C5's class): its t does not depend on the bound it is tested
+    // with and it is accepted exactly when t < tmax, which is what lets a triangle stand without a replay (pine_queue_kernel.h).
+    // Any other primitive -- a scaled Box(AABB, mat4) reports min(exit, tmax) in LOCAL units for a ray that starts inside it, a
+    // smaller t under a smaller bound -- and every triangle hit is settled by the replay.
+    out += std::string("constexpr bool kBakedTopPlainRects = ") + (plain_rects ? "true" : "false") + ";\n";
     out += "__device__ __forceinline__ int baked_top_word(int id) {\n  switch (id) {\n";
     for (size_t k = 0; k < top_words.size(); k++) out += "    case " + std::to_string(k) + ": return " + std::to_string(top_words[k]) + ";\n";
     out += "    default: return -1;\n  }\n}\n";

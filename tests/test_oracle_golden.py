@@ -71,6 +71,23 @@ def test_film_bit_identical_to_reference(oracle, name):
     assert st.camera_samples == w * h * oracle.effective_spp(spp)
 
 
+def _baked_top_films():
+    import baked_top_scenes
+    return list(baked_top_scenes.GOLDEN_FILMS)
+
+
+@pytest.mark.parametrize("name", _baked_top_films())
+def test_one_mesh_film_bit_identical_to_reference(oracle, name):
+    """One-mesh scenes with the mesh last, in the middle under a node with two inner children, and followed by a scaled Box
+    (tests/baked_top_scenes.py): the restatement against the REAL reference's films, which tests/test_baked_top_gpu.py holds the
+    baked top level to as well."""
+    import baked_top_scenes as B
+    ref, ps, spp, depth = load_film(name)
+    assert ps == B.build(B.GOLDEN_FILMS[name], "axis", (24, 24)).describe(), f"{name}: not the scene the reference rendered"
+    film, _ = oracle.render(ps, (24, 24), spp, depth)
+    assert_bit_equal(film, ref, name)
+
+
 @pytest.mark.parametrize("name", SOBOL_FILM_NAMES)
 def test_sobol_sampler_film_bit_identical_to_reference(oracle, name):
     """SobolSampler (sampler.h:83-164, sampler.cpp:81-113): Morton-indexed, base-4 digit permutations, fast Owen

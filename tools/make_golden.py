@@ -9,6 +9,7 @@ and the reference's outputs, no reference source) are committed and travel to th
     python tools/make_golden.py --sampling # BSDF lobes and shape / light sampling per call (tests/test_sampling_fixtures.py)
     python tools/make_golden.py --nodes    # shading-node programs and the material-to-lobe step per call (tests/test_node_fixtures.py)
     python tools/make_golden.py --draws    # Sobol / Halton / Blue sampler draws per call at real film sizes, the strip films (tests/test_sampler_draws.py)
+    python tools/make_golden.py --baked-top   # three one-mesh scenes with the mesh not first (tests/baked_top_scenes.py)
     python tools/make_golden.py --live    # the reference's films of the oracle tests' cbox and seeded random scenes
 """
 import hashlib
@@ -460,8 +461,25 @@ def draws_fixtures(tmp):
     print("total", total, "bytes")
 
 
+def baked_top_fixtures(tmp):
+    """tests/golden/film_baked_top_*.npz: three of the one-mesh scenes of tests/baked_top_scenes.py (mesh last, under a node with two
+    inner children, a scaled Box stored after it) at 24 x 24, for tests/test_baked_top_gpu.py and tests/test_oracle_golden.py."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import baked_top_scenes as B
+    for golden, name in B.GOLDEN_FILMS.items():
+        case = B.SCENES[name]
+        ps, film, info = ref_film(B.build(name, "axis", (24, 24)), case.spp, case.depth, tmp)
+        path = os.path.join(OUT, f"film_{golden}.npz")
+        np.savez_compressed(path, film=film, pscene=np.array(ps), spp=case.spp, depth=case.depth)
+        print(golden, film.shape, hashlib.md5(film.tobytes()).hexdigest(), os.path.getsize(path), "bytes")
+
+
 def main():
     full = "--full" in sys.argv
+    if "--baked-top" in sys.argv:
+        with tempfile.TemporaryDirectory() as tmp:
+            baked_top_fixtures(tmp)
+        return
     if "--draws" in sys.argv:
         with tempfile.TemporaryDirectory() as tmp:
             draws_fixtures(tmp)
